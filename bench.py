@@ -15,6 +15,12 @@ GPU call; it runs `python -m torch.distributed.run --nproc-per-node N bench.py .
 rank 0's line and exits with the children's status).  Under an external launcher (RANK / WORLD_SIZE in the
 environment, as the driver's `python -m torch.distributed.run ... bench.py --gpus N` sets them) it runs as one rank.
 
+A plain run (`--steps K --warmup W`) sets up, tunes the fused launch's schedule, runs the clock warm-up loop (`--sustained`
+launches) and the W warm-up steps, times the K steps, writes the last timed step's outputs if `--dump-outputs DIR` is given
+(DIR/indices.npy float64 [N], DIR/code_usage.npy float64 [K], DIR/z_latent.npy float32: a fixed seeded sample of the
+z_latent rows, at most 32 MB; rank 0's shard with N > 1 GPU) and prints the line.  `--full` adds the side readings below
+(sustained, fast_mode, also, live traffic, power, cpu_baseline + parity_gate); none of them touches `value`.
+
 Prints ONE JSON line (rank 0).  Extra objects:
   roofline      the fused tokenize launch: algorithmic flops per launch (164 736 flop
                 per row at config 2) / mean launch duration (one pair of HIP events over the K timed steps, on the
@@ -23,12 +29,12 @@ Prints ONE JSON line (rank 0).  Extra objects:
                 distance screen on the fp16 MFMA pipe with 3 split products per algorithmic product);
                 `frac_algorithmic_floor` = the stricter reading, algorithmic 2NKD distance flops at the
                 fp16 MFMA peak with no credit for the 3x split.
-  parity_gate   rank 0, N=1: the timed batch's indices against the torch-CPU restatement of the reference on
+  parity_gate   (--full) rank 0, N=1: the timed batch's indices against the torch-CPU restatement of the reference on
                 the cpu_baseline sample.  A mismatch whose two candidates' distances differ by a relative gap
                 >= 1e-6 FAILS the run: no `value`, non-zero exit.
-  sustained     >= 1000 back-to-back launches (>= 0.5 s of GPU time) beside the K-step reading, so the
+  sustained     (--full) >= 1000 back-to-back launches (>= 0.5 s of GPU time) beside the K-step reading, so the
                 number is not a burst-clock figure.
-  cpu_baseline  the torch-CPU restatement of the reference (oracle/lipvq_oracle.py, kind="port"), timed on
+  cpu_baseline  (--full) the torch-CPU restatement of the reference (oracle/lipvq_oracle.py, kind="port"), timed on
                 a bounded row sample on this box's host cores at the best thread count of a short sweep.
 """
 from __future__ import annotations
@@ -135,6 +141,26 @@ def cpu_baseline(model, x_dev, idx_dev, budget_s=10.0):
             "tolerated_gap": PARITY_GAP, "passed": bool(mism == 0 or worst_gap < PARITY_GAP),
             "against": "torch-CPU restatement of the reference (bit-identical to the reference module in-process)"}
     return base, gate
+
+
+DUMP_ZQ_BYTES = 32 << 20     # z_latent rows beyond this are sampled (a fixed seeded row set) so that a dump stays well under 64 MB
+
+
+def dump_outputs(out_dir, idx, zq, usage):
+    """What the timed path's caller receives from its last step, as .npy files that two builds can be compared by:
+    indices [N] and the step's code-usage histogram [K] in float64 (exact), z_latent [N, D] in float32 -- every row, or a
+    seeded sample of rows (ascending) when that is more than DUMP_ZQ_BYTES."""
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    n, dim = zq.shape
+    rows = min(n, DUMP_ZQ_BYTES // (4 * dim))
+    if rows < n:
+        sel = torch.randperm(n, generator=torch.Generator(device="cpu").manual_seed(0))[:rows].sort().values
+        zq = zq[sel.to(zq.device)]
+    np.save(d / "indices.npy", idx.detach().cpu().to(torch.float64).numpy())
+    np.save(d / "z_latent.npy", zq.detach().float().cpu().numpy())
+    np.save(d / "code_usage.npy", usage.detach().cpu().to(torch.float64).numpy())
 
 
 CHILD_SCHEDULE = []          # the counter children run the schedule THIS process tuned (main sets it): ["--schedule", "d,n"]
@@ -355,14 +381,22 @@ def main():
                     help="N > 1: strong = the workload's global batch sharded B/N per rank (BASELINE config 4 as SURVEY 8d defines "
                          "it); weak = every rank tokenizes a full B x T batch of its own")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--sustained", type=int, default=1000, help="back-to-back launches of the sustained reading (0 = skip)")
+    ap.add_argument("--sustained", type=int, default=1000,
+                    help="back-to-back launches before the warm-up, the timed steps' clock warm-up; reported as `sustained` with "
+                         "--full (0 = skip)")
     ap.add_argument("--traffic", default="live", choices=("live", "file", "off"),
-                    help="roofline.traffic: measured now under rocprofv3 --pmc (N=1 only), read from profiles/hbm_traffic.json, or null")
+                    help="roofline.traffic: live = measured now under rocprofv3 --pmc with --full (N=1 only), otherwise read "
+                         "from profiles/hbm_traffic.json; file = read from it; off = null")
     ap.add_argument("--schedule", default=None, help="defer_ze,nt_ze (e.g. 0,1): fix the fused launch's schedule choices instead of tuning")
     ap.add_argument("--no-tune", action="store_true",
                     help="skip LLFQVAE_V4.tune (set-up, untimed): the fused launch's device-dependent schedule choices stay at their defaults")
     ap.add_argument("--metric-only", action="store_true",
                     help="skip the fast-mode / full-forward / training-step side readings (profiling runs: every dispatch is then the metric's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the side readings (sustained, fast mode, full forward, training step, live traffic, power, "
+                         "CPU baseline with its parity gate); a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--rehearse-launcher", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -523,6 +557,7 @@ def main():
     # number of its own (`sustained`), and it leaves the chip in the clock / power state of a job that has been running for a
     # while -- which is what the W warm-up + K timed steps below are then measured in.  (Round 1 timed K = 20 steps straight
     # after model set-up: 11 ms on a GPU that had been idle, 12-15 % below the steady rate of the very same launches.)
+    # A plain run keeps the loop for that clock state and reports its reading only with --full.
     sustained = None
     if args.sustained > 0:
         for _ in range(3):
@@ -569,6 +604,8 @@ def main():
     else:
         usage_rows = int(last_row[0].sum().item())
     idx_timed = idx.clone()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, idx, zq, last_row[0])
 
     tok_ms = sum(a.elapsed_time(b) for a, b in ev_pairs) / max(1, args.steps)      # (first launch's start -> last launch's end) / K
     value = N_global * args.steps / elapsed
@@ -626,13 +663,13 @@ def main():
                      "hbm_frac": (float(N) * (4 * A + 4 * D + 8) / (tok_ms * 1e-3) / 1e9 / PEAK_HBM_GBS) if tok_ms > 0 else 0.0,
                      "rows_decided_by_exact_kernel": exact_rows},
     }
-    if sustained is not None:
+    if sustained is not None and args.full:
         out["sustained"] = sustained
     out["tuned"] = tuned if tuned is not None else "not tuned (--no-tune, no fused launch for this shape, or a latent width above 64 whose instances have no device-dependent choice): library defaults"
     if tuned is not None and "fixed" not in tuned:
         tuned["what"] = ("set-up, untimed, rank 0's device: LLFQVAE_V4.tune timed the fused launch's four (defer_ze, nt_ze) schedule "
                          "combinations (identical results) and the process keeps the fastest")
-    if world == 1 and not args.metric_only and ops.tokenize_fast_supported(A, 64, model.hidden_dim, D, K):
+    if args.full and world == 1 and not args.metric_only and ops.tokenize_fast_supported(A, 64, model.hidden_dim, D, K):
         # reported beside the metric, never as `value`: the opt-in fast mode (fp16 encoder GEMMs, fp32 accumulation and
         # quantizer) on the same batch, with the fraction of indices that differ from the parity run above
         # Same discipline as the metric: a clock warm-up of the kernel being timed, then a loop long enough not to be a burst
@@ -654,7 +691,7 @@ def main():
                             "index_flip_rate_vs_parity": float((idx_fast != idx_timed).float().mean().item()),
                             "launches_timed": nf,
                             "note": "opt-in (tokenize(mode='fast')); not bit-identical, hence not the reported value"}
-    if world == 1 and not args.metric_only:
+    if args.full and world == 1 and not args.metric_only:
         # "report also full fwd (+decode+loss) and fwd+bwd+AdamW step" -- same batch, a few steps each,
         # beside the metric (never `value`)
         def timed_ms(fn, n):
@@ -706,7 +743,7 @@ def main():
     # HBM traffic LAST among the GPU readings: the profiler children run after every timed side reading (and are reaped before
     # this process goes on), so nothing of them can overlap a measurement
     traffic, traffic_src, traffic_detail, sq = None, None, None, None
-    if args.traffic == "live" and world == 1 and not args.metric_only:
+    if args.full and args.traffic == "live" and world == 1 and not args.metric_only:
         try:
             traffic, traffic_src, traffic_detail, sq = measure_traffic_live(
                 args.workload, ("tokenize_kernel", "nearest_rows", "nearest_lists") if ops.tokenize_supported(A, 64, model.hidden_dim, D, K)
@@ -718,7 +755,7 @@ def main():
         t = json.loads(tfile.read_text())
         if t.get("workload") == args.workload:
             traffic, traffic_src = t.get("bytes_per_launch"), (traffic_src or "") + "committed: " + str(t.get("source"))
-    if world == 1 and rank == 0 and not args.metric_only and args.traffic != "off":
+    if args.full and world == 1 and rank == 0 and not args.metric_only and args.traffic != "off":
         def _some():
             for _ in range(200):
                 step(False)
@@ -741,7 +778,7 @@ def main():
                                             "profiles/r04_e_traffic_accounting.md "
                                             "(z_e / z_q rows are nontemporal stores, for which WRITE_SIZE reads 5-15 % above the bytes stored)"})
     failed = False
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"], gate = cpu_baseline(model, x, idx_timed)
         out["parity_gate"] = gate
         out["gpu_vs_cpu"] = value / out["cpu_baseline"]["value"]

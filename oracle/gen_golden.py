@@ -536,6 +536,25 @@ def run_bin_all(ref_root):
     run_bin(binmod, "bin_nb5", 403, 64, 3, 32, nb=5)
 
 
+def run_icl_time_distributed(ref_root):
+    """tensor_utils.icl_time_distributed (the nested [B, T, ...] -> [B * T, ...] -> [B, T, ...] glue, obs_nets.py:2571) on
+    seeded inputs: the inputs and the reference's three outputs, for tests/test_icl_host.py."""
+    tu = load_ref(ref_root, "robomimic/utils/tensor_utils.py", "_ref_tensor_utils")
+    g = torch.Generator().manual_seed(3)
+    names = (("obs/eef", 3), ("obs/joint", 7), ("prompt/obs/eef", 3), ("prompt/obs/joint", 7), ("prompt/action", 12))
+    t = {k: torch.randn(3, 10, w, generator=g) for k, w in names}
+    inp = {"obs": {"eef": t["obs/eef"], "joint": t["obs/joint"]},
+           "prompt": {"obs": {"eef": t["prompt/obs/eef"], "joint": t["prompt/obs/joint"]}, "action": t["prompt/action"]}}
+
+    def op(obs=None, prompt=None):
+        return obs["joint"] + 1, prompt["obs"]["eef"] * 2, prompt["action"].sum(-1, keepdim=True)
+
+    outs = tu.icl_time_distributed(inp, op, inputs_as_kwargs=True)
+    np.savez_compressed(GOLD / "icl_time_distributed.npz", meta=meta_of(name="icl_time_distributed", seed=3, B=3, T=10),
+                        **{"in/" + k: v.numpy() for k, v in t.items()}, **{f"out{i}": o.numpy() for i, o in enumerate(outs)})
+    print("icl_time_distributed:", [tuple(o.shape) for o in outs])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
@@ -543,6 +562,7 @@ def main():
     ap.add_argument("--only-default", action="store_true", help="only the default action branch fixtures")
     ap.add_argument("--only-edge", action="store_true")
     ap.add_argument("--only-embed", action="store_true")
+    ap.add_argument("--only-icl", action="store_true", help="only the icl_time_distributed fixture")
     ap.add_argument("--only-bin", action="store_true")
     ap.add_argument("--only-big", action="store_true")
     ap.add_argument("--only-odd", action="store_true", help="only the near-tie fixtures at latent widths that are not multiples of 8")
@@ -552,6 +572,9 @@ def main():
         GOLD.mkdir(parents=True, exist_ok=True)
         return run_embed_all()
     ref_root = Path(args.ref)
+    if args.only_icl:
+        GOLD.mkdir(parents=True, exist_ok=True)
+        return run_icl_time_distributed(ref_root)
     if args.only_default:
         GOLD.mkdir(parents=True, exist_ok=True)
         torch.set_num_threads(1)
@@ -598,6 +621,7 @@ def main():
     run_init(v5, vq)
     run_embed_all()
     run_default_all()
+    run_icl_time_distributed(ref_root)
     run_bin_all(ref_root)
     run_big_all(v5, orc)
     run_odd_width_all(v5, vq)

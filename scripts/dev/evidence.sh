@@ -5,8 +5,8 @@ set -e
 cd "$(dirname "$0")/../.."
 TAG=$1; OUT=gpurun_out/$TAG; OLD=${2:-}; mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
-for wl in cfg3 icrt; do python bench.py --workload $wl > $OUT/bench_$wl.json 2>> $OUT/bench.err; done
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err
+for wl in cfg3 icrt; do python bench.py --workload $wl --full > $OUT/bench_$wl.json 2>> $OUT/bench.err; done
 # warm-clock kernel traces of ONE bench process per workload, timed steps only (scripts/prof_stats.sh) + SQ counters of the same build
 for wl in cfg2 cfg3 icrt; do bash scripts/prof_stats.sh $TAG $wl 20 > $OUT/prof_stats_$wl.txt 2>&1; done
 for wl in cfg2 cfg3 icrt; do bash scripts/pmc_sq.sh $TAG/sq_$wl --workload $wl > /dev/null 2>&1 && cp $OUT/sq_$wl/sq_counters.txt $OUT/sq_counters_$wl.txt; rm -rf $OUT/sq_$wl; done

@@ -1,17 +1,14 @@
 """CPU: the host glue of SURVEY 8f row 1 -- the nested-dict `icl_time_distributed` and the group-encoder-shaped shim -- with
 stand-in ops (no kernel runs here; the action network itself is covered on the GPU in tests/test_gpu_icl.py)."""
-import importlib.util
 from collections import OrderedDict
-from pathlib import Path
 
+import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 
 import lipvq_vae_amd  # noqa: F401
 from lipvq_vae_amd import icl
-
-REF_TU = Path("/root/reference/robomimic/utils/tensor_utils.py")
 
 
 class _ObsEnc(nn.Module):
@@ -59,20 +56,21 @@ def test_icl_time_distributed_maps_nested_inputs_and_reshapes_the_triple():
         icl.icl_time_distributed({}, op)
 
 
-@pytest.mark.skipif(not REF_TU.exists(), reason="the reference tree is not on this machine")
-def test_icl_time_distributed_equals_the_reference_function():
-    spec = importlib.util.spec_from_file_location("_ref_tensor_utils", REF_TU)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    inp = _inputs(3, 10)
+def test_icl_time_distributed_equals_the_reference_function(golden_dir):
+    """Against the reference function's own outputs on the same inputs (tests/golden/icl_time_distributed.npz,
+    oracle/gen_golden.py --only-icl)."""
+    g = np.load(golden_dir / "icl_time_distributed.npz")
+    t = lambda k: torch.from_numpy(g["in/" + k])
+    inp = {"obs": OrderedDict(eef=t("obs/eef"), joint=t("obs/joint")),
+           "prompt": {"obs": OrderedDict(eef=t("prompt/obs/eef"), joint=t("prompt/obs/joint")), "action": t("prompt/action")}}
 
     def op(obs=None, prompt=None):
         return obs["joint"] + 1, prompt["obs"]["eef"] * 2, prompt["action"].sum(-1, keepdim=True)
 
     got = icl.icl_time_distributed(inp, op, inputs_as_kwargs=True)
-    want = ref.icl_time_distributed(inp, op, inputs_as_kwargs=True)
-    for a, b in zip(got, want):
-        assert torch.equal(a, b)
+    assert len(got) == 3
+    for i, a in enumerate(got):
+        assert torch.equal(a, torch.from_numpy(g[f"out{i}"])), i
 
 
 def test_group_encoder_shim_routes_like_the_reference(monkeypatch):
