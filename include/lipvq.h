@@ -124,13 +124,14 @@ int lipvq_mse_pair_loss_f32(const float* xr, const float* x, int64_t nx, const f
  * Redo it whenever the codebook changes.  prep: lipvq_nearest_prep_bytes(K, D) bytes. */
 size_t lipvq_nearest_prep_bytes(int K, int D);
 int lipvq_nearest_prepare_f32(const float* codebook, void* prep, int K, int D, void* stream);
-int lipvq_nearest_screened_supported(int K, int D);          /* 1 for any D in 1 ... 208 (widths other than 32 / 64 / 128 / 208 run
-                                                               * the next larger instance on zero-padded columns) */
+int lipvq_nearest_screened_supported(int K, int D);          /* 1 for any D in 1 ... 512 (widths other than 32 / 64 / 128 / 208 /
+                                                               * 256 / 384 / 512 run the next larger instance on zero-padded
+                                                               * columns; above 208 a three-product screen only) */
 size_t lipvq_nearest_workspace_bytes(int64_t N);
 /* The screen comes in two strengths with identical results: three fp16 products per algorithmic product (22-bit operands; a
  * fraction of a percent of the rows left to the exact kernel) or ONE (11-bit operands, a third of the matrix work, lower-bound
  * bookkeeping; 10-40 % of the rows left to the exact stage with their two or three candidates each).  The library picks per
- * shape (the one-product screen from K = 4096 on, and from K = 1024 on for D > 64); this query tells which one
+ * shape (the one-product screen from K = 4096 on, and from K = 1024 on for 64 < D <= 208; never for D > 208); this query tells which one
  * a call with (K, D) would run now (environment LIPVQ_SCREEN_MODE=coarse|fine overrides: a measurement knob). */
 int lipvq_screen_is_coarse(int K, int D);
 /* idx / zq / usage exactly as lipvq_nearest_f32.  After the call the first int of `workspace`
@@ -146,7 +147,7 @@ int lipvq_nearest_rows_f32(const float* z, const float* codebook, int64_t* idx, 
 /* The same decision for SMALL batches (the reference's training step and rollouts: B*T = 1 ... a few hundred rows) with the
  * whole chip busy: a workgroup scores 4 rows against 64 codes staged in LDS, the grid is (row groups) x (code groups), a row's
  * partial minima meet behind a counter.  dist: LIPVQ_DIST_NORM | LIPVQ_DIST_SQSUM.  Identical idx / zq / usage.
- * lipvq_nearest_small_supported: N <= 4096, D a multiple of 4 whose LDS image fits (D <= 240).
+ * lipvq_nearest_small_supported: N <= 4096, D a multiple of 4 up to 512.
  * workspace: lipvq_nearest_small_workspace_bytes(N, K) bytes, 16-byte aligned, ZERO on entry; the call leaves it zero (one
  * zero-filled buffer serves every later call on a stream, whatever its shape). */
 int lipvq_nearest_small_supported(int64_t N, int K, int D);
@@ -156,7 +157,7 @@ int lipvq_nearest_small_f32(const float* z, const float* codebook, int64_t* idx,
 /* The plain VQVAE's quantizer (reference robomimic/models/vq_vae/backbone.py:55-63: `(z_e.unsqueeze(1) - E).pow(2).sum(-1)`,
  * argmin) through the same two routes: idx / zq / usage exactly as lipvq_nearest_f32(.., LIPVQ_DIST_SQSUM).  The screen is the
  * same certified MFMA screen (its margin covers the sum rule's rounding too); uncertified rows are decided by the exact kernel in
- * torch's cascade-sum order, first minimum.  prep / workspace as for lipvq_nearest_screened_f32.  D in 1 ... 208. */
+ * torch's cascade-sum order, first minimum.  prep / workspace as for lipvq_nearest_screened_f32.  D in 1 ... 512. */
 int lipvq_vq_nearest_screened_f32(const float* z, const float* codebook, const void* prep, int64_t* idx, float* zq,
                                   int64_t* usage, void* workspace, int64_t N, int K, int D, void* stream);
 int lipvq_vq_nearest_rows_f32(const float* z, const float* codebook, int64_t* idx, float* zq, int64_t* usage, int64_t N,

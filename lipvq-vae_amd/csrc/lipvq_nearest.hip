@@ -151,6 +151,108 @@ static int launch_nearest_direct(const float* z, const float* cb, int64_t* idx, 
     return check_launch("nearest_direct");
 }
 
+// Widths 209 ... 512 (the range of the wide screening instances): the row no longer fits the registers nearest_direct_kernel keeps
+// it in.  A workgroup takes NW_ROWS rows (2 per wave) and streams the codebook through LDS in groups of 64 codes, row stride D + 1
+// floats (nearest_small_kernel's layout: the column reads of the scoring loop hit 32 different banks): lane = code, the row read as
+// LDS broadcasts, torch's orders through lq_sqdist8 / lq_sqdist32.  A group's minimum (smallest value, the lower code among equal
+// values) replaces the running one only when strictly smaller: the first minimum, as nearest_direct_kernel's scan.  A NaN or an
+// infinite distance never wins (the scan's `v < best`).  DT: 256, 384, 512 at compile time (the loops unroll), 0 = any width.
+#define NW_ROWS 8
+#define NW_CODES 64
+static inline size_t nearest_wide_lds_bytes(int D) { return ((size_t)NW_ROWS * D + (size_t)NW_CODES * (D + 1)) * sizeof(float); }
+
+template <int DIST, int DT>
+__global__ __launch_bounds__(256) void nearest_wide_kernel(const float* __restrict__ z, const float* __restrict__ cb,
+                                                           int64_t* __restrict__ idx, float* __restrict__ zq,
+                                                           unsigned long long* __restrict__ usage, float* __restrict__ best_out,
+                                                           int64_t N, int K, int D_rt) {
+    extern __shared__ __attribute__((aligned(16))) float nw_lds[];
+    constexpr int RPW = NW_ROWS / 4;
+    const int D = DT ? DT : D_rt;
+    const int LD = D + 1;
+    float* s_z = nw_lds;                                  // [NW_ROWS][D]
+    float* s_cb = nw_lds + NW_ROWS * D;                   // [NW_CODES][D + 1]
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * NW_ROWS;
+    for (int i = tid; i < NW_ROWS * D; i += 256) {
+        const int r = i / D, d = i - r * D;
+        int64_t row = r0 + r;
+        row = row < N ? row : N - 1;
+        s_z[i] = z[(size_t)row * D + d];
+    }
+    float best_v[RPW];
+    int best_k[RPW];
+#pragma unroll
+    for (int rr = 0; rr < RPW; ++rr) { best_v[rr] = INFINITY; best_k[rr] = 0; }
+    for (int k0 = 0; k0 < K; k0 += NW_CODES) {
+        __syncthreads();                                  // the previous group's readers are done (first pass: s_z is written)
+        for (int i = tid; i < NW_CODES * D; i += 256) {
+            const int c = i / D, d = i - c * D;
+            const int k = k0 + c;
+            s_cb[c * LD + d] = k < K ? cb[(size_t)k * D + d] : 0.0f;
+        }
+        __syncthreads();
+        const int k = k0 + lane;
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) {
+            const float* zr = s_z + (w * RPW + rr) * D;
+            float v = INFINITY;
+            int kk = k < K ? k : K - 1;
+            if (k < K) {
+                const float* c = s_cb + lane * LD;
+                const float t = (DIST == LIPVQ_DIST_NORM) ? lq_sqrt(lq_sqdist8(zr, c, D)) : lq_sqdist32(zr, c, D);
+                if (t < INFINITY) v = t;
+            }
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {          // smallest value, among equal values the lower code
+                const float ov = __shfl_xor(v, off, 64);
+                const int ok = __shfl_xor(kk, off, 64);
+                if (ov < v || (ov == v && ok < kk)) { v = ov; kk = ok; }
+            }
+            if (v < best_v[rr]) { best_v[rr] = v; best_k[rr] = kk; }
+        }
+    }
+#pragma unroll
+    for (int rr = 0; rr < RPW; ++rr) {
+        const int64_t row = r0 + w * RPW + rr;
+        if (row >= N) continue;                           // (wave-uniform)
+        const int bk = best_k[rr];
+        if (lane == 0) {
+            idx[row] = (int64_t)bk;
+            if (best_out) best_out[row] = best_v[rr];
+            if (usage) atomicAdd(&usage[bk], 1ull);
+        }
+        if (zq)
+            for (int d = lane; d < D; d += 64) zq[(size_t)row * D + d] = cb[(size_t)bk * D + d];
+    }
+}
+
+static int launch_nearest_wide(const float* z, const float* cb, int64_t* idx, float* zq, int64_t* usage, float* best,
+                               int64_t N, int K, int D, int dist, hipStream_t st) {
+    const size_t lds = nearest_wide_lds_bytes(D);
+    const unsigned blocks = (unsigned)((N + NW_ROWS - 1) / NW_ROWS);
+    static LqLdsReserve reserved[2][4];                   // per kernel instance: (rule, width slot)
+    int rc = LIPVQ_OK;
+    auto go = [&](auto kfn, int slot) {
+        if (lds > 64 * 1024) {
+            rc = lipvq_reserve_lds(reserved[dist == LIPVQ_DIST_NORM ? 0 : 1][slot], (const void*)kfn, lds, "nearest_wide");
+            if (rc) return;
+        }
+        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), lds, st, z, cb, idx, zq, (unsigned long long*)usage, best, N, K, D);
+    };
+#define LQ_NW(DT_, SLOT_) do { if (dist == LIPVQ_DIST_NORM) go(nearest_wide_kernel<LIPVQ_DIST_NORM, DT_>, SLOT_); \
+                               else go(nearest_wide_kernel<LIPVQ_DIST_SQSUM, DT_>, SLOT_); } while (0)
+    switch (D) {
+        case 256: LQ_NW(256, 0); break;
+        case 384: LQ_NW(384, 1); break;
+        case 512: LQ_NW(512, 2); break;
+        default: LQ_NW(0, 3); break;
+    }
+#undef LQ_NW
+    if (rc) return rc;
+    return check_launch("nearest_wide");
+}
+
 extern "C" int lipvq_nearest_f32(const float* z, const float* codebook, int64_t* idx, float* zq,
                                  int64_t* usage, float* best, int64_t N, int K, int D, int dist,
                                  void* stream) {
@@ -169,6 +271,11 @@ extern "C" int lipvq_nearest_f32(const float* z, const float* codebook, int64_t*
             case 208: return launch_nearest_direct<26>(z, codebook, idx, zq, usage, best, N, K, dist, st);
             default: break;
         }
+    }
+    // 209 ... 512: LDS-staged (scalar staging: any alignment); the generic kernel is left to other widths
+    if (D > 208 && D <= 512) {
+        if ((N + NW_ROWS - 1) / NW_ROWS > 2147483647LL) return fail(LIPVQ_EUNSUPPORTED, "nearest: N too large");
+        return launch_nearest_wide(z, codebook, idx, zq, usage, best, N, K, D, dist, st);
     }
     hipLaunchKernelGGL(nearest_generic_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, z, codebook,
                        idx, zq, (unsigned long long*)usage, best, N, K, D, dist);

@@ -21,12 +21,21 @@ struct PrepLayout {
     size_t o_tiles_hi, tile_bytes_hi;      // the one-product screen's tiles: hi fragments only (half the bytes to stage)
 };
 
-// k-steps (of 16 columns) of the screening instance that serves a D-column latent: the instances are 2, 4, 8 and 13 k-steps
-// (D = 32, 64, 128, 208); any other width up to 208 runs the next larger one on zero-padded columns (zeros add nothing to a
-// dot product, so the screened values and their error bound are those of the unpadded row); 0 = no instance.
+// Wide instances (S > 13: latent widths 209 ... 512) run screen_wide_kernel (lipvq_screen.hip), whose fp32 chain is up to
+// 3 x 32 MFMAs long: their error bound is re-derived there ("Error bound") and is 2^-16.
+#define LIPVQ_SCREEN_GAMMA_WIDE 1.52587890625e-05f   /* 2^-16 */
+#define LQ_SCREEN_NARROW_MAX_S 13
+
+// k-steps (of 16 columns) of the screening instance that serves a D-column latent: the instances are 2, 4, 8, 13, 16, 24 and 32
+// k-steps (D = 32, 64, 128, 208, 256, 384, 512); any other width up to 512 runs the next larger one on zero-padded columns (zeros
+// add nothing to a dot product, so the screened values and their error bound are those of the unpadded row); 0 = no instance.
 __host__ __device__ static inline int lq_screen_S(int D) {
     const int s = (D + 15) / 16;
-    return D <= 0 ? 0 : s <= 2 ? 2 : s <= 4 ? 4 : s <= 8 ? 8 : s <= 13 ? 13 : 0;
+    return D <= 0 ? 0 : s <= 2 ? 2 : s <= 4 ? 4 : s <= 8 ? 8 : s <= 13 ? 13 : s <= 16 ? 16 : s <= 24 ? 24 : s <= 32 ? 32 : 0;
+}
+// the gamma the screened routes certify with (lipvq_screen.hip, "Error bound")
+__host__ __device__ static inline float lq_screen_gamma(int D) {
+    return lq_screen_S(D) > LQ_SCREEN_NARROW_MAX_S ? LIPVQ_SCREEN_GAMMA_WIDE : LIPVQ_SCREEN_GAMMA;
 }
 
 __host__ __device__ static inline PrepLayout prep_layout(int K, int D) {

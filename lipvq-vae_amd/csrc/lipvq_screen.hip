@@ -23,6 +23,8 @@
 // operand magnitudes from 1e-6 to 1e6 (scripts/measure_bound.py, measure_bound_scales.py): 2^-22.  gamma
 // (LIPVQ_SCREEN_GAMMA) is 2^-18: 5x the analytic split bound, 16x the largest error observed;
 // tests/test_gpu_screen.py (test_error_bound_holds, test_any_magnitude) assert a >= 4x margin on every run.
+// That is the bound of the instances up to S = 13 (D <= 208); the wide instances' longer chains have their own (2^-16, derived
+// at screen_wide_kernel below; tests/test_gpu_wide_latent.py).
 #include <stdlib.h>
 #include <string.h>
 
@@ -317,6 +319,221 @@ __global__ __launch_bounds__(SCREEN_WAVES * 64) void screen_kernel(
     if (usage) lq_usage_add(usage, my_k, h == 0 && row < N && certified);
     if (zq) lq_screen_gather(cb, zq, my_k, certified, row0, N, D, lane);
     lq_ws_publish(amb_count);                        // the grid's last workgroup publishes the number of listed rows (lipvq_screen.h)
+}
+
+// ------------------------------------------------------------------------------------------
+// wide screening kernel: S = 16, 24, 32 k-steps (latent widths 209 ... 512), three-product chain
+// ------------------------------------------------------------------------------------------
+// screen_kernel keeps a row group's whole A operand in registers: ah/al[S] take 8 S VGPRs (256 at S = 32), which does not fit
+// beside the accumulators and the bookkeeping.  Here the code sweep runs in COLUMN CHUNKS: a wave keeps the accumulators of T
+// column tiles (T x 32 codes) across the S / CH chunks of CH k-steps each, and holds the A fragments of one chunk only (8 CH
+// VGPRs), rebuilt from its rows (global memory, L2) for every chunk of every tile group.  The codebook goes through a double
+// buffer of LDS stages -- stage = chunk c of the T tiles of group g, plus their |e'|^2 -- loaded into registers one stage ahead
+// (the loads of stage i+1 and of the rows' next chunk are in flight while stage i's MFMAs run) and written behind one barrier per
+// stage.  The values, the bookkeeping, the certificate, the short lists and the gather are screen_kernel's (lq_track_part,
+// lq_screen_decide, lq_screen_emit, lq_screen_gather), with the chain's order per tile unchanged: k-step by k-step, hi*hi, lo*hi,
+// hi*lo.
+//
+// Error bound for these chains (gamma = LIPVQ_SCREEN_GAMMA_WIDE = 2^-16).  In scaled units (Z = row, E = -2 e' code, both after
+// their power-of-two scales) the chain computes sum_s (Zh.Eh + Zl.Eh + Zh.El) over 3 S MFMAs.  (a) The split: the dropped
+// Zl.El term and the fp16 roundings leave at most 3 x 2^-22 sum|Z E| <= 3 x 2^-22 |Z||E|.  (b) The fp32 accumulation: products
+// of fp16 numbers are exact in fp32 and each MFMA rounds its output once; every partial sum is bounded by sum|Z E| <= |Z||E|,
+// so 3 S roundings add at most 3 S x 2^-24 |Z||E|.  (c) |e'|^2 rounded to fp32: 2^-24 E2max.  With |Z||E| <= 2 |z'| Emax
+// (unscaled): |d~ - d| <= (3 x 2^-22 + 3 S x 2^-24) (E2max + 2 |z'| Emax) = 0.94 x 2^-18 at S = 16, 1.31 x 2^-18 at S = 24,
+// 1.69 x 2^-18 at S = 32 -- above the narrow instances' 2^-18 from S = 24 on.  2^-16 is 2.4x that bound at S = 32 and 4.3x
+// at S = 16; tests/test_gpu_wide_latent.py measures the error against float64 and asserts a >= 4x margin to 2^-16.
+template <int S>
+struct WideScreen {
+    static constexpr int T = 4;                         // column tiles per group: 4 x 16 accumulator registers
+    static constexpr int CH = 2;                        // k-steps per chunk: 16 VGPRs of A fragments (4: 256 VGPRs and spills)
+    static constexpr int NCH = S / CH;
+    static constexpr int NT = SCREEN_WAVES * 64;
+    static constexpr int FRAG = T * CH * 2048;          // stage: T tiles x CH k-steps x {hi, lo} x 1 KiB ...
+    static constexpr int STAGE = FRAG + T * 128;        // ... then the T tiles' |e'|^2 (32 floats each)
+    static constexpr int PF = FRAG / (NT * 16);         // 16-byte fragment pieces per thread and stage
+    // the two stages, or the decision scratch that reuses them after the sweep, whichever is larger; then the column means
+    static constexpr int RING = (2 * STAGE > SCREEN_WAVES * LQ_DECIDE_BYTES) ? 2 * STAGE : SCREEN_WAVES * LQ_DECIDE_BYTES;
+    static_assert(S % CH == 0 && PF * NT * 16 == FRAG && T * 8 <= NT && RING % 16 == 0, "whole chunks, whole pieces");
+};
+template <int S>
+static size_t wide_lds_bytes() { return (size_t)WideScreen<S>::RING + sizeof(float) * 16 * (size_t)S; }
+
+template <int S, bool DBG>
+__global__ __launch_bounds__(SCREEN_WAVES * 64) void screen_wide_kernel(
+    const float* __restrict__ z, const unsigned char* __restrict__ prep, const float* __restrict__ cb,
+    int64_t* __restrict__ idx, float* __restrict__ zq, unsigned long long* __restrict__ usage,
+    int* __restrict__ amb_list, int* __restrict__ amb_count, float* __restrict__ dbg, int64_t N, int K, int D,
+    float gamma) {
+    using W = WideScreen<S>;
+    constexpr int T = W::T, CH = W::CH, NCH = W::NCH, NT = W::NT, PF = W::PF;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const PrepLayout L = prep_layout(K, D);
+    const unsigned* hdr = reinterpret_cast<const unsigned*>(prep);
+    const float* mu = reinterpret_cast<const float*>(prep + L.o_mu);
+    const unsigned char* tiles = prep + L.o_tiles;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ln = lane & 31, h = lane >> 5;
+    const int64_t row0 = ((int64_t)blockIdx.x * SCREEN_WAVES + wave) * 32;
+    const int64_t row = row0 + ln;
+    const int64_t rowc = row < N ? row : N - 1;
+    lq_ws_begin(amb_count);
+
+    float* s_mu = reinterpret_cast<float*>(lds + (size_t)W::RING);          // the column means (L.Dpad = 16 S of them, zero past D)
+    for (int d = tid; d < 16 * S; d += NT) s_mu[d] = mu[d];
+    __syncthreads();
+
+    // the row's |z'|^2 and scale: screen_kernel's numbers (slot (h, j) of step s = feature 16 s + 2 j + h)
+    const float* zr = z + (size_t)rowc * D;
+    float n2 = 0.0f, amax = 0.0f;
+    // (loads of 4 k-steps requested together, then selects: written as `(d < D) ? zr[d] - mu[d] : 0`, hipcc branched around every
+    // element and waited for each load on its own -- a serial L2 round trip per element of the row)
+#pragma unroll 4
+    for (int s = 0; s < S; ++s) {
+        float x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int d = 16 * s + 2 * j + h;
+            x[j] = zr[d < D ? d : D - 1];
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int d = 16 * s + 2 * j + h;
+            float t = x[j] - s_mu[d];
+            asm("" : "+v"(t));
+            const float v = (d < D) ? t : 0.0f;
+            n2 = lq_fma(v, v, n2);
+            amax = fmaxf(amax, lq_abs(v));
+        }
+    }
+    n2 += __shfl_xor(n2, 32, 64);
+    amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+    const float fz = lq_pow2f(lq_scale_exp(amax));
+    const float fown = lq_pow2f(lq_scale_exp(amax) + (int)hdr[3]);
+    float frow[16], znr[16];
+    lq_row_factors(fown, lane, frow);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) znr[r] = 0.0f;                // (three-product chain: no per-row residual term)
+    float m1[16], m2[16];
+    int k1[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { m1[r] = INFINITY; m2[r] = INFINITY; k1[r] = 0; }
+
+    // Stage `it` = chunk c of the T tiles of group g.  Thread tid owns the 16-byte pieces tid and tid + NT of the fragments (PF = 2)
+    // and, for tid < 8 T, one piece of the |e'|^2 rows.  Plain scalar variables, loaded unconditionally (the last iteration reloads
+    // its own stage): held in VGPRs across the stage's MFMAs (an array passed to a lambda by reference was left in scratch).
+    static_assert(PF == 2, "two fragment pieces per thread");
+    const int tq0 = tid / (CH * 128), tw0 = tid - tq0 * (CH * 128);
+    const int tq1 = (tid + NT) / (CH * 128), tw1 = (tid + NT) - tq1 * (CH * 128);
+    const int te = (tid < T * 8) ? tid : 0;
+    auto piece = [&](int it, int tq, int tw) {
+        const int g = it / NCH, c = it - g * NCH;
+        return *reinterpret_cast<const float4*>(tiles + (size_t)(g * T + tq) * L.tile_bytes + (size_t)c * CH * 2048 + (size_t)tw * 16);
+    };
+    auto e2piece = [&](int it) {
+        const int g = it / NCH;
+        return *reinterpret_cast<const float4*>(tiles + (size_t)(g * T + te / 8) * L.tile_bytes + (size_t)S * 2048 + (te & 7) * 16);
+    };
+    const int total = (L.ntiles / T) * NCH;                   // ntiles is a multiple of 8
+    float4 pf0 = piece(0, tq0, tw0), pf1 = piece(0, tq1, tw1), pe = e2piece(0);
+    float zv[CH][8];
+#pragma unroll
+    for (int s = 0; s < CH; ++s)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int d = 16 * s + 2 * j + h;
+            zv[s][j] = zr[d < D ? d : D - 1];          // (raw; columns past D are masked where it is used)
+        }
+    {
+        float4* dst = reinterpret_cast<float4*>(lds);
+        dst[tid] = pf0;
+        dst[tid + NT] = pf1;
+        if (tid < T * 8) dst[W::FRAG / 16 + tid] = pe;
+    }
+    __syncthreads();
+    f32x16 acc[T];
+    for (int it = 0; it < total; ++it) {
+        const int g = it / NCH, c = it - g * NCH;
+        const unsigned char* sb = lds + (size_t)(it & 1) * W::STAGE;
+        f16x8 ah[CH], al[CH];
+#pragma unroll
+        for (int s = 0; s < CH; ++s)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int d = 16 * (c * CH + s) + 2 * j + h;
+                float t = zv[s][j] - s_mu[d];
+                asm("" : "+v"(t));                                   // (a select, not a branch around the LDS read)
+                const float v = ((d < D) ? t : 0.0f) * fz;           // the same fp32 value as screen_kernel's
+                const _Float16 vh = (_Float16)v;
+                ah[s][j] = vh;
+                al[s][j] = (_Float16)(v - (float)vh);
+            }
+        {
+            // the next stage's pieces and the rows' next chunk: issued here, consumed after this stage's MFMAs
+            const int nx = (it + 1 < total) ? it + 1 : it;
+            pf0 = piece(nx, tq0, tw0);
+            pf1 = piece(nx, tq1, tw1);
+            pe = e2piece(nx);
+            const int c1 = (c + 1 == NCH) ? 0 : c + 1;
+#pragma unroll
+            for (int s = 0; s < CH; ++s)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int d = 16 * (c1 * CH + s) + 2 * j + h;
+                    zv[s][j] = zr[d < D ? d : D - 1];          // (raw; columns past D are masked where it is used)
+                }
+        }
+        if (c == 0) {
+#pragma unroll
+            for (int t = 0; t < T; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+        }
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int s = 0; s < CH; ++s) {
+                const f16x8 bh = *reinterpret_cast<const f16x8*>(sb + (size_t)t * CH * 2048 + ((size_t)(2 * s) * 64 + lane) * 16);
+                const f16x8 bl = *reinterpret_cast<const f16x8*>(sb + (size_t)t * CH * 2048 + ((size_t)(2 * s + 1) * 64 + lane) * 16);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bh, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s], bh, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bl, acc[t], 0, 0, 0);
+            }
+        if (c == NCH - 1) {
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const float e2 = reinterpret_cast<const float*>(sb + W::FRAG + t * 128)[ln];
+                const int code = (g * T + t) * 32 + ln;
+                if (DBG && dbg && code < L.Kpad) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int64_t rr = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                        if (rr < N) dbg[(size_t)rr * L.Kpad + code] = lq_fma(e2, frow[r], acc[t][r]) / frow[r];
+                    }
+                }
+                lq_track_part<0, 16, false, false>(acc[t], e2, 0.0f, frow, znr, code, 0xffffffffu, m1, m2, k1);
+            }
+        }
+        if (it + 1 < total) {
+            // buffer (it + 1) & 1 was last read in iteration it - 1, which every wave left before the previous barrier
+            float4* dst = reinterpret_cast<float4*>(lds + (size_t)((it + 1) & 1) * W::STAGE);
+            dst[tid] = pf0;
+            dst[tid + NT] = pf1;
+            if (tid < T * 8) dst[W::FRAG / 16 + tid] = pe;
+            __syncthreads();
+        }
+    }
+    __syncthreads();                                  // every wave has left the stages: they become the decision scratch
+    int my_k;
+    unsigned char* scratch = lds + (size_t)wave * LQ_DECIDE_BYTES;
+    LqDecision dec;
+    const bool certified = lq_screen_decide<false, false>(m1, m2, k1, scratch, hdr, n2, fown, gamma, K, D, lane, my_k, dec, 0.0f,
+                                                          0xffffffffu, 0.0f, tiles, L.tile_bytes, S * 2048);
+    lq_screen_emit<false>(dec, certified, !DBG, my_k, row, row < N, amb_count, amb_list, N, K, lane, 0xffffffffu, scratch);
+    if (h == 0 && row < N && certified) idx[row] = (int64_t)my_k;
+    if (usage) lq_usage_add(usage, my_k, h == 0 && row < N && certified);
+    if (zq) lq_screen_gather(cb, zq, my_k, certified, row0, N, D, lane);
+    lq_ws_publish(amb_count);
 }
 
 // Exact scan of codes [kb, ke) for one row held in registers: torch's 8-accumulator order, sqrt comparison, first minimum.
@@ -636,11 +853,14 @@ __global__ __launch_bounds__(256) void nearest_lists_kernel(
 // Any latent width (no compile-time D, rows not necessarily 16-byte aligned): the same decision for a listed row -- short lists,
 // lane masks, or a full scan -- with both operands read straight from global memory (L2) through lq_sqdist8 / lq_sqdist32, i.e.
 // torch's remainder handling included (lipvq_math.h).  The route of widths outside {32, 64, 128, 208}: a few thousand rows at most.
-template <int DIST>
+// DT: the wide screening instances' own widths (256, 384, 512) at compile time -- the distance loop unrolls and its loads are
+// requested in batches instead of one round trip per element -- or 0 for any width.
+template <int DIST, int DT = 0>
 __global__ __launch_bounds__(256) void nearest_rows_any_kernel(
     const float* __restrict__ z, const float* __restrict__ cb, int64_t* __restrict__ idx, float* __restrict__ zq,
     unsigned long long* __restrict__ usage, const int* __restrict__ row_list, const int* __restrict__ row_count,
-    int K, int D, int z_by_slot, int count_direct, const int* __restrict__ cand_list, size_t cand_cap) {
+    int K, int D_rt, int z_by_slot, int count_direct, const int* __restrict__ cand_list, size_t cand_cap) {
+    const int D = DT ? DT : D_rt;
     constexpr int RB = 4, SL = 64;
     __shared__ float s_v[RB][SL];
     __shared__ int s_k[RB][SL];
@@ -803,6 +1023,15 @@ __global__ __launch_bounds__(256) void nearest_small_kernel(const float* __restr
         row = row < count ? row : count - 1;
         zv = reinterpret_cast<const float4*>(z + (size_t)row * D)[q];
     }
+    // widths above 256: the 4 rows are more 16-byte pieces than threads -- a second one per thread (at most 512 pieces: D <= 512)
+    float4 zv2 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool two = (DT == 0 || DT > 256) && tid + 256 < NSM_ROWS * D4;
+    if (two) {
+        const int r = (tid + 256) / D4, q = (tid + 256) - r * D4;
+        int row = rg * NSM_ROWS + r;
+        row = row < count ? row : count - 1;
+        zv2 = reinterpret_cast<const float4*>(z + (size_t)row * D)[q];
+    }
     if constexpr (DT != 0) {
         constexpr int PIECES = NSM_CODES * (DT / 4), NIT = (PIECES + 255) / 256;
         float4 v[NIT];
@@ -832,6 +1061,7 @@ __global__ __launch_bounds__(256) void nearest_small_kernel(const float* __restr
         }
     }
     if (tid < NSM_ROWS * D4) reinterpret_cast<float4*>(s_z)[tid] = zv;
+    if (two) reinterpret_cast<float4*>(s_z)[tid + 256] = zv2;
     __syncthreads();
     const int row = rg * NSM_ROWS + w;
     const bool valid = row < count;
@@ -900,8 +1130,12 @@ __global__ __launch_bounds__(256) void nearest_small_kernel(const float* __restr
             reinterpret_cast<float4*>(zq + (size_t)row * D)[q] = reinterpret_cast<const float4*>(cb + (size_t)bk * D)[q];
 }
 
+// widths up to 240 fit a 64 KiB image; 244 ... 512 take a larger one (up to 137 KiB at D = 512: one workgroup per CU, still
+// RG x CG workgroups over the chip -- 20 x 16 at N = 80, K = 1024)
+#define NSM_MAX_D 512
 extern "C" int lipvq_nearest_small_supported(int64_t N, int K, int D) {
-    return N >= 1 && N <= NSM_MAX_ROWS && K >= 1 && K <= 65536 && D >= 4 && (D & 3) == 0 && nsm_lds_bytes(D) <= 64 * 1024 ? 1 : 0;
+    return N >= 1 && N <= NSM_MAX_ROWS && K >= 1 && K <= 65536 && D >= 4 && (D & 3) == 0 &&
+           (nsm_lds_bytes(D) <= 64 * 1024 || D <= NSM_MAX_D) ? 1 : 0;
 }
 
 extern "C" size_t lipvq_nearest_small_workspace_bytes(int64_t N, int K) {
@@ -926,19 +1160,31 @@ extern "C" int lipvq_nearest_small_f32(const float* z, const float* codebook, in
     int* counters = (int*)workspace;
     unsigned long long* keys = (unsigned long long*)((unsigned char*)workspace + nsm_counter_bytes(N));
     const size_t lds = nsm_lds_bytes(D);
-    auto go = [&](auto kfn) {
+    int rc = LIPVQ_OK;
+    // the reservation belongs to each kernel instance: one slot per (rule, compile-time width) -- every instance has the same
+    // function-pointer type, so a static inside `go` would be shared by all of them
+    static LqLdsReserve reserved[2][8];
+    auto go = [&](auto kfn, int slot) {
+        if (lds > 64 * 1024) {
+            rc = lipvq_reserve_lds(reserved[dist == LIPVQ_DIST_NORM ? 0 : 1][slot], (const void*)kfn, lds, "nearest_small");
+            if (rc) return;
+        }
         hipLaunchKernelGGL(kfn, dim3((unsigned)(RGn * CG)), dim3(256), lds, (hipStream_t)stream, z, codebook, idx, zq,
                            (unsigned long long*)usage, (int)N, K, D, CG, counters, keys);
     };
-#define LQ_NSM(DT_) do { if (dist == LIPVQ_DIST_NORM) go(nearest_small_kernel<LIPVQ_DIST_NORM, DT_>); else go(nearest_small_kernel<LIPVQ_DIST_SQSUM, DT_>); } while (0)
+#define LQ_NSM(DT_, SLOT_) do { if (dist == LIPVQ_DIST_NORM) go(nearest_small_kernel<LIPVQ_DIST_NORM, DT_>, SLOT_); \
+                                else go(nearest_small_kernel<LIPVQ_DIST_SQSUM, DT_>, SLOT_); } while (0)
     switch (D) {
-        case 32: LQ_NSM(32); break;
-        case 64: LQ_NSM(64); break;
-        case 128: LQ_NSM(128); break;
-        case 208: LQ_NSM(208); break;
-        default: LQ_NSM(0); break;
+        case 32: LQ_NSM(32, 0); break;
+        case 64: LQ_NSM(64, 1); break;
+        case 128: LQ_NSM(128, 2); break;
+        case 208: LQ_NSM(208, 3); break;
+        case 256: LQ_NSM(256, 4); break;
+        case 512: LQ_NSM(512, 5); break;
+        default: LQ_NSM(0, 6); break;
     }
 #undef LQ_NSM
+    if (rc) return rc;
     return check_launch("nearest_small");
 }
 
@@ -1143,7 +1389,8 @@ int lq_screen_coarse(int S, int K) {
 // one-product screen for this shape right now (callers that budget the exact stage -- the host-side screen monitor, the bench's
 // roofline -- ask; results do not depend on it)
 extern "C" int lipvq_screen_is_coarse(int K, int D) {
-    return (K > 0 && lq_screen_S(D)) ? lq_screen_coarse(lq_screen_S(D), K) : 0;
+    const int S = lq_screen_S(D);
+    return (K > 0 && S && S <= LQ_SCREEN_NARROW_MAX_S) ? lq_screen_coarse(S, K) : 0;     // (the wide instances are three-product only)
 }
 
 template <int S>
@@ -1166,6 +1413,24 @@ static int launch_screen(const float* z, const unsigned char* prep, const float*
     hipLaunchKernelGGL(kfn, dim3(blocks), dim3(SCREEN_WAVES * 64), lds, st, z, prep, cb, idx, zq,
                        (unsigned long long*)usage, amb_list, amb_count, dbg, N, K, D, gamma);
     return check_launch("screen");
+}
+
+template <int S>
+static int launch_screen_wide(const float* z, const unsigned char* prep, const float* cb, int64_t* idx, float* zq,
+                              int64_t* usage, int* amb_list, int* amb_count, float* dbg, int64_t N, int K, int D,
+                              float gamma, hipStream_t st) {
+    // (the debug hook's negative gamma asks for the one-product chain, which these widths do not have)
+    if (gamma < 0.0f) return fail(LIPVQ_EUNSUPPORTED, "screen_debug: D=%d has no one-product screen", D);
+    const size_t lds = wide_lds_bytes<S>();
+    const int64_t rows_per_block = SCREEN_WAVES * 32;
+    unsigned blocks = (unsigned)((N + rows_per_block - 1) / rows_per_block);
+    auto kfn = dbg ? screen_wide_kernel<S, true> : screen_wide_kernel<S, false>;
+    static LqLdsReserve reserved[2];
+    if (lds > 64 * 1024)
+        if (int rc = lipvq_reserve_lds(reserved[dbg ? 1 : 0], (const void*)kfn, lds, "screen_wide")) return rc;
+    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(SCREEN_WAVES * 64), lds, st, z, prep, cb, idx, zq,
+                       (unsigned long long*)usage, amb_list, amb_count, dbg, N, K, D, gamma);
+    return check_launch("screen_wide");
 }
 
 template <int DCH, int DIST = LIPVQ_DIST_NORM>
@@ -1211,7 +1476,9 @@ static int launch_rows_any(const float* z, int z_by_slot, const float* cb, int64
     if (D <= 0) return fail(LIPVQ_EINVAL, "nearest_rows: D=%d", D);
     int64_t blocks = (N + 3) / 4;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((nearest_rows_any_kernel<DIST>), dim3((unsigned)blocks), dim3(256), 0, st, z, cb, idx, zq,
+    auto kfn = D == 256 ? nearest_rows_any_kernel<DIST, 256> : D == 384 ? nearest_rows_any_kernel<DIST, 384>
+             : D == 512 ? nearest_rows_any_kernel<DIST, 512> : nearest_rows_any_kernel<DIST, 0>;
+    hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), 0, st, z, cb, idx, zq,
                        (unsigned long long*)usage, amb_list, amb_list ? lq_ws_listed(amb_count) : nullptr, K, D, z_by_slot,
                        amb_list ? 0 : (int)N, amb_list ? amb_list + 2 * lq_list_ints(N) : nullptr,
                        amb_list ? lq_cand_cap(N) : (size_t)0);
@@ -1253,14 +1520,17 @@ static int screened_impl(const float* z, const float* cb, const void* prep, int6
         case 4: rc = launch_screen<4>(z, p, cb, idx, zq, usage, amb_list, amb_count, dbg, N, K, D, gamma, st); break;
         case 8: rc = launch_screen<8>(z, p, cb, idx, zq, usage, amb_list, amb_count, dbg, N, K, D, gamma, st); break;
         case 13: rc = launch_screen<13>(z, p, cb, idx, zq, usage, amb_list, amb_count, dbg, N, K, D, gamma, st); break;
-        default: return fail(LIPVQ_EUNSUPPORTED, "nearest_screened: D=%d has no screening instance (1 ... 208)", D);
+        case 16: rc = launch_screen_wide<16>(z, p, cb, idx, zq, usage, amb_list, amb_count, dbg, N, K, D, gamma, st); break;
+        case 24: rc = launch_screen_wide<24>(z, p, cb, idx, zq, usage, amb_list, amb_count, dbg, N, K, D, gamma, st); break;
+        case 32: rc = launch_screen_wide<32>(z, p, cb, idx, zq, usage, amb_list, amb_count, dbg, N, K, D, gamma, st); break;
+        default: return fail(LIPVQ_EUNSUPPORTED, "nearest_screened: D=%d has no screening instance (1 ... 512)", D);
     }
     if (rc) return rc;
     return lipvq_launch_rows(z, 0, cb, idx, zq, usage, amb_list, amb_count, N, K, D, st, dist);
 }
 
 extern "C" int lipvq_nearest_screened_supported(int K, int D) {
-    return (K > 0 && lq_screen_S(D) != 0) ? 1 : 0;            // any width 1 ... 208
+    return (K > 0 && lq_screen_S(D) != 0) ? 1 : 0;            // any width 1 ... 512
 }
 
 // Exact decision of EVERY row by the re-scoring kernel (4 rows x 64 code slices per workgroup): no codebook
@@ -1288,7 +1558,7 @@ extern "C" int lipvq_nearest_screened_f32(const float* z, const float* codebook,
     if (N > 2147483647LL) return fail(LIPVQ_EUNSUPPORTED, "nearest_screened: N too large");
     if (!(D & 3) && (((uintptr_t)z | (uintptr_t)codebook | (uintptr_t)zq) & 15) != 0)       // (the kernels take float4 paths iff D % 4 == 0)
         return fail(LIPVQ_EINVAL, "nearest_screened: z, codebook and zq must be 16-byte aligned");
-    return screened_impl(z, codebook, prep, idx, zq, usage, workspace, nullptr, N, K, D, LIPVQ_SCREEN_GAMMA,
+    return screened_impl(z, codebook, prep, idx, zq, usage, workspace, nullptr, N, K, D, lq_screen_gamma(D),
                          (hipStream_t)stream);
 }
 
@@ -1302,7 +1572,7 @@ extern "C" int lipvq_vq_nearest_screened_f32(const float* z, const float* codebo
     if (N > 2147483647LL) return fail(LIPVQ_EUNSUPPORTED, "vq_nearest_screened: N too large");
     if (!(D & 3) && (((uintptr_t)z | (uintptr_t)codebook | (uintptr_t)zq) & 15) != 0)
         return fail(LIPVQ_EINVAL, "vq_nearest_screened: z, codebook and zq must be 16-byte aligned");
-    return screened_impl(z, codebook, prep, idx, zq, usage, workspace, nullptr, N, K, D, LIPVQ_SCREEN_GAMMA,
+    return screened_impl(z, codebook, prep, idx, zq, usage, workspace, nullptr, N, K, D, lq_screen_gamma(D),
                          (hipStream_t)stream, LIPVQ_DIST_SQSUM);
 }
 

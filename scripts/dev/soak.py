@@ -1,5 +1,5 @@
 """Dev tool (GPU): randomized soak of the quantizer routes against the all-pairs exact kernel (no screen, no lists):
-fused tokenize, stand-alone screened nearest, exact rows -- random shapes (round 3: any latent width 1 ... 208), seeds and
+fused tokenize, stand-alone screened nearest, exact rows -- random shapes (any latent width 1 ... 512), seeds and
 adversarial rows (duplicated codes, bisector near-ties incl. codes congruent mod 32, rows sitting on codes), both distance
 rules, and per case a random screen (three-product / one-product) and fused-kernel shape.  python scripts/dev/soak.py [seconds]"""
 import os, sys, time
@@ -17,8 +17,10 @@ rng = np.random.default_rng(12345)
 t0, cases, rows, unc = time.time(), 0, 0, 0
 last_note = t0
 while time.time() - t0 < budget:
-    D = int(rng.choice([32, 64, 128, 208])) if rng.random() < 0.6 else int(rng.integers(1, 209))
-    K = int(rng.choice([37, 256, 1000, 1024, 2048, 8192])) if D <= 128 else int(rng.choice([128, 1024, 4096]))
+    D = (int(rng.choice([32, 64, 128, 208])) if rng.random() < 0.5 else int(rng.integers(1, 209)) if rng.random() < 0.5
+         else int(rng.choice([256, 384, 512])) if rng.random() < 0.5 else int(rng.integers(209, 513)))
+    K = (int(rng.choice([37, 256, 1000, 1024, 2048, 8192])) if D <= 128 else int(rng.choice([128, 1024, 4096])) if D <= 208
+         else int(rng.choice([37, 128, 1024])))
     ops.set_option("screen_mode", str(rng.choice(["fine", "coarse"])))              # read per launch by the library
     shape = rng.choice(["default", "default", "w8rg1", "w8rg2", "w4rg2", "w4rg1"])          # default: the library's size rule
     ops.set_option("tok_shape", None if shape == "default" else str(shape))
@@ -29,7 +31,8 @@ while time.time() - t0 < budget:
     ops.set_option("tok_ze_ring", None if rng.random() < 0.7 else "0")                       # the z_e scratch as a ring (default) / in full
     _ScreenMonitor.ENABLED = False
     A = int(rng.choice([3, 7, 12]))
-    N = int(rng.choice([1, 33, 257, 2049, 4100, 30000, 70001, 100001, 300000]))
+    N = int(rng.choice([1, 33, 257, 2049, 4100, 30000, 70001, 100001, 300000] if D <= 208 else [1, 33, 257, 2049, 4100, 30000]))
+    # (wide latents: the reference below is the all-pairs kernel, one lane per row straight from L2 -- smaller batches)
     torch.manual_seed(int(rng.integers(1 << 30)))
     model = LLFQVAE_V4(A, D, num_codes=K).cuda()
     trained_like_(model, A, seed=int(rng.integers(1 << 30)))
