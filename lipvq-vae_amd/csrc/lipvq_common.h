@@ -57,6 +57,19 @@ __device__ __forceinline__ void lq_usage_add(unsigned long long* __restrict__ us
     }
     if (active) atomicAdd(&usage[k], 1ull);
 }
+
+// torch.argmin's first minimum over (value, code) pairs: (v, k) takes (ov, ok) if ov is smaller, or equal with a lower code.
+// LQ_WAVE_MIN applies it across the lanes of a wave that differ in lane bits OFF0 and up (OFF0 = 1: all 64 lanes; 4 or 8: per
+// lane class mod OFF0); every lane ends with its class's result.  Macros, not functions: hipcc simplifies an inline function's
+// body before it inlines it, and the fused tokenize kernel (lq_lists_row) then compiled to different code; a macro expands to
+// the statements the kernels had.  Arguments are evaluated more than once: pass variables.
+#define LQ_TAKE_MIN(v, k, ov, ok) { if ((ov) < (v) || ((ov) == (v) && (ok) < (k))) { (v) = (ov); (k) = (ok); } }
+#define LQ_WAVE_MIN(v, k, OFF0)                                                                                   \
+    _Pragma("unroll") for (int lq_off = (OFF0); lq_off < 64; lq_off <<= 1) {                                      \
+        const float lq_ov = __shfl_xor(v, lq_off, 64);                                                            \
+        const int lq_ok = __shfl_xor(k, lq_off, 64);                                                              \
+        LQ_TAKE_MIN(v, k, lq_ov, lq_ok);                                                                          \
+    }
 #endif
 
 // measurement / test knobs: ONE place reads them (lipvq_misc.hip)

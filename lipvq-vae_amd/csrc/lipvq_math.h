@@ -404,6 +404,70 @@ LQ_HD float lq_sqdist32(const float* z, const float* c, int D) {
     return s;
 }
 
+#if defined(__HIPCC__) || defined(__HIP__)
+/* ---- the two orders on the device, for D = 8 DCH: a row held in registers against a code row read as float4 pairs ---------- */
+/* lq_sqdist8's eight accumulators.  add() takes one 8-float chunk of differences, chunk() the row's chunk i (a caller may test
+ * fold() between two chunks: each accumulator only grows and the fold is monotone in each, so a partial fold bounds the full one
+ * from below), fold() adds the lanes left to right. */
+struct LqNorm8 {
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f;
+    __device__ __forceinline__ void add(float d0, float d1, float d2, float d3, float d4, float d5, float d6, float d7) {
+        a0 = lq_fma(d0, d0, a0); a1 = lq_fma(d1, d1, a1);
+        a2 = lq_fma(d2, d2, a2); a3 = lq_fma(d3, d3, a3);
+        a4 = lq_fma(d4, d4, a4); a5 = lq_fma(d5, d5, a5);
+        a6 = lq_fma(d6, d6, a6); a7 = lq_fma(d7, d7, a7);
+    }
+    template <int D>
+    __device__ __forceinline__ void chunk(const float (&zr)[D], const float4* __restrict__ c4, int i) {
+        const float4 lo = c4[2 * i], hi = c4[2 * i + 1];
+        add(zr[8 * i + 0] - lo.x, zr[8 * i + 1] - lo.y, zr[8 * i + 2] - lo.z, zr[8 * i + 3] - lo.w,
+            zr[8 * i + 4] - hi.x, zr[8 * i + 5] - hi.y, zr[8 * i + 6] - hi.z, zr[8 * i + 7] - hi.w);
+    }
+    __device__ __forceinline__ float fold() const { return ((((((a0 + a1) + a2) + a3) + a4) + a5) + a6) + a7; }
+};
+
+/* lq_sqdist8 of the whole row (its square: no root) */
+template <int DCH>
+__device__ __forceinline__ float lq_norm8_row(const float (&zr)[DCH * 8], const float4* __restrict__ c4) {
+    LqNorm8 n;
+#pragma unroll
+    for (int i = 0; i < DCH; ++i) n.chunk(zr, c4, i);
+    return n.fold();
+}
+
+/* lq_sqdist32 (the plain VQVAE's distance) for D = 8 DCH < 512 (rounded squares; 8-vector i -> accumulator i mod 4 while whole groups of four remain,
+ * left-overs -> accumulator 0; accumulators 1..3 added to 0; lanes left to right) */
+template <int DCH>
+__device__ __forceinline__ float lq_sq32_row(const float (&zr)[DCH * 8], const float4* __restrict__ c4) {
+    static_assert(DCH < 64, "the cascade of torch's sum starts at D = 512");
+    float acc[4][8];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int l = 0; l < 8; ++l) acc[q][l] = 0.f;
+#pragma unroll
+    for (int i = 0; i < DCH; ++i) {
+        const int q = (i < (DCH / 4) * 4) ? (i & 3) : 0;
+        const float4 lo = c4[2 * i], hi = c4[2 * i + 1];
+        const float d0 = zr[8 * i + 0] - lo.x, d1 = zr[8 * i + 1] - lo.y;
+        const float d2 = zr[8 * i + 2] - lo.z, d3 = zr[8 * i + 3] - lo.w;
+        const float d4 = zr[8 * i + 4] - hi.x, d5 = zr[8 * i + 5] - hi.y;
+        const float d6 = zr[8 * i + 6] - hi.z, d7 = zr[8 * i + 7] - hi.w;
+        acc[q][0] = acc[q][0] + d0 * d0; acc[q][1] = acc[q][1] + d1 * d1;
+        acc[q][2] = acc[q][2] + d2 * d2; acc[q][3] = acc[q][3] + d3 * d3;
+        acc[q][4] = acc[q][4] + d4 * d4; acc[q][5] = acc[q][5] + d5 * d5;
+        acc[q][6] = acc[q][6] + d6 * d6; acc[q][7] = acc[q][7] + d7 * d7;
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int l = 0; l < 8; ++l) {
+        const float v = ((acc[0][l] + acc[1][l]) + acc[2][l]) + acc[3][l];
+        s = (l == 0) ? v : s + v;
+    }
+    return s;
+}
+#endif
+
 /* ---- AdaptiveBinActionEmbedding (reference robomimic/models/bin_action/backbone.py = "bin") -------------
  * bin:47-49 torch.linspace(min, max, steps) in fp32 as torch's CPU kernel rounds it (probed for 2..257 steps):
  * step = (end - start) / (steps - 1);  element i = fma(step, i, start) below the midpoint, fma(-step, steps-1-i, end)

@@ -47,50 +47,13 @@ __global__ __launch_bounds__(256) void nearest_direct_kernel(
             const float4* c4 = reinterpret_cast<const float4*>(lds + (size_t)kk * D);
             float s;
             if (DIST == LIPVQ_DIST_NORM) {
-                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f;
-#pragma unroll
-                for (int i = 0; i < DCH; ++i) {
-                    const float4 lo = c4[2 * i], hi = c4[2 * i + 1];
-                    const float d0 = zr[8 * i + 0] - lo.x, d1 = zr[8 * i + 1] - lo.y;
-                    const float d2 = zr[8 * i + 2] - lo.z, d3 = zr[8 * i + 3] - lo.w;
-                    const float d4 = zr[8 * i + 4] - hi.x, d5 = zr[8 * i + 5] - hi.y;
-                    const float d6 = zr[8 * i + 6] - hi.z, d7 = zr[8 * i + 7] - hi.w;
-                    a0 = lq_fma(d0, d0, a0); a1 = lq_fma(d1, d1, a1);
-                    a2 = lq_fma(d2, d2, a2); a3 = lq_fma(d3, d3, a3);
-                    a4 = lq_fma(d4, d4, a4); a5 = lq_fma(d5, d5, a5);
-                    a6 = lq_fma(d6, d6, a6); a7 = lq_fma(d7, d7, a7);
-                }
-                s = ((((((a0 + a1) + a2) + a3) + a4) + a5) + a6) + a7;
+                s = lq_norm8_row<DCH>(zr, c4);
                 if (s < best_s) {
                     const float v = lq_sqrt(s);
                     if (v < best_v) { best_v = v; best_s = s; best_k = k0 + kk; }
                 }
             } else {
-                float acc[4][8];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int l = 0; l < 8; ++l) acc[q][l] = 0.f;
-#pragma unroll
-                for (int i = 0; i < DCH; ++i) {
-                    // chunks 0..(DCH/4*4 - 1) cycle through the 4 accumulators; left-overs go to accumulator 0
-                    const int q = (i < (DCH / 4) * 4) ? (i & 3) : 0;
-                    const float4 lo = c4[2 * i], hi = c4[2 * i + 1];
-                    const float d0 = zr[8 * i + 0] - lo.x, d1 = zr[8 * i + 1] - lo.y;
-                    const float d2 = zr[8 * i + 2] - lo.z, d3 = zr[8 * i + 3] - lo.w;
-                    const float d4 = zr[8 * i + 4] - hi.x, d5 = zr[8 * i + 5] - hi.y;
-                    const float d6 = zr[8 * i + 6] - hi.z, d7 = zr[8 * i + 7] - hi.w;
-                    acc[q][0] = acc[q][0] + d0 * d0; acc[q][1] = acc[q][1] + d1 * d1;
-                    acc[q][2] = acc[q][2] + d2 * d2; acc[q][3] = acc[q][3] + d3 * d3;
-                    acc[q][4] = acc[q][4] + d4 * d4; acc[q][5] = acc[q][5] + d5 * d5;
-                    acc[q][6] = acc[q][6] + d6 * d6; acc[q][7] = acc[q][7] + d7 * d7;
-                }
-                s = 0.f;
-#pragma unroll
-                for (int l = 0; l < 8; ++l) {
-                    const float v = ((acc[0][l] + acc[1][l]) + acc[2][l]) + acc[3][l];
-                    s = (l == 0) ? v : s + v;
-                }
+                s = lq_sq32_row<DCH>(zr, c4);
                 if (s < best_v) { best_v = s; best_k = k0 + kk; }
             }
         }
@@ -203,12 +166,7 @@ __global__ __launch_bounds__(256) void nearest_wide_kernel(const float* __restri
                 const float t = (DIST == LIPVQ_DIST_NORM) ? lq_sqrt(lq_sqdist8(zr, c, D)) : lq_sqdist32(zr, c, D);
                 if (t < INFINITY) v = t;
             }
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {          // smallest value, among equal values the lower code
-                const float ov = __shfl_xor(v, off, 64);
-                const int ok = __shfl_xor(kk, off, 64);
-                if (ov < v || (ov == v && ok < kk)) { v = ov; kk = ok; }
-            }
+            LQ_WAVE_MIN(v, kk, 1);
             if (v < best_v[rr]) { best_v[rr] = v; best_k[rr] = kk; }
         }
     }

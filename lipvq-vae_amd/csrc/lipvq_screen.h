@@ -773,6 +773,16 @@ __device__ __forceinline__ void lq_emit_store(bool need, int slot /* valid in bo
     out4[1] = lq_i4{codes[2], codes[3], codes[4], codes[5]};
 }
 
+// Reading a slot lq_emit_store wrote (global memory, or the in-place decisions' LDS copy): cl = its 16 ints, n0 / n1 = its heads
+// (-1 for a row without a slot).  Macros for LQ_TAKE_MIN's reason (lipvq_common.h): lq_lists_row is part of the fused kernel.
+#define LQ_SLOT_HEAD(cl, h) ((cl)[8 * (h)])                                       /* part h's n: >= 0, -2 or -1 (see above) */
+// both parts list their candidates, at least one in all: exactly these n0 + n1 codes can win
+#define LQ_SLOT_SHORT(n0, n1) ((n0) >= 0 && (n1) >= 0 && (n0) + (n1) >= 1 && (n0) <= LQ_CAND_MAX && (n1) <= LQ_CAND_MAX)
+#define LQ_SLOT_CODE(cl, n0, j) ((j) < (n0) ? (cl)[2 + (j)] : (cl)[10 + ((j) - (n0))])   /* listed code j < n0 + n1 */
+#define LQ_SLOT_FIRST(cl, n0) ((cl)[(n0) > 0 ? 2 : 10])                          /* LQ_SLOT_CODE(cl, n0, 0) of a short list */
+// the 32 flagged lanes: part 0's mask in bits 0-15, part 1's above
+#define LQ_SLOT_LANES(cl) (((unsigned)(cl)[1] & 0xffffu) | (((unsigned)(cl)[9] & 0xffffu) << 16))
+
 template <bool PACK>
 __device__ __forceinline__ void lq_screen_emit(const LqDecision& dec, bool certified, bool lists_ok, int my_k, int64_t row,
                                                bool row_valid, int* __restrict__ amb_count, int* __restrict__ amb_list, int64_t N,
@@ -813,12 +823,12 @@ __device__ __forceinline__ int lq_lists_row(ZLOAD zload, const float* __restrict
     constexpr int D = DCH * 8;
     const int g = lane >> 3, j = lane & 7;
     int n0 = -1, n1 = -1;
-    if (cl) { n0 = cl[0]; n1 = cl[8]; }
-    const bool shortlist = n0 >= 0 && n1 >= 0 && n0 + n1 >= 1 && n0 <= LQ_CAND_MAX && n1 <= LQ_CAND_MAX;   // wave-uniform
+    if (cl) { n0 = LQ_SLOT_HEAD(cl, 0); n1 = LQ_SLOT_HEAD(cl, 1); }
+    const bool shortlist = LQ_SLOT_SHORT(n0, n1);                       // wave-uniform
     // lane masks (some lane's second minimum may be within the margin, or a part listed more than LQ_CAND_MAX codes): every
     // code congruent to a flagged lane mod 32 is a candidate -- popcount(mask) x K/32 of them, eight at a time like a short list
     const bool lanescan = !shortlist && n0 != -1 && n1 != -1 && (n0 == -2 || n1 == -2 || n0 > LQ_CAND_MAX || n1 > LQ_CAND_MAX);
-    const unsigned lmask = lanescan ? (((unsigned)cl[1] & 0xffffu) | (((unsigned)cl[9] & 0xffffu) << 16)) : 0u;
+    const unsigned lmask = lanescan ? LQ_SLOT_LANES(cl) : 0u;
     // ... as long as that is a few rounds of eight: a long scan would hold this wave for hundreds of dependent rounds while
     // the scanning kernel spreads a row over 64 slices (measured at K = 8192: 4.6 k such rows, 256 codes per flagged lane:
     // 290 us here against 101 us there)
@@ -852,7 +862,7 @@ __device__ __forceinline__ int lq_lists_row(ZLOAD zload, const float* __restrict
             code = 32 * t + __builtin_ctz(m | 0x80000000u);
             live = live && code < K;
         } else {
-            code = live ? (ci < n0 ? cl[2 + ci] : cl[10 + (ci - n0)]) : cl[n0 > 0 ? 2 : 10];
+            code = live ? LQ_SLOT_CODE(cl, n0, ci) : LQ_SLOT_FIRST(cl, n0);
         }
         code = (code >= 0 && code < K) ? code : 0;                       // (lq_screen_emit lists valid codes only)
         const float* c = cb + (size_t)code * D;
@@ -880,16 +890,11 @@ __device__ __forceinline__ int lq_lists_row(ZLOAD zload, const float* __restrict
         }
         const float v = (live && s == s) ? s : INFINITY;                 // a NaN never wins
         const int kk = live ? code : 0x7fffffff;
-        if (v < best_v || (v == best_v && kk < best_k)) { best_v = v; best_k = kk; }
+        LQ_TAKE_MIN(best_v, best_k, v, kk);
     }
-#pragma unroll
-    for (int off = 8; off < 64; off <<= 1) {
-        const float ov = __shfl_xor(best_v, off, 64);
-        const int ok = __shfl_xor(best_k, off, 64);
-        if (ov < best_v || (ov == best_v && ok < best_k)) { best_v = ov; best_k = ok; }
-    }
+    LQ_WAVE_MIN(best_v, best_k, 8);
     if (best_k < 0 || best_k >= K) {                                     // every value NaN: any valid code of the list
-        const int fb = scanning ? __builtin_ctz(lm_eff) : cl[n0 > 0 ? 2 : 10];
+        const int fb = scanning ? __builtin_ctz(lm_eff) : LQ_SLOT_FIRST(cl, n0);
         best_k = (fb >= 0 && fb < K) ? fb : 0;
     }
     return best_k;

@@ -542,39 +542,6 @@ __global__ __launch_bounds__(SCREEN_WAVES * 64) void screen_wide_kernel(
 // already reaches the best square so far proves the full square does too, and the rest of that code's row is not
 // fetched.  Same results bit for bit; the scan is bound by re-reading the codebook (1.15 ms for 3 317 rows at K = 8192,
 // D = 128 without the early exit).
-// The plain VQVAE's distance (vq:57-60, `(z_e.unsqueeze(1) - E).pow(2).sum(-1)`) of one row in registers against one code:
-// lq_sqdist32's order for D = 8 DCH < 512 (rounded squares; 8-vector i -> accumulator i mod 4 while whole groups of four remain,
-// left-overs -> accumulator 0; accumulators 1..3 added to 0; lanes left to right) -- the same code as nearest_direct_kernel.
-template <int DCH>
-__device__ __forceinline__ float lq_sq32_row(const float (&zr)[DCH * 8], const float4* __restrict__ c4) {
-    static_assert(DCH < 64, "the cascade of torch's sum starts at D = 512");
-    float acc[4][8];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int l = 0; l < 8; ++l) acc[q][l] = 0.f;
-#pragma unroll
-    for (int i = 0; i < DCH; ++i) {
-        const int q = (i < (DCH / 4) * 4) ? (i & 3) : 0;
-        const float4 lo = c4[2 * i], hi = c4[2 * i + 1];
-        const float d0 = zr[8 * i + 0] - lo.x, d1 = zr[8 * i + 1] - lo.y;
-        const float d2 = zr[8 * i + 2] - lo.z, d3 = zr[8 * i + 3] - lo.w;
-        const float d4 = zr[8 * i + 4] - hi.x, d5 = zr[8 * i + 5] - hi.y;
-        const float d6 = zr[8 * i + 6] - hi.z, d7 = zr[8 * i + 7] - hi.w;
-        acc[q][0] = acc[q][0] + d0 * d0; acc[q][1] = acc[q][1] + d1 * d1;
-        acc[q][2] = acc[q][2] + d2 * d2; acc[q][3] = acc[q][3] + d3 * d3;
-        acc[q][4] = acc[q][4] + d4 * d4; acc[q][5] = acc[q][5] + d5 * d5;
-        acc[q][6] = acc[q][6] + d6 * d6; acc[q][7] = acc[q][7] + d7 * d7;
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int l = 0; l < 8; ++l) {
-        const float v = ((acc[0][l] + acc[1][l]) + acc[2][l]) + acc[3][l];
-        s = (l == 0) ? v : s + v;
-    }
-    return s;
-}
-
 template <int DCH, bool SEEDED = false, int DIST = LIPVQ_DIST_NORM>
 __device__ __forceinline__ void lq_exact_scan(const float (&zr)[DCH * 8], const float* __restrict__ cb, int kb, int ke,
                                               float& best_v, float& best_s, int& best_k, float s_prune = INFINITY) {
@@ -600,31 +567,21 @@ __device__ __forceinline__ void lq_exact_scan(const float (&zr)[DCH * 8], const 
 #endif
     for (int k = kb; k < ke; ++k) {
         const float4* c4 = reinterpret_cast<const float4*>(cb + (size_t)k * D);
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f;
+        LqNorm8 n;
         bool dead = false;
 #pragma unroll
         for (int g = 0; g < DCH; g += G) {
 #pragma unroll
-            for (int i = g; i < (g + G < DCH ? g + G : DCH); ++i) {
-                const float4 lo = c4[2 * i], hi = c4[2 * i + 1];
-                const float d0 = zr[8 * i + 0] - lo.x, d1 = zr[8 * i + 1] - lo.y;
-                const float d2 = zr[8 * i + 2] - lo.z, d3 = zr[8 * i + 3] - lo.w;
-                const float d4 = zr[8 * i + 4] - hi.x, d5 = zr[8 * i + 5] - hi.y;
-                const float d6 = zr[8 * i + 6] - hi.z, d7 = zr[8 * i + 7] - hi.w;
-                a0 = lq_fma(d0, d0, a0); a1 = lq_fma(d1, d1, a1);
-                a2 = lq_fma(d2, d2, a2); a3 = lq_fma(d3, d3, a3);
-                a4 = lq_fma(d4, d4, a4); a5 = lq_fma(d5, d5, a5);
-                a6 = lq_fma(d6, d6, a6); a7 = lq_fma(d7, d7, a7);
-            }
+            for (int i = g; i < (g + G < DCH ? g + G : DCH); ++i) n.chunk(zr, c4, i);
 #ifndef LQ_NO_EARLY_EXIT
             if (g + G < DCH) {
-                const float part = ((((((a0 + a1) + a2) + a3) + a4) + a5) + a6) + a7;
+                const float part = n.fold();
                 if (part >= best_s || part > s_prune) { dead = true; break; }
             }
 #endif
         }
         if (dead) continue;
-        const float s = ((((((a0 + a1) + a2) + a3) + a4) + a5) + a6) + a7;
+        const float s = n.fold();
         if (s < best_s) {
             const float v = lq_sqrt(s);
             if (v < best_v) { best_v = v; best_s = s; best_k = k; }
@@ -638,21 +595,7 @@ __device__ __forceinline__ void lq_exact_scan(const float (&zr)[DCH * 8], const 
 // sees them).  The bound only prunes; the result is what the unbounded scan finds.
 template <int DCH>
 __device__ __forceinline__ float lq_seed_bound(const float (&zr)[DCH * 8], const float* __restrict__ cb, int seed) {
-    const float4* c4 = reinterpret_cast<const float4*>(cb + (size_t)seed * (DCH * 8));
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f;
-#pragma unroll
-    for (int i = 0; i < DCH; ++i) {
-        const float4 lo = c4[2 * i], hi = c4[2 * i + 1];
-        const float d0 = zr[8 * i + 0] - lo.x, d1 = zr[8 * i + 1] - lo.y;
-        const float d2 = zr[8 * i + 2] - lo.z, d3 = zr[8 * i + 3] - lo.w;
-        const float d4 = zr[8 * i + 4] - hi.x, d5 = zr[8 * i + 5] - hi.y;
-        const float d6 = zr[8 * i + 6] - hi.z, d7 = zr[8 * i + 7] - hi.w;
-        a0 = lq_fma(d0, d0, a0); a1 = lq_fma(d1, d1, a1);
-        a2 = lq_fma(d2, d2, a2); a3 = lq_fma(d3, d3, a3);
-        a4 = lq_fma(d4, d4, a4); a5 = lq_fma(d5, d5, a5);
-        a6 = lq_fma(d6, d6, a6); a7 = lq_fma(d7, d7, a7);
-    }
-    const float s = ((((((a0 + a1) + a2) + a3) + a4) + a5) + a6) + a7;
+    const float s = lq_norm8_row<DCH>(zr, reinterpret_cast<const float4*>(cb + (size_t)seed * (DCH * 8)));
     const float b = lq_fma(s, 4.76837158203125e-07f, s) + 1.1754944e-38f;      // s (1 + 2^-21), never below s itself
     return (b == b) ? b : INFINITY;                                            // a NaN square prunes nothing
 }
@@ -679,33 +622,14 @@ __device__ __forceinline__ void lq_rows_search(const float (&zr)[DCH * 8], const
     const int* cl = nullptr;
     if (cand_list && (size_t)cslot < cand_cap) {
         cl = cand_list + (size_t)cslot * 16;
-        n0 = cl[0]; n1 = cl[8];
+        n0 = LQ_SLOT_HEAD(cl, 0); n1 = LQ_SLOT_HEAD(cl, 1);
     }
-    if (n0 >= 0 && n1 >= 0 && n0 + n1 >= 1 && n0 <= LQ_CAND_MAX && n1 <= LQ_CAND_MAX) {
+    if (LQ_SLOT_SHORT(n0, n1)) {
         const int j = sl < n0 + n1 ? sl : 0;                      // idle slices repeat candidate 0
-        const int code = j < n0 ? cl[2 + j] : cl[10 + (j - n0)];
+        const int code = LQ_SLOT_CODE(cl, n0, j);
         if (code >= 0 && code < K) {                              // (lq_screen_emit lists valid codes only)
             const float4* c4 = reinterpret_cast<const float4*>(cb + (size_t)code * D);
-            if constexpr (DIST == LIPVQ_DIST_SQSUM) {
-                const float v = lq_sq32_row<DCH>(zr, c4);
-                best_k = code;
-                best_v = (v == v) ? v : INFINITY;
-                return;
-            }
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f;
-#pragma unroll
-            for (int i = 0; i < DCH; ++i) {
-                const float4 lo = c4[2 * i], hi = c4[2 * i + 1];
-                const float d0 = zr[8 * i + 0] - lo.x, d1 = zr[8 * i + 1] - lo.y;
-                const float d2 = zr[8 * i + 2] - lo.z, d3 = zr[8 * i + 3] - lo.w;
-                const float d4 = zr[8 * i + 4] - hi.x, d5 = zr[8 * i + 5] - hi.y;
-                const float d6 = zr[8 * i + 6] - hi.z, d7 = zr[8 * i + 7] - hi.w;
-                a0 = lq_fma(d0, d0, a0); a1 = lq_fma(d1, d1, a1);
-                a2 = lq_fma(d2, d2, a2); a3 = lq_fma(d3, d3, a3);
-                a4 = lq_fma(d4, d4, a4); a5 = lq_fma(d5, d5, a5);
-                a6 = lq_fma(d6, d6, a6); a7 = lq_fma(d7, d7, a7);
-            }
-            const float v = lq_sqrt(((((((a0 + a1) + a2) + a3) + a4) + a5) + a6) + a7);
+            const float v = (DIST == LIPVQ_DIST_SQSUM) ? lq_sq32_row<DCH>(zr, c4) : lq_sqrt(lq_norm8_row<DCH>(zr, c4));
             best_k = code;
             best_v = (v == v) ? v : INFINITY;                     // a NaN root never wins; the code stays valid
             return;
@@ -719,7 +643,7 @@ __device__ __forceinline__ void lq_rows_search(const float (&zr)[DCH * 8], const
     }
     if (n0 != -1 && n1 != -1 && cl) {
         // lane masks (at least one part said -2; a part with a short list contributes the lanes of its mask all the same)
-        const unsigned lanes = ((unsigned)cl[1] & 0xffffu) | (((unsigned)cl[9] & 0xffffu) << 16);
+        const unsigned lanes = LQ_SLOT_LANES(cl);
         const int ntile = (K + 31) / 32;
         for (int t = sl; t < ntile; t += SL) {                    // ascending codes within a slice: first minimum kept
             unsigned m = lanes;
@@ -741,21 +665,13 @@ __device__ __forceinline__ void lq_rows_search(const float (&zr)[DCH * 8], const
 // waves' results through LDS.  (The first version let one thread walk all 64 slices: 17 k cycles of dependent LDS reads,
 // a third of the workgroup's critical path once the search had shrunk to two candidates.)
 __device__ __forceinline__ void lq_rows_reduce(float& bv, int& bk, float (*s_v)[64], int (*s_k)[64], int r, int tid) {
-#pragma unroll
-    for (int off = 4; off < 64; off <<= 1) {
-        const float ov = __shfl_xor(bv, off, 64);
-        const int ok = __shfl_xor(bk, off, 64);
-        if (ov < bv || (ov == bv && ok < bk)) { bv = ov; bk = ok; }
-    }
+    LQ_WAVE_MIN(bv, bk, 4);
     if ((tid & 63) < 4) { s_v[r][tid >> 6] = bv; s_k[r][tid >> 6] = bk; }
     __syncthreads();
     if (tid < 4) {
+        bv = s_v[r][0]; bk = s_k[r][0];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float ov = s_v[r][q];
-            const int ok = s_k[r][q];
-            if (q == 0 || ov < bv || (ov == bv && ok < bk)) { bv = ov; bk = ok; }
-        }
+        for (int q = 1; q < 4; ++q) LQ_TAKE_MIN(bv, bk, s_v[r][q], s_k[r][q]);
     }
 }
 
@@ -885,16 +801,16 @@ __global__ __launch_bounds__(256) void nearest_rows_any_kernel(
         const int* cl = nullptr;
         if (cand_list && (size_t)cslot < cand_cap) {
             cl = cand_list + (size_t)cslot * 16;
-            n0 = cl[0]; n1 = cl[8];
+            n0 = LQ_SLOT_HEAD(cl, 0); n1 = LQ_SLOT_HEAD(cl, 1);
         }
-        if (n0 >= 0 && n1 >= 0 && n0 + n1 >= 1 && n0 <= LQ_CAND_MAX && n1 <= LQ_CAND_MAX) {
+        if (LQ_SLOT_SHORT(n0, n1)) {
             const int j = sl < n0 + n1 ? sl : 0;
-            int code = j < n0 ? cl[2 + j] : cl[10 + (j - n0)];
+            int code = LQ_SLOT_CODE(cl, n0, j);
             code = (code >= 0 && code < K) ? code : 0;
             best_k = code;
             best_v = score(zr, code);
         } else if (n0 != -1 && n1 != -1 && cl) {
-            const unsigned lanes = ((unsigned)cl[1] & 0xffffu) | (((unsigned)cl[9] & 0xffffu) << 16);
+            const unsigned lanes = LQ_SLOT_LANES(cl);
             const int ntile = (K + 31) / 32;
             for (int t = sl; t < ntile; t += SL) {                // ascending codes within a slice: first minimum kept
                 unsigned m = lanes;
@@ -954,18 +870,12 @@ __global__ __launch_bounds__(256) void nearest_rows1_kernel(const float* __restr
         float bv = INFINITY, bs = INFINITY;
         int bk = kb < K ? kb : K - 1;
         lq_exact_scan<DCH, false, DIST>(zr, cb, kb, ke, bv, bs, bk);
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const float ov = __shfl_xor(bv, off, 64);
-            const int ok = __shfl_xor(bk, off, 64);
-            if (ov < bv || (ov == bv && ok < bk)) { bv = ov; bk = ok; }
-        }
+        LQ_WAVE_MIN(bv, bk, 1);
         if ((tid & 63) == 0) { s_v[tid >> 6] = bv; s_k[tid >> 6] = bk; }
         __syncthreads();
         bv = s_v[0]; bk = s_k[0];
 #pragma unroll
-        for (int q = 1; q < 4; ++q)
-            if (s_v[q] < bv || (s_v[q] == bv && s_k[q] < bk)) { bv = s_v[q]; bk = s_k[q]; }
+        for (int q = 1; q < 4; ++q) LQ_TAKE_MIN(bv, bk, s_v[q], s_k[q]);
         if (tid == 0) {
             idx[row] = (int64_t)bk;
             if (usage) atomicAdd(&usage[bk], 1ull);
@@ -1072,18 +982,15 @@ __global__ __launch_bounds__(256) void nearest_small_kernel(const float* __restr
         const float* c = s_cb + lane * LD;
         float v;
         if constexpr (DIST == LIPVQ_DIST_NORM && DT != 0) {
-            // lq_sqdist8's order for a multiple of 8 (accumulator j takes the dimensions j mod 8, then ((((((a0+a1)+a2)+a3)+a4)+a5)+a6)+a7),
-            // written out so that it unrolls over the whole width
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f;
+            // lq_sqdist8's order for a multiple of 8, unrolled over the whole width (the row read as float4 broadcasts)
+            LqNorm8 n;
 #pragma unroll
             for (int i = 0; i < DT; i += 8) {
                 const float4 zl = *reinterpret_cast<const float4*>(zr + i), zh = *reinterpret_cast<const float4*>(zr + i + 4);
-                const float d0 = zl.x - c[i + 0], d1 = zl.y - c[i + 1], d2 = zl.z - c[i + 2], d3 = zl.w - c[i + 3];
-                const float d4 = zh.x - c[i + 4], d5 = zh.y - c[i + 5], d6 = zh.z - c[i + 6], d7 = zh.w - c[i + 7];
-                a0 = lq_fma(d0, d0, a0); a1 = lq_fma(d1, d1, a1); a2 = lq_fma(d2, d2, a2); a3 = lq_fma(d3, d3, a3);
-                a4 = lq_fma(d4, d4, a4); a5 = lq_fma(d5, d5, a5); a6 = lq_fma(d6, d6, a6); a7 = lq_fma(d7, d7, a7);
+                n.add(zl.x - c[i + 0], zl.y - c[i + 1], zl.z - c[i + 2], zl.w - c[i + 3],
+                      zh.x - c[i + 4], zh.y - c[i + 5], zh.z - c[i + 6], zh.w - c[i + 7]);
             }
-            v = lq_sqrt(((((((a0 + a1) + a2) + a3) + a4) + a5) + a6) + a7);
+            v = lq_sqrt(n.fold());
         } else {
             v = (DIST == LIPVQ_DIST_NORM) ? lq_sqrt(lq_sqdist8(zr, c, D)) : lq_sqdist32(zr, c, D);
         }
@@ -1091,12 +998,7 @@ __global__ __launch_bounds__(256) void nearest_small_kernel(const float* __restr
     } else {
         bk = K - 1;
     }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {                  // smallest value, among equal values the lower code
-        const float ov = __shfl_xor(bv, off, 64);
-        const int ok = __shfl_xor(bk, off, 64);
-        if (ov < bv || (ov == bv && ok < bk)) { bv = ov; bk = ok; }
-    }
+    LQ_WAVE_MIN(bv, bk, 1);
     if (CG > 1) {
         // (value, code) as one 64-bit key whose order is the decision rule -- smaller value first, among equal values the lower code
         // (values are non-negative floats: their bit patterns order like the numbers) -- kept COMPLEMENTED, so that "nothing yet" is
