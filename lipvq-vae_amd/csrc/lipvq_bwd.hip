@@ -139,12 +139,8 @@ __global__ __launch_bounds__(64 * WGW_WAVES) void wgrad_wg_kernel(const float* _
 #pragma unroll
             for (int cg = 0; cg < CG; ++cg) {
                 const int c = lane + 64 * cg;
-#ifdef LQ_WG_NOLOAD                /* timing-only ablation */
-                const float gv = (float)(rowc & 7) * 0.125f, hv = (float)(c & 3);
-#else
                 const float gv = G[(size_t)rowc * J + (c < J ? c : J - 1)];
                 const float hv = H[(size_t)hr * Kd + (c < Kd ? c : Kd - 1)];
-#endif
                 gqs[rr][cg] = (in && c < J) ? gv : 0.0f;
                 hqs[rr][cg] = (in && c < Kd) ? hv : 0.0f;
             }
@@ -178,11 +174,7 @@ __global__ __launch_bounds__(64 * WGW_WAVES) void wgrad_wg_kernel(const float* _
                 for (int s2 = 0; s2 < 16; ++s2) { av[s2] = ga[2 * s2 * Jp]; bv[s2] = hb[2 * s2 * Kp]; }
 #pragma unroll
                 for (int s2 = 0; s2 < 16; ++s2) {
-#ifdef LQ_WG_NOMFMA                /* timing-only ablation */
-                    acc[q][s2] += av[s2] * bv[s2];
-#else
                     acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s2], bv[s2], acc[q], 0, 0, 0);
-#endif
                     bsum[q] += av[s2];
                 }
             }
@@ -368,11 +360,9 @@ __global__ __launch_bounds__(64 * WGW_WAVES) void wgrad_wg5_kernel(const float* 
                         float av[16], bv[16];
 #pragma unroll
                         for (int s2 = 0; s2 < 16; ++s2) { av[s2] = ga[2 * (16 * part + s2) * Jp]; bv[s2] = hb[2 * (16 * part + s2) * Kp]; }
-#ifndef LQ_WG5_NO_PIN
                         // all 32 operand reads are REQUESTED before the first MFMA (round 3: left alone, hipcc sinks them to two in
                         // front of each MFMA pair behind `s_waitcnt lgkmcnt(0)` -- an LDS round trip exposed per 128 cycles of MFMA)
                         __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
                         for (int s2 = 0; s2 < 16; ++s2) {
                             acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s2], bv[s2], acc[q], 0, 0, 0);

@@ -200,9 +200,6 @@ __device__ __forceinline__ float lq_dpp(float v) {
 
 // all-reduce over the 16 lanes of a DPP row; partner order l^1, l^2, l^7, l^15 (the oracle's row_allsum)
 __device__ __forceinline__ float lq_row_allsum(float s) {
-#ifdef LQ_EMB_NORED
-    return s;               // ablation only (wrong results)
-#endif
     s = s + lq_dpp<0xB1>(s);        // quad_perm [1,0,3,2]
     s = s + lq_dpp<0x4E>(s);        // quad_perm [2,3,0,1]
     s = s + lq_dpp<0x141>(s);       // row_half_mirror
@@ -269,11 +266,7 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(const EmbedRowsArgs a) 
             for (int j = 0; j < NJ; ++j) {
                 const int q = l + 16 * j;
                 if (q < E4) {
-#ifdef LQ_EMB_NOLOAD
-                    float4 c = make_float4((float)k, (float)q, 1.0f, 2.0f);      // ablation only (wrong results)
-#else
                     float4 c = srow[q];
-#endif
                     if (a.pos) {
                         const float4 p = prow[q];
                         c.x = c.x + p.x; c.y = c.y + p.y; c.z = c.z + p.z; c.w = c.w + p.w;
@@ -307,13 +300,7 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(const EmbedRowsArgs a) 
                     o.z = lq_fma(v[j].z * rstd, w.z, bb.z);
                     o.w = lq_fma(v[j].w * rstd, w.w, bb.w);
                     if (!ok) o = f32x4{qnan, qnan, qnan, qnan};
-#ifdef LQ_EMB_NOSTORE
-                    if (o.x == 12345.678f) *reinterpret_cast<f32x4*>(orow + q) = o;     // ablation only
-#elif defined(LQ_EMB_NO_NT)
-                    *reinterpret_cast<f32x4*>(orow + q) = o;
-#else
                     __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(orow + q));   // written once, read by a later launch
-#endif
                 }
             }
             if (a.stats && live && l == 0) {
@@ -570,9 +557,7 @@ __global__ __launch_bounds__(256) void embed_rows_bwd_kernel(const EmbedBwdArgs 
 // ---------------------------------------------------------------------------------------------------
 static int embed_grid(int64_t rows_per_wg_step, int64_t N) {
     int64_t g = (N + rows_per_wg_step - 1) / rows_per_wg_step;
-#ifndef LQ_EMB_GRID
 #define LQ_EMB_GRID 2048
-#endif
     if (g > LQ_EMB_GRID) g = LQ_EMB_GRID;              // 8 workgroups per CU, grid-stride beyond
     if (g < 1) g = 1;
     return (int)g;
@@ -604,9 +589,7 @@ int lipvq_linear_act_f32(const float* x, const float* W, const float* b, float* 
     if (N == 0) return LIPVQ_OK;
     const int64_t gx = (N + LIN_ROWS - 1) / LIN_ROWS;
     if (gx > 0x7fffffffLL) return fail(LIPVQ_EUNSUPPORTED, "lipvq_linear_act_f32: N too large");
-#ifndef LQ_LIN_BIG_MIN
 #define LQ_LIN_BIG_MIN 512          // workgroups of the 128 x 128 tiling needed before it pays (2 per CU)
-#endif
     const bool narrow = E <= 64;                                  // 256 x 64 tiles instead of 128 x 128
     const int TR = narrow ? 256 : 128, TC = narrow ? 64 : 128;
     const int64_t big_wgs = ((N + TR - 1) / TR) * ((E + TC - 1) / TC);

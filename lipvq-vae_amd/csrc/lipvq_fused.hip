@@ -19,58 +19,25 @@
 #include "lipvq_mlp.h"
 #include "lipvq_screen.h"
 
-#ifdef LQ_ABL_NOGELU            // ablation builds only (scripts/ablate.sh): wrong results, timing only
-#define FUSED_GELU(v) (v)
-#else
-#define FUSED_GELU(v) lq_gelu(v)
-#endif
-#ifdef LQ_ABL_NOSIGMOID
-#define FUSED_SIGMOID(v) (v)
-#else
-#define FUSED_SIGMOID(v) lq_sigmoid(v)
-#endif
-
-#ifndef FUSED_WAVES
 #define FUSED_WAVES 8
-#endif
 #define FUSED_THREADS (FUSED_WAVES * 64)
 // LDS budget: the D = 128 instance holds 105 KB of weights, so its codebook stages are one tile deep
-#ifndef FUSED_HIST_MAX
 #define FUSED_HIST_MAX 2048
-#endif
 // stage ring of the fused kernel (LDS left beside the encoder weights): S <= 4: four buffers of two/four tiles; S = 8: the
 // weights take 98 KB, three buffers of one tile
 // The Lipschitz layer's weights are STREAMED through the stage ring (instead of living in LDS) from this many k-steps on:
 // 13 (D = 208) has no choice -- 112 KB of A operands; for 8 (D = 128) it is a trade measured in round 3: 64 KB of LDS go from
 // a phase that is a twentieth of the work at K = 8192 to the codebook ring of the phase that is the rest.
-#ifndef LQ_STREAM2_MIN_S
 #define LQ_STREAM2_MIN_S 9
-#endif
-#ifndef LQ_RING8_TC
 #define LQ_RING8_TC 1
-#endif
-#ifndef LQ_RING8_NB
 #define LQ_RING8_NB 3
-#endif
-#ifdef LQ_EXP_RING_TC             /* experiment builds: the S = 4 instance's ring shape from the command line */
-constexpr int fused_ring_tc(int S) { return S == 4 ? LQ_EXP_RING_TC : (S <= 2) ? 4 : (S <= 4) ? 2 : (S == 8) ? LQ_RING8_TC : 1; }
-constexpr int fused_ring_nb(int S) { return S == 4 ? LQ_EXP_RING_NB : (S <= 4) ? 4 : (S == 8) ? LQ_RING8_NB : 3; }
-#else
-constexpr int fused_ring_tc(int S) { return (S <= 2) ? 4 : (S <= 4) ? 2 : (S == 8) ? LQ_RING8_TC : 1; }
-#ifndef LQ_RING13_NB
 #define LQ_RING13_NB 3
-#endif
+constexpr int fused_ring_tc(int S) { return (S <= 2) ? 4 : (S <= 4) ? 2 : (S == 8) ? LQ_RING8_TC : 1; }
 constexpr int fused_ring_nb(int S) { return (S <= 4) ? 4 : (S == 8) ? LQ_RING8_NB : LQ_RING13_NB; }
-#endif
-#ifndef LQ_COARSE_TC_WIDE
-#define LQ_COARSE_TC_WIDE 2       /* tiles per stage of the one-product S = 8 instance (1 = as the three-product ring) */
-#endif
+#define LQ_COARSE_TC_WIDE 2       /* tiles per stage of the one-product S = 8 instance */
 // S = 8 (cfg3): 1.610 -> 1.555 ms, same box.  Not S = 13: with two tiles per stage that instance runs 10 ms instead of 0.9 (its
 // 26-k-step stage body no longer fits the registers it has left beside 104 of row fragments) -- profiles/r04_f_coarse_ring_ab.txt
 constexpr int fused_ring_tc_coarse(int S) { return S == 8 ? LQ_COARSE_TC_WIDE * fused_ring_tc(S) : fused_ring_tc(S); }
-#ifndef LQ_EXP_WGS_PER_CU
-#define LQ_EXP_WGS_PER_CU 1
-#endif
 
 // lq_gelu_poly2 (two elements per instruction: v_pk_fma_f32), cut into four stages so that one stage can follow each MFMA of a
 // 4-MFMA group (same operations in the same order as lq_gelu_poly: bit-identical values)
@@ -166,17 +133,6 @@ struct TokArgs {
                                  // caller wants no z_e: lq_ze_ring) -- the rows live in L2 until the wave has decided them
 };
 
-#ifndef LQ_PROLOGUE_DMA_MIN_S
-#define LQ_PROLOGUE_DMA_MIN_S 99  /* measurement knob: instances whose layer-1/2 weights travel by LDS-DMA under the first layer 0 (none: see the prologue) */
-#endif
-#ifdef LQ_CT_SCHEDULE             /* measurement builds: the two schedule choices as compile-time constants (defer_ze | nt_ze << 1) */
-#define LQ_DEFER_FLAG(a) ((LQ_CT_SCHEDULE & 1) != 0)
-#define LQ_NT_FLAG(a) ((LQ_CT_SCHEDULE & 2) != 0)
-#else
-#define LQ_DEFER_FLAG(a) ((a).defer_ze != 0)
-#define LQ_NT_FLAG(a) ((a).nt_ze != 0)
-#endif
-
 // T0 = 2 (64 features), T1 = 4 (128 features): the reference's encoder widths (v5:54-59).
 // FAST: the encoder's three GEMMs as fp16 MFMAs (v_mfma_f32_32x32x16_f16, fp32 accumulation) -- the "fast" mode
 // of SURVEY section 7 / BASELINE config 2's half-precision encoder: NOT bit-identical to the oracle (a fraction of a
@@ -211,7 +167,6 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
     // ring, so they are streamed, one 16 KB output-tile slab at a time, through that ring -- which is idle during the encoder
     // phase -- by the same LDS-DMA + counted-vmcnt mechanism as the codebook (all eight waves work on the same tile).
     constexpr bool STREAM2 = !FAST && S >= LQ_STREAM2_MIN_S;
-    constexpr bool PROLOGUE_DMA = !FAST && S >= LQ_PROLOGUE_DMA_MIN_S;    // layers 1 / 2 copied by LDS-DMA under the first layer 0 (prologue)
     static_assert(!FAST || (S % 2 == 0 && S <= 8), "fast mode: D in {32, 64, 128}");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 #ifdef LQ_STAMPS
@@ -273,9 +228,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
     constexpr int XPF = 8;                                   // fan-in up to 16 is prefetched; wider inputs load at block start
     const bool x_pref = !FAST && a.A <= 2 * XPF;
     float xqg[RG][XPF];
-#ifndef LQ_LANE_W_MIN_S
-#define LQ_LANE_W_MIN_S 8        /* measurement knob: the instances that re-form lane-dependent addresses per use (99: none); at S = 4 nothing spills */
-#endif
+    constexpr int LANE_W_MIN_S = 8;      // the instances that re-form lane-dependent addresses per use; at S = 4 nothing spills
     auto load_x = [&](int64_t blk_, const int g_, float (&xq)[XPF]) {
         int64_t r_ = ((blk_ * WAVES + wave) * RG + g_) * 32 + ln;
         r_ = r_ < a.N ? r_ : a.N - 1;
@@ -283,7 +236,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
         // (S >= 8: the lane half is opaque here -- hipcc had hoisted the XPF partial addresses `x + 4 k` out of the block loop and
         // spilled them; each reload's `vmcnt(0)` sat behind the x load issued just before it: XPF global loads in series per block)
         int h_x = h;
-        if constexpr (S >= LQ_LANE_W_MIN_S) asm volatile("" : "+v"(h_x));
+        if constexpr (S >= LANE_W_MIN_S) asm volatile("" : "+v"(h_x));
 #pragma unroll
         for (int q = 0; q < XPF; ++q) {
             const int k = 2 * q + h_x;
@@ -339,29 +292,22 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
             const float* P0 = a.packed + PL.oP0;
             const float* P1 = a.packed + PL.oP1;
             const float* P2 = a.packed + PL.oP2;
-            // (round 4, measured, NOT the default: S >= LQ_PROLOGUE_DMA_MIN_S) layers 1 and 2 by LDS-DMA, issued BEHIND the loads of
-            // layer 0 / biases / mu / x (vmcnt retires in order: what layer 0 needs is older and is waited for alone) and waited for
-            // only where layer 1 first reads them -- the first row block's layer 0 runs under the copy.  One wave-instruction moves 16
-            // image entries: lane l brings component l & 3 of entry 16 c + (l >> 2).  Same box, against the register-staged copy in
-            // front of one barrier (profiles/r04_l_prologue_dma_ab.txt): cfg2 0.3884 -> 0.3922 ms (0.0592 -> 0.0607 at 65 536 rows: the
-            // dword-granular copy is slower than 16-byte register stores and layer 0 too short to hide it); icrt within the noise.
-            constexpr int RR1 = PROLOGUE_DMA ? 1 : R1, RR2 = PROLOGUE_DMA ? 1 : (R2 > 0 ? R2 : 1);
-            float4 r1[RR1], r2[RR2];
-            if constexpr (!PROLOGUE_DMA) {
+            // (Round 4, measured and not kept: layers 1 and 2 by LDS-DMA under the first row block's layer 0 -- the dword-granular
+            // copy is slower than 16-byte register stores and layer 0 too short to hide it: profiles/r04_l_prologue_dma_ab.txt.)
+            float4 r1[R1], r2[R2 > 0 ? R2 : 1];
 #pragma unroll
-                for (int it = 0; it < R1; ++it) {
-                    int v = tid + it * THREADS;
-                    v = v < NV1 ? v : NV1 - 1;
-                    const float* src = P1 + ((size_t)(v >> 6) * 4) * 64 + (v & 63);
-                    r1[it] = make_float4(src[0], src[64], src[128], src[192]);
-                }
+            for (int it = 0; it < R1; ++it) {
+                int v = tid + it * THREADS;
+                v = v < NV1 ? v : NV1 - 1;
+                const float* src = P1 + ((size_t)(v >> 6) * 4) * 64 + (v & 63);
+                r1[it] = make_float4(src[0], src[64], src[128], src[192]);
+            }
 #pragma unroll
-                for (int it = 0; it < R2; ++it) {
-                    int v = tid + it * THREADS;
-                    v = v < NV2 ? v : NV2 - 1;
-                    const float* src = P2 + ((size_t)(v >> 6) * 4) * 64 + (v & 63);
-                    r2[it] = make_float4(src[0], src[64], src[128], src[192]);
-                }
+            for (int it = 0; it < R2; ++it) {
+                int v = tid + it * THREADS;
+                v = v < NV2 ? v : NV2 - 1;
+                const float* src = P2 + ((size_t)(v >> 6) * 4) * 64 + (v & 63);
+                r2[it] = make_float4(src[0], src[64], src[128], src[192]);
             }
             // layer 0 (fan-in A: S0 k-steps, padded to whole groups of four with zeros), entry v = (t * S0q + sq) * 64 + l
             const int NV0 = T0 * S0q * 64;
@@ -375,38 +321,22 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                 }
             };
             float e0[4];
-            p0_entry(tid < NV0 ? tid : NV0 - 1, e0);                      // (one entry per thread up to fan-in 16: loads first ...)
-            if constexpr (PROLOGUE_DMA) {
-                typedef __attribute__((address_space(3))) void* lds_ptr_t;
-                typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-                auto dma_image = [&](float* dstw, const float* P, int NV) {
-                    for (int c = wave; c < NV / 16; c += WAVES) {
-                        const int v = 16 * c + (lane >> 2);
-                        const float* src = P + ((size_t)(v >> 6) * 4 + (lane & 3)) * 64 + (v & 63);
-                        __builtin_amdgcn_global_load_lds((glb_ptr_t)src, (lds_ptr_t)(dstw + 64 * c), 4, 0, 0);
-                    }
-                };
-                static_assert(NV1 % 16 == 0 && NV2 % 16 == 0, "whole wave-instructions");
-                dma_image(w_P1, P1, NV1);                                 // ... then the copies (younger than every load above)
-                if (NV2 > 0) dma_image(w_P2, P2, NV2);
-            }
+            p0_entry(tid < NV0 ? tid : NV0 - 1, e0);                      // (one entry per thread up to fan-in 16)
             if (tid < NV0) *reinterpret_cast<float4*>(w_P0 + (size_t)tid * 4) = make_float4(e0[0], e0[1], e0[2], e0[3]);
             for (int v0 = tid + THREADS; v0 < NV0; v0 += THREADS) {       // (fan-in > 16 only)
                 float e[4];
                 p0_entry(v0, e);
                 *reinterpret_cast<float4*>(w_P0 + (size_t)v0 * 4) = make_float4(e[0], e[1], e[2], e[3]);
             }
-            if constexpr (!PROLOGUE_DMA) {
 #pragma unroll
-                for (int it = 0; it < R1; ++it) {
-                    const int v = tid + it * THREADS;
-                    if (v < NV1) *reinterpret_cast<float4*>(w_P1 + (size_t)v * 4) = r1[it];
-                }
+            for (int it = 0; it < R1; ++it) {
+                const int v = tid + it * THREADS;
+                if (v < NV1) *reinterpret_cast<float4*>(w_P1 + (size_t)v * 4) = r1[it];
+            }
 #pragma unroll
-                for (int it = 0; it < R2; ++it) {
-                    const int v = tid + it * THREADS;
-                    if (v < NV2) *reinterpret_cast<float4*>(w_P2 + (size_t)v * 4) = r2[it];
-                }
+            for (int it = 0; it < R2; ++it) {
+                const int v = tid + it * THREADS;
+                if (v < NV2) *reinterpret_cast<float4*>(w_P2 + (size_t)v * 4) = r2[it];
             }
         }
         // biases re-laid out [t][h][r] = b[32 t + 2 r + h]: the 16 values of a lane's accumulator tile are 64 contiguous bytes
@@ -418,15 +348,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
         if (use_hist)
             for (int i = tid; i < a.K; i += THREADS) hist[i] = 0u;
     }
-    if constexpr (PROLOGUE_DMA) lq_wg_barrier();      // (LDS stores only: the layer-1/2 copies stay in flight -- waited for behind the first layer 0)
-    else __syncthreads();
-
-#ifdef LQ_EXP_STAGGER             /* experiment: the workgroup in the SIMDs' odd wave slots starts LQ_EXP_STAGGER cycles late */
-    if (__builtin_amdgcn_s_getreg(6148) & 1) {
-        const long long t0_ = __builtin_amdgcn_s_memtime();
-        while (__builtin_amdgcn_s_memtime() - t0_ < LQ_EXP_STAGGER) __builtin_amdgcn_s_sleep(8);
-    }
-#endif
+    __syncthreads();
 
 #ifdef LQ_STAMPS
     // diagnostic build only (scripts/stamps.py): per-wave cycles per segment, accumulated over the row blocks and written to
@@ -439,11 +361,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
 #endif
     // the z_q copy of a row block is deferred to the start of the NEXT block (parity kernel) and routed through LDS (lq_gather_dma):
     // its first round overlaps layer 0, further rounds (wider latents) follow
-#ifdef LQ_NO_DEFER_GATHER
-    constexpr bool DEFER_GATHER = false;
-#else
     constexpr bool DEFER_GATHER = !FAST;
-#endif
     int pend_kg[RG];
     bool pend_okg[RG];
     int64_t pend_row0g[RG];
@@ -477,7 +395,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                     typedef float lq_f4v __attribute__((ext_vector_type(4)));
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
-                        if (S > 4 || TRAIN || LQ_NT_FLAG(a)) __builtin_nontemporal_store((lq_f4v){lo8[2 * q], hi8[2 * q], lo8[2 * q + 1], hi8[2 * q + 1]}, reinterpret_cast<lq_f4v*>(dst) + q);
+                        if (S > 4 || TRAIN || a.nt_ze) __builtin_nontemporal_store((lq_f4v){lo8[2 * q], hi8[2 * q], lo8[2 * q + 1], hi8[2 * q + 1]}, reinterpret_cast<lq_f4v*>(dst) + q);
                         else reinterpret_cast<lq_f4v*>(dst)[q] = (lq_f4v){lo8[2 * q], hi8[2 * q], lo8[2 * q + 1], hi8[2 * q + 1]};   // (launch-uniform: TokArgs; S > 4 and the training instances: always nontemporal -- nothing to choose there, and the second copy of the stores cost icrt 1.4 %)
                 }
             }
@@ -491,10 +409,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
         // z_e of each group's LAST layer-2 tile, stored behind the screen's first copies -- in the instances with registers to spare
         // (S <= 4: cfg2 0.4006 -> 0.3944 ms; at S = 13 the sixteen registers held across the end of layer 2 cost more than the
         // wait they remove: icrt 0.8945 -> 0.9149, profiles/r04_g_ze_store_placement.txt)
-#ifndef LQ_DEFER_ZE_MAX_S
-#define LQ_DEFER_ZE_MAX_S 4
-#endif
-        constexpr bool DEFER_ZE = S <= LQ_DEFER_ZE_MAX_S && !TRAIN;
+        constexpr bool DEFER_ZE = S <= 4 && !TRAIN;
         f32x16 zdefg[RG];
         float n2g[RG], a2g[RG], fzg[RG], fowng[RG];
       // ---- phase A of row group GC: the round-2 block body, on this group's rows / fragments / pending z_q copy ----
@@ -504,7 +419,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
         // invariants hipcc kept the lanes' LDS addresses in registers from the kernel's first lines and spilled them -- a reload is a
         // vector-memory load, and `s_waitcnt vmcnt(0)` in front of its use also waits for every store and copy in flight
         int lane_w = lane;
-        if constexpr (S >= LQ_LANE_W_MIN_S) asm volatile("" : "+v"(lane_w));
+        if constexpr (S >= LANE_W_MIN_S) asm volatile("" : "+v"(lane_w));
         const int h_w = lane_w >> 5;                         // (the centring vector's LDS reads: not hoisted out of the block loop either)
         const int64_t row0 = ((blk * WAVES + wave) * RG + g) * 32;
         const int64_t row = row0 + ln;
@@ -532,7 +447,6 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                 amax = fmaxf(amax, lq_abs(v));
             }
           } else {
-#if !defined(LQ_ABL_NOSIGMOID) && !defined(LQ_SCALAR_SIGMOID)
             if constexpr (!FAST) {
                 // the canonical sigmoid, two elements per instruction; a tile that holds a NaN or an infinity (wave-uniform test,
                 // practically never true) takes the one-element form, whose clamps propagate NaN
@@ -551,17 +465,11 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                     }
                 }
             }
-#endif
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 if (2 * t + (r >> 3) >= S) continue;             // S odd: features past D in the last tile (zero weights) are not z_e
                 // fast mode: hardware exp2 / rcp (1 ulp each) instead of the canonical exp polynomial + IEEE division
-#if !defined(LQ_ABL_NOSIGMOID) && !defined(LQ_SCALAR_SIGMOID)
                 const float zv = FAST ? __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(acc[r] * -1.44269504088896341f)) : acc[r];
-#else
-                const float zv = FAST ? __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(acc[r] * -1.44269504088896341f))
-                                      : FUSED_SIGMOID(acc[r]);
-#endif
                 acc[r] = zv;
                 const float v = zv - w_mu[32 * t + 2 * r + h_w];
                 n2 = lq_fma(v, v, n2);
@@ -578,12 +486,10 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
             // z_e rows for the exact stage (store_ze_tile).  The LAST tile's are not stored here: its sixteen values wait in zdefg and
             // are stored behind the screen's first stage copies (lq_screen_core_rg, DEFER) -- in front of them their write
             // acknowledgements stood between every wave and "stage 0 has landed" (vmcnt retires in order)
-#ifndef LQ_ABL_NOZESTORE
             if (a.ze_out) {
-                if (DEFER_ZE && LQ_DEFER_FLAG(a) && t == T2 - 1) zdefg[g] = acc;
+                if (DEFER_ZE && a.defer_ze && t == T2 - 1) zdefg[g] = acc;
                 else store_ze_tile(row, t, acc);
             }
-#endif
         };
 
         if constexpr (!FAST) {
@@ -622,12 +528,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
             // staging areas used to overlap other waves' scratch: every block began by waiting for its slowest wave)
             unsigned char* gstage = stage0 + (size_t)wave * WSLICE;
             const bool gnow = DEFER_GATHER && have_pend && a.zq;         // wave-uniform
-            if (gnow) {
-#ifdef LQ_GATHER_BARRIER         /* measurement knob: the barrier as it was */
-                lq_wg_barrier();
-#endif
-                lq_gather_dma<GP>(gstage, a.cb, pend_k, pend_ok, pend_row0, a.N, a.D, lane, 0, 0);
-            }
+            if (gnow) lq_gather_dma<GP>(gstage, a.cb, pend_k, pend_ok, pend_row0, a.N, a.D, lane, 0, 0);
             {
 #pragma unroll
                 for (int t = 0; t < T0; ++t) h0[t] = bias16(w_B0, t);
@@ -683,14 +584,10 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                     } else {
 #pragma unroll
                     for (int r = 0; r < 16; r += 2) {
-#ifndef LQ_ABL_NOGELU
                         const lq_v2f g2 = lq_gelu_poly2((lq_v2f){pre[r], pre[r + 1]});
                         h0[t][r] = g2.x; h0[t][r + 1] = g2.y;
-#endif
                     }
-#ifndef LQ_ABL_NOGELU
                     gelu_fixup(h0[t], pre);
-#endif
                     }
                 }
             }
@@ -706,10 +603,6 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                     }
                 }
             }
-            if (PROLOGUE_DMA && g == 0 && blk == (int64_t)blockIdx.x) {   // the workgroup's first row block: layers 1 / 2 have landed
-                lq_wait_vmcnt<0>();
-                lq_wg_barrier();
-            }
             LQ_STAMP(0);
             // ---- layers 1 and 2: one stream of 16-byte weight reads (T1 S1/4 of layer 1, then T2 S2/4 of layer 2), each read
             // issued one 4-MFMA group ahead of its use.  The GELU of tile t-1 is written between the MFMAs of tile t (two
@@ -723,11 +616,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
             // the interleaved stream loses another 9 % to issue arbitration between the two waves (5 843).  Same values either way:
             // cfg2 0.4095 -> 0.3997 ms per launch, same box (profiles/r04_b_lumped_gelu_ab.txt).  Not where every output tile of
             // layer 2 waits at a workgroup barrier for its streamed weights (S = 13: 0.934 -> 1.00 ms lumped) -- there the staging stays.
-#ifdef LQ_NO_LUMPED              /* measurement knob: the staged arrangement everywhere */
-            constexpr bool LUMPED = false;
-#else
             constexpr bool LUMPED = !VQ && !STREAM2;
-#endif
             constexpr int G1 = S1 / 4, G2 = S2 / 4;             // groups per tile
             auto wread = [&](int gidx) {                        // group gidx of the stream (compile-time after unrolling)
                 if (STREAM2 && gidx >= T1 * G1) gidx = T1 * G1 - 1;             // streamed layer 2: its groups are read from the slab ring
@@ -735,10 +624,6 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                                         : *reinterpret_cast<const float4*>(w_P2 + ((gidx - T1 * G1) * 64 + lane_w) * 4);
             };
             auto slab_dma = [&](int t_, int buf_) {             // one 16 KB output-tile slab of layer 2 into a ring buffer: 2 KiB per wave
-#ifdef LQ_SLAB_DMA_BUILTIN
-                typedef __attribute__((address_space(3))) void* lds_ptr_e;
-                typedef const __attribute__((address_space(1))) void* glb_ptr_e;
-#endif
                 const unsigned char* src = reinterpret_cast<const unsigned char*>(a.w2q) + (size_t)t_ * (G2 * 1024);
                 unsigned char* dst = stage0 + (size_t)buf_ * SLAB_STRIDE;
                 // the lane offset is made opaque HERE: the 14 source addresses of a row block's slabs do not change from block to
@@ -746,15 +631,10 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                 // eleven of them -- each DMA then sat behind `scratch_load; s_waitcnt vmcnt(0)`, and vmcnt(0) also waits for every
                 // slab copy in flight: the ring ran one memory round trip per KiB.  Two adds per copy instead.
                 unsigned lane16 = (unsigned)lane * 16u;
-#ifndef LQ_SLAB_DMA_HOISTED       /* measurement knob: the addresses as they were */
                 asm volatile("" : "+v"(lane16));
-#endif
 #pragma unroll
                 for (int j = 0; j < G2 * 1024 / 1024 / WAVES; ++j) {
                     const int off = (wave + j * WAVES) * 1024;
-#ifdef LQ_SLAB_DMA_BUILTIN
-                    __builtin_amdgcn_global_load_lds((glb_ptr_e)(src + off + lane16), (lds_ptr_e)(dst + off), 16, 0, 0);
-#else
                     // issued as inline asm: behind the builtin hipcc guards the tile's first LDS read of the slab ring with
                     // `s_waitcnt vmcnt(0)` (a DS read may alias an LDS-DMA write) -- the copy of slab t+2, issued two instructions
                     // earlier, had to LAND before tile t could start: a memory round trip per tile.  Which read needs which copy
@@ -764,7 +644,6 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                     unsigned m0_keep;                                   // (m0 is handed back: hipcc does not accept it as a clobber)
                     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                                  : "=&s"(m0_keep) : "v"(gaddr), "s"(ldsaddr) : "memory");
-#endif
                 }
             };
             if constexpr (STREAM2) {
@@ -794,30 +673,20 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                     if (t > 0 && !LUMPED) g.stage2();
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, h0[(4 * sq + 3) / 16][(4 * sq + 3) % 16], acc, 0, 0, 0);
                     if (t > 0 && !LUMPED) {
-#ifndef LQ_ABL_NOGELU
                         float o0, o1;
                         g.stage3(o0, o1);
                         h1[t - 1][2 * sq] = o0; h1[t - 1][2 * sq + 1] = o1;
-#else
-                        h1[t - 1][2 * sq] = pend[2 * sq]; h1[t - 1][2 * sq + 1] = pend[2 * sq + 1];
-#endif
                     }
                     __builtin_amdgcn_sched_barrier(0x6);
                 }
-#ifndef LQ_ABL_NOGELU
                 if constexpr (!VQ) { if (t > 0 && !LUMPED) gelu_fixup(h1[t - 1], pend); }
-#endif
                 if constexpr (LUMPED) {
-#ifndef LQ_ABL_NOGELU
 #pragma unroll
                     for (int r = 0; r < 16; r += 2) {
                         const lq_v2f g2 = lq_gelu_poly2((lq_v2f){acc[r], acc[r + 1]});
                         h1[t][r] = g2.x; h1[t][r + 1] = g2.y;
                     }
                     gelu_fixup(h1[t], acc);
-#else
-                    h1[t] = acc;
-#endif
                 }
                 pend = acc;
                 if constexpr (TRAIN) lq_tile_store16(a.pre1, 32 * T1, row, row < a.N, t, h, acc, 32 * T1, true);
@@ -853,9 +722,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                 for (int sq = 0; sq < G2; ++sq) {
                     if (t == 0 && sq == 3 * (S2 / 16)) {
                         // h1[T1-1] is needed from here on (k-steps 48..63 of a 128-wide layer): finish its GELU
-#ifndef LQ_ABL_NOGELU
                         if constexpr (!VQ && !LUMPED) gelu_fixup(h1[T1 - 1], pend);
-#endif
                     }
                     const float4 av = wn;
                     if constexpr (STREAM2) {
@@ -875,13 +742,9 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                     if (pg) g.stage2();
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, h1[(4 * sq + 3) / 16][(4 * sq + 3) % 16], acc, 0, 0, 0);
                     if (pg) {
-#ifndef LQ_ABL_NOGELU
                         float o0, o1;
                         g.stage3(o0, o1);
                         h1[T1 - 1][(2 * sq) & 15] = o0; h1[T1 - 1][(2 * sq + 1) & 15] = o1;
-#else
-                        h1[T1 - 1][(2 * sq) & 15] = pend[(2 * sq) & 15]; h1[T1 - 1][(2 * sq + 1) & 15] = pend[(2 * sq + 1) & 15];
-#endif
                     }
                     __builtin_amdgcn_sched_barrier(0x6);
                 }
@@ -916,7 +779,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
 #pragma unroll
             for (int t = 0; t < T0; ++t)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) b0[2 * t + (r >> 3)][r & 7] = (_Float16)FUSED_GELU(h0[t][r]);
+                for (int r = 0; r < 16; ++r) b0[2 * t + (r >> 3)][r & 7] = (_Float16)lq_gelu(h0[t][r]);
             f16x8 b1[2 * T1];
 #pragma unroll
             for (int t = 0; t < T1; ++t) {
@@ -929,7 +792,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, b0[s2], acc, 0, 0, 0);
                 }
 #pragma unroll
-                for (int r = 0; r < 16; ++r) b1[2 * t + (r >> 3)][r & 7] = (_Float16)FUSED_GELU(acc[r]);
+                for (int r = 0; r < 16; ++r) b1[2 * t + (r >> 3)][r & 7] = (_Float16)lq_gelu(acc[r]);
             }
 #pragma unroll
             for (int t = 0; t < T2; ++t) {
@@ -994,7 +857,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
         }
         // (S = 13: 104 registers of A fragments leave no room for an index array; COARSE: the packed index's perturbation is far
         // below the one-product margin at any S)
-        constexpr bool PACKF = LQ_PACK_FOR(S) || S > 8 || COARSE;
+        constexpr bool PACKF = S <= 4 || S > 8 || COARSE;
         float zng[RG], znrg[RG][16];                       // COARSE: the rows' error scale (lq_track_part), in frow's register layout
 #pragma unroll
         for (int g_ = 0; g_ < RG; ++g_) {
@@ -1005,21 +868,12 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                 for (int r = 0; r < 16; ++r) znrg[g_][r] = 0.0f;
             }
         }
-#ifdef LQ_ABL_NOZESTORE
-        const bool have_def = false;
-#else
-        const bool have_def = DEFER_ZE && LQ_DEFER_FLAG(a) && a.ze_out != nullptr;
-#endif
+        const bool have_def = DEFER_ZE && a.defer_ze && a.ze_out != nullptr;
         auto deferred_ze = [&]() {
 #pragma unroll
             for (int g_ = 0; g_ < RG; ++g_) store_ze_tile(((blk * WAVES + wave) * RG + g_) * 32 + ln, T2 - 1, zdefg[g_]);
         };
-#ifndef LQ_SEED_E2
-#define LQ_SEED_E2 0              /* 1: measurement knob, the three-product chain seeded with |e'|^2 f (lq_screen_core_rg, SEED): 7 vector
-                                     instructions less per tile and 0.8 % SLOWER (profiles/r04_m_seed_e2_ab.txt) -- not the default */
-#endif
-        constexpr bool SEED_E2 = LQ_SEED_E2 && !COARSE && !VQ;                // (VQ: every row its own scale -- sixteen products either way)
-        lq_screen_core_rg<S, THREADS, TCF, NBF, PACKF, RG, COARSE, 4 * RG, decltype(deferred_ze), SEED_E2>(ahg, alg, tiles, L.ntiles, stage0, tid, frow, znrg, m1g, m2g, k1g, have_def, deferred_ze);
+        lq_screen_core_rg<S, THREADS, TCF, NBF, PACKF, RG, COARSE, 4 * RG, decltype(deferred_ze)>(ahg, alg, tiles, L.ntiles, stage0, tid, frow, znrg, m1g, m2g, k1g, have_def, deferred_ze);
         LQ_STAMP(4);
         const unsigned keep_mask = PACKF ? ~((1u << lq_pack_bits(L.ntiles)) - 1u) : 0xffffffffu;
         unsigned char* scratch = stage0 + (size_t)wave * WSLICE;
@@ -1103,9 +957,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // it (0.404 without the deferral) -- and 0.437 ms on a device that answers the denser issue stream with 1.97 GHz (0.403 without:
 // 2.12 GHz).  Defaults: the settings that are never bad (no deferral, nontemporal); lipvq_tokenize_tune_f32 measures the four
 // combinations on the caller's device and shape and keeps the winner for that device; the options tok_defer_ze / tok_nt_ze override.
-#ifndef LQ_DEFAULT_DEFER_ZE
 #define LQ_DEFAULT_DEFER_ZE 0
-#endif
 struct LqSchedule { int defer_ze, nt_ze; };
 static std::atomic<int> g_tuned[64];                 // per device: 0 = not tuned, else 1 + (defer_ze | nt_ze << 1)
 static LqSchedule lq_schedule(int ring = 0) {
@@ -1125,10 +977,8 @@ static LqSchedule lq_schedule(int ring = 0) {
 // 131 072 rows 0.1096 -> 0.1054, 262 144 rows 0.2069 -> 0.1993, 524 288 rows 0.3910 -> 0.3863.  (With the last z_e tile's stores
 // deferred -- the schedule of the round's first builds -- the full batch measured level, 0.3929 -> 0.3936, and a size rule kept
 // it on the list kernel; without the deferral the wave that stops ~2 us for a row no longer costs its workgroup the 6 us saved.)
-// (LIPVQ_TOK_INPLACE=0 / 1: measurement knob -- never / whenever possible; LQ_INPLACE_MAX_ROWS: compile-time size limit; results identical)
-#ifndef LQ_INPLACE_MAX_ROWS
+// (LIPVQ_TOK_INPLACE=0 / 1: measurement knob -- never / whenever possible; LQ_INPLACE_MAX_ROWS: size limit; results identical)
 #define LQ_INPLACE_MAX_ROWS 2147483647
-#endif
 static int lq_inplace(bool have_ze, int coarse, int K, int64_t N) {
     const bool can = have_ze && !coarse && K <= LQ_LISTS_ALL_K;
     if (const char* e = lq_knob("LIPVQ_TOK_INPLACE")) {
@@ -1177,7 +1027,7 @@ static int launch_tokenize_as(KFN kfn, LqLdsReserve& reserved, const TokArgs& a,
     if (int rc = lipvq_reserve_lds(reserved, (const void*)kfn, lds, "tokenize")) return rc;
     const int64_t unit = (int64_t)waves * rg * 32;
     const int64_t nblk = (a.N + unit - 1) / unit;
-    int64_t cap = 256 * LQ_EXP_WGS_PER_CU;                                                        // one persistent workgroup per CU
+    int64_t cap = 256;                                              // one persistent workgroup per CU
     // (LIPVQ_TOK_GRID: measurement knob -- e.g. 252 leaves four CUs to a collective's kernel, scripts/dev/rccl_contention.py)
     if (const char* e = lq_knob("LIPVQ_TOK_GRID")) { const int64_t g_ = atoll(e); if (g_ > 0) cap = g_; }
     const int64_t blocks = nblk < cap ? nblk : cap;

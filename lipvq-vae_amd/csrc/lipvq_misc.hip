@@ -27,8 +27,8 @@ int lipvq_check_launch(const char* what) {
 
 // ------------------------------------------------------------------------------------------
 // options (include/lipvq.h): process-global, set EXPLICITLY through the ABI.  The shipped library reads no environment
-// variable (round 3's thirteen getenv sites meant a stray variable silently changed the product's speed); a development build
-// (-DLIPVQ_ENV_KNOBS, scripts/dev/ab_one.sh) falls back to LIPVQ_<NAME> in the environment for an option that was not set.
+// variable (round 3's thirteen getenv sites meant a stray variable silently changed the product's speed).  For one-off runs the
+// Python binding forwards LIPVQ_<NAME> variables through lipvq_set_option when LIPVQ_DEV_KNOBS=1 (_capi.py).
 // ------------------------------------------------------------------------------------------
 static const char* const g_opt_names[] = {"screen_mode", "tok_shape", "tok_ze_rows", "tok_grid", "rows_grid", "wgrad_chunk",
                                           "wgrad_per_tile", "wgrad_no_wg5", "wgrad_rows", "embed_bwd_grid", "mlp3_small_tiles",
@@ -52,11 +52,7 @@ static int opt_index(const char* name) {          // "screen_mode" or "LIPVQ_SCR
 const char* lq_knob(const char* name) {
     const int i = opt_index(name);
     if (i >= 0 && g_opt_set[i]) return g_opt_vals[i];
-#ifdef LIPVQ_ENV_KNOBS
-    return getenv(name);
-#else
     return nullptr;
-#endif
 }
 
 extern "C" int lipvq_set_option(const char* name, const char* value) {

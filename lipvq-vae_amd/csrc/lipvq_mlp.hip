@@ -310,10 +310,8 @@ __global__ __launch_bounds__(256) void mlp3_kernel(Mlp3Args a) {
 #define MLPS_WAVES 8
 #define MLPS_LD 33
 
-#ifndef MLPS_PF
 #define MLPS_PF 8           // k-steps of packed weights in flight ahead of the MFMAs (16 and 32 measure the same, round 3: at
                             // N = 80 ... 2 048 the launch is its dependent MFMA chains + barriers, 17.5 us forward whatever the depth)
-#endif
 
 __device__ __forceinline__ void mlps_chain(const float* __restrict__ Pt, int S, const float* __restrict__ bp, f32x16& acc) {
     float cur[MLPS_PF], nxt[MLPS_PF];
@@ -591,9 +589,7 @@ __global__ __launch_bounds__(64 * MLPL_WAVES) void mlp3_lds_kernel(Mlp3Args a) {
         // loop invariants hipcc kept `base + lane offset` pairs from the kernel's first lines and spilled them; each reload in front
         // of a store or load is a vector-memory load whose `s_waitcnt vmcnt(0)` also waits for every multiplier tile requested ahead.
         int lane_tile = lane;
-#ifndef LQ_MLPL_LANE_PLAIN
         if constexpr (FUSE == 1) asm volatile("" : "+v"(lane_tile));
-#endif
         const int lane = lane_tile;      // (shadows the kernel's: everything below addresses with this one)
         // one 32-feature slice of the input rows as a B operand; backward: act2'(pre2) folded in and g2 saved
         // (forward: requesting the NEXT tile's first slice under this tile's second and third layer changed nothing -- decoder

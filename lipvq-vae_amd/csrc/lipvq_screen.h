@@ -11,9 +11,7 @@
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 #define LIPVQ_SCREEN_GAMMA 3.814697265625e-06f   /* 2^-18 */
-#ifndef SCREEN_WAVES
 #define SCREEN_WAVES 8
-#endif
 
 struct PrepLayout {
     int S, Dpad, Kpad, ntiles;
@@ -75,11 +73,7 @@ __device__ __forceinline__ int lq_scale_exp(float maxabs) {
 }
 __device__ __forceinline__ float lq_pow2f(int k) { return __uint_as_float((unsigned)(k + 127) << 23); }   // k in [-126, 127]
 
-#ifdef LQ_OPT_TC
-constexpr int screen_default_tc(int S) { return (S <= 4) ? LQ_OPT_TC : (S <= 8) ? 2 : 1; }
-#else
 constexpr int screen_default_tc(int S) { return (S <= 2) ? 8 : (S <= 4) ? 4 : (S <= 8) ? 2 : 1; }
-#endif
 
 template <int S, int TC_ = screen_default_tc(S), bool COARSE = false>
 struct ScreenCfg {
@@ -92,18 +86,12 @@ struct ScreenCfg {
 
 // PACK bookkeeping (tile index in the low mantissa bits, lq_track_one) where the bookkeeping is the bottleneck: few MFMAs per
 // tile (S <= 4: 12 or fewer MFMAs against 80 bookkeeping instructions); wider latents hide it under 24+ MFMAs
-#ifndef LQ_PACK_FOR
-#ifndef LQ_PACK_MAX_S
-#define LQ_PACK_MAX_S 4
-#endif
-#define LQ_PACK_FOR(S) ((S) <= LQ_PACK_MAX_S)
-#endif
 // the stand-alone screen kernel: at most 80 KiB of stage ring, so that two workgroups share a CU
 template <int S>
 struct StandaloneScreen {
     static constexpr int TC = (S <= 2) ? 4 : (S <= 4) ? 2 : 1;
     static constexpr int NB = (S <= 8) ? 4 : 3;
-    static constexpr bool PACK = LQ_PACK_FOR(S);
+    static constexpr bool PACK = S <= 4;
 };
 
 // Bookkeeping of registers [lo, hi) of a finished 32 x 32 tile of d~ - |e'|^2 f (the chain starts from zero; the |e'|^2
@@ -113,13 +101,6 @@ struct StandaloneScreen {
 // smallest value carries its own code and no index array is kept: med3 + min on the packed floats (3 instructions + the fma
 // instead of 4 + the fma, and 16 registers less).  The perturbation, below 2^(TB-23) of the value's own magnitude, is part of
 // the certification margin (lq_screen_decide, pack_eps).  id = the code (unpacked) or the tile index (packed).
-// LQ_ABL_NOE2 (ablation build, wrong results): the |e'|^2 f term is dropped -- what a bookkeeping of 3 instead of 4 vector
-// instructions per element (the term folded into the chain's C operand at no cost) could gain AT MOST
-#ifdef LQ_ABL_NOE2
-#define LQ_E2_TERM(e2, f, a) (a)
-#else
-#define LQ_E2_TERM(e2, f, a) lq_fma(e2, f, a)
-#endif
 template <bool PACK>
 __device__ __forceinline__ void lq_track_one(float v, int id, unsigned keep_mask, float& m1, float& m2, int& k1) {
     if constexpr (PACK) {
@@ -157,37 +138,29 @@ __device__ __forceinline__ float lq_coarse_zn(float a2lo, float n2, float fz, fl
     const float t = lq_fma(rho, lq_fma(3.0f, A, B), A);
     return t * (fown / fz) * 1.0009765625f;                 // (1 + 2^-10): the norms' own fp32 rounding (D + 2 roundings each), generously
 }
-template <int LO, int HI, bool PACK = false, bool COARSE = false, bool SEEDED = COARSE>
+template <int LO, int HI, bool PACK = false, bool COARSE = false>
 __device__ __forceinline__ void lq_track_part(const f32x16& acc, float e2, float en, const float (&frow)[16], const float (&znr)[16],
                                               int id, unsigned keep_mask, float (&m1)[16], float (&m2)[16], int (&k1)[16]) {
-#ifdef LQ_ABL_NOTRACK
-    if (LO == 0) m1[0] = fminf(m1[0], acc[0] + acc[5] + acc[10] + acc[15]);   // keeps the MFMAs alive
-    return;
-#endif
 #pragma unroll
     for (int r = LO; r < HI; ++r) {
-        // COARSE / SEEDED: the chain started from |e'|^2 f (- w) (lq_screen_core_rg seeds it), the accumulator IS the booked value
-        const float v = SEEDED ? acc[r] : LQ_E2_TERM(e2, frow[r], acc[r]);
+        // COARSE: the chain started from |e'|^2 f - w (lq_screen_core_rg seeds it), the accumulator IS the booked value
+        const float v = COARSE ? acc[r] : lq_fma(e2, frow[r], acc[r]);
         lq_track_one<PACK>(v, id, keep_mask, m1[r], m2[r], k1[r]);
     }
 }
 
 // the pending tile's registers that are booked behind MFMA j of the NM MFMAs of the running tile (NM = 3 S, or S for the
 // one-product chain): [16 j / NM, 16 (j + 1) / NM)   (j a compile-time constant after unrolling)
-template <int S, bool PACK, bool COARSE = false, bool SEEDED = COARSE>
+template <int S, bool PACK, bool COARSE = false>
 __device__ __forceinline__ void lq_track_after_mfma(int j, const f32x16& acc, float e2, float en, const float (&frow)[16],
                                                     const float (&znr)[16], int id, unsigned keep_mask, float (&m1)[16],
                                                     float (&m2)[16], int (&k1)[16]) {
-#ifdef LQ_ABL_NOTRACK
-    if (j == 0) m1[0] = fminf(m1[0], acc[0] + acc[5] + acc[10] + acc[15]);
-    return;
-#endif
     constexpr int NM = COARSE ? S : 3 * S;
     const int lo = (16 * j) / NM, hi = (16 * (j + 1)) / NM;
 #pragma unroll
     for (int r = 0; r < 16; ++r)
         if (r >= lo && r < hi) {
-            const float v = SEEDED ? acc[r] : LQ_E2_TERM(e2, frow[r], acc[r]);
+            const float v = COARSE ? acc[r] : lq_fma(e2, frow[r], acc[r]);
             lq_track_one<PACK>(v, id, keep_mask, m1[r], m2[r], k1[r]);
         }
 }
@@ -207,7 +180,9 @@ __device__ __forceinline__ void lq_track_after_mfma(int j, const f32x16& acc, fl
 //  * the bookkeeping of tile t-1 (16/S registers per k-step) is issued between the MFMAs of tile t -- a wave's own vector
 //    instructions do run beside its fp16 MFMAs (scripts/probe/probe_pipes2.hip: four per MFMA are free; beside an fp32
 //    MFMA none are) -- the two chains alternate between two named accumulators, so nothing is copied;
-//  * a chain starts from C = 0 and |e'|^2 f is added by the bookkeeping (no accumulator initialisation on the chain);
+//  * a chain starts from C = 0 and |e'|^2 f is added by the bookkeeping (no accumulator initialisation on the chain; round 4
+//    measured a chain seeded with |e'|^2 f 0.8 % slower at cfg2 -- its first MFMA waits for its C operand where it took an
+//    inline zero: profiles/r04_m_seed_e2_ab.txt);
 //  * stage copies run NB - 1 stages ahead (LDS-DMA stays in flight across barriers: raw s_barrier and COUNTED vmcnt, never
 //    __syncthreads, which drains it); the wait for stage st+1, the barrier and the issue of stage st+NB-1 sit in the MIDDLE
 //    of stage st, so that the last k-steps of a stage can already read the next stage's first fragments.
@@ -233,14 +208,8 @@ __host__ __device__ static inline int lq_pack_bits(int ntiles) { int b = 1; whil
 // and "stage 0 has landed" -- 3.5 % of the cfg2 launch (profiles/r04_g_ze_store_placement.txt).  Behind the copies, the prologue's
 // wait and the first hand-over simply leave NDEF more operations outstanding.
 struct LqNoDeferred { __device__ __forceinline__ void operator()() const {} };
-// SEED (round 4; three-product chains whose rows share ONE scale -- the fused launch's sigmoid latents): the chain of a tile starts
-// from |e'|^2 f, the same value in all sixteen registers (eight v_pk_mov_b32), instead of from zero with the term added per element
-// when the tile is booked (sixteen fmas): the accumulator is the booked value, as in the one-product chain.  MEASURED SLOWER (cfg2
-// 0.3832 -> 0.3861 ms, same box: the chain's first MFMA now waits for its C operand where it took an inline zero, and the fmas it
-// saves sat off the critical path) -- kept behind LQ_SEED_E2 as a record, off by default.  Screening values move
-// by roundings of the partial sums (covered by gamma: lipvq_screen.hip, "Error bound"); indices are whatever the exact arithmetic says.
 template <int S, int NT, int TC_ = screen_default_tc(S), int NB = 4, bool PACK = false, int RG = 1, bool COARSE = false, int NDEF = 0,
-          typename DEFERRED = LqNoDeferred, bool SEED = false>
+          typename DEFERRED = LqNoDeferred>
 __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], const f16x8 (&al)[RG][S],
                                                   const unsigned char* __restrict__ tiles, int ntiles,
                                                   unsigned char* stage0, int tid, const float (&frow)[16],
@@ -259,27 +228,15 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
     constexpr int PD = NB - 1;                                        // stages in flight ahead of the one being read
     constexpr int NSTEP = C::TC * S;                                  // k-steps per stage
     constexpr int MID = (C::TC >= 2) ? (C::TC / 2) * S : S / 2;       // the k-step in front of which the mid-stage hand-over sits
-#ifndef LQ_FRAG_RING_S4
-#define LQ_FRAG_RING_S4 2      /* measured: 4 slots (reads three k-steps ahead) change nothing */
-#endif
-#ifndef LQ_FRAG_RING_S8
-#define LQ_FRAG_RING_S8 2      /* experiment knob: 4 = reads three k-steps ahead at S = 8 */
-#endif
-    constexpr int FR = (S == 4 && NSTEP % LQ_FRAG_RING_S4 == 0) ? LQ_FRAG_RING_S4
-                     : (S == 8 && NSTEP % LQ_FRAG_RING_S8 == 0) ? LQ_FRAG_RING_S8 : 2;      // fragment ring slots; reads run FR - 1 k-steps ahead
+    constexpr int FR = 2;                                             // fragment ring slots; reads run FR - 1 k-steps ahead
     constexpr int FD = FR - 1;
     constexpr int PERIOD = ((C::TC & 1) || (NSTEP % FR)) ? 2 : 1;     // stages per loop trip: an even number of tiles, whole fragment rings
-    static_assert(FR == 2 || NSTEP % FR == 0, "a wider fragment ring needs whole rings per stage");
     static_assert(C::STAGE_BYTES >= 1024 && C::STAGE_BYTES % 16 == 0, "stage copies are whole KiB pieces");
     static_assert(NSTEP - FD >= MID, "next-stage fragments are read after the hand-over");
     static_assert(CPW * PD < 64, "vmcnt immediate");
     const int lane = tid & 63, ln = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // provably wave-uniform: DMA addresses stay scalar base + lane offset
-#ifdef LQ_ABL_NOLOOP
-    const int nstage = 0;            // ablation build only
-#else
     const int nstage = ntiles / C::TC;                              // ntiles is a multiple of 8: nstage % PERIOD == 0
-#endif
     unsigned char* dummy = stage0 + (size_t)NB * C::STAGE_BYTES;    // 1 KiB nobody reads
     // Stage copies go global -> LDS directly (global_load_lds_dwordx4: no VGPR round trip, no ds_write issue).  One
     // wave-instruction moves 64 x 16 B to a wave-uniform LDS base + lane*16.  Wave w copies KiB pieces w, w + NW, ...; the
@@ -290,7 +247,6 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
     typedef __attribute__((address_space(3))) void* lds_ptr_t;
     typedef const __attribute__((address_space(1))) void* glb_ptr_t;
     auto stage_dma = [&](int st, int buf) {
-#ifndef LQ_ABL_NOSTAGE
         const bool real = st < nstage;
         const unsigned char* src = tiles + (real ? (size_t)st * C::STAGE_BYTES : (size_t)0);
         unsigned char* dst = stage0 + (size_t)buf * C::STAGE_BYTES;
@@ -303,7 +259,6 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
             unsigned char* d = real ? dst + off : dummy;
             __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + off + lane * 16), (lds_ptr_t)d, 16, 0, 0);
         }
-#endif
     };
     auto frag = [&](const unsigned char* tb, int s, int hl) {
         return COARSE ? *reinterpret_cast<const f16x8*>(tb + ((size_t)s * 64 + lane) * 16)          // hi-only tiles
@@ -316,13 +271,9 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
     static_assert((PD - 1) * CPW + NDEF < 64, "vmcnt immediate");
     if (NDEF > 0 && have_def) {                   // (launch-uniform)
         deferred();
-#ifndef LQ_ABL_NOSTAGE
         lq_wait_vmcnt<(PD - 1) * CPW + NDEF>();
-#endif
     } else {
-#ifndef LQ_ABL_NOSTAGE
         lq_wait_vmcnt<(PD - 1) * CPW>();
-#endif
     }
     lq_wg_barrier();
 
@@ -341,7 +292,6 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
     float e2q[2] = {0.0f, 0.0f};                  // |e'|^2 of the tile in accumulator A / B
     float enq[2] = {0.0f, 0.0f};                  // COARSE: |e'| of the same tiles
     float enA = 0.0f, enB = 0.0f;
-#ifndef LQ_ABL_NOLDSB
 #pragma unroll
     for (int g = 0; g < FD; ++g) {                // k-steps 0 .. FD-1 of stage 0 (FD <= S: all in tile 0)
         fh[g] = frag(stage0, g, 0);
@@ -350,7 +300,6 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
     e2q[0] = reinterpret_cast<const float*>(stage0 + C::FRAG_BYTES)[ln];
     if constexpr (COARSE) enq[0] = reinterpret_cast<const float*>(stage0 + C::FRAG_BYTES + 128)[ln];
     static_assert(FD <= S, "prologue reads stay in tile 0");
-#endif
     int buf = 0;                                  // ring position of stage st
     auto do_stage = [&](auto POS, int st) {
         constexpr int par = (decltype(POS)::value * C::TC) & 1;    // 0: the stage's first tile runs into accA, 1: into accB
@@ -364,14 +313,10 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
             if (g == MID) {
                 // ---- mid-stage hand-over: stage st+1 has landed everywhere (the PD-2 younger stages may still fly); everyone has
                 // left stage st-1, whose buffer is the one stage st+PD goes to
-#ifndef LQ_ABL_NOSTAGE
                 // (the first hand-over of a pass with deferred stores: they are younger than stage 1's copy and need not be done)
                 if (NDEF > 0 && have_def && st == 0) lq_wait_vmcnt<(PD >= 2 ? (PD - 2) * CPW : 0) + (PD >= 2 ? NDEF : 0)>();
                 else lq_wait_vmcnt<(PD >= 2 ? (PD - 2) * CPW : 0)>();
-#endif
-#ifndef LQ_ABL_NOBARRIER
                 lq_wg_barrier();
-#endif
                 int b = buf + PD; b = b >= NB ? b - NB : b;
                 stage_dma(st + PD, b);
             }
@@ -383,32 +328,10 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
             if (s == 0) {
                 const float e2c = e2q[(c + par) & 1];
                 const float enc = enq[(c + par) & 1];
-                if constexpr (SEED && !COARSE) {
-                    // sixteen copies of one value as register PAIRS: v_pk_mov_b32 moves two dwords per instruction (hipcc writes
-                    // fifteen v_mov_b32 -- as many vector instructions as the fmas this arrangement removes)
-                    typedef float lq_f2 __attribute__((ext_vector_type(2)));
-                    const float e2f = e2c * frow[0];
-                    lq_f2 pr;
-                    pr.x = e2f;
-                    pr.y = e2f;
 #pragma unroll
-                    for (int g_ = 0; g_ < RG; ++g_) {
-                        acc[g_][0] = pr.x;
-                        acc[g_][1] = pr.y;
+                for (int g_ = 0; g_ < RG; ++g_)
 #pragma unroll
-                        for (int q = 1; q < 8; ++q) {
-                            lq_f2 d;
-                            asm volatile("v_pk_mov_b32 %0, %1, %1" : "=v"(d) : "v"(pr));
-                            acc[g_][2 * q] = d.x;
-                            acc[g_][2 * q + 1] = d.y;
-                        }
-                    }
-                } else {
-#pragma unroll
-                    for (int g_ = 0; g_ < RG; ++g_)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[g_][r] = COARSE ? lq_fma(-znr[g_][r], enc, e2c * frow[r]) : 0.0f;
-                }
+                    for (int r = 0; r < 16; ++r) acc[g_][r] = COARSE ? lq_fma(-znr[g_][r], enc, e2c * frow[r]) : 0.0f;
                 int code = PACK ? (st * C::TC + c) : (st * C::TC + c) * 32 + ln;
                 if constexpr (PACK) asm volatile("" : "+v"(code));      // the tile index lives in a vector register (lq_track_one)
                 if (((c + par) & 1) == 0) { e2A = e2c; enA = enc; codeA = code; } else { e2B = e2c; enB = enc; codeB = code; }
@@ -418,9 +341,7 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
             if constexpr (!COARSE) bl = fl[(g + so) % FR];
             // k-step g + FD of this stage, or (g + FD >= NSTEP > MID: the hand-over has passed) of the next stage's first tile.
             // Unconditional: behind the last stage it reads bytes of the ring that nobody uses (no branch in the loop body).
-            // (LQ_FRAG_BEFORE_MFMA: measurement knob, the placement until round 3 -- in front of the k-step's first MFMA.)
             auto read_ahead = [&]() {
-#ifndef LQ_ABL_NOLDSB
                 const int g1 = g + FD;
                 const unsigned char* base = (g1 < NSTEP) ? sb : nsb;
                 const int gg = (g1 < NSTEP) ? g1 : g1 - NSTEP;
@@ -431,11 +352,7 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
                     e2q[(g1 / S + par) & 1] = reinterpret_cast<const float*>(tb + C::FRAG_BYTES)[ln];   // g1 / S >= TC: next stage
                     if constexpr (COARSE) enq[(g1 / S + par) & 1] = reinterpret_cast<const float*>(tb + C::FRAG_BYTES + 128)[ln];
                 }
-#endif
             };
-#ifdef LQ_FRAG_BEFORE_MFMA
-            read_ahead();
-#endif
             // pinned order: first MFMA, the read-ahead, then (its share of the pending tile's bookkeeping, MFMA) x 2 -- left alone, hipcc
             // lumps the bookkeeping behind the chain, where nothing hides it.  The read-ahead sits BEHIND the k-step's first MFMA
             // (round 3): hipcc guards that MFMA's fragment with `s_waitcnt lgkmcnt(0)`, not a counted wait, so reads issued in front
@@ -445,10 +362,8 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
 #pragma unroll
             for (int g_ = 0; g_ < RG; ++g_) {
                 acc[g_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[g_][s], bh, acc[g_], 0, 0, 0);
-#ifndef LQ_FRAG_BEFORE_MFMA
                 if (g_ == 0) { __builtin_amdgcn_sched_barrier(0); read_ahead(); __builtin_amdgcn_sched_barrier(0); }
-#endif
-                lq_track_after_mfma<S, PACK, COARSE, COARSE || SEED>(COARSE ? s : 3 * s + 0, prev[g_], e2_prev, en_prev, frow, znr[g_], code_prev, keep_mask,
+                lq_track_after_mfma<S, PACK, COARSE>(COARSE ? s : 3 * s + 0, prev[g_], e2_prev, en_prev, frow, znr[g_], code_prev, keep_mask,
                                                      m1[g_], m2[g_], k1[g_]);
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -456,14 +371,14 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
 #pragma unroll
                 for (int g_ = 0; g_ < RG; ++g_) {
                     acc[g_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[g_][s], bh, acc[g_], 0, 0, 0);
-                    lq_track_after_mfma<S, PACK, false, SEED>(3 * s + 1, prev[g_], e2_prev, en_prev, frow, znr[g_], code_prev, keep_mask,
+                    lq_track_after_mfma<S, PACK>(3 * s + 1, prev[g_], e2_prev, en_prev, frow, znr[g_], code_prev, keep_mask,
                                                         m1[g_], m2[g_], k1[g_]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
 #pragma unroll
                 for (int g_ = 0; g_ < RG; ++g_) {
                     acc[g_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[g_][s], bl, acc[g_], 0, 0, 0);
-                    lq_track_after_mfma<S, PACK, false, SEED>(3 * s + 2, prev[g_], e2_prev, en_prev, frow, znr[g_], code_prev, keep_mask,
+                    lq_track_after_mfma<S, PACK>(3 * s + 2, prev[g_], e2_prev, en_prev, frow, znr[g_], code_prev, keep_mask,
                                                         m1[g_], m2[g_], k1[g_]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -478,12 +393,10 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
     // the last tile's chain: ntiles is even, so it ran into accB
 #pragma unroll
     for (int g_ = 0; g_ < RG; ++g_)
-        lq_track_part<0, 16, PACK, COARSE, COARSE || SEED>(accB[g_], e2B, enB, frow, znr[g_], codeB, keep_mask, m1[g_], m2[g_], k1[g_]);
+        lq_track_part<0, 16, PACK, COARSE>(accB[g_], e2B, enB, frow, znr[g_], codeB, keep_mask, m1[g_], m2[g_], k1[g_]);
     // the copies issued for stages past the end go to the dummy KiB, but they count: drain them, then every wave has left
     // the stage buffers (the callers reuse them as per-wave scratch: lq_screen_decide)
-#ifndef LQ_ABL_NOSTAGE
     lq_wait_vmcnt<0>();
-#endif
     lq_wg_barrier();
 }
 
@@ -651,11 +564,7 @@ __device__ __forceinline__ bool lq_screen_decide(const float (&m1)[16], const fl
     dec.screen_ok = (twoemax < INFINITY) && (bk >= 0) && (bk < K);
     const float thr = dec.t0 + dec.p * (lq_abs(best) + lq_abs(second));
     // non-finite inputs make the comparison false
-    bool certified = dec.screen_ok && (second - best > thr);
-#ifdef LQ_ABL_CERT_ALL
-    certified = true; my_k = (my_k >= 0 && my_k < K) ? my_k : (lane * 7) % K;
-#endif
-    return certified;
+    return dec.screen_ok && (second - best > thr);
 }
 
 // Rows the screen could not certify (plus rows whose screen is meaningless: fp16 overflow of the codebook, `lists_ok` false):
@@ -808,9 +717,7 @@ __device__ __forceinline__ void lq_screen_emit(const LqDecision& dec, bool certi
     lq_emit_store(need, slot, head, mask, codes, my_k, row, amb_list, N, lane);
 }
 
-#ifndef LQ_LISTS_ALL_K
 #define LQ_LISTS_ALL_K 2048       /* codebooks up to this size: the list kernel decides every listed row (no scanning-kernel launch) */
-#endif
 // One listed row decided by ONE WAVE (round 3; the body of nearest_lists_kernel, lipvq_screen.hip -- and, round 4, of the fused
 // launch's in-place decisions, lq_screen_decide_inplace below): its eight 8-lane groups score eight candidates at once; lane j of a
 // group keeps torch's accumulator j (features j, j + 8, ...: the k-ordered fma chain of lq_sqdist8; for the sum rule the four
@@ -1016,9 +923,6 @@ __device__ __forceinline__ void lq_gather_flush(const unsigned char* wave_stage,
 }
 __device__ __forceinline__ void lq_screen_gather(const float* __restrict__ cb, float* __restrict__ zq, int my_k,
                                                  bool certified, int64_t row0, int64_t N, int D, int lane) {
-#ifdef LQ_ABL_NOGATHER
-    return;
-#endif
     if (D & 3) {
         // rows that are not whole 16-byte vectors (any-width route): 16 lanes copy one row element by element, 4 rows per pass
         for (int p = 0; p < 8; ++p) {

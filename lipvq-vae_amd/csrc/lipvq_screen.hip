@@ -554,9 +554,6 @@ __device__ __forceinline__ void lq_exact_scan(const float (&zr)[DCH * 8], const 
         }
         return;
     }
-#ifdef LQ_SCAN_G
-    constexpr int G = LQ_SCAN_G;
-#else
     // chunks of 8 dimensions between two early-exit tests.  Measured (same-run builds): every 32 dimensions pays at D = 128,
     // K = 8192 (cfg3 launch 4.74 -> 4.10 ms) and is neutral at D = 64; at D = 208 -- the training-step route, where every row
     // of a small batch is scanned and uniform-random data prunes nothing -- six tests per code cost 18 %, so none there.
@@ -564,7 +561,6 @@ __device__ __forceinline__ void lq_exact_scan(const float (&zr)[DCH * 8], const 
     // from the first chunk on, so the test pays at every width.  (Tried and dropped: loading code k+1's first 32 dimensions
     // while code k is tested -- 64 more registers beside the 128 of the row: 345 -> 531 us at K = 8192, D = 128.)
     constexpr int G = (DCH > 16 && !SEEDED) ? DCH : 4;
-#endif
     for (int k = kb; k < ke; ++k) {
         const float4* c4 = reinterpret_cast<const float4*>(cb + (size_t)k * D);
         LqNorm8 n;
@@ -573,12 +569,10 @@ __device__ __forceinline__ void lq_exact_scan(const float (&zr)[DCH * 8], const 
         for (int g = 0; g < DCH; g += G) {
 #pragma unroll
             for (int i = g; i < (g + G < DCH ? g + G : DCH); ++i) n.chunk(zr, c4, i);
-#ifndef LQ_NO_EARLY_EXIT
             if (g + G < DCH) {
                 const float part = n.fold();
                 if (part >= best_s || part > s_prune) { dead = true; break; }
             }
-#endif
         }
         if (dead) continue;
         const float s = n.fold();
@@ -1114,14 +1108,6 @@ __global__ __launch_bounds__(256) void nearest_rows_encode_kernel(
     __shared__ int s_k[RB][SL];
     const int count = *row_count;
     const int tid = threadIdx.x;
-#ifdef LQ_ROWS_STAMPS        /* diagnostic build: one workgroup prints its cycle stamps */
-    long long rst_prev = __builtin_amdgcn_s_memtime(), rst_t[8];
-    int rst_n = 0;
-#define LQ_RSTAMP(name) do { const long long t_ = __builtin_amdgcn_s_memtime(); if (rst_n < 8) rst_t[rst_n++] = t_ - rst_prev; rst_prev = t_; \
-        if (rst_n == 7 && blockIdx.x == 7 && tid == 0) printf("x %lld | L0 %lld | L1 %lld | L2 %lld | search %lld | reduce %lld | zq %lld\n", rst_t[0], rst_t[1], rst_t[2], rst_t[3], rst_t[4], rst_t[5], rst_t[6]); } while (0)
-#else
-#define LQ_RSTAMP(name) do { } while (0)
-#endif
   for (int base = blockIdx.x * RB; base < count; base += gridDim.x * RB) {
     // ---- encoder for the 4 rows -------------------------------------------------------------------------------
     // thread j owns output j of layers 1 and 2 for all four rows; its weight rows are fetched whole (16-byte loads) and FIRST:
@@ -1150,7 +1136,6 @@ __global__ __launch_bounds__(256) void nearest_rows_encode_kernel(
         s_x[r][k] = x[(size_t)row_list[sl_] * A + k];
     }
     __syncthreads();
-    LQ_RSTAMP("x staged");
     {
         const int r = tid >> 6, j = tid & 63;
         float acc = w.b0[j];
@@ -1159,7 +1144,6 @@ __global__ __launch_bounds__(256) void nearest_rows_encode_kernel(
         s_h0[r][j] = lq_gelu(acc);
     }
     __syncthreads();
-    LQ_RSTAMP("layer0");
     if (tid < 128) {
         const int j = tid;
         float acc[RB];
@@ -1180,7 +1164,6 @@ __global__ __launch_bounds__(256) void nearest_rows_encode_kernel(
         for (int r = 0; r < RB; ++r) s_h1[r][j] = lq_gelu(acc[r]);
     }
     __syncthreads();
-    LQ_RSTAMP("layer1");
     if (tid < D) {
         const int j = tid;
         float acc[RB];
@@ -1211,7 +1194,6 @@ __global__ __launch_bounds__(256) void nearest_rows_encode_kernel(
         for (int r = 0; r < RB; ++r) s_z[r][j] = lq_sigmoid(acc[r]);
     }
     __syncthreads();
-    LQ_RSTAMP("layer2");
     // ---- exact search (same as nearest_rows_kernel, z from LDS) ---------------------------------------------------
     const int r = tid & (RB - 1), sl = tid / RB;
     const int slot = base + r;
@@ -1226,7 +1208,6 @@ __global__ __launch_bounds__(256) void nearest_rows_encode_kernel(
     float best_v;
     int best_k;
     lq_rows_search<DCH, SL>(zr, cb, K, sl, valid ? slot : count - 1, seed_list, cand_list, cand_cap, best_v, best_k);
-    LQ_RSTAMP("search");
     lq_rows_reduce(best_v, best_k, s_v, s_k, r, tid);
     if (sl == 0) {
         if (valid) idx[row] = (int64_t)best_k;
@@ -1234,7 +1215,6 @@ __global__ __launch_bounds__(256) void nearest_rows_encode_kernel(
     }
     if (usage && tid < 64) lq_usage_add(usage, (sl == 0 && valid) ? s_k[r][0] : 0, sl == 0 && valid);
     __syncthreads();
-    LQ_RSTAMP("reduce+idx");
     if (zq && valid) {
         const int bk = s_k[r][0];
         const float4* src = reinterpret_cast<const float4*>(cb + (size_t)bk * D);
@@ -1242,7 +1222,6 @@ __global__ __launch_bounds__(256) void nearest_rows_encode_kernel(
         for (int v = sl; v < D / 4; v += SL) dst[v] = src[v];
     }
     __syncthreads();
-    LQ_RSTAMP("zq");
   }
 }
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU box: same-box A/B of library variants (build_ab/<name>/_lipvq_hip.so from scripts/dev/ab_one.sh; "main" = the in-tree build):
+# GPU box: same-box A/B of library variants (build_ab/<name>/_lipvq_hip.so from scripts/ab_build.sh or scripts/ab_head.sh; "main" = the in-tree build):
 #   bash scripts/dev/ab_sweep.sh <outdir under gpurun_out> <workload> "<SWEEP_G list>" <passes> name1 name2 ...
 set -e
 cd "$(dirname "$0")/../.."
