@@ -470,6 +470,33 @@ int lipvq_adamw_f32(float* const* params, const float* const* grads, float* cons
 int lipvq_ema_update_f32(float* cluster_size, float* embed_sum, const int64_t* counts, const float* dw, float* codebook,
                          float decay, float eps, int K, int D, void* workspace, void* stream);
 
+/* ---- opt-in extension: data-dependent codebook initialisation and dead-code revival (not in the reference, whose own
+ *      initialisation maps every row to one code: SURVEY 7; csrc/lipvq_kmeans.hip) ----
+ * D^2 sampling.  Every row n of z [N][D] carries d[n], its comparison value under `dist` to the nearest code written so far
+ * (LIPVQ_DIST_NORM: the norm of lq_sqdist8; LIPVQ_DIST_SQSUM: lq_sqdist32 -- what lipvq_nearest_f32 compares).  Its weight
+ * w = d^2 (norm) or d (sum) is exact in fp64 and is turned into an integer q[n] = floor(ldexp(w, e)); e is fixed once, from the
+ * first weights, as the largest integer with N ldexp(w_max, e) <= 2^62 (0 if w_max = 0), and rows whose d is not finite weigh 0.
+ * A draw u in [0, 1) (fp64, from `draws`) picks, with Q = sum q and r = min(Q - 1, floor(u (double)Q)), the smallest n with
+ * q[0] + ... + q[n] > r; row n is copied into the code bit for bit and every d[n] becomes min(d[n], dist(z[n], code)).
+ * Q == 0 (no row differs from every code written) stops the draws: the remaining codes are left unchanged.
+ * Outputs: picks [K] int64 (the row copied into code k, or -1), written [1] int64 (how many codes were written).
+ * Nothing is read back to the host: a whole call can be captured in a HIP graph.  Two launches per code.
+ * workspace: lipvq_kmeans_workspace_bytes(N, K) bytes, 8-byte aligned, any contents (the call initialises what it reads). */
+size_t lipvq_kmeans_workspace_bytes(int64_t N, int K);
+/* k-means++ seeding of codebook [K][D]: code 0 = row min(N - 1, floor(draws[0] N)), then code k (k = 1 ... K - 1) by the draw
+ * draws[k].  draws [K] fp64. */
+int lipvq_kmeans_seed_f32(const float* z, float* codebook, const double* draws, int64_t* picks, int64_t* written,
+                          void* workspace, int64_t N, int K, int D, int dist, void* stream);
+/* Dead-code revival.  d[n] starts as dist(z[n], codebook[idx[n]]) (idx [N] int64: each row's assigned code; an index outside
+ * [0, K) weighs 0); the codes with counts[k] < threshold (counts [K] int64) are refilled in ascending code order, code k by the
+ * draw draws[k] (draws [K] fp64), the first max_codes of them at most (pass K for all: launches grow with max_codes). */
+int lipvq_kmeans_revive_f32(const float* z, float* codebook, const int64_t* idx, const int64_t* counts, int64_t threshold,
+                            const double* draws, int64_t* picks, int64_t* written, void* workspace, int64_t N, int K, int D,
+                            int dist, int max_codes, void* stream);
+/* The Lloyd update: codebook[k] = sums[k] / (float)counts[k] (IEEE fp32 division) where counts[k] > 0, other codes untouched.
+ * sums [K][D] = the per-code sums of the rows (lipvq_scatter_add_det_f32 / the sequential sorted route), counts [K] int64. */
+int lipvq_kmeans_means_f32(float* codebook, const float* sums, const int64_t* counts, int K, int D, void* stream);
+
 /* ---- multi-GPU: the path's only cross-GPU exchange (the reference is single-GPU,
  *      robomimic/utils/torch_utils.py:48-50, so there is no reference line to cite) ----
  * One process per GPU, rows sharded, parameters replicated.  Per batch the code-usage histogram (and, with the EMA

@@ -107,6 +107,10 @@ SIGNATURES = {
     "lipvq_adamw_workspace_bytes": (_sz, []),
     "lipvq_adamw_f32": (_i, [_vp] * 6 + [_i] + [C.c_double] * 5 + [_vp, _vp]),
     "lipvq_ema_update_f32": (_i, [_vp] * 5 + [C.c_float, C.c_float, _i, _i, _vp, _vp]),
+    "lipvq_kmeans_workspace_bytes": (_sz, [_i64, _i]),
+    "lipvq_kmeans_seed_f32": (_i, [_vp] * 6 + [_i64, _i, _i, _i, _vp]),
+    "lipvq_kmeans_revive_f32": (_i, [_vp] * 4 + [_i64] + [_vp] * 4 + [_i64, _i, _i, _i, _i, _vp]),
+    "lipvq_kmeans_means_f32": (_i, [_vp] * 3 + [_i, _i, _vp]),
     "lipvq_comm_unique_id": (_i, [_vp]),
     "lipvq_comm_init": (_i, [C.POINTER(_vp), _vp, _i, _i]),
     "lipvq_comm_destroy": (_i, [_vp]),

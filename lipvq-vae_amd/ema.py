@@ -43,3 +43,12 @@ class EMACodebook:
         # codebook, autograd's saved-tensor checks) see the change
         torch.autograd.graph.increment_version(self.codebook)
         return counts
+
+    @torch.no_grad()
+    def reset_codes_(self, codes: torch.Tensor):
+        """Restart the statistics of the given codes from their current rows (embed_sum[k] = codebook[k], cluster_size[k] = 1):
+        after a code was rewritten from outside (dead-code revival), the next update() starts from it instead of pulling it back
+        to its stale running mean."""
+        codes = codes.reshape(-1).to(device=self.codebook.device, dtype=torch.int64)
+        self.embed_sum[codes] = self.codebook.detach()[codes]
+        self.cluster_size[codes] = 1.0

@@ -832,6 +832,95 @@ def ema_update(cluster_size, embed_sum, counts, dw, codebook, decay, eps):
                                        float(decay), float(eps), K, D, _ptr(ws), _stream()), "lipvq_ema_update_f32")
 
 
+# ---- opt-in extension: k-means++ seeding, dead-code revival, Lloyd means (include/lipvq.h lipvq_kmeans_*) ----------------------
+
+def _chk_inplace(t, name, dtype=torch.float32):
+    """An output written through its pointer: a contiguous copy would swallow the write."""
+    t2 = _chk(t, name, dtype)
+    if t2 is not t:
+        raise ValueError(f"{name}: must be contiguous (it is written in place)")
+    return t
+
+
+def _kmeans_args(z, K, draws, dist, what):
+    z = _chk(z, "z")
+    if z.dim() != 2 or z.shape[0] < 1 or z.shape[1] < 1:
+        raise ValueError(f"{what}: z must be [N >= 1, D >= 1], got {tuple(z.shape)}")
+    if int(K) < 1:
+        raise ValueError(f"{what}: K must be >= 1, got {K}")
+    draws = _chk(draws, "draws", torch.float64)
+    if draws.dim() != 1 or draws.numel() < K:
+        raise ValueError(f"{what}: draws must hold at least K = {K} values, got {tuple(draws.shape)}")
+    if dist not in (DIST_NORM, DIST_SQSUM):
+        raise ValueError(f"{what}: unknown distance rule {dist}")
+    if draws.device != z.device:
+        raise ValueError(f"{what}: draws must be on {z.device}")
+    return z, draws
+
+
+def kmeans_seed(z, K: int, draws, dist: int = DIST_NORM, out=None):
+    """k-means++ seeding (D^2 sampling, include/lipvq.h lipvq_kmeans_seed_f32) of K codes from the rows of z [N, D]: code 0 is
+    row floor(draws[0] N), code k the row drawn with draws[k] (fp64 in [0, 1)).  out: the [K, D] codebook written in place
+    (codes the draws cannot reach stay as they were); a new zero-filled one when None.  Returns (codebook, picks [K] int64:
+    the row copied into each code or -1, written [1] int64), all on the device: nothing is synchronised."""
+    K = int(K)
+    z, draws = _kmeans_args(z, K, draws, dist, "kmeans_seed")
+    N, D = z.shape
+    if out is None:
+        out = torch.zeros((K, D), device=z.device, dtype=torch.float32)
+    out = _chk_inplace(out, "out")
+    if tuple(out.shape) != (K, D) or out.device != z.device:
+        raise ValueError(f"kmeans_seed: out must be [{K}, {D}] on {z.device}")
+    picks = torch.empty(K, device=z.device, dtype=torch.int64)
+    written = torch.empty(1, device=z.device, dtype=torch.int64)
+    ws = torch.empty(lib.lipvq_kmeans_workspace_bytes(N, K), device=z.device, dtype=torch.uint8)
+    with _on(z.device):
+        check(lib.lipvq_kmeans_seed_f32(_ptr(z), _ptr(out), _ptr(draws), _ptr(picks), _ptr(written), _ptr(ws), N, K, D, int(dist),
+                                        _stream()), "lipvq_kmeans_seed_f32")
+    return out, picks, written
+
+
+def kmeans_revive_(codebook, z, idx, counts, threshold: int, draws, dist: int = DIST_NORM, max_codes: int | None = None):
+    """Dead-code revival in place (include/lipvq.h lipvq_kmeans_revive_f32): the codes with counts[k] < threshold are refilled
+    in ascending code order by D^2 sampling over the rows of z, starting from each row's distance to its assigned code idx[n];
+    code k uses draws[k].  max_codes bounds how many dead codes are served (default K; each costs two launches whether it
+    exists or not).  Returns (picks [K] int64: the row copied into each code or -1, written [1] int64), on the device."""
+    codebook = _chk_inplace(codebook, "codebook")
+    if codebook.dim() != 2:
+        raise ValueError("kmeans_revive_: codebook must be [K, D]")
+    K, D = codebook.shape
+    z, draws = _kmeans_args(z, K, draws, dist, "kmeans_revive_")
+    N = z.shape[0]
+    idx, counts = _chk(idx, "idx", torch.int64), _chk(counts, "counts", torch.int64)
+    if z.shape[1] != D or idx.numel() != N or counts.numel() != K:
+        raise ValueError("kmeans_revive_: shapes do not match (z [N, D], idx [N], counts [K], codebook [K, D])")
+    if codebook.device != z.device or idx.device != z.device or counts.device != z.device:
+        raise ValueError("kmeans_revive_: every tensor must be on one device")
+    max_codes = K if max_codes is None else min(int(max_codes), K)
+    if max_codes < 0:
+        raise ValueError("kmeans_revive_: max_codes must be >= 0")
+    picks = torch.empty(K, device=z.device, dtype=torch.int64)
+    written = torch.empty(1, device=z.device, dtype=torch.int64)
+    ws = torch.empty(lib.lipvq_kmeans_workspace_bytes(N, K), device=z.device, dtype=torch.uint8)
+    with _on(z.device):
+        check(lib.lipvq_kmeans_revive_f32(_ptr(z), _ptr(codebook), _ptr(idx), _ptr(counts), int(threshold), _ptr(draws), _ptr(picks),
+                                          _ptr(written), _ptr(ws), N, K, D, int(dist), max_codes, _stream()), "lipvq_kmeans_revive_f32")
+    return picks, written
+
+
+def kmeans_means_(codebook, sums, counts):
+    """The Lloyd update in place: codebook[k] = sums[k] / (float)counts[k] where counts[k] > 0 (lipvq_kmeans_means_f32)."""
+    codebook = _chk_inplace(codebook, "codebook")
+    sums, counts = _chk(sums, "sums"), _chk(counts, "counts", torch.int64)
+    if codebook.dim() != 2 or tuple(sums.shape) != tuple(codebook.shape) or counts.numel() != codebook.shape[0]:
+        raise ValueError("kmeans_means_: codebook and sums must be [K, D], counts [K]")
+    if sums.device != codebook.device or counts.device != codebook.device:
+        raise ValueError("kmeans_means_: every tensor must be on one device")
+    K, D = codebook.shape
+    with _on(codebook.device):
+        check(lib.lipvq_kmeans_means_f32(_ptr(codebook), _ptr(sums), _ptr(counts), K, D, _stream()), "lipvq_kmeans_means_f32")
+
+
 # ---------------------------------------------------------------------------------------------------
 # the default action branch (obs_nets.py:1244-1260; csrc/lipvq_xf.hip)
 # ---------------------------------------------------------------------------------------------------

@@ -17,7 +17,8 @@ works unchanged.
 
 Extras that the reference does not have (allowed by SURVEY.md section 8b): ``last_indices``,
 ``code_usage`` (int64 [K], accumulated over forwards), ``tokenize()`` (encode + quantize
-only: the BASELINE metric's path) and ``perplexity()``.
+only: the BASELINE metric's path) and ``perplexity()``; opt-in, never called by ``forward()``: ``init_codebook_()`` and
+``revive_dead_codes_()`` (kmeans.py).
 """
 from __future__ import annotations
 
@@ -177,6 +178,48 @@ class _TokenizerBase(nn.Module):
             self.invalidate_caches()
         return out
 
+    # -- opt-in codebook maintenance (extensions, not reference behaviour: kmeans.py) -------------------
+    def _codebook_written(self):
+        """After an in-place write through a raw pointer: bump the version (autograd's saved-tensor checks), drop the prepared
+        codebook and the fused workspace, and forget what the screen monitor learnt about the OLD codebook (a collapsed one sets
+        its all-pairs bypass)."""
+        torch.autograd.graph.increment_version(self._codebook())
+        self.invalidate_caches()
+        self._screen_monitor = _ScreenMonitor()
+
+    @torch.no_grad()
+    def init_codebook_(self, x, iters: int = 10, generator=None, seed_rows=None):
+        """Data-dependent codebook initialisation: k-means++ seeding on the encoder outputs of x, then ``iters`` Lloyd steps
+        (kmeans.kmeans, with this tokenizer's distance rule).  Writes the codebook in place; returns self."""
+        from .kmeans import kmeans
+        z = self.encode(x)
+        kmeans(z, self._codebook().detach(), iters=iters, generator=generator, dist=self._DIST, seed_rows=seed_rows)
+        self._codebook_written()
+        return self
+
+    @torch.no_grad()
+    def revive_dead_codes_(self, x, threshold: int = 1, generator=None, ema=None):
+        """Refill the codes used fewer than ``threshold`` times since reset_usage() (``code_usage``) by D^2 sampling over the
+        encoder outputs of x, starting from each row's distance to its assigned code.  Resets ``code_usage``; with an
+        ``ema.EMACodebook`` of this codebook, restarts the revived codes' statistics.  Returns the revived code ids (int64).
+        Not inside a captured graph replay (icl.GraphedTokenizerStep): call it between replays."""
+        from .kmeans import assign, draws
+        cb = self._codebook().detach()
+        K = cb.shape[0]
+        z = self.encode(x)
+        idx = assign(z, cb, self._DIST)
+        u = draws(K, generator, z.device)
+        n_dead = int((self.code_usage < threshold).sum())
+        revived = torch.zeros(0, device=cb.device, dtype=torch.int64)
+        if n_dead and z.shape[0] > 0:
+            picks, _ = ops.kmeans_revive_(cb, z, idx, self.code_usage, threshold, u, self._DIST, max_codes=n_dead)
+            revived = torch.nonzero(picks >= 0).reshape(-1)
+            if ema is not None:
+                ema.reset_codes_(revived)
+            self._codebook_written()
+        self.reset_usage()
+        return revived
+
     def perplexity(self):
         """exp(entropy) of the accumulated code-usage histogram."""
         c = self.code_usage.to(torch.float64)
@@ -207,6 +250,11 @@ class LLFQVAE_V4(_TokenizerBase):
         self.to_output = nn.Linear(hidden_dim, feature_dim)
         self.feature_dim, self.latent_dim, self.num_codes, self.hidden_dim = feature_dim, latent_dim, num_codes, hidden_dim
         self._init_extras(num_codes)
+
+    _DIST = DIST_NORM
+
+    def _codebook(self):
+        return self.quantizer.codebook
 
     # -- packed weights ---------------------------------------------------------------------
     def _enc_params(self):
@@ -361,6 +409,11 @@ class VQVAE(_TokenizerBase):
         self.embedding = nn.Embedding(num_embeddings, latent_dim)
         self.embedding.weight.data.uniform_(-1 / num_embeddings, 1 / num_embeddings)
         self._init_extras(num_embeddings)
+
+    _DIST = DIST_SQSUM
+
+    def _codebook(self):
+        return self.embedding.weight
 
     def _enc_params(self):
         e = self.encoder
