@@ -48,22 +48,18 @@ const char* lipvq_last_error(void);
 
 /* Options: process-global switches for tests and measurements, set EXPLICITLY -- the library reads no environment variable.
  * Results are identical under every setting (the parity suites run both screens and every kernel shape); only speed changes.
- * value = NULL restores the default.  Unknown name: LIPVQ_EINVAL.  Read per launch unless noted.
+ * value = NULL restores the default.  Unknown name: LIPVQ_EINVAL.  Read per launch.
  *   screen_mode       "coarse" | "fine": force the one-product / three-product screen (default: the shape's measured winner,
  *                     lipvq_screen_is_coarse)
- *   tok_shape         "w8rg1" | "w8rg2" | "w4rg2" | "w4rg1": (waves per workgroup, row groups per wave) of the fused launch
+ *   tok_shape         "w8rg1" | "w4rg1": 8 or 4 waves per workgroup of the fused launch (default: 4 up to 32 768 rows in
+ *                     the parity mode, else 8)
  *   tok_ze_rows       batch size up to which a fused launch stores z_e for its exact stage when nothing else asks for it
- *   tok_grid          workgroups of the fused launch's persistent grid (default 256 = one per CU)
  *   tok_inplace       "0" | "1": the fused launch never / whenever possible lets its waves decide their uncertified rows in place
  *                     instead of listing them for a second kernel (default: whenever possible = K <= 2048 under the three-product
  *                     screen with z_e rows stored)
  *   tok_defer_ze, tok_nt_ze   "0" | "1": the fused launch's two device-dependent schedule choices (the last z_e tile's stores issued
  *                     behind the screen's first stage copies; z_e rows stored nontemporal) -- overrides the defaults (0, 1) and
- *                     whatever lipvq_tokenize_tune_f32 found for the device
- *   tok_ze_ring       "0": the z_e scratch of an in-place launch is written in full (N x D floats) instead of as a 2 048-wave ring
- *   rows_grid, wgrad_chunk, wgrad_per_tile, wgrad_no_wg5, wgrad_rows, embed_bwd_grid, mlp3_small_tiles, mlp3_sub, mlp3_lds_rows
- *                     grid / route choices of the exact-rows, weight-gradient, embedding-backward and MLP kernels (read ONCE, at the
- *                     first launch of that kind: set them before it) */
+ *                     whatever lipvq_tokenize_tune_f32 found for the device */
 int lipvq_set_option(const char* name, const char* value);
 const char* lipvq_get_option(const char* name);        /* NULL = default */
 

@@ -14,12 +14,6 @@
 // rows per chunk: enough chunks that the (chunk x tile) grid fills the chip even for training-step batches -- with one
 // 2048-row chunk a 1024-row batch was ONE dependent chain of 512 load+MFMA steps per wave (248 us per call).
 static inline int wgrad_chunk_rows(int64_t N) {
-    static int forced = -1;                      // LIPVQ_WGRAD_CHUNK: measurement knob
-    if (forced < 0) {
-        const char* e = lq_knob("LIPVQ_WGRAD_CHUNK");
-        forced = e ? atoi(e) : 0;
-    }
-    if (forced > 0) return forced;
     if (N <= 128) return 128;                    // ONE chunk: lipvq_wgrad_f32 then writes the result directly (no reduce launch)
     return N >= 262144 ? 1024 : (N >= 16384 ? 256 : 64);
 }
@@ -455,10 +449,6 @@ extern "C" int lipvq_wgrad_f32(const float* G, const float* H, const int64_t* hi
     float* partW = (float*)workspace;
     float* partB = partW + (size_t)nch * J * Kd;
     const size_t lds = (size_t)32 * 32 * (TI + TJ) * sizeof(float);
-    static int use_wg = -1;                     // LIPVQ_WGRAD_PER_TILE=1 forces the one-wave-per-tile kernel (measurement knob)
-    if (use_wg < 0) use_wg = lq_knob("LIPVQ_WGRAD_PER_TILE") ? 0 : 1;
-    static int use_wg5 = -1;                    // LIPVQ_WGRAD_NO_WG5=1: the single-buffered kernels (measurement knob)
-    if (use_wg5 < 0) use_wg5 = lq_knob("LIPVQ_WGRAD_NO_WG5") ? 0 : 1;
     // one chunk (training-step batches of <= 128 rows): the kernel's slab IS the result, no reduce launch
     const bool direct = nch == 1;
     if (direct) { partW = gW; if (gb) partB = gb; }
@@ -468,7 +458,7 @@ extern "C" int lipvq_wgrad_f32(const float* G, const float* H, const int64_t* hi
     const bool wide = TI > 7 && J % 128 == 0;
     const int TIk = wide ? 4 : TI, ycount = wide ? J / 128 : 1;
     const int ci = tcode(TIk), cj = tcode(TJ);
-    if (use_wg && use_wg5 && ci >= 0 && cj >= 0 && ((J & 3) == 0 || TI == 1) && ((Kd & 3) == 0 || TJ == 1) &&
+    if (ci >= 0 && cj >= 0 && ((J & 3) == 0 || TI == 1) && ((Kd & 3) == 0 || TJ == 1) &&
         (((uintptr_t)G | (uintptr_t)H) & 15) == 0) {
         typedef void (*wg5_fn)(const float*, const float*, const int64_t*, int, float*, float*, int64_t, int, int, int, int);
         wg5_fn kfn = nullptr;
@@ -476,10 +466,7 @@ extern "C" int lipvq_wgrad_f32(const float* G, const float* H, const int64_t* hi
         // 98 KB and more -- one workgroup per CU, every barrier and staging phase exposed -- while at 32 rows two or three
         // workgroups share a CU and fill each other's gaps: 128x64 178 -> 146 us, 64x128 217 -> 174 us at N = 524 288 (the narrow
         // pairs lose 5-15 % at 32 rows; a deeper register prefetch instead of occupancy changed nothing).
-        // LIPVQ_WGRAD_ROWS=32|64 forces one size (measurement knob).
-        static int rows_knob = -1;
-        if (rows_knob < 0) { const char* e = lq_knob("LIPVQ_WGRAD_ROWS"); rows_knob = e ? atoi(e) : 0; }
-        const bool r64 = TIk + TJ <= 10 && (rows_knob == 64 || (rows_knob != 32 && TIk + TJ < 6));
+        const bool r64 = TIk + TJ < 6;
 #define LQ_W5(TI_, TJ_) if (TIk == TI_ && TJ == TJ_) kfn = r64 ? (wg5_fn)wgrad_wg5_kernel<TI_, TJ_, (TI_ + TJ_ <= 10 ? 64 : 32)> : (wg5_fn)wgrad_wg5_kernel<TI_, TJ_, 32>;
         LQ_W5(1, 1) LQ_W5(1, 2) LQ_W5(1, 4) LQ_W5(1, 7) LQ_W5(2, 1) LQ_W5(2, 2) LQ_W5(2, 4) LQ_W5(2, 7)
         LQ_W5(4, 1) LQ_W5(4, 2) LQ_W5(4, 4) LQ_W5(4, 7) LQ_W5(7, 1) LQ_W5(7, 2) LQ_W5(7, 4) LQ_W5(7, 7)
@@ -491,7 +478,7 @@ extern "C" int lipvq_wgrad_f32(const float* G, const float* H, const int64_t* hi
             if (int rc = lipvq_reserve_lds(reserved5[(r64 ? 16 : 0) + ci * 4 + cj], (const void*)kfn, lds5, "wgrad")) return rc;
         hipLaunchKernelGGL(kfn, dim3(nch, ycount), dim3(64 * WGW_WAVES), lds5, st, G, H, hidx, h_act, partW, partB, N, J, Kd,
                            wgrad_chunk_rows(N), J);
-    } else if (use_wg && TI * TJ <= WGW_WAVES * WGW_MAXT && TI <= 8 && TJ <= 8 && lds <= 64 * 1024) {
+    } else if (TI * TJ <= WGW_WAVES * WGW_MAXT && TI <= 8 && TJ <= 8 && lds <= 64 * 1024) {
         const int wide = 32 * (TI > TJ ? TI : TJ);
         const int tpw = (TI * TJ + WGW_WAVES - 1) / WGW_WAVES;
         typedef void (*wg_fn)(const float*, const float*, const int64_t*, int, float*, float*, int64_t, int, int, int, int, int);

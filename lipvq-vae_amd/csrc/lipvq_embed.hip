@@ -688,9 +688,7 @@ int lipvq_embed_rows_bwd_ws_f32(const float* gout, const float* src, const int64
     int64_t* idx_clean = (g_src && idx) ? (int64_t*)((char*)workspace + gvb) : nullptr;
     EmbedBwdArgs a{gout, src, idx, pos, stats, ln_w, g_src, g_pos, g_lnw, g_lnb, N, src_rows,
                    out_batch_stride, out_t_stride, out_offset, T, E, gv, idx_clean};
-    static int grid_knob = -1;                                 // LIPVQ_EMBED_BWD_GRID: measurement knob
-    if (grid_knob < 0) { const char* e = lq_knob("LIPVQ_EMBED_BWD_GRID"); grid_knob = e ? atoi(e) : 1024; }
-    const dim3 grid(grid_knob < T ? T : grid_knob), block(256);   // >= one workgroup per time step (T <= 1024)
+    const dim3 grid(1024 < T ? T : 1024), block(256);          // >= one workgroup per time step (T <= 1024)
     hipStream_t st = (hipStream_t)stream;
     switch ((E + 255) / 256) {
         case 1: hipLaunchKernelGGL(embed_rows_bwd_gv_kernel<1>, grid, block, 0, st, a); break;

@@ -139,22 +139,19 @@ struct TokArgs {
 // percent of the indices differ, all between near-equidistant codes); everything after z_e is the parity path.
 // TRAIN: also stores the pre-activations of the three layers (16-byte stores, lq_tile_store16) -- the forward half of a training
 // step in this one launch instead of mlp3_wg_kernel (with saved pre-activations) + the stand-alone screen + its z_e round trip.
-// RG, WAVES (round 3): a wave owns RG groups of 32 rows per iteration (phase A runs once per group, phase B multiplies all of
-// them against every codebook fragment it reads: lq_screen_core_rg), WAVES waves per workgroup.  (8, RG = 1) is the round-2
-// kernel; (8, 2) halves the LDS fragment reads, |e'|^2 reads and stage hand-overs per MFMA at two waves per SIMD; (4, 2) is
-// ONE wave per SIMD with the whole 512-register file (the D = 128 instance: its A fragments alone are 64 registers per group).
-// COARSE (round 3): phase B runs the one-product screen (lq_screen_core_rg<.., COARSE>): a third of the matrix work, lower-bound
+// WAVES: waves per workgroup, each owning 32 rows per iteration.  8 is the round-2 kernel (two waves per SIMD); 4 is ONE wave per
+// SIMD with the whole 512-register file.
+// COARSE (round 3): phase B runs the one-product screen (lq_screen_core<.., COARSE>): a third of the matrix work, lower-bound
 // bookkeeping, 10-40 % of the rows left to the exact kernel with their two or three candidates -- which then needs z_e, so the
 // host always passes a z_e buffer in this mode (a.ze_out).
 // VQ (round 3): the plain VQVAE's encoder in the same launch (reference backbone.py:14-21: three Linear + ReLU, the last one on the
 // latent itself) -- ReLU instead of GELU / GELU / sigmoid, no Lipschitz scale (the packed weights are the plain ones).  A ReLU
 // latent is unbounded, so the launch-wide fp16 scale of the sigmoid instance does not exist: the row keeps its centred latent
 // in fp32 until all tiles are finished and is then split with its OWN power of two, as the stand-alone screen does.
-template <int S, bool FAST, bool TRAIN, int RG, int WAVES, bool COARSE = false, bool VQ = false>
+template <int S, bool FAST, bool TRAIN, int WAVES, bool COARSE = false, bool VQ = false>
 __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
     static_assert(!(FAST && TRAIN), "training uses the parity arithmetic");
-    static_assert(!VQ || (RG == 1 && !FAST), "the ReLU instance: one row group, parity arithmetic");
-    static_assert(RG == 1 || RG == 2, "one or two row groups per wave");
+    static_assert(!VQ || !FAST, "the ReLU instance: parity arithmetic");
     constexpr int THREADS = WAVES * 64;
     // the one-product screen stages hi-only tiles (half the bytes): twice the tiles per stage in the same LDS, i.e. half the
     // stage hand-overs (vmcnt wait + workgroup barrier + DMA issue) per tile where a stage was ONE tile (S = 8)
@@ -222,15 +219,15 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
     const float fz = lq_pow2f(sz);
     const float fown = lq_pow2f(sz + (int)hdr[3]);
     const float tiny2 = (float)(16 * S) * lq_pow2f(-10 - 2 * sz);
-    const int64_t nblk = (a.N + WAVES * RG * 32 - 1) / (WAVES * RG * 32);
+    const int64_t nblk = (a.N + WAVES * 32 - 1) / (WAVES * 32);
     // this lane's inputs of the NEXT row block (k = 2 q + h, q < XPF), fetched a whole screening phase ahead: the first version
     // loaded each x value right in front of the MFMA that consumed it (four serialised HBM round trips per block)
     constexpr int XPF = 8;                                   // fan-in up to 16 is prefetched; wider inputs load at block start
     const bool x_pref = !FAST && a.A <= 2 * XPF;
-    float xqg[RG][XPF];
+    float xq[XPF];
     constexpr int LANE_W_MIN_S = 8;      // the instances that re-form lane-dependent addresses per use; at S = 4 nothing spills
-    auto load_x = [&](int64_t blk_, const int g_, float (&xq)[XPF]) {
-        int64_t r_ = ((blk_ * WAVES + wave) * RG + g_) * 32 + ln;
+    auto load_x = [&](int64_t blk_, float (&out)[XPF]) {
+        int64_t r_ = (blk_ * WAVES + wave) * 32 + ln;
         r_ = r_ < a.N ? r_ : a.N - 1;
         const int64_t last = a.N * a.A - 1;
         // (S >= 8: the lane half is opaque here -- hipcc had hoisted the XPF partial addresses `x + 4 k` out of the block loop and
@@ -243,13 +240,10 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
             int64_t i_ = r_ * a.A + k;
             i_ = i_ < last ? i_ : last;                      // always a valid address; masked below (no divergent branch)
             const float v = a.x[i_];
-            xq[q] = (k < a.A) ? v : 0.0f;
+            out[q] = (k < a.A) ? v : 0.0f;
         }
     };
-    if (x_pref) {
-#pragma unroll
-        for (int g_ = 0; g_ < RG; ++g_) load_x(blockIdx.x, g_, xqg[g_]);
-    }
+    if (x_pref) load_x(blockIdx.x, xq);
     lq_ws_begin(a.amb_count);
     // ---- once per workgroup: weights (re-laid out 4 k-steps per 16-byte LDS read), biases, mu --------
     {
@@ -362,12 +356,10 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
     // the z_q copy of a row block is deferred to the start of the NEXT block (parity kernel) and routed through LDS (lq_gather_dma):
     // its first round overlaps layer 0, further rounds (wider latents) follow
     constexpr bool DEFER_GATHER = !FAST;
-    int pend_kg[RG];
-    bool pend_okg[RG];
-    int64_t pend_row0g[RG];
+    int pend_k = 0;
+    bool pend_ok = false;
+    int64_t pend_row0 = 0;
     bool have_pend = false;
-#pragma unroll
-    for (int g_ = 0; g_ < RG; ++g_) { pend_kg[g_] = 0; pend_okg[g_] = false; pend_row0g[g_] = 0; }
     // z_e row store of one finished 32-feature tile.  Lane (n, h) holds features 32t + 2r + h (r = 0..15) of row n: the even ones in
     // the low half-wave, the odd ones in the high half.  One v_permlane32_swap per register pair (low half's r >= 8 <-> high
     // half's r < 8) leaves the low lane with features 32t .. 32t+15 and the high lane with 32t+16 .. 32t+31, i.e. four 16-byte
@@ -404,32 +396,25 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
 #ifdef LQ_STAMPS
         st_prev = __builtin_amdgcn_s_memtime();
 #endif
-        ze_shift = a.ze_ring ? (blk - (int64_t)blockIdx.x) * (WAVES * RG * 32) : 0;
-        f16x8 ahg[RG][S], alg[RG][S];
-        // z_e of each group's LAST layer-2 tile, stored behind the screen's first copies -- in the instances with registers to spare
+        ze_shift = a.ze_ring ? (blk - (int64_t)blockIdx.x) * (WAVES * 32) : 0;
+        f16x8 ah[S], al[S];
+        // z_e of the LAST layer-2 tile, stored behind the screen's first copies -- in the instances with registers to spare
         // (S <= 4: cfg2 0.4006 -> 0.3944 ms; at S = 13 the sixteen registers held across the end of layer 2 cost more than the
         // wait they remove: icrt 0.8945 -> 0.9149, profiles/r04_g_ze_store_placement.txt)
         constexpr bool DEFER_ZE = S <= 4 && !TRAIN;
-        f32x16 zdefg[RG];
-        float n2g[RG], a2g[RG], fzg[RG], fowng[RG];
-      // ---- phase A of row group GC: the round-2 block body, on this group's rows / fragments / pending z_q copy ----
-      auto encode_group = [&](auto GC) {
-        constexpr int g = decltype(GC)::value;
+        f32x16 zdef;
+        float row_n2, row_a2, row_fz, row_fown;              // phase A's row statistics and scales (the VQ instance: the row's own)
+      // ---- phase A: the wave's 32 rows through the encoder, split into the screen's fp16 fragments ----
+      auto encode = [&]() {
         // the lane index the LDS weight reads are addressed with, opaque per row block in the instances that spill (S >= 8): as loop
         // invariants hipcc kept the lanes' LDS addresses in registers from the kernel's first lines and spilled them -- a reload is a
         // vector-memory load, and `s_waitcnt vmcnt(0)` in front of its use also waits for every store and copy in flight
         int lane_w = lane;
         if constexpr (S >= LANE_W_MIN_S) asm volatile("" : "+v"(lane_w));
         const int h_w = lane_w >> 5;                         // (the centring vector's LDS reads: not hoisted out of the block loop either)
-        const int64_t row0 = ((blk * WAVES + wave) * RG + g) * 32;
+        const int64_t row0 = (blk * WAVES + wave) * 32;
         const int64_t row = row0 + ln;
         const int64_t rowc = row < a.N ? row : a.N - 1;
-        f16x8 (&ah)[S] = ahg[g];
-        f16x8 (&al)[S] = alg[g];
-        const float (&xq)[XPF] = xqg[g];
-        const int pend_k = pend_kg[g];
-        const bool pend_ok = pend_okg[g];
-        const int64_t pend_row0 = pend_row0g[g];
         float n2 = 0.0f, a2lo = 0.0f, amax = 0.0f;
         float zt[VQ ? T2 : 1][16];                           // VQ: the centred latent in fp32 until the row's scale is known
         // sigmoid, centring, row statistics and the optional z_e store of one finished 32-feature tile
@@ -483,11 +468,11 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                 if constexpr (COARSE) a2lo = lq_fma(rs, rs, a2lo);
             }
           }
-            // z_e rows for the exact stage (store_ze_tile).  The LAST tile's are not stored here: its sixteen values wait in zdefg and
-            // are stored behind the screen's first stage copies (lq_screen_core_rg, DEFER) -- in front of them their write
+            // z_e rows for the exact stage (store_ze_tile).  The LAST tile's are not stored here: its sixteen values wait in zdef and
+            // are stored behind the screen's first stage copies (lq_screen_core, DEFER) -- in front of them their write
             // acknowledgements stood between every wave and "stage 0 has landed" (vmcnt retires in order)
             if (a.ze_out) {
-                if (DEFER_ZE && a.defer_ze && t == T2 - 1) zdefg[g] = acc;
+                if (DEFER_ZE && a.defer_ze && t == T2 - 1) zdef = acc;
                 else store_ze_tile(row, t, acc);
             }
         };
@@ -809,16 +794,16 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
         }
         LQ_STAMP(2);
         n2 += __shfl_xor(n2, 32, 64);
-        n2g[g] = n2;
-        fzg[g] = fz;
-        fowng[g] = fown;
+        row_n2 = n2;
+        row_fz = fz;
+        row_fown = fown;
         if constexpr (VQ) {
             // the row's own scale (block floating point, lipvq_screen.h): its largest |z'| lands in [2^13, 2^14)
             amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
             const int szr = lq_scale_exp(amax);
             const float fzr = lq_pow2f(szr);
-            fzg[g] = fzr;
-            fowng[g] = lq_pow2f(szr + (int)hdr[3]);
+            row_fz = fzr;
+            row_fown = lq_pow2f(szr + (int)hdr[3]);
 #pragma unroll
             for (int t = 0; t < T2; ++t)
 #pragma unroll
@@ -833,85 +818,66 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                 }
         }
         if constexpr (COARSE) a2lo += __shfl_xor(a2lo, 32, 64);
-        a2g[g] = a2lo;
+        row_a2 = a2lo;
       };
-        encode_group(std::integral_constant<int, 0>{});
-        if constexpr (RG > 1) encode_group(std::integral_constant<int, 1>{});
+        encode();
         float frow[16];                                       // one scale for every row here (see fz): a single register
-        if constexpr (VQ) lq_row_factors(fowng[0], lane, frow);  // (the ReLU instance: every row its own)
+        if constexpr (VQ) lq_row_factors(row_fown, lane, frow);  // (the ReLU instance: every row its own)
         else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) frow[r] = fown;
         }
-        // ================= phase B: MFMA screen (lq_screen_core_rg, lipvq_screen.h) ==============
-        float m1g[RG][16], m2g[RG][16];
-        int k1g[RG][16];
+        // ================= phase B: MFMA screen (lq_screen_core, lipvq_screen.h) ==============
+        float m1[16], m2[16];
+        int k1[16];
 #pragma unroll
-        for (int g_ = 0; g_ < RG; ++g_)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { m1g[g_][r] = INFINITY; m2g[g_][r] = INFINITY; k1g[g_][r] = 0; }
+        for (int r = 0; r < 16; ++r) { m1[r] = INFINITY; m2[r] = INFINITY; k1[r] = 0; }
         LQ_STAMP(3);
-        if (x_pref) {                                         // next row block's inputs: a whole phase ahead
-#pragma unroll
-            for (int g_ = 0; g_ < RG; ++g_) load_x(blk + gridDim.x < nblk ? blk + gridDim.x : blk, g_, xqg[g_]);
-        }
+        if (x_pref) load_x(blk + gridDim.x < nblk ? blk + gridDim.x : blk, xq);      // next row block's inputs: a whole phase ahead
         // (S = 13: 104 registers of A fragments leave no room for an index array; COARSE: the packed index's perturbation is far
         // below the one-product margin at any S)
         constexpr bool PACKF = S <= 4 || S > 8 || COARSE;
-        float zng[RG], znrg[RG][16];                       // COARSE: the rows' error scale (lq_track_part), in frow's register layout
+        const float zn = COARSE ? lq_coarse_zn(row_a2, row_n2, row_fz, row_fown, __uint_as_float(hdr[5])) : 0.0f;
+        float znr[16];                                        // COARSE: the rows' error scale (lq_track_part), in frow's register layout
+        if constexpr (COARSE) lq_row_factors(zn, lane, znr);
+        else {
 #pragma unroll
-        for (int g_ = 0; g_ < RG; ++g_) {
-            zng[g_] = COARSE ? lq_coarse_zn(a2g[g_], n2g[g_], fzg[g_], fowng[g_], __uint_as_float(hdr[5])) : 0.0f;
-            if constexpr (COARSE) lq_row_factors(zng[g_], lane, znrg[g_]);
-            else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) znrg[g_][r] = 0.0f;
-            }
+            for (int r = 0; r < 16; ++r) znr[r] = 0.0f;
         }
         const bool have_def = DEFER_ZE && a.defer_ze && a.ze_out != nullptr;
-        auto deferred_ze = [&]() {
-#pragma unroll
-            for (int g_ = 0; g_ < RG; ++g_) store_ze_tile(((blk * WAVES + wave) * RG + g_) * 32 + ln, T2 - 1, zdefg[g_]);
-        };
-        lq_screen_core_rg<S, THREADS, TCF, NBF, PACKF, RG, COARSE, 4 * RG, decltype(deferred_ze)>(ahg, alg, tiles, L.ntiles, stage0, tid, frow, znrg, m1g, m2g, k1g, have_def, deferred_ze);
+        auto deferred_ze = [&]() { store_ze_tile((blk * WAVES + wave) * 32 + ln, T2 - 1, zdef); };
+        lq_screen_core<S, THREADS, TCF, NBF, PACKF, COARSE, 4, decltype(deferred_ze)>(ah, al, tiles, L.ntiles, stage0, tid, frow, znr, m1, m2, k1, have_def, deferred_ze);
         LQ_STAMP(4);
         const unsigned keep_mask = PACKF ? ~((1u << lq_pack_bits(L.ntiles)) - 1u) : 0xffffffffu;
         unsigned char* scratch = stage0 + (size_t)wave * WSLICE;
-#pragma unroll
-        for (int g_ = 0; g_ < RG; ++g_) {
-            const int64_t row0 = ((blk * WAVES + wave) * RG + g_) * 32;
-            const int64_t row = row0 + ln;
-            int my_k;
-            LqDecision dec;
-            bool certified = lq_screen_decide<PACKF, COARSE>(m1g[g_], m2g[g_], k1g[g_], scratch, hdr, n2g[g_], fowng[g_], a.gamma, a.K, a.D, lane,
-                                                             my_k, dec, PACKF ? lq_pow2f(lq_pack_bits(L.ntiles) - 23) : 0.0f, keep_mask,
-                                                             zng[g_], tiles, tile_bytes, ScreenCfg<S, TCF, COARSE>::FRAG_BYTES);
-            const bool row_sane = VQ || n2g[g_] >= tiny2;             // (see fz above; such a row's screen values bound nothing)
-            certified = certified && row_sane;
-            // in place (round 4; small codebooks under the three-product screen): this wave decides its uncertified rows itself
-            // (lq_screen_decide_inplace) and they go on as certified ones -- no list kernel behind the launch
-            if (!COARSE && a.inplace)
-                certified = lq_screen_decide_inplace<PACKF, 2 * S, VQ ? LIPVQ_DIST_SQSUM : LIPVQ_DIST_NORM>(
-                    dec, certified, row_sane, my_k, row0 - ze_shift, row < a.N, a.amb_count, a.ze_out, a.cb, a.K, lane, keep_mask, scratch);
-            else
-                lq_screen_emit<PACKF>(dec, certified, row_sane, my_k, row, row < a.N, a.amb_count, a.amb_list, a.N, a.K, lane, keep_mask, scratch);
-            if (h == 0 && row < a.N && certified) {
-                a.idx[row] = (int64_t)my_k;
-                if (use_hist) atomicAdd(&hist[my_k], 1u);              // LDS atomic
-            }
-            if (a.usage && !use_hist) lq_usage_add(a.usage, my_k, h == 0 && row < a.N && certified);
-            if (DEFER_GATHER) { pend_kg[g_] = my_k; pend_okg[g_] = certified; pend_row0g[g_] = row0; }
-            else if (a.zq) lq_screen_gather(a.cb, a.zq, my_k, certified, row0, a.N, a.D, lane);
-            if (RG > 1 && g_ + 1 < RG) __builtin_amdgcn_wave_barrier();     // the next group's transposes reuse this wave's scratch
+        const int64_t row0 = (blk * WAVES + wave) * 32;
+        const int64_t row = row0 + ln;
+        int my_k;
+        LqDecision dec;
+        bool certified = lq_screen_decide<PACKF, COARSE>(m1, m2, k1, scratch, hdr, row_n2, row_fown, a.gamma, a.K, a.D, lane,
+                                                         my_k, dec, PACKF ? lq_pow2f(lq_pack_bits(L.ntiles) - 23) : 0.0f, keep_mask,
+                                                         zn, tiles, tile_bytes, ScreenCfg<S, TCF, COARSE>::FRAG_BYTES);
+        const bool row_sane = VQ || row_n2 >= tiny2;              // (see fz above; such a row's screen values bound nothing)
+        certified = certified && row_sane;
+        // in place (round 4; small codebooks under the three-product screen): this wave decides its uncertified rows itself
+        // (lq_screen_decide_inplace) and they go on as certified ones -- no list kernel behind the launch
+        if (!COARSE && a.inplace)
+            certified = lq_screen_decide_inplace<PACKF, 2 * S, VQ ? LIPVQ_DIST_SQSUM : LIPVQ_DIST_NORM>(
+                dec, certified, row_sane, my_k, row0 - ze_shift, row < a.N, a.amb_count, a.ze_out, a.cb, a.K, lane, keep_mask, scratch);
+        else
+            lq_screen_emit<PACKF>(dec, certified, row_sane, my_k, row, row < a.N, a.amb_count, a.amb_list, a.N, a.K, lane, keep_mask, scratch);
+        if (h == 0 && row < a.N && certified) {
+            a.idx[row] = (int64_t)my_k;
+            if (use_hist) atomicAdd(&hist[my_k], 1u);              // LDS atomic
         }
+        if (a.usage && !use_hist) lq_usage_add(a.usage, my_k, h == 0 && row < a.N && certified);
+        if (DEFER_GATHER) { pend_k = my_k; pend_ok = certified; pend_row0 = row0; }
+        else if (a.zq) lq_screen_gather(a.cb, a.zq, my_k, certified, row0, a.N, a.D, lane);
         if (DEFER_GATHER) have_pend = true;
         LQ_STAMP(5);
         LQ_STAMP(6);
     }
-    if (DEFER_GATHER && have_pend && a.zq) {                                                                          // the last block's
-#pragma unroll
-        for (int g_ = 0; g_ < RG; ++g_) lq_screen_gather(a.cb, a.zq, pend_kg[g_], pend_okg[g_], pend_row0g[g_], a.N, a.D, lane);
-    }
+    if (DEFER_GATHER && have_pend && a.zq) lq_screen_gather(a.cb, a.zq, pend_k, pend_ok, pend_row0, a.N, a.D, lane);   // the last block's
 #ifdef LQ_STAMPS
     if (lane == 0) {
         long long* dbg = reinterpret_cast<long long*>(a.amb_list + (a.N / 2 & ~1)) + ((size_t)blockIdx.x * WAVES + wave) * 16;
@@ -936,21 +902,18 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
 }
 
 // two waves per SIMD (8 waves, 256 registers each) / one wave per SIMD (4 waves, the whole 512-register file each)
-template <int S, bool FAST, bool TRAIN = false, int RG = 1, bool COARSE = false, bool VQ = false>
+template <int S, bool FAST, bool TRAIN = false, bool COARSE = false, bool VQ = false>
 __global__ __launch_bounds__(FUSED_THREADS) void tokenize_kernel(TokArgs a) {
-    tokenize_body<S, FAST, TRAIN, RG, FUSED_WAVES, COARSE, VQ>(a);
+    tokenize_body<S, FAST, TRAIN, FUSED_WAVES, COARSE, VQ>(a);
 }
-template <int S, bool FAST, bool TRAIN, int RG, bool COARSE = false>
+template <int S, bool FAST, bool TRAIN, bool COARSE = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void tokenize_kernel_w4(TokArgs a) {
-    tokenize_body<S, FAST, TRAIN, RG, 4, COARSE>(a);
+    tokenize_body<S, FAST, TRAIN, 4, COARSE>(a);
 }
 
-// Which (waves per workgroup, row groups per wave) instance runs.  Measured on one box (profiles/r03_d_tokenize_shapes_ab.txt):
-//   cfg2 (S = 4): w8rg1 0.468 ms, w8rg2 0.480 (99 spilled registers), w4rg2 0.526, w4rg1 0.549
-//   cfg3 (S = 8): w8rg1 2.98 ms,  w4rg2 3.05 (no spills, half the LDS reads per MFMA -- and nothing gained), w4rg1 3.53
-//   icrt (S = 13): w8rg1 1.19 ms, w4rg1 1.27
-// so the round-2 shape stays the default everywhere; the others remain as instances the parity tests run
-// (LIPVQ_TOK_SHAPE=w8rg1|w8rg2|w4rg2|w4rg1: measurement knob; results identical).
+// Which instance runs: w8rg1 (8 waves per workgroup, one 32-row group per wave) is the default at every latent width -- cfg2 0.468 ms
+// against w4rg1 0.549, cfg3 2.98 against 3.53, icrt 1.19 against 1.27, same box (profiles/r03_d_tokenize_shapes_ab.txt).  Two row
+// groups per wave (round 3) lost everywhere (cfg2 w8rg2 0.480 ms with 99 spilled registers, cfg3 w4rg2 3.05) and was dropped.
 // Schedule choices of the fused launch with IDENTICAL results whose better setting depends on the DEVICE (round 4,
 // profiles/r04_i_clock_ab.txt): MI355X devices hold different clocks under the same kernel (MI355X_MICROARCH.md, DVFS give-back items
 // 3-5).  With the last tile's z_e stores deferred and nontemporal, cfg2's launch takes 0.387 ms on a device that keeps 2.22 GHz under
@@ -977,15 +940,14 @@ static LqSchedule lq_schedule(int ring = 0) {
 // 131 072 rows 0.1096 -> 0.1054, 262 144 rows 0.2069 -> 0.1993, 524 288 rows 0.3910 -> 0.3863.  (With the last z_e tile's stores
 // deferred -- the schedule of the round's first builds -- the full batch measured level, 0.3929 -> 0.3936, and a size rule kept
 // it on the list kernel; without the deferral the wave that stops ~2 us for a row no longer costs its workgroup the 6 us saved.)
-// (LIPVQ_TOK_INPLACE=0 / 1: measurement knob -- never / whenever possible; LQ_INPLACE_MAX_ROWS: size limit; results identical)
-#define LQ_INPLACE_MAX_ROWS 2147483647
-static int lq_inplace(bool have_ze, int coarse, int K, int64_t N) {
+// (tok_inplace = 0 / 1: never / whenever possible; results identical)
+static int lq_inplace(bool have_ze, int coarse, int K) {
     const bool can = have_ze && !coarse && K <= LQ_LISTS_ALL_K;
     if (const char* e = lq_knob("LIPVQ_TOK_INPLACE")) {
         if (e[0] == '0') return 0;
         if (e[0] == '1') return can ? 1 : 0;
     }
-    return (can && N <= LQ_INPLACE_MAX_ROWS) ? 1 : 0;
+    return can ? 1 : 0;
 }
 // Ring mode of the z_e scratch (round 4, late): where the launch decides its uncertified rows in place and the caller wants no z_e,
 // nothing reads a row's z_e after its wave has decided the row block -- so every block's 32 rows of a wave go to the SAME 32 rows of
@@ -993,43 +955,34 @@ static int lq_inplace(bool have_ze, int coarse, int K, int64_t N) {
 // alternating passes (profiles/r04_n_ze_ring_ab.txt): cfg2 0.3848 -> 0.3829 ms.  The stores still leave the L2 (WRITE_SIZE 275 -> 250
 // MB per launch, HBM traffic 298 -> 270 MB: this L2 writes the rows through whether or not they are overwritten 50 us later), so the
 // gain is the read side of the in-place decisions and 118 MB of address range less, not the 134 MB of stores hoped for.
-// (LIPVQ_TOK_ZE_RING=0: measurement knob, the full scratch.)
-static int lq_ze_ring(bool caller_wants_ze, int inplace) {
-    if (const char* e = lq_knob("LIPVQ_TOK_ZE_RING")) if (e[0] == '0') return 0;
-    return (!caller_wants_ze && inplace) ? 1 : 0;
-}
-struct TokShape { int waves, rg; };
+static int lq_ze_ring(bool caller_wants_ze, int inplace) { return (!caller_wants_ze && inplace) ? 1 : 0; }
+struct TokShape { int waves; };
 static TokShape tok_shape_env() {              // read per launch (a getenv: nanoseconds), so that a test can switch shapes in-process
     const char* e = lq_knob("LIPVQ_TOK_SHAPE");
-    TokShape t{0, 0};
-    if (e && !strcmp(e, "w8rg1")) t = {8, 1};
-    if (e && !strcmp(e, "w8rg2")) t = {8, 2};
-    if (e && !strcmp(e, "w4rg2")) t = {4, 2};
-    if (e && !strcmp(e, "w4rg1")) t = {4, 1};
+    TokShape t{0};
+    if (e && !strcmp(e, "w8rg1")) t = {8};
+    if (e && !strcmp(e, "w4rg1")) t = {4};
     return t;
 }
 template <int S, bool FAST, bool TRAIN>
 static TokShape tok_shape(int64_t N) {
-    constexpr bool HAS_RG2 = !FAST && !TRAIN && S <= 8;      // the instances that exist (launch_tokenize)
     constexpr bool HAS_W4 = !FAST && !TRAIN;
     TokShape t = tok_shape_env();
     // Size rule (round 4): a launch of at most 32 768 rows is at most one 32-row block per SIMD of the chip -- as 4-wave workgroups
     // (one wave per SIMD, 256 CUs) instead of 8-wave ones (two per SIMD on half the CUs): same box, 32 768 rows, w8rg1 -> w4rg1:
     // icrt 0.137 -> 0.099 ms, cfg3 0.205 -> 0.184, cfg2 0.0528 -> 0.0509 (profiles/r04_k_small_launch_shape_ab.txt).  An explicit
     // tok_shape is honoured at any batch size.
-    if (t.waves == 0) t = (HAS_W4 && N <= 4 * 32 * 256) ? TokShape{4, 1} : TokShape{8, 1};
-    if ((t.rg == 2 && !HAS_RG2) || (t.waves == 4 && !HAS_W4)) t = {8, 1};
+    if (t.waves == 0) t = (HAS_W4 && N <= 4 * 32 * 256) ? TokShape{4} : TokShape{8};
+    if (t.waves == 4 && !HAS_W4) t = {8};
     return t;
 }
 
 template <typename KFN>
-static int launch_tokenize_as(KFN kfn, LqLdsReserve& reserved, const TokArgs& a, size_t lds, int waves, int rg, hipStream_t st) {
+static int launch_tokenize_as(KFN kfn, LqLdsReserve& reserved, const TokArgs& a, size_t lds, int waves, hipStream_t st) {
     if (int rc = lipvq_reserve_lds(reserved, (const void*)kfn, lds, "tokenize")) return rc;
-    const int64_t unit = (int64_t)waves * rg * 32;
+    const int64_t unit = (int64_t)waves * 32;
     const int64_t nblk = (a.N + unit - 1) / unit;
-    int64_t cap = 256;                                              // one persistent workgroup per CU
-    // (LIPVQ_TOK_GRID: measurement knob -- e.g. 252 leaves four CUs to a collective's kernel, scripts/dev/rccl_contention.py)
-    if (const char* e = lq_knob("LIPVQ_TOK_GRID")) { const int64_t g_ = atoll(e); if (g_ > 0) cap = g_; }
+    const int64_t cap = 256;                                        // one persistent workgroup per CU
     const int64_t blocks = nblk < cap ? nblk : cap;
     hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(waves * 64), lds, st, a);
     return check_launch("tokenize");
@@ -1040,22 +993,17 @@ static int launch_tokenize(const TokArgs& a, hipStream_t st) {
     const size_t lds = fused_lds_bytes<S, FAST>(a.A, a.K);
     if (lds > 160 * 1024) return fail(LIPVQ_EUNSUPPORTED, "tokenize: %zu B of LDS needed", lds);
     const TokShape sh = tok_shape<S, FAST, TRAIN>(a.N);
-    static LqLdsReserve reserved[6];            // per instantiation and shape: per-device, thread-safe (lipvq_common.h)
+    static LqLdsReserve reserved[4];            // per instantiation and shape: per-device, thread-safe (lipvq_common.h)
     if constexpr (!FAST && !TRAIN && S >= 8) {  // (one wave per SIMD with the whole register file: the instances that spill at two)
-        if (a.coarse && sh.waves == 4 && sh.rg == 1)
-            return launch_tokenize_as(tokenize_kernel_w4<S, FAST, TRAIN, 1, true>, reserved[5], a, lds, 4, 1, st);
+        if (a.coarse && sh.waves == 4) return launch_tokenize_as(tokenize_kernel_w4<S, FAST, TRAIN, true>, reserved[3], a, lds, 4, st);
     }
     if constexpr (!FAST) {                      // (parity and training instances; the training forward writes z_e anyway)
-        if (a.coarse) return launch_tokenize_as(tokenize_kernel<S, FAST, TRAIN, 1, true>, reserved[4], a, lds, 8, 1, st);
+        if (a.coarse) return launch_tokenize_as(tokenize_kernel<S, FAST, TRAIN, true>, reserved[2], a, lds, 8, st);
     }
     if constexpr (!FAST && !TRAIN) {
-        if (sh.waves == 4 && sh.rg == 1) return launch_tokenize_as(tokenize_kernel_w4<S, FAST, TRAIN, 1>, reserved[3], a, lds, 4, 1, st);
+        if (sh.waves == 4) return launch_tokenize_as(tokenize_kernel_w4<S, FAST, TRAIN>, reserved[1], a, lds, 4, st);
     }
-    if constexpr (!FAST && !TRAIN && S <= 8) {
-        if (sh.waves == 8 && sh.rg == 2) return launch_tokenize_as(tokenize_kernel<S, FAST, TRAIN, 2>, reserved[1], a, lds, 8, 2, st);
-        if (sh.waves == 4 && sh.rg == 2) return launch_tokenize_as(tokenize_kernel_w4<S, FAST, TRAIN, 2>, reserved[2], a, lds, 4, 2, st);
-    }
-    return launch_tokenize_as(tokenize_kernel<S, FAST, TRAIN, 1>, reserved[0], a, lds, 8, 1, st);
+    return launch_tokenize_as(tokenize_kernel<S, FAST, TRAIN>, reserved[0], a, lds, 8, st);
 }
 
 // the plain VQVAE's instances (ReLU encoder, per-row scales): both screens
@@ -1065,11 +1013,11 @@ static int launch_tokenize_vq(const TokArgs& a, hipStream_t st) {
     if (lds > 160 * 1024) return fail(LIPVQ_EUNSUPPORTED, "vq_tokenize: %zu B of LDS needed", lds);
     static LqLdsReserve reserved[4];
     if (a.pre0) {                                              // the training forward: the three pre-activations are stored too
-        if (a.coarse) return launch_tokenize_as(tokenize_kernel<S, false, true, 1, true, true>, reserved[3], a, lds, 8, 1, st);
-        return launch_tokenize_as(tokenize_kernel<S, false, true, 1, false, true>, reserved[2], a, lds, 8, 1, st);
+        if (a.coarse) return launch_tokenize_as(tokenize_kernel<S, false, true, true, true>, reserved[3], a, lds, 8, st);
+        return launch_tokenize_as(tokenize_kernel<S, false, true, false, true>, reserved[2], a, lds, 8, st);
     }
-    if (a.coarse) return launch_tokenize_as(tokenize_kernel<S, false, false, 1, true, true>, reserved[1], a, lds, 8, 1, st);
-    return launch_tokenize_as(tokenize_kernel<S, false, false, 1, false, true>, reserved[0], a, lds, 8, 1, st);
+    if (a.coarse) return launch_tokenize_as(tokenize_kernel<S, false, false, true, true>, reserved[1], a, lds, 8, st);
+    return launch_tokenize_as(tokenize_kernel<S, false, false, false, true>, reserved[0], a, lds, 8, st);
 }
 
 // fp16 MFMA fragments of the encoder stack for the fast mode: [layer][tile t][step s][lane][8 halfs] with
@@ -1204,7 +1152,7 @@ static int tokenize_impl(const float* x, const float* packed, const void* packed
     }
     TokArgs a{x, packed, (const unsigned char*)packed16, (const unsigned char*)prep, codebook, idx, zq,
               (unsigned long long*)usage, ze_buf, amb_count, amb_list, w2q, pre0, pre1, pre2, N, A, D, K, LIPVQ_SCREEN_GAMMA, coarse,
-              lq_inplace(ze_buf != nullptr, coarse, K, N), 0, 0, 0};
+              lq_inplace(ze_buf != nullptr, coarse, K), 0, 0, 0};
     a.ze_ring = lq_ze_ring(ze_out != nullptr, a.inplace);
     a.defer_ze = lq_schedule(a.ze_ring).defer_ze;
     a.nt_ze = lq_schedule(a.ze_ring).nt_ze;
@@ -1295,7 +1243,7 @@ extern "C" int lipvq_tokenize_tune_f32(const float* x, const float* packed, cons
     if (rc) { g_tuned[dev].store(before, std::memory_order_relaxed); return rc; }
     // the default of this launch's mode stays unless another combination is faster by more than half a percent (ties are common, and
     // the ring's plain stores are what keeps its rows out of HBM)
-    const int ring = lq_ze_ring(ze_out != nullptr, lq_inplace(true, lq_screen_coarse(lq_screen_S(D), K), K, N));
+    const int ring = lq_ze_ring(ze_out != nullptr, lq_inplace(true, lq_screen_coarse(lq_screen_S(D), K), K));
     const int dflt = LQ_DEFAULT_DEFER_ZE | ((ring ? 0 : 1) << 1);
     int win = dflt;
     for (int c = 0; c < 4; ++c) if (best[c] < 0.995f * best[dflt] && best[c] < best[win]) win = c;
@@ -1345,7 +1293,7 @@ static int vq_tokenize_impl(const float* x, const float* packed, const float* co
     }
     const int coarse = lq_screen_coarse(lq_screen_S(D), K);
     TokArgs a{x, packed, nullptr, (const unsigned char*)prep, codebook, idx, zq, (unsigned long long*)usage, ze_out, amb_count,
-              amb_list, w2q, pre0, pre1, pre2, N, A, D, K, LIPVQ_SCREEN_GAMMA, coarse, lq_inplace(true, coarse, K, N),
+              amb_list, w2q, pre0, pre1, pre2, N, A, D, K, LIPVQ_SCREEN_GAMMA, coarse, lq_inplace(true, coarse, K),
               lq_schedule().defer_ze, lq_schedule().nt_ze, 0};
     int rc;
     switch (D) {

@@ -764,35 +764,21 @@ static mlp3_fn mlp3_select(int T0, int T1) {
     return nullptr;
 }
 
-// tiles up to which the 8-waves-per-tile kernel is used: all of them, unless LIPVQ_MLP3_SMALL_TILES says otherwise
-// (measurement knob: 0 forces the one-wave-per-tile kernel)
-static int64_t mlp3_small_tiles() {
-    static int64_t v = -1;
-    if (v < 0) {
-        const char* e = lq_knob("LIPVQ_MLP3_SMALL_TILES");
-        v = e ? atoll(e) : INT64_MAX;
-    }
-    return v;
-}
-
 template <bool BWD>
 static int launch_mlp3_wg(const Mlp3Args& a, hipStream_t st, const char* what, bool* done) {
     *done = false;
     const size_t plane = ((size_t)2 * ((a.K0 + 1) / 2) + a.J0 + a.J1) * MLPS_LD * sizeof(float);
     // two 32-row sub-tiles per workgroup from 4 096 rows on (more waves busy per layer, barriers shared by 64 rows); training-step
-    // batches keep one, so that N = 80 still spreads over three workgroups.  LIPVQ_MLP3_SUB=1|2: measurement knob.
-    static int forced = -1;
-    if (forced < 0) { const char* e = lq_knob("LIPVQ_MLP3_SUB"); forced = e ? atoi(e) : 0; }
+    // batches keep one, so that N = 80 still spreads over three workgroups.
     // (two only while two such workgroups still share a CU's LDS: the 208-wide decoder input is faster with one; four is slower
     // everywhere: 3.75 -> 4.25 ms for the cfg2 training step)
-    int nsub = (forced == 1 || forced == 2 || forced == 4) ? forced : ((a.N >= 4096 && 2 * plane <= 80 * 1024) ? 2 : 1);
-    while (nsub > 1 && plane * nsub > 150 * 1024) nsub >>= 1;
+    const int nsub = (a.N >= 4096 && 2 * plane <= 80 * 1024) ? 2 : 1;
     const int64_t ntiles = (a.N + 32 * nsub - 1) / (32 * nsub);
     const size_t lds = plane * nsub;
-    if ((a.N + 31) / 32 > mlp3_small_tiles() || lds > 150 * 1024) return LIPVQ_OK;
-    static LqLdsReserve reserved[3];            // per instantiation: per-device, thread-safe (lipvq_common.h)
-    auto kfn = nsub == 4 ? mlp3_wg_kernel<BWD, 4> : nsub == 2 ? mlp3_wg_kernel<BWD, 2> : mlp3_wg_kernel<BWD, 1>;
-    if (int rc = lipvq_reserve_lds(reserved[nsub == 4 ? 2 : nsub - 1], (const void*)kfn, 150 * 1024, what)) return rc;
+    if (lds > 150 * 1024) return LIPVQ_OK;
+    static LqLdsReserve reserved[2];            // per instantiation: per-device, thread-safe (lipvq_common.h)
+    auto kfn = nsub == 2 ? mlp3_wg_kernel<BWD, 2> : mlp3_wg_kernel<BWD, 1>;
+    if (int rc = lipvq_reserve_lds(reserved[nsub - 1], (const void*)kfn, 150 * 1024, what)) return rc;
     if (ntiles > 0x7fffffffLL) return LIPVQ_OK;
     hipLaunchKernelGGL(kfn, dim3((unsigned)ntiles), dim3(64 * MLPS_WAVES), lds, st, a);
     *done = true;
@@ -800,16 +786,9 @@ static int launch_mlp3_wg(const Mlp3Args& a, hipStream_t st, const char* what, b
 }
 
 
-// rows from which the LDS-resident kernel is used (LIPVQ_MLP3_LDS_ROWS: measurement knob; 0 = never)
-static int64_t mlp3_lds_rows() {
-    static int64_t v = -1;
-    if (v < 0) {
-        const char* e = lq_knob("LIPVQ_MLP3_LDS_ROWS");
-        v = e ? atoll(e) : 65536;              // crossover with mlp3_wg_kernel (backward: 35 vs 56 us at 32 768, 67 vs 65 at 65 536, 145 vs 117 at 131 072)
-        if (v == 0) v = INT64_MAX;
-    }
-    return v;
-}
+// rows from which the LDS-resident kernel is used: the crossover with mlp3_wg_kernel (backward: 35 vs 56 us at 32 768, 67 vs 65 at
+// 65 536, 145 vs 117 at 131 072)
+constexpr int64_t LQ_MLP3_LDS_ROWS = 65536;
 
 template <bool BWD, int FUSE>
 static mlp3_fn mlp3_lds_select(int T0, int T1) {      // the reference's hidden widths (64, 128) only; others keep mlp3_wg_kernel
@@ -821,7 +800,7 @@ static mlp3_fn mlp3_lds_select(int T0, int T1) {      // the reference's hidden 
 
 // does the LDS-resident kernel take this chain?  (also what lipvq_mlp3_bwd_vq_supported answers: only that kernel folds the VQ terms)
 static bool mlp3_lds_takes(int64_t N, int K0, int J0, int J1, int J2) {
-    if (N < mlp3_lds_rows()) return false;
+    if (N < LQ_MLP3_LDS_ROWS) return false;
     const PackedLayout L = packed_layout(K0, J0, J1, J2);
     return L.total * sizeof(float) <= 156 * 1024 && ((J0 == 64 && J1 == 128) || (J0 == 128 && J1 == 64));
 }

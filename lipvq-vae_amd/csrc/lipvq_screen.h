@@ -143,7 +143,7 @@ __device__ __forceinline__ void lq_track_part(const f32x16& acc, float e2, float
                                               int id, unsigned keep_mask, float (&m1)[16], float (&m2)[16], int (&k1)[16]) {
 #pragma unroll
     for (int r = LO; r < HI; ++r) {
-        // COARSE: the chain started from |e'|^2 f - w (lq_screen_core_rg seeds it), the accumulator IS the booked value
+        // COARSE: the chain started from |e'|^2 f - w (lq_screen_core seeds it), the accumulator IS the booked value
         const float v = COARSE ? acc[r] : lq_fma(e2, frow[r], acc[r]);
         lq_track_one<PACK>(v, id, keep_mask, m1[r], m2[r], k1[r]);
     }
@@ -199,23 +199,21 @@ constexpr size_t lq_ring_bytes() { return (size_t)NB * ScreenCfg<S, TC_>::STAGE_
 // number of low mantissa bits that hold the tile index in PACK mode, and the relative perturbation that costs
 __host__ __device__ static inline int lq_pack_bits(int ntiles) { int b = 1; while ((1 << b) < ntiles) ++b; return b; }
 
-// RG row groups per wave (round 3): the wave multiplies RG x 32 rows against every tile, so that one pair of B-fragment reads,
-// one |e'|^2 read, one stage hand-over (wait, barrier, DMA issue) serve RG x 3 MFMAs per k-step instead of 3, and consecutive
-// MFMAs go to different accumulators.  ah/al/m1/m2/k1 carry the group as their leading dimension.
+// The screen loop of a wave's 32 rows (screen_kernel, tokenize_kernel): ah/al are the rows' fp16 fragments, m1/m2/k1 their running
+// best and second-best bounds and best code.
 // DEFER (round 4): the caller's last vector-memory stores before the screen (the fused launch's z_e rows of its last layer-2 tile:
 // NDEF store instructions per wave when `have_def`) are issued by `deferred()` BEHIND the prologue's stage copies instead of in
 // front of them.  vmcnt retires in order: issued in front, their write acknowledgements (microseconds) stood between every wave
 // and "stage 0 has landed" -- 3.5 % of the cfg2 launch (profiles/r04_g_ze_store_placement.txt).  Behind the copies, the prologue's
 // wait and the first hand-over simply leave NDEF more operations outstanding.
 struct LqNoDeferred { __device__ __forceinline__ void operator()() const {} };
-template <int S, int NT, int TC_ = screen_default_tc(S), int NB = 4, bool PACK = false, int RG = 1, bool COARSE = false, int NDEF = 0,
+template <int S, int NT, int TC_ = screen_default_tc(S), int NB = 4, bool PACK = false, bool COARSE = false, int NDEF = 0,
           typename DEFERRED = LqNoDeferred>
-__device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], const f16x8 (&al)[RG][S],
-                                                  const unsigned char* __restrict__ tiles, int ntiles,
-                                                  unsigned char* stage0, int tid, const float (&frow)[16],
-                                                  const float (&znr)[RG][16],
-                                                  float (&m1)[RG][16], float (&m2)[RG][16], int (&k1)[RG][16],
-                                                  bool have_def = false, DEFERRED deferred = DEFERRED()) {
+__device__ __forceinline__ void lq_screen_core(const f16x8 (&ah)[S], const f16x8 (&al)[S],
+                                               const unsigned char* __restrict__ tiles, int ntiles,
+                                               unsigned char* stage0, int tid, const float (&frow)[16], const float (&znr)[16],
+                                               float (&m1)[16], float (&m2)[16], int (&k1)[16],
+                                               bool have_def = false, DEFERRED deferred = DEFERRED()) {
     using C = ScreenCfg<S, TC_, COARSE>;
     // NB = 2 is NOT a ring this loop can run: with one stage in flight (PD = 1) stage st+1 is only ISSUED at the hand-over in the
     // middle of stage st, and nothing waits for it before the read-ahead crosses into it.  (An experiment build with 2 x 4 tiles
@@ -277,12 +275,10 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
     }
     lq_wg_barrier();
 
-    // two named accumulators (per row group): the chain of tile i runs into one while the other (tile i-1) is booked
-    f32x16 accA[RG], accB[RG];
+    // two named accumulators: the chain of tile i runs into one while the other (tile i-1) is booked
+    f32x16 accA, accB;
 #pragma unroll
-    for (int g_ = 0; g_ < RG; ++g_)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) accB[g_][r] = INFINITY;      // "no previous tile": INFINITY never beats anything
+    for (int r = 0; r < 16; ++r) accB[r] = INFINITY;              // "no previous tile": INFINITY never beats anything
     float e2A = 0.0f, e2B = 0.0f;
     int codeA = 0, codeB = 0;                     // the code of the lane in the tile (unpacked) or the tile index (PACK)
     const unsigned keep_mask = PACK ? ~((1u << lq_pack_bits(ntiles)) - 1u) : 0xffffffffu;
@@ -320,8 +316,8 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
                 int b = buf + PD; b = b >= NB ? b - NB : b;
                 stage_dma(st + PD, b);
             }
-            f32x16 (&acc)[RG] = (((c + par) & 1) == 0) ? accA : accB;
-            const f32x16 (&prev)[RG] = (((c + par) & 1) == 0) ? accB : accA;
+            f32x16& acc = (((c + par) & 1) == 0) ? accA : accB;
+            const f32x16& prev = (((c + par) & 1) == 0) ? accB : accA;
             const float e2_prev = (((c + par) & 1) == 0) ? e2B : e2A;
             const float en_prev = (((c + par) & 1) == 0) ? enB : enA;
             const int code_prev = (((c + par) & 1) == 0) ? codeB : codeA;
@@ -329,9 +325,7 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
                 const float e2c = e2q[(c + par) & 1];
                 const float enc = enq[(c + par) & 1];
 #pragma unroll
-                for (int g_ = 0; g_ < RG; ++g_)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[g_][r] = COARSE ? lq_fma(-znr[g_][r], enc, e2c * frow[r]) : 0.0f;
+                for (int r = 0; r < 16; ++r) acc[r] = COARSE ? lq_fma(-znr[r], enc, e2c * frow[r]) : 0.0f;
                 int code = PACK ? (st * C::TC + c) : (st * C::TC + c) * 32 + ln;
                 if constexpr (PACK) asm volatile("" : "+v"(code));      // the tile index lives in a vector register (lq_track_one)
                 if (((c + par) & 1) == 0) { e2A = e2c; enA = enc; codeA = code; } else { e2B = e2c; enB = enc; codeB = code; }
@@ -359,29 +353,19 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
             // of it were waited for at once -- a whole LDS round trip exposed per k-step (cfg2 -3.6 %, cfg3 -3 %, same box; a 4-slot
             // ring on top changes nothing more: profiles/r03_z_frag_read_placement_ab.txt)
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int g_ = 0; g_ < RG; ++g_) {
-                acc[g_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[g_][s], bh, acc[g_], 0, 0, 0);
-                if (g_ == 0) { __builtin_amdgcn_sched_barrier(0); read_ahead(); __builtin_amdgcn_sched_barrier(0); }
-                lq_track_after_mfma<S, PACK, COARSE>(COARSE ? s : 3 * s + 0, prev[g_], e2_prev, en_prev, frow, znr[g_], code_prev, keep_mask,
-                                                     m1[g_], m2[g_], k1[g_]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bh, acc, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            read_ahead();
+            __builtin_amdgcn_sched_barrier(0);
+            lq_track_after_mfma<S, PACK, COARSE>(COARSE ? s : 3 * s + 0, prev, e2_prev, en_prev, frow, znr, code_prev, keep_mask, m1, m2, k1);
+            __builtin_amdgcn_sched_barrier(0);
             if constexpr (!COARSE) {
-#pragma unroll
-                for (int g_ = 0; g_ < RG; ++g_) {
-                    acc[g_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[g_][s], bh, acc[g_], 0, 0, 0);
-                    lq_track_after_mfma<S, PACK>(3 * s + 1, prev[g_], e2_prev, en_prev, frow, znr[g_], code_prev, keep_mask,
-                                                        m1[g_], m2[g_], k1[g_]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#pragma unroll
-                for (int g_ = 0; g_ < RG; ++g_) {
-                    acc[g_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[g_][s], bl, acc[g_], 0, 0, 0);
-                    lq_track_after_mfma<S, PACK>(3 * s + 2, prev[g_], e2_prev, en_prev, frow, znr[g_], code_prev, keep_mask,
-                                                        m1[g_], m2[g_], k1[g_]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s], bh, acc, 0, 0, 0);
+                lq_track_after_mfma<S, PACK>(3 * s + 1, prev, e2_prev, en_prev, frow, znr, code_prev, keep_mask, m1, m2, k1);
+                __builtin_amdgcn_sched_barrier(0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bl, acc, 0, 0, 0);
+                lq_track_after_mfma<S, PACK>(3 * s + 2, prev, e2_prev, en_prev, frow, znr, code_prev, keep_mask, m1, m2, k1);
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
         buf = nbuf;
@@ -391,26 +375,13 @@ __device__ __forceinline__ void lq_screen_core_rg(const f16x8 (&ah)[RG][S], cons
         if constexpr (PERIOD == 2) do_stage(std::integral_constant<int, 1>{}, st + 1);
     }
     // the last tile's chain: ntiles is even, so it ran into accB
-#pragma unroll
-    for (int g_ = 0; g_ < RG; ++g_)
-        lq_track_part<0, 16, PACK, COARSE>(accB[g_], e2B, enB, frow, znr[g_], codeB, keep_mask, m1[g_], m2[g_], k1[g_]);
+    lq_track_part<0, 16, PACK, COARSE>(accB, e2B, enB, frow, znr, codeB, keep_mask, m1, m2, k1);
     // the copies issued for stages past the end go to the dummy KiB, but they count: drain them, then every wave has left
     // the stage buffers (the callers reuse them as per-wave scratch: lq_screen_decide)
     lq_wait_vmcnt<0>();
     lq_wg_barrier();
 }
 
-// one row group: the original interface (screen_kernel, tokenize_kernel's 32-row instances)
-template <int S, int NT, int TC_ = screen_default_tc(S), int NB = 4, bool PACK = false>
-__device__ __forceinline__ void lq_screen_core(const f16x8 (&ah)[S], const f16x8 (&al)[S],
-                                               const unsigned char* __restrict__ tiles, int ntiles,
-                                               unsigned char* stage0, int tid, const float (&frow)[16],
-                                               float (&m1)[16], float (&m2)[16], int (&k1)[16]) {
-    lq_screen_core_rg<S, NT, TC_, NB, PACK, 1, false>(reinterpret_cast<const f16x8 (&)[1][S]>(ah), reinterpret_cast<const f16x8 (&)[1][S]>(al),
-                                                      tiles, ntiles, stage0, tid, frow, reinterpret_cast<const float (&)[1][16]>(frow),
-                                                      reinterpret_cast<float (&)[1][16]>(m1), reinterpret_cast<float (&)[1][16]>(m2),
-                                                      reinterpret_cast<int (&)[1][16]>(k1));
-}
 
 // frow[r] = factor of row (r, h) = the row this lane's accumulator register r belongs to, fetched from the lane that
 // owns that row (row i lives in lanes i and i + 32, both hold fown)

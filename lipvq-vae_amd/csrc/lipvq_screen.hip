@@ -294,10 +294,7 @@ __global__ __launch_bounds__(SCREEN_WAVES * 64) void screen_kernel(
             lq_track_part<0, 16, false, COARSE>(acc, e2, en, frow, znr, code, 0xffffffffu, m1, m2, k1);
         }
     } else {
-        lq_screen_core_rg<S, SCREEN_WAVES * 64, SC::TC, SC::NB, PK, 1, COARSE>(
-            reinterpret_cast<const f16x8 (&)[1][S]>(ah), reinterpret_cast<const f16x8 (&)[1][S]>(al), tiles, L.ntiles, lds, tid, frow,
-            reinterpret_cast<const float (&)[1][16]>(znr), reinterpret_cast<float (&)[1][16]>(m1), reinterpret_cast<float (&)[1][16]>(m2),
-            reinterpret_cast<int (&)[1][16]>(k1));
+        lq_screen_core<S, SCREEN_WAVES * 64, SC::TC, SC::NB, PK, COARSE>(ah, al, tiles, L.ntiles, lds, tid, frow, znr, m1, m2, k1);
     }
     int my_k;
     const float pack_eps = (PK && !DBG) ? lq_pow2f(lq_pack_bits(L.ntiles) - 23) : 0.0f;
@@ -1231,9 +1228,7 @@ int lipvq_launch_rows_encode(const float* x, const float* const* raw6, int A, co
     const int* amb_seed = amb_list + lq_list_ints(N);
     RawEncoder w{raw6[0], raw6[1], raw6[2], raw6[3], raw6[4], raw6[5]};
     int64_t blocks = (N + 3) / 4;
-    static int grid_cap = -1;                   // LIPVQ_ROWS_GRID: measurement knob
-    if (grid_cap < 0) { const char* e = lq_knob("LIPVQ_ROWS_GRID"); grid_cap = e ? atoi(e) : 1024; }      // (the count lives on the device; the grid strides)
-    if (blocks > grid_cap) blocks = grid_cap;
+    if (blocks > 1024) blocks = 1024;           // (the count lives on the device; the grid strides)
     auto go = [&](auto kfn) {
         hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), 0, st, x, w, A, cb, idx, zq,
                            (unsigned long long*)usage, amb_list, lq_ws_listed(amb_count), K, amb_seed, amb_list + 2 * lq_list_ints(N),

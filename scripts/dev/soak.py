@@ -22,13 +22,12 @@ while time.time() - t0 < budget:
     K = (int(rng.choice([37, 256, 1000, 1024, 2048, 8192])) if D <= 128 else int(rng.choice([128, 1024, 4096])) if D <= 208
          else int(rng.choice([37, 128, 1024])))
     ops.set_option("screen_mode", str(rng.choice(["fine", "coarse"])))              # read per launch by the library
-    shape = rng.choice(["default", "default", "w8rg1", "w8rg2", "w4rg2", "w4rg1"])          # default: the library's size rule
+    shape = rng.choice(["default", "default", "w8rg1", "w4rg1"])                            # default: the library's size rule
     ops.set_option("tok_shape", None if shape == "default" else str(shape))
     inpl = rng.choice(["default", "0", "1"])                                                 # uncertified rows in place / listed
     ops.set_option("tok_inplace", None if inpl == "default" else str(inpl))
     ops.set_option("tok_defer_ze", str(rng.integers(2)))
     ops.set_option("tok_nt_ze", str(rng.integers(2)))
-    ops.set_option("tok_ze_ring", None if rng.random() < 0.7 else "0")                       # the z_e scratch as a ring (default) / in full
     _ScreenMonitor.ENABLED = False
     A = int(rng.choice([3, 7, 12]))
     N = int(rng.choice([1, 33, 257, 2049, 4100, 30000, 70001, 100001, 300000] if D <= 208 else [1, 33, 257, 2049, 4100, 30000]))

@@ -17,8 +17,6 @@ def timed(fn, n=200):
     return a.elapsed_time(b) / n * 1e3
 
 
-import os
-print("LIPVQ_MLP3_SMALL_TILES =", os.environ.get("LIPVQ_MLP3_SMALL_TILES", "(default)"))
 for (N, K0, J0, J1, J2) in [(80, 12, 64, 128, 208), (80, 208, 64, 128, 12), (500, 12, 64, 128, 208), (2048, 12, 64, 128, 208),
                             (8192, 12, 64, 128, 208), (16384, 7, 64, 128, 64), (32768, 7, 64, 128, 64), (131072, 7, 64, 128, 64),
                             (524288, 7, 64, 128, 64), (131072, 12, 64, 128, 208)]:

@@ -1,6 +1,5 @@
-"""Dev tool (GPU): wgrad at BASELINE config 2's batch for the layer shapes of the tokenizer (LIPVQ_WGRAD_CHUNK overrides
-the rows per chunk)."""
-import os, sys
+"""Dev tool (GPU): wgrad at BASELINE config 2's batch for the layer shapes of the tokenizer."""
+import sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch
@@ -17,7 +16,6 @@ def timed(fn, n=10):
     return a.elapsed_time(b) / n * 1e3
 
 
-print("LIPVQ_WGRAD_CHUNK =", os.environ.get("LIPVQ_WGRAD_CHUNK", "(default)"))
 for N in (524288, 65536):
     for J, Kd, act in ((128, 64, ops.ACT_GELU), (64, 128, ops.ACT_GELU), (64, 7, ops.ACT_NONE), (7, 128, ops.ACT_GELU), (64, 64, ops.ACT_NONE),
                        (128, 64, ops.ACT_NONE)):
