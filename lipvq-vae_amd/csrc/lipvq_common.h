@@ -24,6 +24,17 @@ struct LqLdsReserve {
     std::atomic<size_t> got[kMaxDev];
 };
 int lipvq_reserve_lds(LqLdsReserve& r, const void* kernel, size_t bytes, const char* what);
+
+// A runtime value as a compile-time constant (a latent width, a distance rule picking a template instance): calls
+// f(std::integral_constant<int, V>{}) for the V of the list that equals v and returns true, or calls nothing and returns false.
+#include <type_traits>
+template <typename F>
+static inline bool lq_dispatch(int, F&&) { return false; }
+template <int V, int... Vs, typename F>
+static inline bool lq_dispatch(int v, F&& f) {
+    if (v == V) { f(std::integral_constant<int, V>{}); return true; }
+    return lq_dispatch<Vs...>(v, f);
+}
 #endif
 
 #if defined(__HIPCC__)

@@ -28,7 +28,7 @@
 // The Lipschitz layer's weights are STREAMED through the stage ring (instead of living in LDS) from this many k-steps on:
 // 13 (D = 208) has no choice -- 112 KB of A operands; for 8 (D = 128) it is a trade measured in round 3: 64 KB of LDS go from
 // a phase that is a twentieth of the work at K = 8192 to the codebook ring of the phase that is the rest.
-#define LQ_STREAM2_MIN_S 9
+// (LQ_STREAM2_MIN_S = 9 lives in lipvq_screen.h: it also sizes the streamed weights' region of the workspace)
 #define LQ_RING8_TC 1
 #define LQ_RING8_NB 3
 #define LQ_RING13_NB 3
@@ -116,8 +116,8 @@ struct TokArgs {
     float* zq;                   // [N][D] or NULL
     unsigned long long* usage;   // [K] or NULL
     float* ze_out;               // [N][D] or NULL
-    int* amb_count;              // workspace[0]
-    int* amb_list;               // [N]
+    int* amb_count;              // LqWorkspace::live()     } the two workspace pointers device code gets the view back
+    int* amb_list;               // LqWorkspace::row_list() } from (lipvq_screen.h)
     const float* w2q;            // layer-2 weights re-laid out for streaming (S > 8 only; lives in the workspace)
     float* pre0;                 // TRAIN instances: the three pre-activations [N][64], [N][128], [N][D] the backward needs
     float* pre1;
@@ -880,7 +880,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
     if (DEFER_GATHER && have_pend && a.zq) lq_screen_gather(a.cb, a.zq, pend_k, pend_ok, pend_row0, a.N, a.D, lane);   // the last block's
 #ifdef LQ_STAMPS
     if (lane == 0) {
-        long long* dbg = reinterpret_cast<long long*>(a.amb_list + (a.N / 2 & ~1)) + ((size_t)blockIdx.x * WAVES + wave) * 16;
+        long long* dbg = LqWorkspace::from_lists(a.amb_list, a.N).stamps() + ((size_t)blockIdx.x * WAVES + wave) * 16;
         for (int i = 0; i < 7; ++i) dbg[i] = st_acc[i];
         dbg[7] = 0;
         dbg[8] = __builtin_amdgcn_s_memtime() - st_begin;
@@ -909,115 +909,6 @@ __global__ __launch_bounds__(FUSED_THREADS) void tokenize_kernel(TokArgs a) {
 template <int S, bool FAST, bool TRAIN, bool COARSE = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void tokenize_kernel_w4(TokArgs a) {
     tokenize_body<S, FAST, TRAIN, 4, COARSE>(a);
-}
-
-// Which instance runs: w8rg1 (8 waves per workgroup, one 32-row group per wave) is the default at every latent width -- cfg2 0.468 ms
-// against w4rg1 0.549, cfg3 2.98 against 3.53, icrt 1.19 against 1.27, same box (profiles/r03_d_tokenize_shapes_ab.txt).  Two row
-// groups per wave (round 3) lost everywhere (cfg2 w8rg2 0.480 ms with 99 spilled registers, cfg3 w4rg2 3.05) and was dropped.
-// Schedule choices of the fused launch with IDENTICAL results whose better setting depends on the DEVICE (round 4,
-// profiles/r04_i_clock_ab.txt): MI355X devices hold different clocks under the same kernel (MI355X_MICROARCH.md, DVFS give-back items
-// 3-5).  With the last tile's z_e stores deferred and nontemporal, cfg2's launch takes 0.387 ms on a device that keeps 2.22 GHz under
-// it (0.404 without the deferral) -- and 0.437 ms on a device that answers the denser issue stream with 1.97 GHz (0.403 without:
-// 2.12 GHz).  Defaults: the settings that are never bad (no deferral, nontemporal); lipvq_tokenize_tune_f32 measures the four
-// combinations on the caller's device and shape and keeps the winner for that device; the options tok_defer_ze / tok_nt_ze override.
-#define LQ_DEFAULT_DEFER_ZE 0
-struct LqSchedule { int defer_ze, nt_ze; };
-static std::atomic<int> g_tuned[64];                 // per device: 0 = not tuned, else 1 + (defer_ze | nt_ze << 1)
-static LqSchedule lq_schedule(int ring = 0) {
-    LqSchedule sc{LQ_DEFAULT_DEFER_ZE, ring ? 0 : 1};      // (ring rows are meant to stay in L2: plain stores unless tuned / told otherwise)
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-        const int t = g_tuned[dev].load(std::memory_order_relaxed);
-        if (t) { sc.defer_ze = (t - 1) & 1; sc.nt_ze = ((t - 1) >> 1) & 1; }
-    }
-    if (const char* e = lq_knob("LIPVQ_TOK_DEFER_ZE")) sc.defer_ze = e[0] != '0';
-    if (const char* e = lq_knob("LIPVQ_TOK_NT_ZE")) sc.nt_ze = e[0] != '0';
-    return sc;
-}
-
-// In-place decisions (lq_screen_decide_inplace): three-product screen, codebooks the list kernel would finish alone, z_e rows stored.
-// Same box, cfg2, in place against the list kernel behind the launch (profiles/r04_j_inplace_ab.txt): 65 536 rows 0.0637 -> 0.0585 ms,
-// 131 072 rows 0.1096 -> 0.1054, 262 144 rows 0.2069 -> 0.1993, 524 288 rows 0.3910 -> 0.3863.  (With the last z_e tile's stores
-// deferred -- the schedule of the round's first builds -- the full batch measured level, 0.3929 -> 0.3936, and a size rule kept
-// it on the list kernel; without the deferral the wave that stops ~2 us for a row no longer costs its workgroup the 6 us saved.)
-// (tok_inplace = 0 / 1: never / whenever possible; results identical)
-static int lq_inplace(bool have_ze, int coarse, int K) {
-    const bool can = have_ze && !coarse && K <= LQ_LISTS_ALL_K;
-    if (const char* e = lq_knob("LIPVQ_TOK_INPLACE")) {
-        if (e[0] == '0') return 0;
-        if (e[0] == '1') return can ? 1 : 0;
-    }
-    return can ? 1 : 0;
-}
-// Ring mode of the z_e scratch (round 4, late): where the launch decides its uncertified rows in place and the caller wants no z_e,
-// nothing reads a row's z_e after its wave has decided the row block -- so every block's 32 rows of a wave go to the SAME 32 rows of
-// the scratch (2 048 waves x 32 rows x D floats: 16 MB at D = 64) instead of streaming over N x D floats.  Measured, same box, three
-// alternating passes (profiles/r04_n_ze_ring_ab.txt): cfg2 0.3848 -> 0.3829 ms.  The stores still leave the L2 (WRITE_SIZE 275 -> 250
-// MB per launch, HBM traffic 298 -> 270 MB: this L2 writes the rows through whether or not they are overwritten 50 us later), so the
-// gain is the read side of the in-place decisions and 118 MB of address range less, not the 134 MB of stores hoped for.
-static int lq_ze_ring(bool caller_wants_ze, int inplace) { return (!caller_wants_ze && inplace) ? 1 : 0; }
-struct TokShape { int waves; };
-static TokShape tok_shape_env() {              // read per launch (a getenv: nanoseconds), so that a test can switch shapes in-process
-    const char* e = lq_knob("LIPVQ_TOK_SHAPE");
-    TokShape t{0};
-    if (e && !strcmp(e, "w8rg1")) t = {8};
-    if (e && !strcmp(e, "w4rg1")) t = {4};
-    return t;
-}
-template <int S, bool FAST, bool TRAIN>
-static TokShape tok_shape(int64_t N) {
-    constexpr bool HAS_W4 = !FAST && !TRAIN;
-    TokShape t = tok_shape_env();
-    // Size rule (round 4): a launch of at most 32 768 rows is at most one 32-row block per SIMD of the chip -- as 4-wave workgroups
-    // (one wave per SIMD, 256 CUs) instead of 8-wave ones (two per SIMD on half the CUs): same box, 32 768 rows, w8rg1 -> w4rg1:
-    // icrt 0.137 -> 0.099 ms, cfg3 0.205 -> 0.184, cfg2 0.0528 -> 0.0509 (profiles/r04_k_small_launch_shape_ab.txt).  An explicit
-    // tok_shape is honoured at any batch size.
-    if (t.waves == 0) t = (HAS_W4 && N <= 4 * 32 * 256) ? TokShape{4} : TokShape{8};
-    if (t.waves == 4 && !HAS_W4) t = {8};
-    return t;
-}
-
-template <typename KFN>
-static int launch_tokenize_as(KFN kfn, LqLdsReserve& reserved, const TokArgs& a, size_t lds, int waves, hipStream_t st) {
-    if (int rc = lipvq_reserve_lds(reserved, (const void*)kfn, lds, "tokenize")) return rc;
-    const int64_t unit = (int64_t)waves * 32;
-    const int64_t nblk = (a.N + unit - 1) / unit;
-    const int64_t cap = 256;                                        // one persistent workgroup per CU
-    const int64_t blocks = nblk < cap ? nblk : cap;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(waves * 64), lds, st, a);
-    return check_launch("tokenize");
-}
-
-template <int S, bool FAST, bool TRAIN = false>
-static int launch_tokenize(const TokArgs& a, hipStream_t st) {
-    const size_t lds = fused_lds_bytes<S, FAST>(a.A, a.K);
-    if (lds > 160 * 1024) return fail(LIPVQ_EUNSUPPORTED, "tokenize: %zu B of LDS needed", lds);
-    const TokShape sh = tok_shape<S, FAST, TRAIN>(a.N);
-    static LqLdsReserve reserved[4];            // per instantiation and shape: per-device, thread-safe (lipvq_common.h)
-    if constexpr (!FAST && !TRAIN && S >= 8) {  // (one wave per SIMD with the whole register file: the instances that spill at two)
-        if (a.coarse && sh.waves == 4) return launch_tokenize_as(tokenize_kernel_w4<S, FAST, TRAIN, true>, reserved[3], a, lds, 4, st);
-    }
-    if constexpr (!FAST) {                      // (parity and training instances; the training forward writes z_e anyway)
-        if (a.coarse) return launch_tokenize_as(tokenize_kernel<S, FAST, TRAIN, true>, reserved[2], a, lds, 8, st);
-    }
-    if constexpr (!FAST && !TRAIN) {
-        if (sh.waves == 4) return launch_tokenize_as(tokenize_kernel_w4<S, FAST, TRAIN>, reserved[1], a, lds, 4, st);
-    }
-    return launch_tokenize_as(tokenize_kernel<S, FAST, TRAIN>, reserved[0], a, lds, 8, st);
-}
-
-// the plain VQVAE's instances (ReLU encoder, per-row scales): both screens
-template <int S>
-static int launch_tokenize_vq(const TokArgs& a, hipStream_t st) {
-    const size_t lds = fused_lds_bytes<S, false>(a.A, a.K);
-    if (lds > 160 * 1024) return fail(LIPVQ_EUNSUPPORTED, "vq_tokenize: %zu B of LDS needed", lds);
-    static LqLdsReserve reserved[4];
-    if (a.pre0) {                                              // the training forward: the three pre-activations are stored too
-        if (a.coarse) return launch_tokenize_as(tokenize_kernel<S, false, true, true, true>, reserved[3], a, lds, 8, st);
-        return launch_tokenize_as(tokenize_kernel<S, false, true, false, true>, reserved[2], a, lds, 8, st);
-    }
-    if (a.coarse) return launch_tokenize_as(tokenize_kernel<S, false, false, true, true>, reserved[1], a, lds, 8, st);
-    return launch_tokenize_as(tokenize_kernel<S, false, false, false, true>, reserved[0], a, lds, 8, st);
 }
 
 // fp16 MFMA fragments of the encoder stack for the fast mode: [layer][tile t][step s][lane][8 halfs] with
@@ -1069,9 +960,56 @@ extern "C" int lipvq_tokenize_fast_supported(int A, int J0, int J1, int D, int K
     return (lipvq_tokenize_supported(A, J0, J1, D, K) && D != 208) ? 1 : 0;
 }
 
-// layer-2 weights of the streamed instance (D = 208): [t][16 groups][64 lanes][4 k-steps], i.e. the LDS image of one output
-// tile's A operands as contiguous 16 KB slabs, so that the kernel can copy them with the LDS-DMA
-static size_t w2q_floats(int D) { return (D + 15) / 16 >= LQ_STREAM2_MIN_S ? (size_t)((D + 31) / 32) * 16 * 256 : 0; }
+// Schedule choices of the fused launch with IDENTICAL results whose better setting depends on the DEVICE (round 4,
+// profiles/r04_i_clock_ab.txt): MI355X devices hold different clocks under the same kernel (MI355X_MICROARCH.md, DVFS give-back items
+// 3-5).  With the last tile's z_e stores deferred and nontemporal, cfg2's launch takes 0.387 ms on a device that keeps 2.22 GHz under
+// it (0.404 without the deferral) -- and 0.437 ms on a device that answers the denser issue stream with 1.97 GHz (0.403 without:
+// 2.12 GHz).  Defaults: the settings that are never bad (no deferral, nontemporal); lipvq_tokenize_tune_f32 measures the four
+// combinations on the caller's device and shape and keeps the winner for that device; the options tok_defer_ze / tok_nt_ze override.
+#define LQ_DEFAULT_DEFER_ZE 0
+struct LqSchedule { int defer_ze, nt_ze; };
+static std::atomic<int> g_tuned[64];                 // per device: 0 = not tuned, else 1 + (defer_ze | nt_ze << 1)
+static LqSchedule lq_schedule(int ring) {
+    LqSchedule sc{LQ_DEFAULT_DEFER_ZE, ring ? 0 : 1};      // (ring rows are meant to stay in L2: plain stores unless tuned / told otherwise)
+    int dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
+        const int t = g_tuned[dev].load(std::memory_order_relaxed);
+        if (t) { sc.defer_ze = (t - 1) & 1; sc.nt_ze = ((t - 1) >> 1) & 1; }
+    }
+    if (const char* e = lq_knob("tok_defer_ze")) sc.defer_ze = e[0] != '0';
+    if (const char* e = lq_knob("tok_nt_ze")) sc.nt_ze = e[0] != '0';
+    return sc;
+}
+
+// In-place decisions (lq_screen_decide_inplace): three-product screen, codebooks the list kernel would finish alone, z_e rows stored.
+// Same box, cfg2, in place against the list kernel behind the launch (profiles/r04_j_inplace_ab.txt): 65 536 rows 0.0637 -> 0.0585 ms,
+// 131 072 rows 0.1096 -> 0.1054, 262 144 rows 0.2069 -> 0.1993, 524 288 rows 0.3910 -> 0.3863.  (With the last z_e tile's stores
+// deferred -- the schedule of the round's first builds -- the full batch measured level, 0.3929 -> 0.3936, and a size rule kept
+// it on the list kernel; without the deferral the wave that stops ~2 us for a row no longer costs its workgroup the 6 us saved.)
+// (tok_inplace = 0: never; otherwise whenever possible; results identical)
+static int lq_inplace(bool have_ze, int coarse, int K) {
+    const char* e = lq_knob("tok_inplace");
+    return (have_ze && !coarse && K <= LQ_LISTS_ALL_K && !(e && e[0] == '0')) ? 1 : 0;
+}
+// Ring mode of the z_e scratch (round 4, late): where the launch decides its uncertified rows in place and the caller wants no z_e,
+// nothing reads a row's z_e after its wave has decided the row block -- so every block's 32 rows of a wave go to the SAME 32 rows of
+// the scratch (2 048 waves x 32 rows x D floats: 16 MB at D = 64) instead of streaming over N x D floats.  Measured, same box, three
+// alternating passes (profiles/r04_n_ze_ring_ab.txt): cfg2 0.3848 -> 0.3829 ms.  The stores still leave the L2 (WRITE_SIZE 275 -> 250
+// MB per launch, HBM traffic 298 -> 270 MB: this L2 writes the rows through whether or not they are overwritten 50 us later), so the
+// gain is the read side of the in-place decisions and 118 MB of address range less, not the 134 MB of stores hoped for.
+static int lq_ze_ring(bool caller_wants_ze, int inplace) { return (!caller_wants_ze && inplace) ? 1 : 0; }
+
+// Waves per workgroup of a parity launch (the fast, training and plain-VQVAE instances have 8 only).  Option tok_shape = w8rg1 | w4rg1,
+// read per launch so that a test can switch shapes in-process and honoured at any batch size; otherwise the size rule (round 4): a
+// launch of at most 32 768 rows is at most one 32-row block per SIMD of the chip -- as 4-wave workgroups (one wave per SIMD, 256
+// CUs) instead of 8-wave ones (two per SIMD on half the CUs): same box, 32 768 rows, w8rg1 -> w4rg1: icrt 0.137 -> 0.099 ms, cfg3
+// 0.205 -> 0.184, cfg2 0.0528 -> 0.0509 (profiles/r04_k_small_launch_shape_ab.txt).
+static int tok_waves(int64_t N) {
+    const char* e = lq_knob("tok_shape");
+    if (e && !strcmp(e, "w8rg1")) return 8;
+    if (e && !strcmp(e, "w4rg1")) return 4;
+    return N <= 4 * 32 * 256 ? 4 : 8;
+}
 
 __global__ void w2q_pack_kernel(const float* __restrict__ P2, float* __restrict__ out, int T2, int S2) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1080,49 +1018,103 @@ __global__ void w2q_pack_kernel(const float* __restrict__ P2, float* __restrict_
     out[i] = P2[((size_t)t * S2 + 4 * sq + q) * 64 + l];
 }
 
+// One kernel instance's launch: its LDS reservation (one slot per instance, per device inside), for the streamed instance the
+// re-layout of layer 2's packed weights into the workspace (one small launch: the weights may have changed since the last call
+// and the library keeps no state), then one persistent workgroup per CU.
+template <int S, bool FAST, bool TRAIN, int WAVES, bool COARSE, bool VQ>
+static int launch_tokenize_as(const TokArgs& a, hipStream_t st) {
+    static_assert(WAVES == 8 || !VQ, "the plain VQVAE's instances have 8 waves");
+    static LqLdsReserve reserved;
+    const size_t lds = fused_lds_bytes<S, FAST>(a.A, a.K);
+    if (lds > 160 * 1024) return fail(LIPVQ_EUNSUPPORTED, "tokenize: %zu B of LDS needed", lds);
+    void (*kfn)(TokArgs);
+    if constexpr (WAVES == 4) kfn = tokenize_kernel_w4<S, FAST, TRAIN, COARSE>;
+    else kfn = tokenize_kernel<S, FAST, TRAIN, COARSE, VQ>;
+    if (int rc = lipvq_reserve_lds(reserved, (const void*)kfn, lds, "tokenize")) return rc;
+    if (a.w2q) {
+        const PackedLayout PL = packed_layout(a.A, 64, 128, a.D);
+        const size_t n = LqWorkspace::w2q_floats(a.D);
+        hipLaunchKernelGGL(w2q_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.packed + PL.oP2,
+                           LqWorkspace::from_lists(a.amb_list, a.N).w2q(), PL.T2, PL.S2);
+    }
+    const int64_t unit = (int64_t)WAVES * 32;
+    const int64_t nblk = (a.N + unit - 1) / unit;
+    const int64_t cap = 256;                                        // one persistent workgroup per CU
+    hipLaunchKernelGGL(kfn, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(WAVES * 64), lds, st, a);
+    return check_launch("tokenize");
+}
+
+// Which instance runs.  The four families differ in what the kernel does, MODE names them; within one, a.coarse (the one-product
+// screen), a.pre0 (the plain VQVAE's training forward) and tok_waves pick.  w8rg1 (8 waves per workgroup, one 32-row group per wave)
+// is the default at every latent width -- cfg2 0.468 ms against w4rg1 0.549, cfg3 2.98 against 3.53, icrt 1.19 against 1.27, same box
+// (profiles/r03_d_tokenize_shapes_ab.txt); tok_waves has the exception.
+enum { TOK_TRAIN, TOK_FAST, TOK_PARITY, TOK_VQ };
+template <int S, int MODE>
+static int launch_tokenize(const TokArgs& a, hipStream_t st) {
+    if constexpr (MODE == TOK_TRAIN) {          // (the training forward writes z_e anyway)
+        return a.coarse ? launch_tokenize_as<S, false, true, 8, true, false>(a, st) : launch_tokenize_as<S, false, true, 8, false, false>(a, st);
+    } else if constexpr (MODE == TOK_FAST) {    // (tokenize_run has refused the widths without a fast instance)
+        if constexpr (S <= 8) return launch_tokenize_as<S, true, false, 8, false, false>(a, st);
+        else return LIPVQ_EUNSUPPORTED;
+    } else if constexpr (MODE == TOK_PARITY) {
+        const int waves = tok_waves(a.N);
+        if constexpr (S >= 8) {                 // (one wave per SIMD with the whole register file: the instances that spill at two)
+            if (a.coarse && waves == 4) return launch_tokenize_as<S, false, false, 4, true, false>(a, st);
+        }
+        if (a.coarse) return launch_tokenize_as<S, false, false, 8, true, false>(a, st);
+        if (waves == 4) return launch_tokenize_as<S, false, false, 4, false, false>(a, st);
+        return launch_tokenize_as<S, false, false, 8, false, false>(a, st);
+    } else {                                    // the plain VQVAE's instances (ReLU encoder, per-row scales): both screens
+        if (a.pre0) return a.coarse ? launch_tokenize_as<S, false, true, 8, true, true>(a, st) : launch_tokenize_as<S, false, true, 8, false, true>(a, st);
+        return a.coarse ? launch_tokenize_as<S, false, false, 8, true, true>(a, st) : launch_tokenize_as<S, false, false, 8, false, true>(a, st);
+    }
+}
+
 // Zero the header of a workspace of lipvq_tokenize_workspace_bytes / lipvq_nearest_workspace_bytes: ONCE, before its first use by
 // lipvq_tokenize_f32 / _fast / _train / lipvq_vq_tokenize*_f32.  Those calls leave the header's counters at zero themselves.
 extern "C" int lipvq_tokenize_workspace_init(void* workspace, void* stream) {
     if (!workspace) return fail(LIPVQ_EINVAL, "tokenize_workspace_init: null pointer");
-    hipError_t e = hipMemsetAsync(workspace, 0, 64, (hipStream_t)stream);
+    hipError_t e = hipMemsetAsync(workspace, 0, LqWorkspace::kHeaderBytes, (hipStream_t)stream);
     if (e != hipSuccess) return fail(LIPVQ_EHIP, "tokenize_workspace_init: %s", hipGetErrorString(e));
     return LIPVQ_OK;
 }
 
-extern "C" size_t lipvq_tokenize_workspace_bytes(int64_t N, int D) {
-    if (N <= 0 || D <= 0) return 0;
-    // uncertified-row counter, row list, best-candidate list, short lists, then (D = 208) the streamed layer-2 weights, then a z_e
-    // scratch [N][D] for the one-product screen's exact stage (used when the caller passes no ze_out; always part of the size, so
-    // that the mode may change between calls)
-    return 64 + lq_lists_bytes(N) + sizeof(float) * w2q_floats(D) + 256 + sizeof(float) * (size_t)N * (size_t)D;
-}
+// (the z_e scratch is always part of the size, so that the mode may change between calls)
+extern "C" size_t lipvq_tokenize_workspace_bytes(int64_t N, int D) { return (N <= 0 || D <= 0) ? 0 : LqWorkspace::tokenize_bytes(N, D); }
 
-// Fused encode + quantize (reference v5:71-74).  packed: lipvq_mlp3_pack_f32 of the encoder stack
-// (A -> 64 -> 128 -> D with the Lipschitz-normalised W2, activations gelu, gelu, sigmoid); raw6: the same six
-// tensors unpacked, {W0, b0, W1, b1, W2, b2} (device pointers; the array itself is host memory); prep:
-// lipvq_nearest_prepare_f32 of the codebook; workspace: lipvq_tokenize_workspace_bytes(N, D).
-// Outputs exactly as lipvq_mlp3_f32 + lipvq_nearest_f32(LIPVQ_DIST_NORM): idx, zq (may be NULL),
-// usage (may be NULL, accumulated), ze_out (may be NULL).  workspace[0] (int) = rows decided by the exact kernel.
-static int tokenize_impl(const float* x, const float* packed, const void* packed16, const float* const* raw6,
-                         const float* codebook, const void* prep, int64_t* idx, float* zq, int64_t* usage, float* ze_out,
-                         void* workspace, int64_t N, int A, int J0, int J1, int D, int K, void* stream,
-                         float* pre0 = nullptr, float* pre1 = nullptr, float* pre2 = nullptr) {
-    if (N < 0) return fail(LIPVQ_EINVAL, "tokenize: N < 0");
+// The host side of every fused launch.  What the entry points differ in is `vq` and which pointers they pass:
+//   !vq  Fused encode + quantize (reference v5:71-74).  packed: lipvq_mlp3_pack_f32 of the encoder stack (A -> 64 -> 128 -> D with
+//        the Lipschitz-normalised W2, activations gelu, gelu, sigmoid); raw6: the same six tensors unpacked, {W0, b0, W1, b1, W2, b2}
+//        (device pointers; the array itself is host memory); packed16: the fast mode's fp16 fragments or NULL.  Outputs exactly as
+//        lipvq_mlp3_f32 + lipvq_nearest_f32(LIPVQ_DIST_NORM).  ze_out may be NULL.
+//   vq   The plain VQVAE (reference backbone.py:40-66: encoder = Linear/ReLU x 3, then `(z_e.unsqueeze(1) - E).pow(2).sum(-1)`,
+//        argmin, embedding lookup).  packed: the plain weights; no raw6, no packed16; ze_out [N][D] is REQUIRED (the straight-through
+//        value z_e + (z_q - z_e) of vq:74 needs it, and so does the exact stage).  Same results as lipvq_mlp3_f32(relu, relu, relu)
+//        followed by lipvq_nearest_f32(LIPVQ_DIST_SQSUM).
+// prep: lipvq_nearest_prepare_f32 of the codebook; workspace: lipvq_tokenize_workspace_bytes(N, D); zq, usage (accumulated) may be
+// NULL; pre0..2: all three (the training forward) or none.  After the call workspace[0] (int) = rows decided by an exact stage.
+// Every check comes before the first launch; a launch that fails zeroes the header, so that no counter is left for the next call
+// (a call that succeeds leaves the live counters at zero itself: lq_ws_publish; lipvq_tokenize_workspace_init zeroes a fresh one).
+static int tokenize_run(const char* who, bool vq, const float* x, const float* packed, const void* packed16, const float* const* raw6,
+                        const float* codebook, const void* prep, int64_t* idx, float* zq, int64_t* usage, float* ze_out,
+                        float* pre0, float* pre1, float* pre2, void* workspace, int64_t N, int A, int J0, int J1, int D, int K,
+                        void* stream) {
+    if (N < 0) return fail(LIPVQ_EINVAL, "%s: N < 0", who);
     if (N == 0) return LIPVQ_OK;
-    if (!x || !packed || !raw6 || !codebook || !prep || !idx || !workspace) return fail(LIPVQ_EINVAL, "tokenize: null pointer");
-    for (int i = 0; i < 6; ++i)
-        if (!raw6[i]) return fail(LIPVQ_EINVAL, "tokenize: raw encoder weight %d is null", i);
+    if (!x || !packed || !codebook || !prep || !idx || !workspace || (vq ? !ze_out : !raw6)) return fail(LIPVQ_EINVAL, "%s: null pointer", who);
+    for (int i = 0; !vq && i < 6; ++i)
+        if (!raw6[i]) return fail(LIPVQ_EINVAL, "%s: raw encoder weight %d is null", who, i);
     if (!lipvq_tokenize_supported(A, J0, J1, D, K))
-        return fail(LIPVQ_EUNSUPPORTED, "tokenize: unsupported shape A=%d J0=%d J1=%d D=%d K=%d", A, J0, J1, D, K);
-    if (N > 2147483647LL) return fail(LIPVQ_EUNSUPPORTED, "tokenize: N too large");
-    if ((((uintptr_t)codebook | (uintptr_t)zq | (uintptr_t)ze_out | (uintptr_t)workspace | (uintptr_t)packed16) & 15) != 0)
-        return fail(LIPVQ_EINVAL, "tokenize: codebook, zq, ze_out, workspace and packed16 must be 16-byte aligned");
+        return fail(LIPVQ_EUNSUPPORTED, "%s: unsupported shape A=%d J0=%d J1=%d D=%d K=%d", who, A, J0, J1, D, K);
+    if (N > 2147483647LL) return fail(LIPVQ_EUNSUPPORTED, "%s: N too large", who);
+    if ((((uintptr_t)codebook | (uintptr_t)zq | (uintptr_t)ze_out | (uintptr_t)workspace | (uintptr_t)packed16 | (uintptr_t)pre0 |
+          (uintptr_t)pre1 | (uintptr_t)pre2) & 15) != 0)
+        return fail(LIPVQ_EINVAL, "%s: codebook, zq, ze_out, workspace, packed16 and pre0..2 must be 16-byte aligned", who);
+    if (packed16 && !lipvq_tokenize_fast_supported(A, J0, J1, D, K))
+        return fail(LIPVQ_EUNSUPPORTED, "%s: D=%d has no fast instance (32, 64, 128)", who, D);
     hipStream_t st = (hipStream_t)stream;
-    unsigned char* ws = (unsigned char*)workspace;
-    int* amb_count = (int*)ws + LQ_WS_LIVE;           // the header's live counters (lipvq_screen.h: zero between calls)
-    int* amb_list = (int*)(ws + 64);
-    // z_e goes to the caller's buffer when one is given (training), otherwise -- see below -- to a scratch in the workspace
-    float* ze_buf = ze_out;
+    const LqWorkspace ws{(unsigned char*)workspace, N, D};
+    const LqOut out{idx, zq, usage};
     // the one-product screen (parity instances only): its exact stage reads z_e rows, so one is always written
     const int coarse = !packed16 ? lq_screen_coarse(lq_screen_S(D), K) : 0;
     // ... and with the three-product screen too (round 3, late): the exact stage on stored rows (nearest_lists_kernel: a wave per
@@ -1131,69 +1123,56 @@ static int tokenize_impl(const float* x, const float* packed, const void* packed
     // not feel (it is matrix-pipe bound at 0.4 TB/s of HBM traffic; `traffic` in bench.py's roofline shows them: 171 -> 305 MB).
     // Until then only batches of <= 131 072 rows stored z_e.  The fast mode keeps that limit: above it its uncertified rows are
     // re-encoded with the fp32 encoder and get the parity mode's answer.
-    // (LIPVQ_TOK_ZE_ROWS: measurement knob, the batch size up to which a launch stores z_e when nothing else asks for it; per launch)
+    // (tok_ze_rows: measurement knob, the batch size up to which a launch stores z_e when nothing else asks for it; per launch)
     int64_t ze_rows = packed16 ? 131072 : INT64_MAX;
-    if (const char* ev = lq_knob("LIPVQ_TOK_ZE_ROWS")) ze_rows = atoll(ev);
-    if ((coarse || N <= ze_rows) && !ze_buf) {
-        size_t off = 64 + lq_lists_bytes(N) + sizeof(float) * w2q_floats(D);
-        off = (off + 255) & ~(size_t)255;
-        ze_buf = reinterpret_cast<float*>(ws + off);
-    }
-    // (no fill of the header here since round 4: the call's last kernel leaves the live counters at zero, lq_ws_finish;
-    // lipvq_tokenize_workspace_init zeroes a fresh workspace once)
-    float* w2q = nullptr;
-    if (w2q_floats(D)) {
-        // the streamed instance: re-lay out layer 2's packed weights into the workspace (one small launch; the weights may have
-        // changed since the last call and the library keeps no state)
-        w2q = reinterpret_cast<float*>(ws + 64 + lq_lists_bytes(N));
-        const PackedLayout PL = packed_layout(A, J0, J1, D);
-        const size_t n = w2q_floats(D);
-        hipLaunchKernelGGL(w2q_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, packed + PL.oP2, w2q, PL.T2, PL.S2);
-    }
-    TokArgs a{x, packed, (const unsigned char*)packed16, (const unsigned char*)prep, codebook, idx, zq,
-              (unsigned long long*)usage, ze_buf, amb_count, amb_list, w2q, pre0, pre1, pre2, N, A, D, K, LIPVQ_SCREEN_GAMMA, coarse,
-              lq_inplace(ze_buf != nullptr, coarse, K), 0, 0, 0};
+    if (const char* ev = lq_knob("tok_ze_rows")) ze_rows = atoll(ev);
+    // z_e goes to the caller's buffer when one is given (training, the plain VQVAE), otherwise to the workspace's scratch
+    float* ze_buf = (ze_out || !(coarse || N <= ze_rows)) ? ze_out : ws.ze_scratch();
+    TokArgs a{};
+    a.x = x;
+    a.packed = packed;
+    a.packed16 = (const unsigned char*)packed16;
+    a.prep = (const unsigned char*)prep;
+    a.cb = codebook;
+    a.idx = idx;
+    a.zq = zq;
+    a.usage = (unsigned long long*)usage;
+    a.ze_out = ze_buf;
+    a.amb_count = ws.live();
+    a.amb_list = ws.row_list();
+    a.w2q = LqWorkspace::w2q_floats(D) ? ws.w2q() : nullptr;
+    a.pre0 = pre0;
+    a.pre1 = pre1;
+    a.pre2 = pre2;
+    a.N = N;
+    a.A = A;
+    a.D = D;
+    a.K = K;
+    a.gamma = LIPVQ_SCREEN_GAMMA;
+    a.coarse = coarse;
+    a.inplace = lq_inplace(ze_buf != nullptr, coarse, K);
     a.ze_ring = lq_ze_ring(ze_out != nullptr, a.inplace);
-    a.defer_ze = lq_schedule(a.ze_ring).defer_ze;
-    a.nt_ze = lq_schedule(a.ze_ring).nt_ze;
-    int rc;
-    if (pre0) {
-        if ((((uintptr_t)pre0 | (uintptr_t)pre1 | (uintptr_t)pre2) & 15) != 0)
-            return fail(LIPVQ_EINVAL, "tokenize_train: the pre-activation buffers must be 16-byte aligned");
-        switch (D) {
-            case 32: rc = launch_tokenize<2, false, true>(a, st); break;
-            case 64: rc = launch_tokenize<4, false, true>(a, st); break;
-            case 128: rc = launch_tokenize<8, false, true>(a, st); break;
-            default: rc = launch_tokenize<13, false, true>(a, st); break;
-        }
-    } else if (packed16) {
-        switch (D) {
-            case 32: rc = launch_tokenize<2, true>(a, st); break;
-            case 64: rc = launch_tokenize<4, true>(a, st); break;
-            case 128: rc = launch_tokenize<8, true>(a, st); break;
-            default: return fail(LIPVQ_EUNSUPPORTED, "tokenize_fast: D=%d has no fast instance (32, 64, 128)", D);
-        }
-    } else {
-        switch (D) {
-            case 32: rc = launch_tokenize<2, false>(a, st); break;
-            case 64: rc = launch_tokenize<4, false>(a, st); break;
-            case 128: rc = launch_tokenize<8, false>(a, st); break;
-            default: rc = launch_tokenize<13, false>(a, st); break;
-        }
-    }
+    const LqSchedule sc = lq_schedule(a.ze_ring);
+    a.defer_ze = sc.defer_ze;
+    a.nt_ze = sc.nt_ze;
+    int rc = LIPVQ_OK;
+    lq_dispatch<TOK_TRAIN, TOK_FAST, TOK_PARITY, TOK_VQ>(vq ? TOK_VQ : pre0 ? TOK_TRAIN : packed16 ? TOK_FAST : TOK_PARITY, [&](auto mode) {
+        lq_dispatch<32, 64, 128, 208>(D, [&](auto d) { rc = launch_tokenize<(d() + 15) / 16, mode()>(a, st); });
+    });
     if (!rc && !a.inplace) {
         // uncertified rows (count on the device): exact decision, from the stored z_e rows or from x
-        if (ze_buf) rc = lipvq_launch_rows(ze_buf, 0, codebook, idx, zq, usage, amb_list, amb_count, N, K, D, st);
-        else rc = lipvq_launch_rows_encode(x, raw6, A, codebook, idx, zq, usage, amb_list, amb_count, N, K, D, st);
+        if (ze_buf) rc = lipvq_launch_rows(ze_buf, 0, codebook, out, ws, K, st, vq ? LIPVQ_DIST_SQSUM : LIPVQ_DIST_NORM);
+        else rc = lipvq_launch_rows_encode(x, raw6, A, codebook, out, ws, K, st);
     }
-    if (rc) (void)hipMemsetAsync(ws, 0, 64, st);     // a failed call must not leave counters behind for the next one
+    if (rc) (void)hipMemsetAsync(ws.header(), 0, LqWorkspace::kHeaderBytes, st);
     return rc;
 }
 
 extern "C" int lipvq_tokenize_f32(const float* x, const float* packed, const float* const* raw6, const float* codebook,
                                   const void* prep, int64_t* idx, float* zq, int64_t* usage, float* ze_out,
                                   void* workspace, int64_t N, int A, int J0, int J1, int D, int K, void* stream) {
-    return tokenize_impl(x, packed, nullptr, raw6, codebook, prep, idx, zq, usage, ze_out, workspace, N, A, J0, J1, D, K, stream);
+    return tokenize_run("tokenize", false, x, packed, nullptr, raw6, codebook, prep, idx, zq, usage, ze_out, nullptr, nullptr, nullptr,
+                        workspace, N, A, J0, J1, D, K, stream);
 }
 
 // lipvq_tokenize_f32's schedule tuned on the caller's device, shape and data: the four (defer_ze, nt_ze) combinations, each warmed
@@ -1224,7 +1203,7 @@ extern "C" int lipvq_tokenize_tune_f32(const float* x, const float* packed, cons
     int rc = LIPVQ_OK;
     auto run = [&](int n) {
         for (int i = 0; i < n && !rc; ++i)
-            rc = tokenize_impl(x, packed, nullptr, raw6, codebook, prep, idx, zq, usage, ze_out, workspace, N, A, J0, J1, D, K, stream);
+            rc = lipvq_tokenize_f32(x, packed, raw6, codebook, prep, idx, zq, usage, ze_out, workspace, N, A, J0, J1, D, K, stream);
     };
     run(launches);                                                       // the chip's clock and power state of a running job
     for (int round = 0; round < 2 && !rc; ++round)
@@ -1260,58 +1239,16 @@ extern "C" int lipvq_tokenize_train_f32(const float* x, const float* packed, con
                                         float* pre1, float* pre2, void* workspace, int64_t N, int A, int J0, int J1, int D, int K,
                                         void* stream) {
     if (!ze_out || !pre0 || !pre1 || !pre2) return fail(LIPVQ_EINVAL, "tokenize_train: z_e and the three pre-activation buffers are required");
-    return tokenize_impl(x, packed, nullptr, raw6, codebook, prep, idx, zq, usage, ze_out, workspace, N, A, J0, J1, D, K, stream,
-                         pre0, pre1, pre2);
+    return tokenize_run("tokenize_train", false, x, packed, nullptr, raw6, codebook, prep, idx, zq, usage, ze_out, pre0, pre1, pre2,
+                        workspace, N, A, J0, J1, D, K, stream);
 }
 
-// The plain VQVAE's encode + quantize in one launch (reference backbone.py:40-66: encoder = Linear/ReLU x 3, then
-// `(z_e.unsqueeze(1) - E).pow(2).sum(-1)`, argmin, embedding lookup).  packed: lipvq_mlp3_pack_f32 of the encoder (A -> 64 -> 128 -> D,
-// plain weights); prep: lipvq_nearest_prepare_f32 of the embedding table; ze_out [N][D] is REQUIRED (the straight-through value
-// z_e + (z_q - z_e) of vq:74 needs it, and so does the exact stage).  Same results as lipvq_mlp3_f32(relu, relu, relu) followed by
-// lipvq_nearest_f32(LIPVQ_DIST_SQSUM).  workspace: lipvq_tokenize_workspace_bytes(N, D).
-static int vq_tokenize_impl(const float* x, const float* packed, const float* codebook, const void* prep, int64_t* idx,
-                            float* zq, int64_t* usage, float* ze_out, float* pre0, float* pre1, float* pre2, void* workspace, int64_t N,
-                            int A, int J0, int J1, int D, int K, void* stream) {
-    if (N < 0) return fail(LIPVQ_EINVAL, "vq_tokenize: N < 0");
-    if (N == 0) return LIPVQ_OK;
-    if (!x || !packed || !codebook || !prep || !idx || !ze_out || !workspace) return fail(LIPVQ_EINVAL, "vq_tokenize: null pointer");
-    if (!lipvq_tokenize_supported(A, J0, J1, D, K))
-        return fail(LIPVQ_EUNSUPPORTED, "vq_tokenize: unsupported shape A=%d J0=%d J1=%d D=%d K=%d", A, J0, J1, D, K);
-    if (N > 2147483647LL) return fail(LIPVQ_EUNSUPPORTED, "vq_tokenize: N too large");
-    if ((((uintptr_t)codebook | (uintptr_t)zq | (uintptr_t)ze_out | (uintptr_t)workspace) & 15) != 0)
-        return fail(LIPVQ_EINVAL, "vq_tokenize: codebook, zq, ze_out and workspace must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    unsigned char* ws = (unsigned char*)workspace;
-    int* amb_count = (int*)ws + LQ_WS_LIVE;           // the header's live counters: zero between calls (lq_ws_finish)
-    int* amb_list = (int*)(ws + 64);
-    float* w2q = nullptr;
-    if (w2q_floats(D)) {
-        w2q = reinterpret_cast<float*>(ws + 64 + lq_lists_bytes(N));
-        const PackedLayout PL = packed_layout(A, J0, J1, D);
-        const size_t n = w2q_floats(D);
-        hipLaunchKernelGGL(w2q_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, packed + PL.oP2, w2q, PL.T2, PL.S2);
-    }
-    const int coarse = lq_screen_coarse(lq_screen_S(D), K);
-    TokArgs a{x, packed, nullptr, (const unsigned char*)prep, codebook, idx, zq, (unsigned long long*)usage, ze_out, amb_count,
-              amb_list, w2q, pre0, pre1, pre2, N, A, D, K, LIPVQ_SCREEN_GAMMA, coarse, lq_inplace(true, coarse, K),
-              lq_schedule().defer_ze, lq_schedule().nt_ze, 0};
-    int rc;
-    switch (D) {
-        case 32: rc = launch_tokenize_vq<2>(a, st); break;
-        case 64: rc = launch_tokenize_vq<4>(a, st); break;
-        case 128: rc = launch_tokenize_vq<8>(a, st); break;
-        default: rc = launch_tokenize_vq<13>(a, st); break;
-    }
-    if (!rc && !a.inplace) rc = lipvq_launch_rows(ze_out, 0, codebook, idx, zq, usage, amb_list, amb_count, N, K, D, st, LIPVQ_DIST_SQSUM);
-    if (rc) (void)hipMemsetAsync(ws, 0, 64, st);     // a failed call must not leave counters behind for the next one
-    return rc;
-}
-
+// The plain VQVAE's encode + quantize in one launch (tokenize_run, vq).
 extern "C" int lipvq_vq_tokenize_f32(const float* x, const float* packed, const float* codebook, const void* prep, int64_t* idx,
                                      float* zq, int64_t* usage, float* ze_out, void* workspace, int64_t N, int A, int J0, int J1,
                                      int D, int K, void* stream) {
-    return vq_tokenize_impl(x, packed, codebook, prep, idx, zq, usage, ze_out, nullptr, nullptr, nullptr, workspace, N, A, J0, J1, D, K,
-                            stream);
+    return tokenize_run("vq_tokenize", true, x, packed, nullptr, nullptr, codebook, prep, idx, zq, usage, ze_out, nullptr, nullptr, nullptr,
+                        workspace, N, A, J0, J1, D, K, stream);
 }
 
 // The training forward of the plain VQVAE in one launch: lipvq_vq_tokenize_f32 that also stores the three pre-activations
@@ -1320,8 +1257,10 @@ extern "C" int lipvq_vq_tokenize_train_f32(const float* x, const float* packed, 
                                            float* zq, int64_t* usage, float* ze_out, float* pre0, float* pre1, float* pre2,
                                            void* workspace, int64_t N, int A, int J0, int J1, int D, int K, void* stream) {
     if (N > 0 && (!pre0 || !pre1 || !pre2)) return fail(LIPVQ_EINVAL, "vq_tokenize_train: the three pre-activation buffers are required");
+    // (ahead of every other check, as this entry point has always answered)
     if ((((uintptr_t)pre0 | (uintptr_t)pre1 | (uintptr_t)pre2) & 15) != 0) return fail(LIPVQ_EINVAL, "vq_tokenize_train: pre0..2 must be 16-byte aligned");
-    return vq_tokenize_impl(x, packed, codebook, prep, idx, zq, usage, ze_out, pre0, pre1, pre2, workspace, N, A, J0, J1, D, K, stream);
+    return tokenize_run("vq_tokenize_train", true, x, packed, nullptr, nullptr, codebook, prep, idx, zq, usage, ze_out, pre0, pre1, pre2,
+                        workspace, N, A, J0, J1, D, K, stream);
 }
 
 // Fast mode: the encoder's GEMMs on fp16 MFMAs (packed16 = lipvq_mlp3_pack_f16_f32 of the same weights; `packed` still
@@ -1331,5 +1270,6 @@ extern "C" int lipvq_tokenize_fast_f32(const float* x, const float* packed, cons
                                        const float* codebook, const void* prep, int64_t* idx, float* zq, int64_t* usage,
                                        void* workspace, int64_t N, int A, int J0, int J1, int D, int K, void* stream) {
     if (!packed16) return fail(LIPVQ_EINVAL, "tokenize_fast: packed16 is null");
-    return tokenize_impl(x, packed, packed16, raw6, codebook, prep, idx, zq, usage, nullptr, workspace, N, A, J0, J1, D, K, stream);
+    return tokenize_run("tokenize_fast", false, x, packed, packed16, raw6, codebook, prep, idx, zq, usage, nullptr, nullptr, nullptr,
+                        nullptr, workspace, N, A, J0, J1, D, K, stream);
 }

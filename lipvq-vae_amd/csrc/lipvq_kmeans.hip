@@ -308,15 +308,9 @@ template <int DIST>
 static void km_pass_any(int mode, const float* z, const float* cb, const int64_t* cidx, KmState* st, float* d,
                         unsigned long long* part, int64_t N, int K, int D, hipStream_t s) {
     const bool aligned = ((uintptr_t)z & 15) == 0;
-    if (aligned && mode != KM_QSUM) {
-        switch (D) {
-            case 32: return km_pass<32, DIST>(mode, z, cb, cidx, st, d, part, N, K, D, s);
-            case 64: return km_pass<64, DIST>(mode, z, cb, cidx, st, d, part, N, K, D, s);
-            case 128: return km_pass<128, DIST>(mode, z, cb, cidx, st, d, part, N, K, D, s);
-            case 208: return km_pass<208, DIST>(mode, z, cb, cidx, st, d, part, N, K, D, s);
-            default: break;
-        }
-    }
+    if (aligned && mode != KM_QSUM &&
+        lq_dispatch<32, 64, 128, 208>(D, [&](auto dt) { km_pass<dt(), DIST>(mode, z, cb, cidx, st, d, part, N, K, D, s); }))
+        return;
     km_pass<0, DIST>(mode, z, cb, cidx, st, d, part, N, K, D, s);
 }
 

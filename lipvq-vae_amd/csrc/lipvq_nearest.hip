@@ -105,12 +105,10 @@ static int launch_nearest_direct(const float* z, const float* cb, int64_t* idx, 
     if (KT > K) KT = K;
     size_t lds = (size_t)KT * D * sizeof(float);
     unsigned blocks = (unsigned)((N + 255) / 256);
-    if (dist == LIPVQ_DIST_NORM)
-        hipLaunchKernelGGL((nearest_direct_kernel<DCH, LIPVQ_DIST_NORM>), dim3(blocks), dim3(256), lds, st,
-                           z, cb, idx, zq, (unsigned long long*)usage, best, N, K, KT);
-    else
-        hipLaunchKernelGGL((nearest_direct_kernel<DCH, LIPVQ_DIST_SQSUM>), dim3(blocks), dim3(256), lds, st,
-                           z, cb, idx, zq, (unsigned long long*)usage, best, N, K, KT);
+    lq_dispatch<LIPVQ_DIST_NORM, LIPVQ_DIST_SQSUM>(dist, [&](auto rule) {
+        hipLaunchKernelGGL((nearest_direct_kernel<DCH, rule()>), dim3(blocks), dim3(256), lds, st, z, cb, idx, zq,
+                           (unsigned long long*)usage, best, N, K, KT);
+    });
     return check_launch("nearest_direct");
 }
 
@@ -189,24 +187,19 @@ static int launch_nearest_wide(const float* z, const float* cb, int64_t* idx, fl
                                int64_t N, int K, int D, int dist, hipStream_t st) {
     const size_t lds = nearest_wide_lds_bytes(D);
     const unsigned blocks = (unsigned)((N + NW_ROWS - 1) / NW_ROWS);
-    static LqLdsReserve reserved[2][4];                   // per kernel instance: (rule, width slot)
     int rc = LIPVQ_OK;
-    auto go = [&](auto kfn, int slot) {
-        if (lds > 64 * 1024) {
-            rc = lipvq_reserve_lds(reserved[dist == LIPVQ_DIST_NORM ? 0 : 1][slot], (const void*)kfn, lds, "nearest_wide");
-            if (rc) return;
-        }
-        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), lds, st, z, cb, idx, zq, (unsigned long long*)usage, best, N, K, D);
+    auto go = [&](auto dt) {                              // (dt = the compile-time width, 0: any)
+        lq_dispatch<LIPVQ_DIST_NORM, LIPVQ_DIST_SQSUM>(dist, [&](auto rule) {
+            static LqLdsReserve reserved;                 // per kernel instance: one per instantiation of this lambda
+            auto kfn = nearest_wide_kernel<rule(), dt()>;
+            if (lds > 64 * 1024) {
+                rc = lipvq_reserve_lds(reserved, (const void*)kfn, lds, "nearest_wide");
+                if (rc) return;
+            }
+            hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), lds, st, z, cb, idx, zq, (unsigned long long*)usage, best, N, K, D);
+        });
     };
-#define LQ_NW(DT_, SLOT_) do { if (dist == LIPVQ_DIST_NORM) go(nearest_wide_kernel<LIPVQ_DIST_NORM, DT_>, SLOT_); \
-                               else go(nearest_wide_kernel<LIPVQ_DIST_SQSUM, DT_>, SLOT_); } while (0)
-    switch (D) {
-        case 256: LQ_NW(256, 0); break;
-        case 384: LQ_NW(384, 1); break;
-        case 512: LQ_NW(512, 2); break;
-        default: LQ_NW(0, 3); break;
-    }
-#undef LQ_NW
+    if (!lq_dispatch<256, 384, 512>(D, go)) go(std::integral_constant<int, 0>{});
     if (rc) return rc;
     return check_launch("nearest_wide");
 }
@@ -221,15 +214,9 @@ extern "C" int lipvq_nearest_f32(const float* z, const float* codebook, int64_t*
     if (N > 2147483647LL * 64) return fail(LIPVQ_EUNSUPPORTED, "nearest: N too large");
     hipStream_t st = (hipStream_t)stream;
     const bool aligned = (((uintptr_t)z | (uintptr_t)codebook | (uintptr_t)zq) & 15) == 0;
-    if (aligned) {
-        switch (D) {
-            case 32: return launch_nearest_direct<4>(z, codebook, idx, zq, usage, best, N, K, dist, st);
-            case 64: return launch_nearest_direct<8>(z, codebook, idx, zq, usage, best, N, K, dist, st);
-            case 128: return launch_nearest_direct<16>(z, codebook, idx, zq, usage, best, N, K, dist, st);
-            case 208: return launch_nearest_direct<26>(z, codebook, idx, zq, usage, best, N, K, dist, st);
-            default: break;
-        }
-    }
+    int rc = LIPVQ_OK;
+    if (aligned && lq_dispatch<32, 64, 128, 208>(D, [&](auto d) { rc = launch_nearest_direct<d() / 8>(z, codebook, idx, zq, usage, best, N, K, dist, st); }))
+        return rc;
     // 209 ... 512: LDS-staged (scalar staging: any alignment); the generic kernel is left to other widths
     if (D > 208 && D <= 512) {
         if ((N + NW_ROWS - 1) / NW_ROWS > 2147483647LL) return fail(LIPVQ_EUNSUPPORTED, "nearest: N too large");

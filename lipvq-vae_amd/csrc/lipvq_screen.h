@@ -553,30 +553,80 @@ __device__ __forceinline__ bool lq_screen_decide(const float (&m1)[16], const fl
 //   n = -1 : no information (scan all K codes).
 // `mask` is always valid unless n = -1; the exact kernels use the lane masks of both parts as soon as one part says -2.
 #define LQ_CAND_MAX 6
-__host__ __device__ static inline size_t lq_list_ints(int64_t N);
-// slots that get a list (later slots: full scan).  Every row can have one since round 3: the one-product screen leaves 10-40 % of
-// the rows to the exact kernel -- each with its two or three candidates -- where the three-product screen left a fraction of a percent
-__host__ __device__ static inline size_t lq_cand_cap(int64_t N) { return (size_t)N + 64; }
 
-// Workspace header of the screened routes (16 ints), round 4.  PUBLISHED by the screening launch before it ends (what the
-// kernels behind it and the host read): [0] rows the screen left to an exact decision (listed + decided in the launch's tail),
-// [1] listed rows (slots).  LIVE counters at [LQ_WS_LIVE ...], zero between calls:
-//   +0/+1 one 64-bit word: low half = listed rows (slot reservations add to it), high half = workgroups of the screening launch
+// ------------------------------------------------------------------------------------------
+// The workspace of the screened and fused routes: THE description of its layout, for host and device.
+//   [64 B header][row list][best-candidate list][short lists][slot-2 list]      lipvq_nearest_workspace_bytes(N)
+//   ... [streamed layer-2 weights][pad to 256 B][z_e scratch N x D]               lipvq_tokenize_workspace_bytes(N, D)
+// Header (16 ints).  PUBLISHED by the screening launch before it ends (what the kernels behind it and the host read):
+// [0] rows the screen left to an exact decision (listed + decided in the launch's tail), [1] listed rows (slots).  LIVE counters,
+// zero between calls:
+//   [8], [9]  one 64-bit word: low half = listed rows (slot reservations add to it), high half = workgroups of the screening launch
 //         that have arrived at its end.  The workgroup whose arrival completes the grid gets both halves back from its own
 //         atomic: it publishes [0] and [1] and zeroes the word -- every other workgroup's reservations returned before that
 //         workgroup arrived, so the low half is final;
-//   +2    slots the list kernel left to the scanning kernel -- zeroed by the NEXT screening launch's first workgroup (nothing
+//   [10]  slots the list kernel left to the scanning kernel -- zeroed by the NEXT screening launch's first workgroup (nothing
 //         reads or writes it between the scanning kernel of one call and the list kernel of the next);
 // No fill launch per call (it was a 4.7 us launch of its own, a twelfth of a 65 536-row shard's time), no finishing pass in the
 // kernels behind the launch (their grids are thousands of workgroups: that many arrivals on one word serialise for tens of
 // microseconds).  lipvq_tokenize_workspace_init zeroes a fresh workspace once.
-#define LQ_WS_LIVE 8
-#define LQ_WS_SLOT2 2
-// host side: the published number of listed rows, given the pointer to the live counters
-static inline const int* lq_ws_listed(const int* live) { return live - LQ_WS_LIVE + 1; }
+// Lists: a listed row owns one SLOT: row_list[slot] = the row, best_list[slot] = the screen's best candidate (bounds a full exact
+// scan), short_lists[16 slot ...] = its two parts' {n, mask, c0 .. c5} (above) -- every row can have one since round 3: the
+// one-product screen leaves 10-40 % of the rows to the exact kernel; slot2_list = the slots the list kernel left to the scanning kernel.
+// The kernels take the pointers as plain arguments (their signatures predate the view): a launch site derives them from the view,
+// device code that needs a neighbouring region gets the view back from the pointer it was given (from_lists, from_live).
+// scripts/ws_layout.py restates the offsets for the measurement scripts.
+// ------------------------------------------------------------------------------------------
+#define LQ_STREAM2_MIN_S 9       /* k-steps from which the fused launch streams its layer-2 weights (lipvq_fused.hip, STREAM2) */
+struct LqWorkspace {
+    unsigned char* base;         // 16-byte aligned; nullptr: no lists (the exact stage then decides all N rows)
+    int64_t N;                   // rows
+    int D;                       // latent width: sizes the fused calls' two regions behind the lists
+
+    static constexpr int kHeaderBytes = 64, kLive = 8, kSlot2 = kLive + 2;
+    __host__ __device__ static inline LqWorkspace from_lists(int* row_list, int64_t N) {
+        return LqWorkspace{reinterpret_cast<unsigned char*>(row_list) - kHeaderBytes, N, 0};
+    }
+    __host__ __device__ static inline LqWorkspace from_live(int* live) {
+        return LqWorkspace{reinterpret_cast<unsigned char*>(live - kLive), 0, 0};
+    }
+    __host__ __device__ static inline size_t list_ints(int64_t N) { return ((size_t)N + 15) & ~(size_t)15; }
+    __host__ __device__ static inline size_t short_cap(int64_t N) { return (size_t)N + 64; }   // slots that get a short list
+    // layer-2 weights of the streamed instance (D = 208): [t][16 groups][64 lanes][4 k-steps], the LDS image of one output tile's A
+    // operands as contiguous 16 KB slabs (w2q_pack_kernel), so that the kernel can copy them with the LDS-DMA
+    __host__ __device__ static inline size_t w2q_floats(int D) {
+        return (D + 15) / 16 >= LQ_STREAM2_MIN_S ? (size_t)((D + 31) / 32) * 16 * 256 : 0;
+    }
+    __host__ __device__ static inline size_t lists_end(int64_t N) {
+        return kHeaderBytes + sizeof(int) * (3 * list_ints(N) + 16 * short_cap(N));
+    }
+    __host__ __device__ static inline size_t nearest_bytes(int64_t N) { return lists_end(N); }
+    // (256 flat bytes for the pad in front of the z_e scratch, whatever its actual length: the size callers have always been told)
+    __host__ __device__ static inline size_t tokenize_bytes(int64_t N, int D) {
+        return lists_end(N) + sizeof(float) * w2q_floats(D) + 256 + sizeof(float) * (size_t)N * (size_t)D;
+    }
+
+    __host__ __device__ inline int* header() const { return reinterpret_cast<int*>(base); }
+    __host__ __device__ inline int* published() const { return header(); }                 // [0] exact rows, [1] listed rows
+    __host__ __device__ inline const int* listed() const { return header() + 1; }
+    __host__ __device__ inline int* live() const { return header() + kLive; }              // the 64-bit word
+    __host__ __device__ inline int* slot2_count() const { return header() + kSlot2; }
+    __host__ __device__ inline int* row_list() const { return reinterpret_cast<int*>(base + kHeaderBytes); }
+    __host__ __device__ inline int* best_list() const { return row_list() + list_ints(N); }
+    __host__ __device__ inline int* short_lists() const { return row_list() + 2 * list_ints(N); }
+    __host__ __device__ inline size_t short_cap() const { return short_cap(N); }
+    __host__ __device__ inline int* slot2_list() const { return row_list() + (2 * list_ints(N) + 16 * short_cap(N)); }
+    __host__ __device__ inline float* w2q() const { return reinterpret_cast<float*>(base + lists_end(N)); }
+    __host__ __device__ inline float* ze_scratch() const {
+        return reinterpret_cast<float*>(base + ((lists_end(N) + sizeof(float) * w2q_floats(D) + 255) & ~(size_t)255));
+    }
+    // -DLQ_STAMPS builds: 16 cycle counters per wave of the fused launch, over the second half of the (then mostly idle) row list
+    __host__ __device__ inline long long* stamps() const { return reinterpret_cast<long long*>(row_list() + (N / 2 & ~1)); }
+};
+
 #if defined(__HIPCC__)
 __device__ __forceinline__ void lq_ws_begin(int* __restrict__ live) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) live[LQ_WS_SLOT2] = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *LqWorkspace::from_live(live).slot2_count() = 0;
 }
 // every thread of every workgroup of the screening launch calls this once, last thing
 __device__ __forceinline__ void lq_ws_publish(int* __restrict__ live) {
@@ -586,8 +636,9 @@ __device__ __forceinline__ void lq_ws_publish(int* __restrict__ live) {
         const unsigned long long old = atomicAdd(reinterpret_cast<unsigned long long*>(live), 1ull << 32);
         if ((unsigned)(old >> 32) == gridDim.x - 1u) {                   // the last workgroup of the grid
             const int listed = (int)(unsigned)old;
-            live[-LQ_WS_LIVE] = listed;
-            live[-LQ_WS_LIVE + 1] = listed;
+            int* published = LqWorkspace::from_live(live).published();
+            published[0] = listed;
+            published[1] = listed;
             *reinterpret_cast<unsigned long long*>(live) = 0ull;
         }
     }
@@ -638,12 +689,13 @@ __device__ __forceinline__ void lq_emit_store(bool need, int slot /* valid in bo
                                               const int (&codes)[LQ_CAND_MAX], int my_k, int64_t row, int* __restrict__ amb_list,
                                               int64_t N, int lane) {
     const int h = lane >> 5;
+    const LqWorkspace ws = LqWorkspace::from_lists(amb_list, N);
     if (h == 0 && need) {
-        amb_list[slot] = (int)row;
-        amb_list[lq_list_ints(N) + slot] = my_k;                        // the screen's best candidate: bounds the exact scan
+        ws.row_list()[slot] = (int)row;
+        ws.best_list()[slot] = my_k;                                    // the screen's best candidate: bounds the exact scan
     }
-    if (!need || (size_t)slot >= lq_cand_cap(N)) return;
-    int* out = amb_list + 2 * lq_list_ints(N) + (size_t)slot * 16 + 8 * h;
+    if (!need || (size_t)slot >= ws.short_cap()) return;
+    int* out = ws.short_lists() + (size_t)slot * 16 + 8 * h;
     // the part's eight ints {n, mask, c0 .. c5} as TWO 16-byte stores (the slot is 64-byte aligned, the part 32): eight scattered
     // dword stores per listed half-row kept the wave's vmcnt busy well into the next block (its z_q copy waits for vmcnt(0))
     static_assert(LQ_CAND_MAX == 6, "a part is {n, mask, six codes}");
@@ -912,7 +964,7 @@ __device__ __forceinline__ void lq_screen_gather(const float* __restrict__ cb, f
     }
 }
 
-// Which screen a shape runs by default (LIPVQ_SCREEN_MODE=coarse|fine overrides per launch: lipvq_screen.hip).  Measured on one box
+// Which screen a shape runs by default (option screen_mode = coarse | fine overrides per launch: lipvq_screen.hip).  Measured on one box
 // (profiles/r03_y_coarse_sweep_last_build.txt: 524 288 rows, whole call incl. the exact stage, one-product / three-product time):
 //   D =  64: K = 1024 0.99, 4096 0.78, 8192 0.68      D = 128: K = 1024 0.87, 2048 0.76, 4096 0.65, 8192 0.57 (BASELINE config 3)
 //   D = 208: K = 1024 0.91 (the reference's own widths), 4096 0.64, 8192 0.55
@@ -922,21 +974,18 @@ __device__ __forceinline__ void lq_screen_gather(const float* __restrict__ cb, f
 static inline int lq_screen_coarse_default(int S, int K) { return (K >= 4096 || (S >= 8 && K >= 1024)) ? 1 : 0; }
 int lq_screen_coarse(int S, int K);
 
-// workspace of the screened routes: [64 B: counter] [row list: lq_list_ints(N) ints] [best-candidate list: the same]
-// [short lists: 16 ints x lq_cand_cap(N)]
-__host__ __device__ static inline size_t lq_list_ints(int64_t N) { return ((size_t)N + 15) & ~(size_t)15; }
-// ... [slots the list kernel left to the scanning kernel: lq_list_ints(N) ints; their count is the header's second int]
-__host__ __device__ static inline size_t lq_lists_bytes(int64_t N) { return sizeof(int) * (3 * lq_list_ints(N) + 16 * lq_cand_cap(N)); }
-__host__ __device__ static inline size_t lq_slot2_offset_ints(int64_t N) { return 2 * lq_list_ints(N) + 16 * lq_cand_cap(N); }
-
-// exact decision for listed rows (lipvq_screen.hip); z_by_slot: z is a compact [count][D] buffer
+// The groups the exact stage's launch helpers pass along (lipvq_screen.hip): where the decisions go ...
+struct LqOut {
+    int64_t* idx;                // [N]
+    float* zq;                   // [N][D] or NULL
+    int64_t* usage;              // [K] or NULL, accumulated
+};
+// ... and exact decision for the rows of ws's lists, or (ws.base == nullptr) for all ws.N rows; z_by_slot: z is a compact [count][D] buffer
 // dist: LIPVQ_DIST_NORM (v5:43-46: torch.norm's order, roots compared) or LIPVQ_DIST_SQSUM (vq:57-63: pow(2).sum's order)
-int lipvq_launch_rows(const float* z, int z_by_slot, const float* cb, int64_t* idx, float* zq, int64_t* usage,
-                      const int* amb_list, const int* amb_count, int64_t N, int K, int D, hipStream_t st,
+int lipvq_launch_rows(const float* z, int z_by_slot, const float* cb, const LqOut& out, const LqWorkspace& ws, int K, hipStream_t st,
                       int dist = LIPVQ_DIST_NORM);
 // the same for rows whose z_e was never stored: recomputed from x with the raw (unpacked) encoder weights
 // raw6 = {W0, b0, W1, b1, W2 (Lipschitz-normalised), b2}
-int lipvq_launch_rows_encode(const float* x, const float* const* raw6, int A, const float* cb, int64_t* idx, float* zq,
-                             int64_t* usage, const int* amb_list, const int* amb_count, int64_t N, int K, int D,
-                             hipStream_t st);
+int lipvq_launch_rows_encode(const float* x, const float* const* raw6, int A, const float* cb, const LqOut& out, const LqWorkspace& ws,
+                             int K, hipStream_t st);
 #endif

@@ -1054,29 +1054,20 @@ extern "C" int lipvq_nearest_small_f32(const float* z, const float* codebook, in
     unsigned long long* keys = (unsigned long long*)((unsigned char*)workspace + nsm_counter_bytes(N));
     const size_t lds = nsm_lds_bytes(D);
     int rc = LIPVQ_OK;
-    // the reservation belongs to each kernel instance: one slot per (rule, compile-time width) -- every instance has the same
-    // function-pointer type, so a static inside `go` would be shared by all of them
-    static LqLdsReserve reserved[2][8];
-    auto go = [&](auto kfn, int slot) {
-        if (lds > 64 * 1024) {
-            rc = lipvq_reserve_lds(reserved[dist == LIPVQ_DIST_NORM ? 0 : 1][slot], (const void*)kfn, lds, "nearest_small");
-            if (rc) return;
-        }
-        hipLaunchKernelGGL(kfn, dim3((unsigned)(RGn * CG)), dim3(256), lds, (hipStream_t)stream, z, codebook, idx, zq,
-                           (unsigned long long*)usage, (int)N, K, D, CG, counters, keys);
+    // (DT = the compile-time width, 0: any; `reserved` belongs to the kernel instance: one per instantiation of this lambda)
+    auto go = [&](auto dt) {
+        lq_dispatch<LIPVQ_DIST_NORM, LIPVQ_DIST_SQSUM>(dist, [&](auto rule) {
+            static LqLdsReserve reserved;
+            auto kfn = nearest_small_kernel<rule(), dt()>;
+            if (lds > 64 * 1024) {
+                rc = lipvq_reserve_lds(reserved, (const void*)kfn, lds, "nearest_small");
+                if (rc) return;
+            }
+            hipLaunchKernelGGL(kfn, dim3((unsigned)(RGn * CG)), dim3(256), lds, (hipStream_t)stream, z, codebook, idx, zq,
+                               (unsigned long long*)usage, (int)N, K, D, CG, counters, keys);
+        });
     };
-#define LQ_NSM(DT_, SLOT_) do { if (dist == LIPVQ_DIST_NORM) go(nearest_small_kernel<LIPVQ_DIST_NORM, DT_>, SLOT_); \
-                                else go(nearest_small_kernel<LIPVQ_DIST_SQSUM, DT_>, SLOT_); } while (0)
-    switch (D) {
-        case 32: LQ_NSM(32, 0); break;
-        case 64: LQ_NSM(64, 1); break;
-        case 128: LQ_NSM(128, 2); break;
-        case 208: LQ_NSM(208, 3); break;
-        case 256: LQ_NSM(256, 4); break;
-        case 512: LQ_NSM(512, 5); break;
-        default: LQ_NSM(0, 6); break;
-    }
-#undef LQ_NSM
+    if (!lq_dispatch<32, 64, 128, 208, 256, 512>(D, go)) go(std::integral_constant<int, 0>{});
     if (rc) return rc;
     return check_launch("nearest_small");
 }
@@ -1222,40 +1213,29 @@ __global__ __launch_bounds__(256) void nearest_rows_encode_kernel(
   }
 }
 
-int lipvq_launch_rows_encode(const float* x, const float* const* raw6, int A, const float* cb, int64_t* idx, float* zq,
-                             int64_t* usage, const int* amb_list, const int* amb_count, int64_t N, int K, int D,
-                             hipStream_t st) {
-    const int* amb_seed = amb_list + lq_list_ints(N);
+int lipvq_launch_rows_encode(const float* x, const float* const* raw6, int A, const float* cb, const LqOut& out, const LqWorkspace& ws,
+                             int K, hipStream_t st) {
     RawEncoder w{raw6[0], raw6[1], raw6[2], raw6[3], raw6[4], raw6[5]};
-    int64_t blocks = (N + 3) / 4;
+    int64_t blocks = (ws.N + 3) / 4;
     if (blocks > 1024) blocks = 1024;           // (the count lives on the device; the grid strides)
-    auto go = [&](auto kfn) {
-        hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), 0, st, x, w, A, cb, idx, zq,
-                           (unsigned long long*)usage, amb_list, lq_ws_listed(amb_count), K, amb_seed, amb_list + 2 * lq_list_ints(N),
-                           lq_cand_cap(N));
-    };
-    switch (D) {
-        case 32: go(nearest_rows_encode_kernel<4>); break;
-        case 64: go(nearest_rows_encode_kernel<8>); break;
-        case 128: go(nearest_rows_encode_kernel<16>); break;
-        case 208: go(nearest_rows_encode_kernel<26>); break;
-        default: return fail(LIPVQ_EUNSUPPORTED, "nearest_rows_encode: D=%d has no instance", D);
-    }
+    if (!lq_dispatch<32, 64, 128, 208>(ws.D, [&](auto d) {
+            hipLaunchKernelGGL((nearest_rows_encode_kernel<d() / 8>), dim3((unsigned)blocks), dim3(256), 0, st, x, w, A, cb, out.idx,
+                               out.zq, (unsigned long long*)out.usage, ws.row_list(), ws.listed(), K, ws.best_list(), ws.short_lists(),
+                               ws.short_cap());
+        }))
+        return fail(LIPVQ_EUNSUPPORTED, "nearest_rows_encode: D=%d has no instance", ws.D);
     return check_launch("nearest_rows_encode");
 }
 
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-extern "C" size_t lipvq_nearest_workspace_bytes(int64_t N) {
-    if (N <= 0) return 0;
-    return 64 + lq_lists_bytes(N);    // [0] uncertified-row counter, then the row list, the best-candidate list and the short lists
-}
+extern "C" size_t lipvq_nearest_workspace_bytes(int64_t N) { return N <= 0 ? 0 : LqWorkspace::nearest_bytes(N); }
 
-// One-product ("coarse") or three-product screen.  LIPVQ_SCREEN_MODE=coarse|fine (read per launch; measurement knob --
+// One-product ("coarse") or three-product screen.  Option screen_mode = coarse | fine (read per launch; measurement knob --
 // identical results): the default is the shape's measured winner (lq_screen_coarse_default).
 int lq_screen_coarse(int S, int K) {
-    const char* e = lq_knob("LIPVQ_SCREEN_MODE");
+    const char* e = lq_knob("screen_mode");
     if (e && !strcmp(e, "coarse")) return 1;
     if (e && !strcmp(e, "fine")) return 0;
     return lq_screen_coarse_default(S, K);
@@ -1269,144 +1249,141 @@ extern "C" int lipvq_screen_is_coarse(int K, int D) {
     return (K > 0 && S && S <= LQ_SCREEN_NARROW_MAX_S) ? lq_screen_coarse(S, K) : 0;     // (the wide instances are three-product only)
 }
 
+// the screening launch of a screened call: every kernel below takes (row list, live word) as its two workspace arguments
 template <int S>
-static int launch_screen(const float* z, const unsigned char* prep, const float* cb, int64_t* idx, float* zq,
-                         int64_t* usage, int* amb_list, int* amb_count, float* dbg, int64_t N, int K, int D,
-                         float gamma, hipStream_t st) {
-    using SC = StandaloneScreen<S>;
-    size_t lds = lq_ring_bytes<S, SC::TC, SC::NB>();
-    if (lds < (size_t)SCREEN_WAVES * LQ_DECIDE_BYTES) lds = (size_t)SCREEN_WAVES * LQ_DECIDE_BYTES;      // per-wave transpose slices reuse the stages
-    const int64_t rows_per_block = SCREEN_WAVES * 32;
-    unsigned blocks = (unsigned)((N + rows_per_block - 1) / rows_per_block);
-    // the debug hook takes the arithmetic from the sign of its gamma (negative: the one-product chain, bound factor |gamma|)
-    const bool coarse = dbg ? (gamma < 0.0f) : (lq_screen_coarse(S, K) != 0);
-    if (gamma < 0.0f) gamma = -gamma;
-    auto kfn = dbg ? (coarse ? screen_kernel<S, true, true> : screen_kernel<S, true, false>)
-                   : (coarse ? screen_kernel<S, false, true> : screen_kernel<S, false, false>);
-    static LqLdsReserve reserved[4];            // per instantiation and kernel flavour: per-device, thread-safe (lipvq_common.h)
-    if (lds > 64 * 1024)
-        if (int rc = lipvq_reserve_lds(reserved[(dbg ? 1 : 0) + (coarse ? 2 : 0)], (const void*)kfn, lds, "screen")) return rc;
-    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(SCREEN_WAVES * 64), lds, st, z, prep, cb, idx, zq,
-                       (unsigned long long*)usage, amb_list, amb_count, dbg, N, K, D, gamma);
-    return check_launch("screen");
+static int launch_screen(const float* z, const unsigned char* prep, const float* cb, const LqOut& out, const LqWorkspace& ws,
+                         float* dbg, int K, float gamma, hipStream_t st) {
+    const unsigned blocks = (unsigned)((ws.N + SCREEN_WAVES * 32 - 1) / (SCREEN_WAVES * 32));
+    auto go = [&](auto kfn, LqLdsReserve& reserved, size_t lds, const char* what) {
+        if (lds > 64 * 1024)
+            if (int rc = lipvq_reserve_lds(reserved, (const void*)kfn, lds, what)) return rc;
+        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(SCREEN_WAVES * 64), lds, st, z, prep, cb, out.idx, out.zq,
+                           (unsigned long long*)out.usage, ws.row_list(), ws.live(), dbg, ws.N, K, ws.D, gamma);
+        return check_launch(what);
+    };
+    if constexpr (S > LQ_SCREEN_NARROW_MAX_S) {
+        // (the debug hook's negative gamma asks for the one-product chain, which these widths do not have)
+        if (gamma < 0.0f) return fail(LIPVQ_EUNSUPPORTED, "screen_debug: D=%d has no one-product screen", ws.D);
+        static LqLdsReserve reserved[2];
+        return go(dbg ? screen_wide_kernel<S, true> : screen_wide_kernel<S, false>, reserved[dbg ? 1 : 0], wide_lds_bytes<S>(), "screen_wide");
+    } else {
+        using SC = StandaloneScreen<S>;
+        size_t lds = lq_ring_bytes<S, SC::TC, SC::NB>();
+        if (lds < (size_t)SCREEN_WAVES * LQ_DECIDE_BYTES) lds = (size_t)SCREEN_WAVES * LQ_DECIDE_BYTES;      // per-wave transpose slices reuse the stages
+        // the debug hook takes the arithmetic from the sign of its gamma (negative: the one-product chain, bound factor |gamma|)
+        const bool coarse = dbg ? (gamma < 0.0f) : (lq_screen_coarse(S, K) != 0);
+        if (gamma < 0.0f) gamma = -gamma;
+        auto kfn = dbg ? (coarse ? screen_kernel<S, true, true> : screen_kernel<S, true, false>)
+                       : (coarse ? screen_kernel<S, false, true> : screen_kernel<S, false, false>);
+        static LqLdsReserve reserved[4];            // per instantiation and kernel flavour: per-device, thread-safe (lipvq_common.h)
+        return go(kfn, reserved[(dbg ? 1 : 0) + (coarse ? 2 : 0)], lds, "screen");
+    }
 }
 
-template <int S>
-static int launch_screen_wide(const float* z, const unsigned char* prep, const float* cb, int64_t* idx, float* zq,
-                              int64_t* usage, int* amb_list, int* amb_count, float* dbg, int64_t N, int K, int D,
-                              float gamma, hipStream_t st) {
-    // (the debug hook's negative gamma asks for the one-product chain, which these widths do not have)
-    if (gamma < 0.0f) return fail(LIPVQ_EUNSUPPORTED, "screen_debug: D=%d has no one-product screen", D);
-    const size_t lds = wide_lds_bytes<S>();
-    const int64_t rows_per_block = SCREEN_WAVES * 32;
-    unsigned blocks = (unsigned)((N + rows_per_block - 1) / rows_per_block);
-    auto kfn = dbg ? screen_wide_kernel<S, true> : screen_wide_kernel<S, false>;
-    static LqLdsReserve reserved[2];
-    if (lds > 64 * 1024)
-        if (int rc = lipvq_reserve_lds(reserved[dbg ? 1 : 0], (const void*)kfn, lds, "screen_wide")) return rc;
-    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(SCREEN_WAVES * 64), lds, st, z, prep, cb, idx, zq,
-                       (unsigned long long*)usage, amb_list, amb_count, dbg, N, K, D, gamma);
-    return check_launch("screen_wide");
-}
-
-template <int DCH, int DIST = LIPVQ_DIST_NORM>
-static int launch_rows_t(const float* z, int z_by_slot, const float* cb, int64_t* idx, float* zq, int64_t* usage,
-                         const int* amb_list, const int* amb_count, int64_t N, int K, hipStream_t st) {
-    if (!amb_list && N <= 4096 && K >= 512) {                // every row of a small batch: one row per workgroup
-        hipLaunchKernelGGL((nearest_rows1_kernel<DCH, DIST>), dim3((unsigned)N), dim3(256), 0, st, z, cb, idx, zq,
-                           (unsigned long long*)usage, (int)N, K);
+template <int DCH, int DIST>
+static int launch_rows_t(const float* z, int z_by_slot, const float* cb, const LqOut& out, const LqWorkspace& ws, int K, hipStream_t st) {
+    const int64_t N = ws.N;
+    unsigned long long* usage = (unsigned long long*)out.usage;
+    if (!ws.base && N <= 4096 && K >= 512) {                 // every row of a small batch: one row per workgroup
+        hipLaunchKernelGGL((nearest_rows1_kernel<DCH, DIST>), dim3((unsigned)N), dim3(256), 0, st, z, cb, out.idx, out.zq, usage, (int)N, K);
         return check_launch("nearest_rows1");
     }
     // the count lives on the device: a bounded grid strides over however many rows were listed
     int64_t blocks = (N + 3) / 4;
     if (blocks > 4096) blocks = 4096;
-    // counts on the device (lipvq_screen.h, workspace header): the screening launch PUBLISHED the number of listed rows before it
-    // ended (lq_ws_publish); the list kernel appends what it leaves to the slot-2 list behind the header's slot-2 counter
-    const int* listed = amb_list ? lq_ws_listed(amb_count) : nullptr;
-    if (amb_list) {
-        // rows with short candidate lists (95 % and more of the listed rows): one wave per row, eight candidates at a time;
-        // what it leaves (lane masks, no list) goes through slot2 to the scanning kernel
-        int* slot2_list = const_cast<int*>(amb_list) + lq_slot2_offset_ints(N);
-        int* slot2_count = const_cast<int*>(amb_count) + LQ_WS_SLOT2;       // zeroed by the screening launch's first workgroup
+    if (ws.base) {
+        // counts on the device (LqWorkspace): the screening launch PUBLISHED the number of listed rows before it ended (lq_ws_publish);
+        // the list kernel appends what it leaves to the slot-2 list behind the slot-2 counter (zeroed by the screening launch's first
+        // workgroup).  Rows with short candidate lists (95 % and more of the listed rows): one wave per row, eight candidates at a
+        // time; what it leaves (lane masks, no list) goes through slot2 to the scanning kernel
         int64_t lb = (N + 3) / 4;
         if (lb > 2048) lb = 2048;
         const int all_here = K <= LQ_LISTS_ALL_K ? 1 : 0;
-        hipLaunchKernelGGL((nearest_lists_kernel<DCH, DIST>), dim3((unsigned)lb), dim3(256), 0, st, z, cb, idx, zq,
-                           (unsigned long long*)usage, amb_list, listed, K, z_by_slot, amb_list + 2 * lq_list_ints(N),
-                           lq_cand_cap(N), slot2_list, slot2_count, all_here);
+        hipLaunchKernelGGL((nearest_lists_kernel<DCH, DIST>), dim3((unsigned)lb), dim3(256), 0, st, z, cb, out.idx, out.zq, usage,
+                           ws.row_list(), ws.listed(), K, z_by_slot, ws.short_lists(), ws.short_cap(), ws.slot2_list(), ws.slot2_count(),
+                           all_here);
         if (int rc = check_launch("nearest_lists")) return rc;
         if (all_here) return LIPVQ_OK;                                       // nothing was left to the scanning kernel
-        hipLaunchKernelGGL((nearest_rows_kernel<DCH, DIST>), dim3((unsigned)blocks), dim3(256), 0, st, z, cb, idx, zq,
-                           (unsigned long long*)usage, amb_list, slot2_count, K, z_by_slot, 0, amb_list + lq_list_ints(N),
-                           amb_list + 2 * lq_list_ints(N), lq_cand_cap(N), slot2_list);
+        hipLaunchKernelGGL((nearest_rows_kernel<DCH, DIST>), dim3((unsigned)blocks), dim3(256), 0, st, z, cb, out.idx, out.zq, usage,
+                           ws.row_list(), ws.slot2_count(), K, z_by_slot, 0, ws.best_list(), ws.short_lists(), ws.short_cap(),
+                           ws.slot2_list());
         return check_launch("nearest_rows");
     }
-    hipLaunchKernelGGL((nearest_rows_kernel<DCH, DIST>), dim3((unsigned)blocks), dim3(256), 0, st, z, cb, idx, zq,
-                       (unsigned long long*)usage, nullptr, nullptr, K, z_by_slot, (int)N, nullptr, nullptr, (size_t)0, nullptr);
+    hipLaunchKernelGGL((nearest_rows_kernel<DCH, DIST>), dim3((unsigned)blocks), dim3(256), 0, st, z, cb, out.idx, out.zq, usage, nullptr,
+                       nullptr, K, z_by_slot, (int)N, nullptr, nullptr, (size_t)0, nullptr);
     return check_launch("nearest_rows");
 }
 
 template <int DIST>
-static int launch_rows_any(const float* z, int z_by_slot, const float* cb, int64_t* idx, float* zq, int64_t* usage,
-                           const int* amb_list, const int* amb_count, int64_t N, int K, int D, hipStream_t st) {
+static int launch_rows_any(const float* z, int z_by_slot, const float* cb, const LqOut& out, const LqWorkspace& ws, int K, hipStream_t st) {
+    const int D = ws.D;
     if (D <= 0) return fail(LIPVQ_EINVAL, "nearest_rows: D=%d", D);
-    int64_t blocks = (N + 3) / 4;
+    int64_t blocks = (ws.N + 3) / 4;
     if (blocks > 4096) blocks = 4096;
     auto kfn = D == 256 ? nearest_rows_any_kernel<DIST, 256> : D == 384 ? nearest_rows_any_kernel<DIST, 384>
              : D == 512 ? nearest_rows_any_kernel<DIST, 512> : nearest_rows_any_kernel<DIST, 0>;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), 0, st, z, cb, idx, zq,
-                       (unsigned long long*)usage, amb_list, amb_list ? lq_ws_listed(amb_count) : nullptr, K, D, z_by_slot,
-                       amb_list ? 0 : (int)N, amb_list ? amb_list + 2 * lq_list_ints(N) : nullptr,
-                       amb_list ? lq_cand_cap(N) : (size_t)0);
+    const bool lists = ws.base != nullptr;
+    hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), 0, st, z, cb, out.idx, out.zq, (unsigned long long*)out.usage,
+                       lists ? ws.row_list() : nullptr, lists ? ws.listed() : nullptr, K, D, z_by_slot, lists ? 0 : (int)ws.N,
+                       lists ? ws.short_lists() : nullptr, lists ? ws.short_cap() : (size_t)0);
     return check_launch("nearest_rows_any");
 }
 
-int lipvq_launch_rows(const float* z, int z_by_slot, const float* cb, int64_t* idx, float* zq, int64_t* usage,
-                      const int* amb_list, const int* amb_count, int64_t N, int K, int D, hipStream_t st, int dist) {
-    if (dist == LIPVQ_DIST_SQSUM) {
-        switch (D) {
-            case 32: return launch_rows_t<4, LIPVQ_DIST_SQSUM>(z, z_by_slot, cb, idx, zq, usage, amb_list, amb_count, N, K, st);
-            case 64: return launch_rows_t<8, LIPVQ_DIST_SQSUM>(z, z_by_slot, cb, idx, zq, usage, amb_list, amb_count, N, K, st);
-            case 128: return launch_rows_t<16, LIPVQ_DIST_SQSUM>(z, z_by_slot, cb, idx, zq, usage, amb_list, amb_count, N, K, st);
-            case 208: return launch_rows_t<26, LIPVQ_DIST_SQSUM>(z, z_by_slot, cb, idx, zq, usage, amb_list, amb_count, N, K, st);
-            default: return launch_rows_any<LIPVQ_DIST_SQSUM>(z, z_by_slot, cb, idx, zq, usage, amb_list, amb_count, N, K, D, st);
-        }
-    }
-    switch (D) {
-        case 32: return launch_rows_t<4>(z, z_by_slot, cb, idx, zq, usage, amb_list, amb_count, N, K, st);
-        case 64: return launch_rows_t<8>(z, z_by_slot, cb, idx, zq, usage, amb_list, amb_count, N, K, st);
-        case 128: return launch_rows_t<16>(z, z_by_slot, cb, idx, zq, usage, amb_list, amb_count, N, K, st);
-        case 208: return launch_rows_t<26>(z, z_by_slot, cb, idx, zq, usage, amb_list, amb_count, N, K, st);
-        default: return launch_rows_any<LIPVQ_DIST_NORM>(z, z_by_slot, cb, idx, zq, usage, amb_list, amb_count, N, K, D, st);
-    }
+int lipvq_launch_rows(const float* z, int z_by_slot, const float* cb, const LqOut& out, const LqWorkspace& ws, int K, hipStream_t st,
+                      int dist) {
+    int rc = LIPVQ_OK;
+    lq_dispatch<LIPVQ_DIST_SQSUM, LIPVQ_DIST_NORM>(dist == LIPVQ_DIST_SQSUM ? dist : LIPVQ_DIST_NORM, [&](auto rule) {
+        if (!lq_dispatch<32, 64, 128, 208>(ws.D, [&](auto d) { rc = launch_rows_t<d() / 8, rule()>(z, z_by_slot, cb, out, ws, K, st); }))
+            rc = launch_rows_any<rule()>(z, z_by_slot, cb, out, ws, K, st);
+    });
+    return rc;
 }
 
-static int screened_impl(const float* z, const float* cb, const void* prep, int64_t* idx, float* zq,
-                         int64_t* usage, void* workspace, float* dbg, int64_t N, int K, int D, float gamma,
-                         hipStream_t st, int dist = LIPVQ_DIST_NORM) {
-    int* amb_count = (int*)workspace + LQ_WS_LIVE;          // the header's live counters (lipvq_screen.h); [0] = the reported count
-    int* amb_list = (int*)((unsigned char*)workspace + 64);
-    // (this entry point takes a workspace in any state, hence the fill; the fused launches keep theirs clean: lq_ws_finish)
-    hipError_t e = hipMemsetAsync(workspace, 0, 64, st);
+static int screened_impl(const float* z, const float* cb, const void* prep, const LqOut& out, void* workspace, float* dbg, int64_t N,
+                         int K, int D, float gamma, hipStream_t st, int dist = LIPVQ_DIST_NORM) {
+    const LqWorkspace ws{(unsigned char*)workspace, N, D};
+    // (this entry point takes a workspace in any state, hence the fill; the fused launches keep theirs clean: lq_ws_publish)
+    hipError_t e = hipMemsetAsync(ws.header(), 0, LqWorkspace::kHeaderBytes, st);
     if (e != hipSuccess) return fail(LIPVQ_EHIP, "nearest_screened: %s", hipGetErrorString(e));
-    const unsigned char* p = (const unsigned char*)prep;
-    int rc;
-    switch (lq_screen_S(D)) {                   // widths between the instances run the next larger one on zero-padded columns
-        case 2: rc = launch_screen<2>(z, p, cb, idx, zq, usage, amb_list, amb_count, dbg, N, K, D, gamma, st); break;
-        case 4: rc = launch_screen<4>(z, p, cb, idx, zq, usage, amb_list, amb_count, dbg, N, K, D, gamma, st); break;
-        case 8: rc = launch_screen<8>(z, p, cb, idx, zq, usage, amb_list, amb_count, dbg, N, K, D, gamma, st); break;
-        case 13: rc = launch_screen<13>(z, p, cb, idx, zq, usage, amb_list, amb_count, dbg, N, K, D, gamma, st); break;
-        case 16: rc = launch_screen_wide<16>(z, p, cb, idx, zq, usage, amb_list, amb_count, dbg, N, K, D, gamma, st); break;
-        case 24: rc = launch_screen_wide<24>(z, p, cb, idx, zq, usage, amb_list, amb_count, dbg, N, K, D, gamma, st); break;
-        case 32: rc = launch_screen_wide<32>(z, p, cb, idx, zq, usage, amb_list, amb_count, dbg, N, K, D, gamma, st); break;
-        default: return fail(LIPVQ_EUNSUPPORTED, "nearest_screened: D=%d has no screening instance (1 ... 512)", D);
-    }
+    int rc = LIPVQ_OK;
+    // widths between the instances run the next larger one on zero-padded columns
+    if (!lq_dispatch<2, 4, 8, 13, 16, 24, 32>(lq_screen_S(D), [&](auto s) {
+            rc = launch_screen<s()>(z, (const unsigned char*)prep, cb, out, ws, dbg, K, gamma, st);
+        }))
+        return fail(LIPVQ_EUNSUPPORTED, "nearest_screened: D=%d has no screening instance (1 ... 512)", D);
     if (rc) return rc;
-    return lipvq_launch_rows(z, 0, cb, idx, zq, usage, amb_list, amb_count, N, K, D, st, dist);
+    return lipvq_launch_rows(z, 0, cb, out, ws, K, st, dist);
 }
 
 extern "C" int lipvq_nearest_screened_supported(int K, int D) {
     return (K > 0 && lq_screen_S(D) != 0) ? 1 : 0;            // any width 1 ... 512
+}
+
+// The argument checks of the four entry points below (screened: the ones that take a prepared codebook and a workspace).
+// LIPVQ_OK with *go = false: nothing to do.
+static int nearest_check(const char* who, bool screened, const float* z, const float* cb, const void* prep, const int64_t* idx,
+                         const float* zq, const void* workspace, int64_t N, int K, int D, bool* go) {
+    *go = false;
+    if (N < 0 || K <= 0 || (screened && D <= 0)) return fail(LIPVQ_EINVAL, "%s: bad sizes", who);
+    if (N == 0) return LIPVQ_OK;
+    if (!z || !cb || !idx || (screened && (!prep || !workspace))) return fail(LIPVQ_EINVAL, "%s: null pointer", who);
+    if (N > 2147483647LL) return fail(LIPVQ_EUNSUPPORTED, "%s: N too large", who);
+    if (screened && !(D & 3) && (((uintptr_t)z | (uintptr_t)cb | (uintptr_t)zq) & 15) != 0)   // (the kernels take float4 paths iff D % 4 == 0)
+        return fail(LIPVQ_EINVAL, "%s: z, codebook and zq must be 16-byte aligned", who);
+    *go = true;
+    return LIPVQ_OK;
+}
+static int nearest_rows_entry(const char* who, int dist, const float* z, const float* cb, int64_t* idx, float* zq, int64_t* usage,
+                              int64_t N, int K, int D, void* stream) {
+    bool go;
+    const int rc = nearest_check(who, false, z, cb, nullptr, idx, zq, nullptr, N, K, D, &go);
+    return go ? lipvq_launch_rows(z, 0, cb, LqOut{idx, zq, usage}, LqWorkspace{nullptr, N, D}, K, (hipStream_t)stream, dist) : rc;
+}
+static int nearest_screened_entry(const char* who, int dist, const float* z, const float* cb, const void* prep, int64_t* idx, float* zq,
+                                  int64_t* usage, void* workspace, int64_t N, int K, int D, void* stream) {
+    bool go;
+    const int rc = nearest_check(who, true, z, cb, prep, idx, zq, workspace, N, K, D, &go);
+    return go ? screened_impl(z, cb, prep, LqOut{idx, zq, usage}, workspace, nullptr, N, K, D, lq_screen_gamma(D), (hipStream_t)stream, dist) : rc;
 }
 
 // Exact decision of EVERY row by the re-scoring kernel (4 rows x 64 code slices per workgroup): no codebook
@@ -1414,11 +1391,7 @@ extern "C" int lipvq_nearest_screened_supported(int K, int D) {
 // (the preparation alone costs ~110 us) and a screen launch has a ~75 us floor: 13 us at N = 80, D = 208, K = 1024.
 extern "C" int lipvq_nearest_rows_f32(const float* z, const float* codebook, int64_t* idx, float* zq, int64_t* usage,
                                       int64_t N, int K, int D, void* stream) {
-    if (N < 0 || K <= 0) return fail(LIPVQ_EINVAL, "nearest_rows: bad sizes");
-    if (N == 0) return LIPVQ_OK;
-    if (!z || !codebook || !idx) return fail(LIPVQ_EINVAL, "nearest_rows: null pointer");
-    if (N > 0x7fffffffLL) return fail(LIPVQ_EUNSUPPORTED, "nearest_rows: N too large");
-    return lipvq_launch_rows(z, 0, codebook, idx, zq, usage, nullptr, nullptr, N, K, D, (hipStream_t)stream);
+    return nearest_rows_entry("nearest_rows", LIPVQ_DIST_NORM, z, codebook, idx, zq, usage, N, K, D, stream);
 }
 
 // Same contract as lipvq_nearest_f32(.., LIPVQ_DIST_NORM) -- identical idx / zq / usage -- through the
@@ -1428,37 +1401,19 @@ extern "C" int lipvq_nearest_rows_f32(const float* z, const float* codebook, int
 extern "C" int lipvq_nearest_screened_f32(const float* z, const float* codebook, const void* prep, int64_t* idx,
                                           float* zq, int64_t* usage, void* workspace, int64_t N, int K, int D,
                                           void* stream) {
-    if (N < 0 || K <= 0 || D <= 0) return fail(LIPVQ_EINVAL, "nearest_screened: bad sizes");
-    if (N == 0) return LIPVQ_OK;
-    if (!z || !codebook || !prep || !idx || !workspace) return fail(LIPVQ_EINVAL, "nearest_screened: null pointer");
-    if (N > 2147483647LL) return fail(LIPVQ_EUNSUPPORTED, "nearest_screened: N too large");
-    if (!(D & 3) && (((uintptr_t)z | (uintptr_t)codebook | (uintptr_t)zq) & 15) != 0)       // (the kernels take float4 paths iff D % 4 == 0)
-        return fail(LIPVQ_EINVAL, "nearest_screened: z, codebook and zq must be 16-byte aligned");
-    return screened_impl(z, codebook, prep, idx, zq, usage, workspace, nullptr, N, K, D, lq_screen_gamma(D),
-                         (hipStream_t)stream);
+    return nearest_screened_entry("nearest_screened", LIPVQ_DIST_NORM, z, codebook, prep, idx, zq, usage, workspace, N, K, D, stream);
 }
 
 // The plain VQVAE's rule (vq:57-63) through the same two routes (include/lipvq.h).
 extern "C" int lipvq_vq_nearest_screened_f32(const float* z, const float* codebook, const void* prep, int64_t* idx,
                                              float* zq, int64_t* usage, void* workspace, int64_t N, int K, int D,
                                              void* stream) {
-    if (N < 0 || K <= 0 || D <= 0) return fail(LIPVQ_EINVAL, "vq_nearest_screened: bad sizes");
-    if (N == 0) return LIPVQ_OK;
-    if (!z || !codebook || !prep || !idx || !workspace) return fail(LIPVQ_EINVAL, "vq_nearest_screened: null pointer");
-    if (N > 2147483647LL) return fail(LIPVQ_EUNSUPPORTED, "vq_nearest_screened: N too large");
-    if (!(D & 3) && (((uintptr_t)z | (uintptr_t)codebook | (uintptr_t)zq) & 15) != 0)
-        return fail(LIPVQ_EINVAL, "vq_nearest_screened: z, codebook and zq must be 16-byte aligned");
-    return screened_impl(z, codebook, prep, idx, zq, usage, workspace, nullptr, N, K, D, lq_screen_gamma(D),
-                         (hipStream_t)stream, LIPVQ_DIST_SQSUM);
+    return nearest_screened_entry("vq_nearest_screened", LIPVQ_DIST_SQSUM, z, codebook, prep, idx, zq, usage, workspace, N, K, D, stream);
 }
 
 extern "C" int lipvq_vq_nearest_rows_f32(const float* z, const float* codebook, int64_t* idx, float* zq, int64_t* usage,
                                          int64_t N, int K, int D, void* stream) {
-    if (N < 0 || K <= 0) return fail(LIPVQ_EINVAL, "vq_nearest_rows: bad sizes");
-    if (N == 0) return LIPVQ_OK;
-    if (!z || !codebook || !idx) return fail(LIPVQ_EINVAL, "vq_nearest_rows: null pointer");
-    if (N > 0x7fffffffLL) return fail(LIPVQ_EUNSUPPORTED, "vq_nearest_rows: N too large");
-    return lipvq_launch_rows(z, 0, codebook, idx, zq, usage, nullptr, nullptr, N, K, D, (hipStream_t)stream, LIPVQ_DIST_SQSUM);
+    return nearest_rows_entry("vq_nearest_rows", LIPVQ_DIST_SQSUM, z, codebook, idx, zq, usage, N, K, D, stream);
 }
 
 // Test hook: also writes the approximate distances d~ [N][Kpad] and uses the caller's gamma
@@ -1468,5 +1423,5 @@ extern "C" int lipvq_screen_debug_f32(const float* z, const float* codebook, con
                                       int64_t N, int K, int D, void* stream) {
     if (!z || !codebook || !prep || !idx || !workspace || N <= 0) return fail(LIPVQ_EINVAL, "screen_debug: bad argument");
     if (!lipvq_nearest_screened_supported(K, D)) return fail(LIPVQ_EUNSUPPORTED, "screen_debug: unsupported D");
-    return screened_impl(z, codebook, prep, idx, zq, usage, workspace, dtilde, N, K, D, gamma, (hipStream_t)stream);
+    return screened_impl(z, codebook, prep, LqOut{idx, zq, usage}, workspace, dtilde, N, K, D, gamma, (hipStream_t)stream);
 }

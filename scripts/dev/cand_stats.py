@@ -6,6 +6,7 @@ import numpy as np, torch
 import lipvq_vae_amd
 from lipvq_vae_amd.tokenizer import LLFQVAE_V4
 from bench import WORKLOADS, trained_like_
+from scripts import ws_layout
 wl = sys.argv[1] if len(sys.argv) > 1 else "cfg2"
 B, T, A, D, K = WORKLOADS[wl]
 N = B * T
@@ -15,8 +16,8 @@ trained_like_(model, A)
 x = torch.randn(N, A, device="cuda")
 model.tokenize(x); torch.cuda.synchronize()
 ws = model._tok_ws.cpu().numpy()
-cnt = int(ws[0]); L = (N + 15) & ~15; cap = N + 64      # lq_cand_cap (round 3: every row can have a list)
-cl = ws[16 + 2 * L: 16 + 2 * L + 16 * cap].reshape(cap, 16)[:min(cnt, cap)]
+cnt = int(ws[0]); cap = ws_layout.short_cap(N)                    # (round 3: every row can have a list)
+cl = ws[ws_layout.short_lists(N):ws_layout.slot2_list(N)].reshape(cap, 16)[:min(cnt, cap)]
 n0, n1 = cl[:, 0], cl[:, 8]
 full = (n0 == -1) | (n1 == -1)
 lanes = ~full & ((n0 == -2) | (n1 == -2))

@@ -10,6 +10,7 @@ import torch
 import lipvq_vae_amd  # noqa: F401
 from lipvq_vae_amd.tokenizer import LLFQVAE_V4
 from bench import WORKLOADS, trained_like_
+from scripts import ws_layout
 wl = sys.argv[1] if len(sys.argv) > 1 else "cfg2"
 B, T, A, D, K = WORKLOADS[wl]
 N = int(sys.argv[2]) if len(sys.argv) > 2 else B * T
@@ -22,7 +23,7 @@ for _ in range(300):
 torch.cuda.synchronize()
 NW = 4 if N <= 32768 else 8
 NWG = min(256, -(-N // (NW * 32)))
-off = 16 + ((N // 2) & ~1)
+off = ws_layout.stamps(N)
 ends = []
 for rep in range(4):
     for _ in range(20):

@@ -8,6 +8,7 @@ import torch
 import lipvq_vae_amd
 from lipvq_vae_amd.tokenizer import LLFQVAE_V4
 from bench import WORKLOADS, trained_like_
+from scripts import ws_layout
 wl = sys.argv[1] if len(sys.argv) > 1 else "cfg2"
 B, T, A, D, K = WORKLOADS[wl]
 N = int(sys.argv[2]) if len(sys.argv) > 2 else B * T           # optional: a shard of that many rows
@@ -21,9 +22,9 @@ torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record(); model.tokenize(x); e1.record(); torch.cuda.synchronize()
 ws = model._tok_ws.cpu().numpy()
-off = 16 + ((N // 2) & ~1)
+off = ws_layout.stamps(N)
 import os
-_shape = lipvq_vae_amd._capi.get_option("tok_shape") or ("w4rg1" if N <= 32768 else "w8rg1")   # (the library's size rule, lipvq_fused.hip::tok_shape)
+_shape = lipvq_vae_amd._capi.get_option("tok_shape") or ("w4rg1" if N <= 32768 else "w8rg1")   # (the library's size rule, lipvq_fused.hip::tok_waves)
 NW = 4 if _shape.startswith("w4") else 8      # waves per workgroup of the instance that ran
 # (options come from the environment only with LIPVQ_DEV_KNOBS=1: lipvq-vae_amd/_capi.py)
 NWG = min(256, -(-N // (NW * 32)))                              # workgroups of the launch

@@ -45,6 +45,33 @@ def test_ctypes_table_matches_header():
     assert _capi.lib.lipvq_wgrad_workspace_bytes(300000, 128, 64) == 293 * (128 * 64 + 128) * 4
 
 
+# lipvq_nearest_workspace_bytes(N) / lipvq_tokenize_workspace_bytes(N, D) as the library answered before the workspace layout
+# moved into one struct (LqWorkspace, lipvq_screen.h): recorded from that build, not computed here from the same formula
+_NEAREST_WS_BYTES = {1: 4416, 15: 5312, 16: 5376, 17: 5632, 80: 10240, 4096: 315456, 32768: 2494528, 524288: 39850048}
+_TOKENIZE_WS_BYTES = {      # N: bytes at D = 7, 32, 64, 128, 208, 512
+    1: (4700, 4800, 4928, 5184, 120192, 268864),
+    15: (5988, 7488, 9408, 13248, 132736, 298432),
+    16: (6080, 7680, 9728, 13824, 133632, 300544),
+    17: (6364, 8064, 10240, 14592, 134720, 302848),
+    80: (12736, 20736, 30976, 51456, 191744, 436480),
+    4096: (430400, 840000, 1364288, 2412864, 3838272, 8966464),
+    32768: (3412288, 6689088, 10883392, 19272000, 29872448, 69865792),
+    524288: (54530368, 106959168, 174068032, 308285760, 476172608, 1113854272),
+}
+
+
+def test_workspace_sizes_are_the_recorded_ones():
+    import lipvq_vae_amd
+    from lipvq_vae_amd import _capi
+    for N, want in _NEAREST_WS_BYTES.items():
+        assert _capi.lib.lipvq_nearest_workspace_bytes(N) == want, N
+    for N, row in _TOKENIZE_WS_BYTES.items():
+        for D, want in zip((7, 32, 64, 128, 208, 512), row):
+            assert _capi.lib.lipvq_tokenize_workspace_bytes(N, D) == want, (N, D)
+    assert _capi.lib.lipvq_nearest_workspace_bytes(0) == 0 and _capi.lib.lipvq_tokenize_workspace_bytes(0, 64) == 0
+    assert _capi.lib.lipvq_tokenize_workspace_bytes(16, 0) == 0
+
+
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
     """The product must not fall back to anything when the extension is absent."""
     import importlib.util
