@@ -1,10 +1,16 @@
 """GPU: the fused encode+quantize launch (lipvq_tokenize_f32) equals the oracle bit for bit and equals the
 unfused path (lipvq_mlp3_f32 + lipvq_nearest_f32), including z_e when requested."""
+import sys
+from pathlib import Path
+
 import numpy as np
 import pytest
 import torch
 
 from oracle import lipvq_oracle as O
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+from backward_ref import oracle_grads_cpu  # noqa: E402  (float64 autograd on the CPU, code indices from the launch)
 
 pytestmark = pytest.mark.gpu
 
@@ -315,37 +321,6 @@ def test_vq_decoder_launch_with_straight_through_and_loss_equals_separate_launch
     with torch.no_grad():
         z_m, loss_m = model(xt)
     assert torch.equal(z_m, z_st) and loss_m.item() == l3[2].item()
-
-
-def oracle_grads_cpu(model, xt, kind, gscale):
-    """Parameter gradients of gscale * loss by torch autograd on the CPU in float64 (stock ops, the reference's forward as
-    oracle/lipvq_oracle.py restates it; float64 so that the comparison sees the launches' rounding only -- a sequential fp32
-    index_add_ over the thousands of rows of one code is itself 1e-5 off), with the code indices taken from the launch (the [N, K, D] distance tensor of the
-    reference's argmin is 17 GB at these batches; index parity is what the other tests are for)."""
-    import torch.nn.functional as F
-    p = {k: v.detach().cpu().double().requires_grad_(True) for k, v in model.named_parameters()}
-    x = xt.cpu().double()
-    idx = model.last_indices.cpu()
-    if kind == "llfq":
-        z_e = O.torch_llfq_encode(p, x)
-        z_q = p["quantizer.codebook"][idx]
-        h = F.gelu(F.linear(z_q, p["decoder.0.weight"], p["decoder.0.bias"]))
-        h = F.gelu(F.linear(h, p["decoder.2.weight"], p["decoder.2.bias"]))
-        x_rec = F.linear(h, p["to_output.weight"], p["to_output.bias"])
-        loss = F.mse_loss(x_rec, x) + 0.25 * F.mse_loss(z_q.detach(), z_e) + 0.25 * F.mse_loss(z_q, z_e.detach())
-    else:
-        h = x
-        for i in (0, 2, 4):
-            h = F.relu(F.linear(h, p[f"encoder.{i}.weight"], p[f"encoder.{i}.bias"]))
-        z_e = h
-        z_q = F.embedding(idx, p["embedding.weight"])
-        q_loss = F.mse_loss(z_q, z_e.detach()) + float(model.commitment_cost) * F.mse_loss(z_q.detach(), z_e)
-        h = z_e + (z_q - z_e).detach()
-        for i in (0, 2, 4):
-            h = F.relu(F.linear(h, p[f"decoder.{i}.weight"], p[f"decoder.{i}.bias"]))
-        loss = F.mse_loss(h, x) + q_loss
-    (loss * gscale).backward()
-    return {k: (v.grad if v.grad is not None else torch.zeros_like(v)).float() for k, v in p.items()}
 
 
 @pytest.mark.parametrize("kind,N,A,D,K", [("llfq", 66000, 7, 64, 1024), ("llfq", 65537, 12, 128, 1000), ("llfq", 65600, 12, 208, 1024),
