@@ -446,6 +446,38 @@ int lipvq_add_layernorm_f32(const float* a, const float* b, const float* w, cons
 int lipvq_layernorm_bwd_f32(const float* gy, const float* xhat, const float* rstd, const float* w, float* gx, float* gw,
                             float* gb, int64_t N, int E, void* stream);
 
+/* ---- the transformer backbone (tf = robomimic/models/transformers.py; tf:321-440 GPT_Backbone, built at obs_nets.py:2453-2463
+ *      with embed_dim 512, 8 heads, 6 layers, context 3 T = 30): pre-norm blocks x + attn(ln1(x)), x + mlp(ln2(x)), then output_ln.
+ *      Linears: lipvq_linear_act_f32 / lipvq_wgrad_f32 above.  lipvq-vae_amd/csrc/lipvq_gpt.hip, lipvq-vae_amd/gpt.py ---- */
+
+/* tf:173-201 SelfAttention.forward between the qkv Linear and the output Linear, for all B sequences and H heads in ONE launch:
+ * qkv [B][L][3E] = q | k | v column blocks (tf:174 chunk), head h owns columns [h E/H, (h+1) E/H) of each (tf:175-177);
+ * att = (q k^T) / sqrt(E/H) (tf:184); with causal != 0 key j is open to query i only for j <= i (tf:146-151, :189 masked_fill),
+ * otherwise every key; softmax over keys (tf:190); out [B][L][E] = att v already in the layout of tf:201 (heads concatenated);
+ * lse [B][H][L] = log-sum-exp of the masked scaled scores (for the backward).  keep [B][H][L][L] bytes (may be NULL): the
+ * attn_dropout mask of training mode (tf:195), kept probabilities scaled by 1 / keep_prob, as in lipvq_attention_f32.
+ * E/H is 16, 32 or 64; L <= 128 (longer: LIPVQ_EUNSUPPORTED); B == 0 or L == 0 is a no-op.  qkv and out 16-byte aligned. */
+int lipvq_gpt_attention_f32(const float* qkv, float* out, float* lse, const unsigned char* keep, float keep_prob, int64_t B,
+                            int L, int E, int H, int causal, void* stream);
+/* Its backward: gqkv [B][L][3E] from gout [B][L][E] and the forward's out, lse; delta [B][H][L] is scratch.  Two launches, no
+ * atomics: the same bits on every run. */
+int lipvq_gpt_attention_bwd_f32(const float* qkv, const float* out, const float* gout, const float* lse, float* gqkv,
+                                float* delta, const unsigned char* keep, float keep_prob, int64_t B, int L, int E, int H,
+                                int causal, void* stream);
+
+/* tf:300-301, :439 the residual add and the LayerNorm that follows it, in one pass over rows of E floats (E % 4 == 0, E <= 1024):
+ * s = a + b (the `x + ...` of tf:300-301; b may be NULL: s = a), y = LayerNorm(s) * w + bias (the next ln1 / ln2 / output_ln).
+ * s [N][E] may be NULL (not stored); xhat [N][E] and rstd [N] (either may be NULL) are saved for the backward.  N == 0: no-op. */
+int lipvq_gpt_layernorm_f32(const float* a, const float* b, const float* w, const float* bias, float eps, float* s, float* y,
+                            float* xhat, float* rstd, int64_t N, int E, void* stream);
+/* Its backward: gs [N][E] = the LayerNorm's gradient with respect to s PLUS gres [N][E] (the residual stream's own incoming
+ * gradient, may be NULL) -- the gradient of both a and b; gw [E], gb [E] are WRITTEN (not accumulated, unlike
+ * lipvq_layernorm_bwd_f32: per-workgroup partial sums added in a fixed order, so the bits repeat from run to run).
+ * workspace: lipvq_gpt_layernorm_bwd_workspace_bytes(N, E) bytes, any contents. */
+size_t lipvq_gpt_layernorm_bwd_workspace_bytes(int64_t N, int E);
+int lipvq_gpt_layernorm_bwd_f32(const float* gy, const float* xhat, const float* rstd, const float* w, const float* gres,
+                                float* gs, float* gw, float* gb, void* workspace, int64_t N, int E, void* stream);
+
 /* icl.py:885-889, :970  optim.AdamW(vq_vae_model.parameters(), lr=1e-3, weight_decay=1e-4).step() for a LIST of tensors in
  * two launches (torch's foreach form is 8-10): params / grads / exp_avg / exp_avg_sq / steps are HOST arrays of `count`
  * DEVICE pointers (count <= 32), numels their element counts; steps[i] is a float32 device scalar (torch's capturable layout),

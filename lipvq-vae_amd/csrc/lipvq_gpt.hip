@@ -1,0 +1,516 @@
+// lipvq_gpt.hip -- what the ICRT transformer backbone (reference robomimic/models/transformers.py:80-439, GPT_Backbone: pre-norm
+// blocks of causal multi-head self-attention and a GELU MLP over the [B][3T][E] tensor of ICLInputEmbedding) needs beyond the
+// Linears of lipvq_linear_act_f32 / lipvq_wgrad_f32:
+//   gpt_attention_kernel        softmax(mask(Q K^T / sqrt(dh))) V for every (batch, head) in one launch, head width 16 / 32 / 64,
+//                               sequence 1..128, fp32 MFMA (v_mfma_f32_32x32x2_f32) for both products, exact two-pass softmax
+//   gpt_attention_bwd_q/kv      its backward in two passes (probabilities recomputed from the saved log-sum-exp), no atomics
+//   gpt_layernorm_kernel        s = a + b, y = LayerNorm(s) w + bias in one pass (pre-norm: the residual stream AND the next
+//                               sub-layer's input), rows of E <= 1024 floats
+//   gpt_layernorm_bwd_kernel    gradient of s with the stream's own incoming gradient folded in; gw / gb through per-workgroup
+//                               partial sums and a fixed-order second pass (bit-reproducible)
+// ABI: include/lipvq.h ("the transformer backbone").  Tolerances: tests/test_gpu_gpt.py.
+//
+// Attention layout.  One WAVE owns one (batch, head, 32-query tile); workgroups are single waves and use no LDS, so a step of
+// B = 8 sequences spreads its 64 (b, h) pairs over 64 compute units and a large batch fills the chip with independent waves.
+// Scores are evaluated TRANSPOSED, S^T = K Q^T: keys are the MFMA A operand (32 keys x 2 d), queries the B operand (2 d x 32
+// queries), so the 32x32 result has the QUERY on the lane (col = lane & 31) and 16 keys in the lane's registers: the softmax
+// over keys is a loop over registers plus one exchange with lane ^ 32.  The keys are handed to the MFMA in the row order
+// gpt_perm, chosen so that register g of lane half hf holds key 2 g + hf of the tile -- exactly the B-operand layout of the
+// second product O^T = V^T P^T (k-step g takes keys 2 g and 2 g + 1), which therefore reads the probabilities straight from the
+// accumulator registers.  Both products are fmaf chains in ascending k (d for the scores, key for the values).
+#include "lipvq_common.h"
+
+#define GPT_MAXL 128
+#define GPT_MAXE 1024
+
+// row r of a 32x32x2 MFMA result sits in register (r & 3) + 4 (r >> 3) of lane half (r >> 2) & 1; the A operand's row r is
+// loaded from tile element gpt_perm(r) = 2 register + half, so that (register g, half hf) carries element 2 g + hf
+__device__ __forceinline__ int gpt_perm(int r) { return 2 * ((r & 3) + 4 * (r >> 3)) + ((r >> 2) & 1); }
+
+// elements 2 s + hf (s = 0 .. DH/2 - 1) of one head row: the lane's share of an A or B operand over the head width
+template <int DH>
+__device__ __forceinline__ void gpt_load_half(const float* __restrict__ row, int hf, float (&r)[DH / 2]) {
+#pragma unroll
+    for (int t = 0; t < DH / 4; ++t) {
+        const float4 v = *reinterpret_cast<const float4*>(row + 4 * t);
+        r[2 * t] = hf ? v.y : v.x;
+        r[2 * t + 1] = hf ? v.w : v.z;
+    }
+}
+
+template <int DH>
+__device__ __forceinline__ f32x16 gpt_dot(const float (&a)[DH / 2], const float (&b)[DH / 2]) {
+    f32x16 acc;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) acc[g] = 0.0f;
+#pragma unroll
+    for (int s = 0; s < DH / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b[s], acc, 0, 0, 0);
+    return acc;
+}
+
+// the transposed [d][row] result tiles of a wave -> rows of DH floats at dst + row stride `ld` (lane = row, 4 consecutive d per store)
+template <int DH, int DT>
+__device__ __forceinline__ void gpt_store_t(float* __restrict__ dst, const f32x16 (&o)[DT], int hf, float mul) {
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+            const int d0 = 32 * dt + 8 * g4 + 4 * hf;
+            if (d0 < DH)
+                *reinterpret_cast<float4*>(dst + d0) =
+                    make_float4(o[dt][4 * g4] * mul, o[dt][4 * g4 + 1] * mul, o[dt][4 * g4 + 2] * mul, o[dt][4 * g4 + 3] * mul);
+        }
+}
+
+template <int DH, int NKT>
+__global__ __launch_bounds__(64) void gpt_attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse,
+                                                           const unsigned char* __restrict__ keep, float inv_keep, int L, int E, int H,
+                                                           int causal) {
+    constexpr int DT = DH > 32 ? DH / 32 : 1;
+    const int lane = threadIdx.x, c = lane & 31, hf = lane >> 5;
+    const int qt = blockIdx.x % NKT;
+    const size_t bh = blockIdx.x / NKT;
+    const int h = (int)(bh % H);
+    const size_t b = bh / H;
+    const float* __restrict__ base = qkv + b * (size_t)L * 3 * E + (size_t)h * DH;
+    const int i = qt * 32 + c, ic = i < L ? i : L - 1;
+    const float scale = 1.0f / lq_sqrt((float)DH);
+    const int kt_end = causal ? qt + 1 : NKT;                       // (wave-uniform)
+    float q[DH / 2];
+    gpt_load_half<DH>(base + (size_t)ic * 3 * E, hf, q);
+    f32x16 s[NKT];
+    float m = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+        if (kt < kt_end) {
+            const int jr = kt * 32 + gpt_perm(c), jrc = jr < L ? jr : L - 1;
+            float k[DH / 2];
+            gpt_load_half<DH>(base + (size_t)jrc * 3 * E + E, hf, k);
+            const f32x16 acc = gpt_dot<DH>(k, q);
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                const int j = kt * 32 + 2 * g + hf;
+                const bool ok = j < L && (!causal || j <= i);
+                const float v = ok ? acc[g] * scale : -INFINITY;
+                s[kt][g] = v;
+                m = fmaxf(m, v);
+            }
+        }
+    }
+    m = fmaxf(m, __shfl_xor(m, 32, 64));                            // (key 0 is open to every query: m is finite)
+    float l = 0.0f;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+        if (kt < kt_end) {
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                const float e = lq_expf(s[kt][g] - m);             // (masked: exp(-inf) = 0)
+                s[kt][g] = e;
+                l += e;
+            }
+        }
+    }
+    l += __shfl_xor(l, 32, 64);
+    const float inv = 1.0f / l;
+    f32x16 o[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) o[dt][g] = 0.0f;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+        if (kt < kt_end) {
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                const int j = kt * 32 + 2 * g + hf, jc = j < L ? j : L - 1;
+                float p = s[kt][g] * inv;
+                if (keep) p = keep[(bh * L + ic) * L + jc] ? p * inv_keep : 0.0f;
+#pragma unroll
+                for (int dt = 0; dt < DT; ++dt) {
+                    const float a = (DH >= 32 || c < DH) ? base[(size_t)jc * 3 * E + 2 * E + 32 * dt + c] : 0.0f;
+                    o[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, p, o[dt], 0, 0, 0);
+                }
+            }
+        }
+    }
+    if (i < L) {
+        gpt_store_t<DH, DT>(out + (b * L + i) * (size_t)E + (size_t)h * DH, o, hf, 1.0f);
+        if (hf == 0) lse[bh * L + i] = m + lq_logf_ge1(l);         // (l >= 1: the row maximum contributes exp(0))
+    }
+}
+
+// Backward.  delta[i] = sum_d dO[i][d] O[i][d];  P_ij = exp(s_ij - lse_i);  dP_ij = (keep_ij / keep_prob) dO_i . V_j;
+// dS_ij = P_ij (dP_ij - delta_i);  dQ_i = scale sum_j dS_ij K_j;  dK_j = scale sum_i dS_ij Q_i;  dV_j = sum_i (keep_ij / keep_prob) P_ij dO_i.
+// gpt_attention_bwd_q: wave = (b, h, 32 queries), loops over key tiles -> dQ, delta.  gpt_attention_bwd_kv: wave = (b, h, 32 keys),
+// loops over query tiles -> dK, dV.  The same transposed-score layout as the forward: the lane owns the row the wave reduces INTO.
+template <int DH>
+__global__ __launch_bounds__(64) void gpt_attention_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
+                                                                 const float* __restrict__ go, const float* __restrict__ lse,
+                                                                 float* __restrict__ gqkv, float* __restrict__ delta,
+                                                                 const unsigned char* __restrict__ keep, float inv_keep, int L, int E, int H,
+                                                                 int causal, int NT) {
+    constexpr int DT = DH > 32 ? DH / 32 : 1;
+    const int lane = threadIdx.x, c = lane & 31, hf = lane >> 5;
+    const int qt = blockIdx.x % NT;
+    const size_t bh = blockIdx.x / NT;
+    const int h = (int)(bh % H);
+    const size_t b = bh / H;
+    const float* __restrict__ base = qkv + b * (size_t)L * 3 * E + (size_t)h * DH;
+    const int i = qt * 32 + c, ic = i < L ? i : L - 1;
+    const float scale = 1.0f / lq_sqrt((float)DH);
+    const int kt_end = causal ? qt + 1 : NT;
+    float q[DH / 2], gor[DH / 2];
+    gpt_load_half<DH>(base + (size_t)ic * 3 * E, hf, q);
+    gpt_load_half<DH>(go + (b * L + ic) * (size_t)E + (size_t)h * DH, hf, gor);
+    float dl = 0.0f;
+    {
+        float orow[DH / 2];
+        gpt_load_half<DH>(o + (b * L + ic) * (size_t)E + (size_t)h * DH, hf, orow);
+#pragma unroll
+        for (int t = 0; t < DH / 2; ++t) dl = lq_fma(gor[t], orow[t], dl);
+    }
+    dl += __shfl_xor(dl, 32, 64);
+    const float ls = lse[bh * L + ic];
+    if (hf == 0 && i < L) delta[bh * L + i] = dl;
+    f32x16 dq[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) dq[dt][g] = 0.0f;
+#pragma unroll 1
+    for (int kt = 0; kt < kt_end; ++kt) {
+        const int jr = kt * 32 + gpt_perm(c), jrc = jr < L ? jr : L - 1;
+        f32x16 sa, pa;
+        {
+            float k[DH / 2];
+            gpt_load_half<DH>(base + (size_t)jrc * 3 * E + E, hf, k);
+            sa = gpt_dot<DH>(k, q);
+        }
+        {
+            float v[DH / 2];
+            gpt_load_half<DH>(base + (size_t)jrc * 3 * E + 2 * E, hf, v);
+            pa = gpt_dot<DH>(v, gor);
+        }
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            const int j = kt * 32 + 2 * g + hf, jc = j < L ? j : L - 1;
+            const bool ok = j < L && (!causal || j <= i);
+            const float p = ok ? lq_expf(sa[g] * scale - ls) : 0.0f;
+            float dp = pa[g];
+            if (keep) dp = keep[(bh * L + ic) * L + jc] ? dp * inv_keep : 0.0f;
+            sa[g] = p * (dp - dl);
+        }
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            const int j = kt * 32 + 2 * g + hf, jc = j < L ? j : L - 1;
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+                const float a = (DH >= 32 || c < DH) ? base[(size_t)jc * 3 * E + E + 32 * dt + c] : 0.0f;
+                dq[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, sa[g], dq[dt], 0, 0, 0);
+            }
+        }
+    }
+    if (i < L) gpt_store_t<DH, DT>(gqkv + (b * L + i) * (size_t)3 * E + (size_t)h * DH, dq, hf, scale);
+}
+
+template <int DH>
+__global__ __launch_bounds__(64) void gpt_attention_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ go,
+                                                                  const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                  float* __restrict__ gqkv, const unsigned char* __restrict__ keep,
+                                                                  float inv_keep, int L, int E, int H, int causal, int NT) {
+    constexpr int DT = DH > 32 ? DH / 32 : 1;
+    const int lane = threadIdx.x, c = lane & 31, hf = lane >> 5;
+    const int kt = blockIdx.x % NT;
+    const size_t bh = blockIdx.x / NT;
+    const int h = (int)(bh % H);
+    const size_t b = bh / H;
+    const float* __restrict__ base = qkv + b * (size_t)L * 3 * E + (size_t)h * DH;
+    const float* __restrict__ gbase = go + b * (size_t)L * E + (size_t)h * DH;
+    const int j = kt * 32 + c, jc = j < L ? j : L - 1;
+    const float scale = 1.0f / lq_sqrt((float)DH);
+    float k[DH / 2], v[DH / 2];
+    gpt_load_half<DH>(base + (size_t)jc * 3 * E + E, hf, k);
+    gpt_load_half<DH>(base + (size_t)jc * 3 * E + 2 * E, hf, v);
+    f32x16 dk[DT], dv[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) { dk[dt][g] = 0.0f; dv[dt][g] = 0.0f; }
+#pragma unroll 1
+    for (int qt = causal ? kt : 0; qt < NT; ++qt) {
+        const int ir = qt * 32 + gpt_perm(c), irc = ir < L ? ir : L - 1;
+        f32x16 sa, pa;
+        {
+            float q[DH / 2];
+            gpt_load_half<DH>(base + (size_t)irc * 3 * E, hf, q);
+            sa = gpt_dot<DH>(q, k);
+        }
+        {
+            float g[DH / 2];
+            gpt_load_half<DH>(gbase + (size_t)irc * E, hf, g);
+            pa = gpt_dot<DH>(g, v);
+        }
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            const int i = qt * 32 + 2 * g + hf, ic = i < L ? i : L - 1;
+            const bool ok = i < L && j < L && (!causal || j <= i);
+            const float p = ok ? lq_expf(sa[g] * scale - lse[bh * L + ic]) : 0.0f;
+            float kp = 1.0f;
+            if (keep) kp = keep[(bh * L + ic) * L + jc] ? inv_keep : 0.0f;
+            sa[g] = p * (pa[g] * kp - delta[bh * L + ic]);
+            pa[g] = p * kp;
+        }
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            const int i = qt * 32 + 2 * g + hf, ic = i < L ? i : L - 1;
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+                const bool col = DH >= 32 || c < DH;
+                const float ag = col ? gbase[(size_t)ic * E + 32 * dt + c] : 0.0f;
+                const float aq = col ? base[(size_t)ic * 3 * E + 32 * dt + c] : 0.0f;
+                dv[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(ag, pa[g], dv[dt], 0, 0, 0);
+                dk[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq, sa[g], dk[dt], 0, 0, 0);
+            }
+        }
+    }
+    if (j < L) {
+        float* __restrict__ dst = gqkv + (b * L + j) * (size_t)3 * E + (size_t)h * DH;
+        gpt_store_t<DH, DT>(dst + E, dk, hf, scale);
+        gpt_store_t<DH, DT>(dst + 2 * E, dv, hf, 1.0f);
+    }
+}
+
+static int gpt_attention_args(const char* what, int64_t B, int L, int E, int H, const void* keep, float keep_prob, bool* empty) {
+    if (B < 0 || L < 0 || E <= 0 || H <= 0 || E % H != 0) return fail(LIPVQ_EINVAL, "%s: B=%lld L=%d E=%d H=%d", what, (long long)B, L, E, H);
+    const int dh = E / H;
+    if (dh != 16 && dh != 32 && dh != 64) return fail(LIPVQ_EUNSUPPORTED, "%s: head width E/H=%d (16, 32 or 64)", what, dh);
+    if (L > GPT_MAXL) return fail(LIPVQ_EUNSUPPORTED, "%s: sequence length L=%d (1..%d)", what, L, GPT_MAXL);
+    if (keep && !(keep_prob > 0.0f)) return fail(LIPVQ_EINVAL, "%s: keep_prob=%g with a keep mask", what, (double)keep_prob);
+    *empty = B == 0 || L == 0;
+    if (!*empty && B * H * ((L + 31) / 32) > 0x7fffffffLL) return fail(LIPVQ_EUNSUPPORTED, "%s: B=%lld is too many (b, h) pairs for one launch", what, (long long)B);
+    return 0;
+}
+
+extern "C" int lipvq_gpt_attention_f32(const float* qkv, float* out, float* lse, const unsigned char* keep, float keep_prob,
+                                       int64_t B, int L, int E, int H, int causal, void* stream) {
+    bool empty = false;
+    if (int rc = gpt_attention_args("gpt_attention", B, L, E, H, keep, keep_prob, &empty)) return rc;
+    if (empty) return 0;
+    if (!qkv || !out || !lse) return fail(LIPVQ_EINVAL, "gpt_attention: null pointer");
+    if ((((uintptr_t)qkv | (uintptr_t)out) & 15) != 0) return fail(LIPVQ_EINVAL, "gpt_attention: qkv / out must be 16-byte aligned");
+    typedef void (*fn_t)(const float*, float*, float*, const unsigned char*, float, int, int, int, int);
+    const int dh = E / H, NT = (L + 31) / 32;
+    fn_t kfn = nullptr;
+#define LQ_GA(DH_) if (dh == DH_) kfn = NT == 1 ? (fn_t)gpt_attention_kernel<DH_, 1> : NT == 2 ? (fn_t)gpt_attention_kernel<DH_, 2> \
+                                      : NT == 3 ? (fn_t)gpt_attention_kernel<DH_, 3> : (fn_t)gpt_attention_kernel<DH_, 4>;
+    LQ_GA(16) LQ_GA(32) LQ_GA(64)
+#undef LQ_GA
+    hipLaunchKernelGGL(kfn, dim3((unsigned)(B * H * NT)), dim3(64), 0, (hipStream_t)stream, qkv, out, lse, keep,
+                       keep ? 1.0f / keep_prob : 1.0f, L, E, H, causal);
+    return check_launch("gpt_attention");
+}
+
+extern "C" int lipvq_gpt_attention_bwd_f32(const float* qkv, const float* out, const float* gout, const float* lse, float* gqkv,
+                                           float* delta, const unsigned char* keep, float keep_prob, int64_t B, int L, int E, int H,
+                                           int causal, void* stream) {
+    bool empty = false;
+    if (int rc = gpt_attention_args("gpt_attention_bwd", B, L, E, H, keep, keep_prob, &empty)) return rc;
+    if (empty) return 0;
+    if (!qkv || !out || !gout || !lse || !gqkv || !delta) return fail(LIPVQ_EINVAL, "gpt_attention_bwd: null pointer");
+    if ((((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)gout | (uintptr_t)gqkv) & 15) != 0)
+        return fail(LIPVQ_EINVAL, "gpt_attention_bwd: qkv / out / gout / gqkv must be 16-byte aligned");
+    const int dh = E / H, NT = (L + 31) / 32;
+    const dim3 grid((unsigned)(B * H * NT));
+    const float ik = keep ? 1.0f / keep_prob : 1.0f;
+    auto kq = dh == 16 ? gpt_attention_bwd_q_kernel<16> : (dh == 32 ? gpt_attention_bwd_q_kernel<32> : gpt_attention_bwd_q_kernel<64>);
+    auto kkv = dh == 16 ? gpt_attention_bwd_kv_kernel<16> : (dh == 32 ? gpt_attention_bwd_kv_kernel<32> : gpt_attention_bwd_kv_kernel<64>);
+    hipLaunchKernelGGL(kq, grid, dim3(64), 0, (hipStream_t)stream, qkv, out, gout, lse, gqkv, delta, keep, ik, L, E, H, causal, NT);
+    hipLaunchKernelGGL(kkv, grid, dim3(64), 0, (hipStream_t)stream, qkv, gout, lse, delta, gqkv, keep, ik, L, E, H, causal, NT);
+    return check_launch("gpt_attention_bwd");
+}
+
+// ---------------------------------------------------------------------------------------------------
+// s = a + b;  y = LayerNorm(s) * w + bias over rows of E <= 1024 floats, E % 4 == 0: one wave per row, up to four float4 per
+// lane, two-pass moments in registers (as add_layernorm_kernel of lipvq_xf.hip).
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void gpt_layernorm_kernel(const float4* __restrict__ a, const float4* __restrict__ b,
+                                                            const float4* __restrict__ w, const float4* __restrict__ bias, float eps,
+                                                            float4* __restrict__ s_out, float4* __restrict__ y, float4* __restrict__ xhat,
+                                                            float* __restrict__ rstd, int64_t N, int E) {
+    const int lane = threadIdx.x & 63, E4 = E >> 2;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= N) return;
+    const size_t r0 = (size_t)row * E4;
+    float4 x[4];
+    float s = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = lane + 64 * i;
+        x[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (e < E4) {
+            x[i] = a[r0 + e];
+            if (b) { const float4 t = b[r0 + e]; x[i].x += t.x; x[i].y += t.y; x[i].z += t.z; x[i].w += t.w; }
+            if (s_out) s_out[r0 + e] = x[i];
+            s += (x[i].x + x[i].y) + (x[i].z + x[i].w);
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off, 64);
+    const float mean = s / (float)E;
+    float v = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (lane + 64 * i < E4) {
+            x[i].x -= mean; x[i].y -= mean; x[i].z -= mean; x[i].w -= mean;
+            v = lq_fma(x[i].x, x[i].x, v); v = lq_fma(x[i].y, x[i].y, v); v = lq_fma(x[i].z, x[i].z, v); v = lq_fma(x[i].w, x[i].w, v);
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+    const float rs = 1.0f / lq_sqrt(v / (float)E + eps);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = lane + 64 * i;
+        if (e < E4) {
+            const float4 xh = make_float4(x[i].x * rs, x[i].y * rs, x[i].z * rs, x[i].w * rs);
+            if (xhat) xhat[r0 + e] = xh;
+            const float4 ww = w[e], bb = bias[e];
+            y[r0 + e] = make_float4(lq_fma(xh.x, ww.x, bb.x), lq_fma(xh.y, ww.y, bb.y), lq_fma(xh.z, ww.z, bb.z), lq_fma(xh.w, ww.w, bb.w));
+        }
+    }
+    if (rstd && lane == 0) rstd[row] = rs;
+}
+
+extern "C" int lipvq_gpt_layernorm_f32(const float* a, const float* b, const float* w, const float* bias, float eps, float* s,
+                                       float* y, float* xhat, float* rstd, int64_t N, int E, void* stream) {
+    if (N < 0 || E <= 0) return fail(LIPVQ_EINVAL, "gpt_layernorm: N=%lld E=%d", (long long)N, E);
+    if (E > GPT_MAXE || (E & 3) != 0) return fail(LIPVQ_EUNSUPPORTED, "gpt_layernorm: E=%d (a multiple of 4, <= %d)", E, GPT_MAXE);
+    if (N == 0) return 0;
+    if (!a || !w || !bias || !y) return fail(LIPVQ_EINVAL, "gpt_layernorm: null pointer");
+    if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)s | (uintptr_t)y | (uintptr_t)xhat) & 15) != 0)
+        return fail(LIPVQ_EINVAL, "gpt_layernorm: pointers must be 16-byte aligned");
+    if ((N + 3) / 4 > 0x7fffffffLL) return fail(LIPVQ_EUNSUPPORTED, "gpt_layernorm: N=%lld", (long long)N);
+    hipLaunchKernelGGL(gpt_layernorm_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const float4*)a,
+                       (const float4*)b, (const float4*)w, (const float4*)bias, eps, (float4*)s, (float4*)y, (float4*)xhat, rstd, N, E);
+    return check_launch("gpt_layernorm");
+}
+
+// gs = rstd (g w - mean(g w) - xhat mean(g w xhat)) + gres;  gw = sum_rows g xhat;  gb = sum_rows g.
+// Pass 1: a workgroup takes rows_per_block rows (wave w the rows w, w + 4, ...), keeps its column sums in registers, adds the four
+// waves in LDS in wave order and writes ONE partial row pair to part [nblk][2][E].  Pass 2 adds the partials of a column in
+// block order (four interleaved chains, then ((0 + 1) + 2) + 3).  No atomics: the same bits every run.
+#define GPT_LN_MAXBLK 512
+static inline int gpt_ln_rows_per_block(int64_t N) {
+    int64_t rpb = (N + GPT_LN_MAXBLK - 1) / GPT_LN_MAXBLK;
+    rpb = (rpb + 3) / 4 * 4;
+    return (int)(rpb < 4 ? 4 : rpb);
+}
+
+__global__ __launch_bounds__(256) void gpt_layernorm_bwd_kernel(const float4* __restrict__ gy, const float4* __restrict__ xhat,
+                                                                const float* __restrict__ rstd, const float4* __restrict__ w,
+                                                                const float4* __restrict__ gres, float4* __restrict__ gs,
+                                                                float* __restrict__ part, int64_t N, int E, int rows_per_block) {
+    __shared__ float s_gw[4][GPT_MAXE], s_gb[4][GPT_MAXE];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, E4 = E >> 2;
+    float4 pgw[4], pgb[4], ww[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        pgw[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        pgb[i] = pgw[i];
+        ww[i] = lane + 64 * i < E4 ? w[lane + 64 * i] : pgw[i];
+    }
+    const int64_t rbeg = (int64_t)blockIdx.x * rows_per_block;
+    int64_t rend = rbeg + rows_per_block;
+    if (rend > N) rend = N;
+    for (int64_t row = rbeg + wv; row < rend; row += 4) {
+        const size_t r0 = (size_t)row * E4;
+        float4 g[4], xh[4];
+        float s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = lane + 64 * i;
+            g[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            xh[i] = g[i];
+            if (e < E4) {
+                g[i] = gy[r0 + e];
+                xh[i] = xhat[r0 + e];
+                pgw[i].x = lq_fma(g[i].x, xh[i].x, pgw[i].x); pgw[i].y = lq_fma(g[i].y, xh[i].y, pgw[i].y);
+                pgw[i].z = lq_fma(g[i].z, xh[i].z, pgw[i].z); pgw[i].w = lq_fma(g[i].w, xh[i].w, pgw[i].w);
+                pgb[i].x += g[i].x; pgb[i].y += g[i].y; pgb[i].z += g[i].z; pgb[i].w += g[i].w;
+                g[i].x *= ww[i].x; g[i].y *= ww[i].y; g[i].z *= ww[i].z; g[i].w *= ww[i].w;
+                s1 += (g[i].x + g[i].y) + (g[i].z + g[i].w);
+                s2 = lq_fma(g[i].x, xh[i].x, s2); s2 = lq_fma(g[i].y, xh[i].y, s2);
+                s2 = lq_fma(g[i].z, xh[i].z, s2); s2 = lq_fma(g[i].w, xh[i].w, s2);
+            }
+        }
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { s1 += __shfl_xor(s1, off, 64); s2 += __shfl_xor(s2, off, 64); }
+        const float m1 = s1 / (float)E, m2 = s2 / (float)E, rs = rstd[row];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = lane + 64 * i;
+            if (e < E4) {
+                float4 r = make_float4(rs * (g[i].x - m1 - xh[i].x * m2), rs * (g[i].y - m1 - xh[i].y * m2),
+                                       rs * (g[i].z - m1 - xh[i].z * m2), rs * (g[i].w - m1 - xh[i].w * m2));
+                if (gres) { const float4 t = gres[r0 + e]; r.x += t.x; r.y += t.y; r.z += t.z; r.w += t.w; }
+                gs[r0 + e] = r;
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = 4 * (lane + 64 * i);
+        if (e < E) {
+            s_gw[wv][e] = pgw[i].x; s_gw[wv][e + 1] = pgw[i].y; s_gw[wv][e + 2] = pgw[i].z; s_gw[wv][e + 3] = pgw[i].w;
+            s_gb[wv][e] = pgb[i].x; s_gb[wv][e + 1] = pgb[i].y; s_gb[wv][e + 2] = pgb[i].z; s_gb[wv][e + 3] = pgb[i].w;
+        }
+    }
+    __syncthreads();
+    float* __restrict__ p = part + (size_t)blockIdx.x * 2 * E;
+    for (int e = threadIdx.x; e < E; e += 256) {
+        p[e] = ((s_gw[0][e] + s_gw[1][e]) + s_gw[2][e]) + s_gw[3][e];
+        p[E + e] = ((s_gb[0][e] + s_gb[1][e]) + s_gb[2][e]) + s_gb[3][e];
+    }
+}
+
+// grid (ceil(E / 64), 2): 64 columns x 4 chains per workgroup; y = 0 -> gw, y = 1 -> gb
+__global__ __launch_bounds__(256) void gpt_layernorm_bwd_reduce_kernel(const float* __restrict__ part, float* __restrict__ gw,
+                                                                       float* __restrict__ gb, int nblk, int E) {
+    __shared__ float s_p[4][64];
+    const int col = threadIdx.x & 63, ch = threadIdx.x >> 6;
+    const int e = blockIdx.x * 64 + col, which = blockIdx.y;
+    float acc = 0.0f;
+    if (e < E)
+        for (int k = ch; k < nblk; k += 4) acc += part[((size_t)k * 2 + which) * E + e];
+    s_p[ch][col] = acc;
+    __syncthreads();
+    if (ch == 0 && e < E) (which ? gb : gw)[e] = ((s_p[0][col] + s_p[1][col]) + s_p[2][col]) + s_p[3][col];
+}
+
+extern "C" size_t lipvq_gpt_layernorm_bwd_workspace_bytes(int64_t N, int E) {
+    if (N <= 0 || E <= 0) return 0;
+    const int rpb = gpt_ln_rows_per_block(N);
+    return (size_t)((N + rpb - 1) / rpb) * 2 * (size_t)E * sizeof(float);
+}
+
+extern "C" int lipvq_gpt_layernorm_bwd_f32(const float* gy, const float* xhat, const float* rstd, const float* w, const float* gres,
+                                           float* gs, float* gw, float* gb, void* workspace, int64_t N, int E, void* stream) {
+    if (N < 0 || E <= 0) return fail(LIPVQ_EINVAL, "gpt_layernorm_bwd: N=%lld E=%d", (long long)N, E);
+    if (E > GPT_MAXE || (E & 3) != 0) return fail(LIPVQ_EUNSUPPORTED, "gpt_layernorm_bwd: E=%d (a multiple of 4, <= %d)", E, GPT_MAXE);
+    if (!gw || !gb) return fail(LIPVQ_EINVAL, "gpt_layernorm_bwd: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 0) {                                       // no rows: the parameter gradients are zero
+        if (hipMemsetAsync(gw, 0, (size_t)E * sizeof(float), st) != hipSuccess || hipMemsetAsync(gb, 0, (size_t)E * sizeof(float), st) != hipSuccess)
+            return fail(LIPVQ_EHIP, "gpt_layernorm_bwd: memset failed");
+        return 0;
+    }
+    if (!gy || !xhat || !rstd || !w || !gs || !workspace) return fail(LIPVQ_EINVAL, "gpt_layernorm_bwd: null pointer");
+    if ((((uintptr_t)gy | (uintptr_t)xhat | (uintptr_t)w | (uintptr_t)gres | (uintptr_t)gs) & 15) != 0)
+        return fail(LIPVQ_EINVAL, "gpt_layernorm_bwd: pointers must be 16-byte aligned");
+    const int rpb = gpt_ln_rows_per_block(N);
+    const int nblk = (int)((N + rpb - 1) / rpb);
+    hipLaunchKernelGGL(gpt_layernorm_bwd_kernel, dim3(nblk), dim3(256), 0, st, (const float4*)gy, (const float4*)xhat, rstd,
+                       (const float4*)w, (const float4*)gres, (float4*)gs, (float*)workspace, N, E, rpb);
+    hipLaunchKernelGGL(gpt_layernorm_bwd_reduce_kernel, dim3((E + 63) / 64, 2), dim3(256), 0, st, (const float*)workspace, gw, gb, nblk, E);
+    return check_launch("gpt_layernorm_bwd");
+}

@@ -1,0 +1,250 @@
+"""The ICRT transformer backbone -- the reference's ``GPT_Backbone`` (robomimic/models/transformers.py:80-439), which
+``ICLTransformer`` builds at obs_nets.py:2453-2463 (embed_dim 512, 8 heads, 6 layers, context 3 T = 30, icl_config.py:133-153)
+and feeds with the ``[B, 3T, E]`` tensor that ``ICLInputEmbedding`` (embedding.py) writes -- on the HIP library.
+
+``GPTBackbone`` has the reference's constructor signature and the reference's module tree (``nets.transformer.{i}.nets.
+attention.nets.qkv`` ...), built in the reference's order, so ``state_dict()`` keys, shapes and order, the RNG consumption of a
+seeded construction (default ``nn.Linear`` init, then ``normal_(0, 0.02)`` in ``apply`` order) and therefore the parameter
+bytes are the reference's, and a checkpoint's ``policy.nets.transformer.*`` sub-dict loads with ``strict=True``.  The
+children are parameter CONTAINERS only: ``forward`` never calls them.  Per block the compute is
+
+    lipvq_gpt_layernorm_f32      s = x + previous sub-layer, y = ln1(s)              (one launch, both written)
+    lipvq_linear_act_f32         qkv = y Wqkv^T                                      (no bias, transformers.py:136)
+    lipvq_gpt_attention_f32      batched causal attention, all (b, h) in one launch
+    lipvq_linear_act_f32         output projection
+    lipvq_gpt_layernorm_f32      s = s + attention branch, y = ln2(s)
+    lipvq_linear_act_f32 x 2     Linear(E, 4E) + GELU, Linear(4E, E)
+
+and one more lipvq_gpt_layernorm_f32 closes the last residual and applies ``output_ln``: 6 launches per block, 37 for the ICRT
+model.  Every op is a ``torch.autograd.Function`` over the backward kernels (lipvq_gpt_attention_bwd_f32,
+lipvq_gpt_layernorm_bwd_f32 -- which folds the residual stream's incoming gradient in --, lipvq_act_bwd_f32, lipvq_wgrad_f32);
+none of them uses float atomics, so gradients repeat bit for bit.
+
+Dropout (training mode, torch's RNG): the attention-probability mask is drawn here as ``keep`` bytes ``[B, H, L, L]`` and
+applied inside the attention kernel; the two block-output dropouts (transformers.py:205, :289) are applied BY TORCH
+(``F.dropout`` on the branch before the fused residual launch) -- they are elementwise over ``[B L, E]`` and vanish in eval.
+Training-mode outputs match the reference in distribution, not in bits (torch draws the attention mask inside its own
+dropout kernel).  ``activation="geglu"`` is not implemented (the ICRT configuration uses ``gelu``).
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import ops
+from .ops import ACT_GELU, ACT_NONE
+
+__all__ = ["GPTBackbone", "GraphedGPTBackbone"]
+
+
+class _LinearFn(torch.autograd.Function):
+    """act(x W^T + b) over the last dimension, b optional; backward = act' (elementwise), one more Linear (gx), the wgrad kernel."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, act):
+        ctx.act, ctx.has_bias, ctx.shape = act, b is not None, x.shape
+        x2 = x.reshape(-1, x.shape[-1])
+        if act != ACT_NONE:
+            y, pre = ops.linear(x2, W, b, act=act, save_pre=True)
+            ctx.save_for_backward(x2, W, pre)
+        else:
+            y = ops.linear(x2, W, b)
+            ctx.save_for_backward(x2, W)
+        return y.view(*x.shape[:-1], W.shape[0])
+
+    @staticmethod
+    def backward(ctx, gy):
+        gy = gy.reshape(-1, gy.shape[-1]).contiguous()
+        if ctx.act != ACT_NONE:
+            x2, W, pre = ctx.saved_tensors
+            gy = ops.act_bwd(gy, pre, ctx.act)
+        else:
+            x2, W = ctx.saved_tensors
+        gx = ops.linear(gy, W.t().contiguous()).view(ctx.shape) if ctx.needs_input_grad[0] else None
+        gW = gb = None
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            gW, gb = ops.wgrad(gy, x2, want_bias=ctx.has_bias)
+        return gx, gW, gb, None
+
+
+class _AttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, nhead, causal, keep, keep_prob):
+        out, lse = ops.gpt_attention(qkv, nhead, causal, keep, keep_prob)
+        ctx.nhead, ctx.causal, ctx.keep, ctx.keep_prob = nhead, causal, keep, keep_prob
+        ctx.save_for_backward(qkv, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        qkv, out, lse = ctx.saved_tensors
+        return (ops.gpt_attention_bwd(qkv, out, gout.contiguous(), lse, ctx.nhead, ctx.causal, ctx.keep, ctx.keep_prob),
+                None, None, None, None)
+
+
+class _AddLayerNormFn(torch.autograd.Function):
+    """(s, y) = (a + b, LayerNorm(a + b) w + bias), b optional; s is None unless want_s (the closing LayerNorm discards it, and
+    without b the caller keeps using a).  Backward: the gradient of a and of b is LayerNorm's plus the gradient that arrives for
+    s (the residual stream), added inside the kernel."""
+
+    @staticmethod
+    def forward(ctx, a, b, w, bias, eps, want_s):
+        ctx.set_materialize_grads(False)
+        ctx.has_b = b is not None
+        if not any(ctx.needs_input_grad):                      # eval / no_grad: nothing is kept for a backward
+            return ops.gpt_layernorm(a, b, w, bias, eps, want_s=want_s)
+        s, y, xhat, rstd = ops.gpt_layernorm(a, b, w, bias, eps, want_s=want_s, save=True)
+        ctx.save_for_backward(xhat, rstd, w)
+        return s, y
+
+    @staticmethod
+    def backward(ctx, gs, gy):
+        if gy is None:
+            return gs, (gs if ctx.has_b else None), None, None, None, None
+        xhat, rstd, w = ctx.saved_tensors
+        g, gw, gb = ops.gpt_layernorm_bwd(gy.contiguous(), xhat, rstd, w, None if gs is None else gs.contiguous())
+        return g, (g if ctx.has_b else None), gw, gb, None, None
+
+
+class _SelfAttention(nn.Module):
+    """Parameter container with the reference's names (transformers.py:133-151)."""
+
+    def __init__(self, embed_dim, num_heads, context_length, causal, attn_dropout, output_dropout):
+        super().__init__()
+        self.nets = nn.ModuleDict()
+        self.nets["qkv"] = nn.Linear(embed_dim, 3 * embed_dim, bias=False)
+        self.nets["attn_dropout"] = nn.Dropout(attn_dropout)
+        self.nets["output_dropout"] = nn.Dropout(output_dropout)
+        self.nets["output"] = nn.Linear(embed_dim, embed_dim)
+        mask = torch.ones(context_length, context_length)
+        if causal:
+            mask = torch.tril(mask)
+        self.register_buffer("mask", mask.view(1, 1, context_length, context_length))
+
+
+class _SelfAttentionBlock(nn.Module):
+    """Parameter container with the reference's names (transformers.py:267-294)."""
+
+    def __init__(self, embed_dim, num_heads, context_length, causal, attn_dropout, output_dropout):
+        super().__init__()
+        self.nets = nn.ModuleDict()
+        self.nets["attention"] = _SelfAttention(embed_dim, num_heads, context_length, causal, attn_dropout, output_dropout)
+        self.nets["mlp"] = nn.Sequential(nn.Linear(embed_dim, 4 * embed_dim), nn.GELU(), nn.Linear(4 * embed_dim, embed_dim),
+                                         nn.Dropout(output_dropout))
+        self.nets["ln1"] = nn.LayerNorm(embed_dim)
+        self.nets["ln2"] = nn.LayerNorm(embed_dim)
+
+
+class GPTBackbone(nn.Module):
+    """Drop-in for the reference's ``GPT_Backbone`` (transformers.py:321-440) on the HIP library."""
+
+    MAX_CONTEXT, MAX_EMBED, HEAD_WIDTHS = 128, 1024, (16, 32, 64)
+
+    def __init__(self, embed_dim, context_length, causal=True, attn_dropout=0.1, block_output_dropout=0.1, num_layers=6,
+                 num_heads=8, activation="gelu"):
+        super().__init__()
+        if activation == "geglu":
+            raise NotImplementedError("GPTBackbone: activation='geglu' is not implemented on the HIP path (the ICRT configuration "
+                                      "uses 'gelu'); keep the reference's GPT_Backbone for GEGLU models")
+        if activation != "gelu":
+            raise ValueError(f"GPTBackbone: unknown activation {activation!r}")
+        if embed_dim % num_heads != 0 or embed_dim // num_heads not in self.HEAD_WIDTHS:
+            raise ValueError(f"GPTBackbone: embed_dim={embed_dim} / num_heads={num_heads} must give a head width in {self.HEAD_WIDTHS}")
+        if embed_dim > self.MAX_EMBED or not 1 <= context_length <= self.MAX_CONTEXT:
+            raise ValueError(f"GPTBackbone: embed_dim <= {self.MAX_EMBED} and 1 <= context_length <= {self.MAX_CONTEXT} "
+                             f"(got {embed_dim}, {context_length})")
+        self.embed_dim = embed_dim
+        self.num_layers = num_layers
+        self.num_heads = num_heads
+        self.context_length = context_length
+        self.causal = causal
+        self.attn_dropout = attn_dropout
+        self.block_output_dropout = block_output_dropout
+        self.nets = nn.ModuleDict()
+        self.nets["transformer"] = nn.Sequential(*[
+            _SelfAttentionBlock(embed_dim, num_heads, context_length, causal, attn_dropout, block_output_dropout)
+            for _ in range(num_layers)])
+        self.nets["output_ln"] = nn.LayerNorm(embed_dim)
+        self.apply(self._init_weights)
+
+    @staticmethod
+    def _init_weights(module):
+        if isinstance(module, nn.Linear):
+            module.weight.data.normal_(mean=0.0, std=0.02)
+            if module.bias is not None:
+                module.bias.data.zero_()
+        elif isinstance(module, nn.LayerNorm):
+            module.bias.data.zero_()
+            module.weight.data.fill_(1.0)
+
+    def output_shape(self, input_shape=None):
+        return list(input_shape)
+
+    def forward(self, inputs: torch.Tensor) -> torch.Tensor:
+        assert inputs.shape[1:] == (self.context_length, self.embed_dim), inputs.shape
+        if not inputs.is_cuda:
+            raise RuntimeError("GPTBackbone runs on the HIP library only (no CPU path)")
+        x = inputs.contiguous().float()
+        B, L, H = x.shape[0], self.context_length, self.num_heads
+        a, b = x, None
+        for blk in self.nets["transformer"]:
+            att, mlp, ln1, ln2 = blk.nets["attention"], blk.nets["mlp"], blk.nets["ln1"], blk.nets["ln2"]
+            p_att = float(att.nets["attn_dropout"].p) if self.training else 0.0
+            p_out = float(att.nets["output_dropout"].p) if self.training else 0.0
+            p_mlp = float(mlp[3].p) if self.training else 0.0
+            keep, keep_prob = None, 1.0
+            if p_att > 0.0:
+                keep = (torch.rand((B, H, L, L), device=x.device) >= p_att).to(torch.uint8)
+                keep_prob = 1.0 - p_att
+            if b is None:                                      # first block: the stream is the input itself, nothing to add or copy
+                s, y = a, _AddLayerNormFn.apply(a, None, ln1.weight, ln1.bias, ln1.eps, False)[1]
+            else:
+                s, y = _AddLayerNormFn.apply(a, b, ln1.weight, ln1.bias, ln1.eps, True)
+            qkv = _LinearFn.apply(y, att.nets["qkv"].weight, None, ACT_NONE)
+            o = _AttentionFn.apply(qkv, H, bool(self.causal), keep, keep_prob)
+            o = _LinearFn.apply(o, att.nets["output"].weight, att.nets["output"].bias, ACT_NONE)
+            if p_out > 0.0:
+                o = F.dropout(o, p_out, True)
+            s, y = _AddLayerNormFn.apply(s, o, ln2.weight, ln2.bias, ln2.eps, True)
+            f = _LinearFn.apply(y, mlp[0].weight, mlp[0].bias, ACT_GELU)
+            f = _LinearFn.apply(f, mlp[2].weight, mlp[2].bias, ACT_NONE)
+            if p_mlp > 0.0:
+                f = F.dropout(f, p_mlp, True)
+            a, b = s, f
+        ln = self.nets["output_ln"]
+        out = _AddLayerNormFn.apply(a, b, ln.weight, ln.bias, ln.eps, False)[1]
+        return out
+
+
+class GraphedGPTBackbone:
+    """Eval-mode forward of a GPTBackbone captured in ONE HIP graph for a fixed [B, L, E] shape.
+
+    The backbone is 6 small launches per block; at the ICRT step shape (B = 8, 240 rows) each is microseconds of GPU work, so
+    an eager call is bound by Python + ctypes issue and a graph replay costs the GPU time alone.  Rollouts call the policy
+    once per environment step with the same shape, which is what this serves.  Parameters are read at replay time through
+    their storage, so in-place updates (optimizer steps, load_state_dict) are seen; re-capture after anything that REPLACES a
+    parameter tensor (.to(), .cuda()).  The returned tensor is the graph's own output buffer: copy it before the next call if
+    it must survive."""
+
+    def __init__(self, net: GPTBackbone, example_inputs: torch.Tensor):
+        if net.training:
+            raise RuntimeError("GraphedGPTBackbone captures the eval-mode forward: call net.eval() first")
+        self.net = net
+        self._x = example_inputs.detach().contiguous().float().clone()
+        side = torch.cuda.Stream(device=self._x.device)
+        side.wait_stream(torch.cuda.current_stream(self._x.device))
+        with torch.no_grad(), torch.cuda.stream(side):            # first-use work stays out of the capture
+            for _ in range(3):
+                net(self._x)
+        torch.cuda.current_stream(self._x.device).wait_stream(side)
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(self._graph):
+            self._y = net(self._x)
+
+    def __call__(self, inputs: torch.Tensor) -> torch.Tensor:
+        if inputs.shape != self._x.shape:
+            raise ValueError(f"captured for {tuple(self._x.shape)}, got {tuple(inputs.shape)}")
+        self._x.copy_(inputs)
+        self._graph.replay()
+        return self._y

@@ -1009,3 +1009,84 @@ def layernorm_bwd(gy, xhat, rstd, w):
         check(lib.lipvq_layernorm_bwd_f32(_ptr(gy), _ptr(xhat), _ptr(_chk(rstd, "rstd")), _ptr(_chk(w, "w")), _ptr(gx), _ptr(gw),
                                           _ptr(gb), N, E, _stream()), "lipvq_layernorm_bwd_f32")
     return gx, gw, gb
+
+
+# ---------------------------------------------------------------------------------------------------
+# the transformer backbone (csrc/lipvq_gpt.hip; reference robomimic/models/transformers.py:80-439)
+# ---------------------------------------------------------------------------------------------------
+
+def _gpt_keep(keep, B, H, L, dev):
+    if keep is None:
+        return None
+    if keep.dtype != torch.uint8 or keep.shape != (B, H, L, L) or not keep.is_contiguous() or keep.device != dev:
+        raise ValueError("gpt_attention: keep must be a contiguous uint8 [B, H, L, L] tensor on the input's device")
+    return keep
+
+
+def gpt_attention(qkv, nhead: int, causal: bool = True, keep=None, keep_prob: float = 1.0):
+    """(out [B, L, E], lse [B, H, L]) of batched multi-head self-attention over qkv [B, L, 3E] (q | k | v), causal or not."""
+    qkv = _chk(qkv, "qkv")
+    if qkv.dim() != 3 or qkv.shape[2] % 3 != 0:
+        raise ValueError(f"gpt_attention: qkv {tuple(qkv.shape)}")
+    B, L, E = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
+    keep = _gpt_keep(keep, B, nhead, L, qkv.device)
+    out = torch.empty((B, L, E), device=qkv.device, dtype=torch.float32)
+    lse = torch.empty((B, nhead, L), device=qkv.device, dtype=torch.float32)
+    with _on(qkv.device):
+        check(lib.lipvq_gpt_attention_f32(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(keep), float(keep_prob), B, L, E, int(nhead),
+                                          int(bool(causal)), _stream()), "lipvq_gpt_attention_f32")
+    return out, lse
+
+
+def gpt_attention_bwd(qkv, out, gout, lse, nhead: int, causal: bool = True, keep=None, keep_prob: float = 1.0):
+    qkv, out, gout, lse = _chk(qkv, "qkv"), _chk(out, "out"), _chk(gout, "gout"), _chk(lse, "lse")
+    B, L, E = out.shape
+    if qkv.shape != (B, L, 3 * E) or gout.shape != out.shape or lse.shape != (B, nhead, L):
+        raise ValueError("gpt_attention_bwd: shapes do not match")
+    keep = _gpt_keep(keep, B, nhead, L, qkv.device)
+    gqkv = torch.empty_like(qkv)
+    delta = torch.empty_like(lse)
+    with _on(qkv.device):
+        check(lib.lipvq_gpt_attention_bwd_f32(_ptr(qkv), _ptr(out), _ptr(gout), _ptr(lse), _ptr(gqkv), _ptr(delta), _ptr(keep),
+                                              float(keep_prob), B, L, E, int(nhead), int(bool(causal)), _stream()),
+              "lipvq_gpt_attention_bwd_f32")
+    return gqkv
+
+
+def gpt_layernorm(a, b, w, bias, eps: float, want_s: bool = True, save: bool = False):
+    """s = a + b (b may be None) and y = LayerNorm(s) * w + bias over the last dimension, one launch.
+    Returns (s or None, y) and, with save=True, (s or None, y, xhat, rstd)."""
+    a = _chk(a, "a")
+    if b is not None:
+        b = _chk(b, "b")
+        if b.shape != a.shape:
+            raise ValueError("gpt_layernorm: shapes differ")
+    E = a.shape[-1]
+    N = a.numel() // E if E else 0
+    s = torch.empty_like(a) if want_s else None
+    y = torch.empty_like(a)
+    xhat = torch.empty_like(a) if save else None
+    rstd = torch.empty(N, device=a.device, dtype=torch.float32) if save else None
+    with _on(a.device):
+        check(lib.lipvq_gpt_layernorm_f32(_ptr(a), _ptr(b), _ptr(_chk(w, "w")), _ptr(_chk(bias, "bias")), float(eps), _ptr(s), _ptr(y),
+                                          _ptr(xhat), _ptr(rstd), N, E, _stream()), "lipvq_gpt_layernorm_f32")
+    return (s, y, xhat, rstd) if save else (s, y)
+
+
+def gpt_layernorm_bwd(gy, xhat, rstd, w, gres=None):
+    """(gs, gw, gb): gs = LayerNorm backward + gres (the residual stream's incoming gradient, may be None)."""
+    gy, xhat = _chk(gy, "gy"), _chk(xhat, "xhat")
+    if gres is not None:
+        gres = _chk(gres, "gres")
+        if gres.shape != gy.shape:
+            raise ValueError("gpt_layernorm_bwd: gres shape")
+    E = gy.shape[-1]
+    N = gy.numel() // E if E else 0
+    gs = torch.empty_like(gy)
+    gw = torch.empty(E, device=gy.device, dtype=torch.float32)
+    gb = torch.empty(E, device=gy.device, dtype=torch.float32)
+    ws = torch.empty(max(1, lib.lipvq_gpt_layernorm_bwd_workspace_bytes(N, E)), device=gy.device, dtype=torch.uint8)
+    with _on(gy.device):
+        check(lib.lipvq_gpt_layernorm_bwd_f32(_ptr(gy), _ptr(xhat), _ptr(_chk(rstd, "rstd")), _ptr(_chk(w, "w")), _ptr(gres), _ptr(gs),
+                                              _ptr(gw), _ptr(gb), _ptr(ws), N, E, _stream()), "lipvq_gpt_layernorm_bwd_f32")
+    return gs, gw, gb
