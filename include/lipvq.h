@@ -438,13 +438,11 @@ int lipvq_attention_f32(const float* qkv, float* out, float* lse, const unsigned
 int lipvq_attention_bwd_f32(const float* qkv, const float* out, const float* gout, const float* lse, float* gqkv,
                             float* delta, const unsigned char* keep, float keep_prob, int64_t S, int D, int H, void* stream);
 
-/* ob:1245 post-norm residual of TransformerEncoderLayer (norm_first = False): y = LayerNorm(a + b) * w + bias, rows of
- * E <= 256 floats; b may be NULL.  xhat [N][E] and rstd [N] (either may be NULL) are saved for the backward. */
-int lipvq_add_layernorm_f32(const float* a, const float* b, const float* w, const float* bias, float eps, float* y,
-                            float* xhat, float* rstd, int64_t N, int E, void* stream);
-/* gx [N][E] (the gradient of BOTH a and b), and gw [E], gb [E] ACCUMULATED (caller zero-fills). */
-int lipvq_layernorm_bwd_f32(const float* gy, const float* xhat, const float* rstd, const float* w, float* gx, float* gw,
-                            float* gb, int64_t N, int E, void* stream);
+/* ob:1245 post-norm residual of TransformerEncoderLayer (norm_first = False), y = LayerNorm(a + b) * w + bias, and its backward:
+ * lipvq_gpt_layernorm_f32 with s = NULL and lipvq_gpt_layernorm_bwd_f32 with gres = NULL, declared with the backbone below
+ * (D is a multiple of 8 here, so every row width is a multiple of 4; those entry points want a, b, w, bias and the gradient
+ * rows 16-byte aligned and answer LIPVQ_EINVAL otherwise -- a LayerNorm parameter that is a view into a flat buffer must start
+ * at a multiple of 4 floats). */
 
 /* ---- the transformer backbone (tf = robomimic/models/transformers.py; tf:321-440 GPT_Backbone, built at obs_nets.py:2453-2463
  *      with embed_dim 512, 8 heads, 6 layers, context 3 T = 30): pre-norm blocks x + attn(ln1(x)), x + mlp(ln2(x)), then output_ln.
@@ -465,14 +463,16 @@ int lipvq_gpt_attention_bwd_f32(const float* qkv, const float* out, const float*
                                 float* delta, const unsigned char* keep, float keep_prob, int64_t B, int L, int E, int H,
                                 int causal, void* stream);
 
-/* tf:300-301, :439 the residual add and the LayerNorm that follows it, in one pass over rows of E floats (E % 4 == 0, E <= 1024):
- * s = a + b (the `x + ...` of tf:300-301; b may be NULL: s = a), y = LayerNorm(s) * w + bias (the next ln1 / ln2 / output_ln).
- * s [N][E] may be NULL (not stored); xhat [N][E] and rstd [N] (either may be NULL) are saved for the backward.  N == 0: no-op. */
+/* The residual add and the LayerNorm that follows it, in one pass over rows of E floats (E % 4 == 0, E <= 1024), for both
+ * modules: s = a + b (b may be NULL: s = a), y = LayerNorm(s) * w + bias.  The backbone (tf:300-301, :439) keeps s, the `x + ...`
+ * of its pre-norm residual stream, and y is the next ln1 / ln2 / output_ln; the default branch's post-norm residual (ob:1245) passes
+ * s = NULL and carries y on.  s [N][E] may be NULL (not stored); xhat [N][E] and rstd [N] (either may be NULL) are saved for the
+ * backward.  N == 0: no-op. */
 int lipvq_gpt_layernorm_f32(const float* a, const float* b, const float* w, const float* bias, float eps, float* s, float* y,
                             float* xhat, float* rstd, int64_t N, int E, void* stream);
 /* Its backward: gs [N][E] = the LayerNorm's gradient with respect to s PLUS gres [N][E] (the residual stream's own incoming
- * gradient, may be NULL) -- the gradient of both a and b; gw [E], gb [E] are WRITTEN (not accumulated, unlike
- * lipvq_layernorm_bwd_f32: per-workgroup partial sums added in a fixed order, so the bits repeat from run to run).
+ * gradient; NULL where nothing but the LayerNorm reads s, as in the default branch) -- the gradient of both a and b; gw [E],
+ * gb [E] are WRITTEN, not accumulated: per-workgroup partial sums added in a fixed order, so the bits repeat from run to run.
  * workspace: lipvq_gpt_layernorm_bwd_workspace_bytes(N, E) bytes, any contents. */
 size_t lipvq_gpt_layernorm_bwd_workspace_bytes(int64_t N, int E);
 int lipvq_gpt_layernorm_bwd_f32(const float* gy, const float* xhat, const float* rstd, const float* w, const float* gres,

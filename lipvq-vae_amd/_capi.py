@@ -102,8 +102,6 @@ SIGNATURES = {
     "lipvq_spectral_norm_bwd_f32": (_i, [_vp] * 6 + [_i, _i, _vp]),
     "lipvq_attention_f32": (_i, [_vp] * 4 + [C.c_float, _i64, _i, _i, _vp]),
     "lipvq_attention_bwd_f32": (_i, [_vp] * 7 + [C.c_float, _i64, _i, _i, _vp]),
-    "lipvq_add_layernorm_f32": (_i, [_vp] * 4 + [C.c_float] + [_vp] * 3 + [_i64, _i, _vp]),
-    "lipvq_layernorm_bwd_f32": (_i, [_vp] * 7 + [_i64, _i, _vp]),
     "lipvq_gpt_attention_f32": (_i, [_vp] * 4 + [C.c_float, _i64, _i, _i, _i, _i, _vp]),
     "lipvq_gpt_attention_bwd_f32": (_i, [_vp] * 7 + [C.c_float, _i64, _i, _i, _i, _i, _vp]),
     "lipvq_gpt_layernorm_f32": (_i, [_vp] * 4 + [C.c_float] + [_vp] * 4 + [_i64, _i, _vp]),

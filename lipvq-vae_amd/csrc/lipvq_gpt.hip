@@ -331,7 +331,7 @@ extern "C" int lipvq_gpt_attention_bwd_f32(const float* qkv, const float* out, c
 
 // ---------------------------------------------------------------------------------------------------
 // s = a + b;  y = LayerNorm(s) * w + bias over rows of E <= 1024 floats, E % 4 == 0: one wave per row, up to four float4 per
-// lane, two-pass moments in registers (as add_layernorm_kernel of lipvq_xf.hip).
+// lane, two-pass moments in registers.  With s_out == NULL this is the post-norm residual of the default action branch.
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gpt_layernorm_kernel(const float4* __restrict__ a, const float4* __restrict__ b,
                                                             const float4* __restrict__ w, const float4* __restrict__ bias, float eps,

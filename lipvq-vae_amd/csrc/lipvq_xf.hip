@@ -6,9 +6,10 @@
 //   attention_kernel       softmax(Q K^T / sqrt(dh)) V per head on an UNBATCHED sequence [S][3D] (the reference hands the
 //                          encoder a 2-D [B*T][D] tensor: every action of the batch attends to every other), fp32, online softmax
 //   attention_bwd_q/kv     its backward (probabilities recomputed from the saved log-sum-exp)
-//   add_layernorm_kernel   y = LayerNorm(a + b) * w + bias  (post-norm residual), and its backward
-// The Linears run on the existing lipvq_linear_act_f32 / lipvq_wgrad_f32.  All sizes here are small (S = B*T rows of a training
-// step, D <= 256): the kernels are written for launch latency and occupancy of a few workgroups, not for a roofline.
+// The Linears run on the existing lipvq_linear_act_f32 / lipvq_wgrad_f32, the post-norm residual y = LayerNorm(a + b) * w + bias
+// and its backward on lipvq_gpt_layernorm_f32 / lipvq_gpt_layernorm_bwd_f32 (lipvq_gpt.hip) with s = NULL, gres = NULL.
+// All sizes here are small (S = B*T rows of a training step, D <= 256): the kernels are written for launch latency and
+// occupancy of a few workgroups, not for a roofline.
 // ABI: include/lipvq.h ("default action branch").  Tolerance against torch: 1e-5 of each tensor's scale (tests/test_gpu_default.py).
 #include "lipvq_common.h"
 
@@ -123,6 +124,14 @@ extern "C" int lipvq_spectral_norm_bwd_f32(const float* gWsn, const float* Wsn, 
 #define XF_KT 64
 __device__ __forceinline__ float xf_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
 
+// the size and keep_prob checks shared by the forward and the backward entry point
+static int attention_args(const char* what, const unsigned char* keep, float keep_prob, int64_t S, int D, int H) {
+    if (S <= 0 || D <= 0 || H <= 0 || D % H != 0 || D / H > XF_DH)
+        return fail(LIPVQ_EUNSUPPORTED, "%s: S=%lld D=%d H=%d (head width 1..%d)", what, (long long)S, D, H, XF_DH);
+    if (S > 65535LL * XF_QB || (keep && !(keep_prob > 0.0f))) return fail(LIPVQ_EINVAL, "%s: bad S / keep_prob", what);
+    return 0;
+}
+
 template <int DH>
 __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse,
                                                         const unsigned char* __restrict__ keep, float inv_keep, int S, int D, int H) {
@@ -192,9 +201,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
 extern "C" int lipvq_attention_f32(const float* qkv, float* out, float* lse, const unsigned char* keep, float keep_prob,
                                    int64_t S, int D, int H, void* stream) {
     if (!qkv || !out || !lse) return fail(LIPVQ_EINVAL, "attention: null pointer");
-    if (S <= 0 || D <= 0 || H <= 0 || D % H != 0 || D / H > XF_DH)
-        return fail(LIPVQ_EUNSUPPORTED, "attention: S=%lld D=%d H=%d (head width 1..%d)", (long long)S, D, H, XF_DH);
-    if (S > 65535LL * XF_QB || (keep && !(keep_prob > 0.0f))) return fail(LIPVQ_EINVAL, "attention: bad S / keep_prob");
+    if (int rc = attention_args("attention", keep, keep_prob, S, D, H)) return rc;
     // head width padded to 8, 16 or 32 columns (compile-time loops: the reference's 8 heads give 8 at D = 64, 26 at D = 208)
     const int dh = D / H;
     auto kfn = dh <= 8 ? attention_kernel<8> : (dh <= 16 ? attention_kernel<16> : attention_kernel<32>);
@@ -334,9 +341,7 @@ __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const float* __re
 extern "C" int lipvq_attention_bwd_f32(const float* qkv, const float* out, const float* gout, const float* lse, float* gqkv,
                                        float* delta, const unsigned char* keep, float keep_prob, int64_t S, int D, int H, void* stream) {
     if (!qkv || !out || !gout || !lse || !gqkv || !delta) return fail(LIPVQ_EINVAL, "attention_bwd: null pointer");
-    if (S <= 0 || D <= 0 || H <= 0 || D % H != 0 || D / H > XF_DH)
-        return fail(LIPVQ_EUNSUPPORTED, "attention_bwd: S=%lld D=%d H=%d (head width 1..%d)", (long long)S, D, H, XF_DH);
-    if (S > 65535LL * XF_QB || (keep && !(keep_prob > 0.0f))) return fail(LIPVQ_EINVAL, "attention_bwd: bad S / keep_prob");
+    if (int rc = attention_args("attention_bwd", keep, keep_prob, S, D, H)) return rc;
     const dim3 grid((unsigned)((S + XF_QB - 1) / XF_QB), H);
     const float ik = keep ? 1.0f / keep_prob : 1.0f;
     const int dh = D / H;
@@ -345,113 +350,4 @@ extern "C" int lipvq_attention_bwd_f32(const float* qkv, const float* out, const
     hipLaunchKernelGGL(kq, grid, dim3(256), 0, (hipStream_t)stream, qkv, out, gout, lse, gqkv, delta, keep, ik, (int)S, D, H);
     hipLaunchKernelGGL(kkv, grid, dim3(256), 0, (hipStream_t)stream, qkv, gout, lse, delta, gqkv, keep, ik, (int)S, D, H);
     return check_launch("attention_bwd");
-}
-
-// ---------------------------------------------------------------------------------------------------
-// y = LayerNorm(a + b) * w + bias over rows of E <= 256 floats (one wave per row; two-pass moments in registers).
-// Saves xhat [N][E] (normalised rows) and rstd [N] for the backward.
-// ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void add_layernorm_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                            const float* __restrict__ w, const float* __restrict__ bias, float eps,
-                                                            float* __restrict__ y, float* __restrict__ xhat, float* __restrict__ rstd,
-                                                            int64_t N, int E) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= N) return;
-    float x[4];
-    float s = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int e = lane + 64 * i;
-        x[i] = e < E ? a[(size_t)row * E + e] + (b ? b[(size_t)row * E + e] : 0.0f) : 0.0f;
-        s += x[i];
-    }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off, 64);
-    const float mean = s / (float)E;
-    float v = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int e = lane + 64 * i;
-        const float d = e < E ? x[i] - mean : 0.0f;
-        x[i] = d;
-        v = lq_fma(d, d, v);
-    }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
-    const float rs = 1.0f / lq_sqrt(v / (float)E + eps);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int e = lane + 64 * i;
-        if (e < E) {
-            const float xh = x[i] * rs;
-            if (xhat) xhat[(size_t)row * E + e] = xh;
-            y[(size_t)row * E + e] = lq_fma(xh, w[e], bias[e]);
-        }
-    }
-    if (rstd && lane == 0) rstd[row] = rs;
-}
-
-extern "C" int lipvq_add_layernorm_f32(const float* a, const float* b, const float* w, const float* bias, float eps, float* y,
-                                       float* xhat, float* rstd, int64_t N, int E, void* stream) {
-    if (!a || !w || !bias || !y) return fail(LIPVQ_EINVAL, "add_layernorm: null pointer");
-    if (N <= 0 || E <= 0 || E > 256) return fail(LIPVQ_EUNSUPPORTED, "add_layernorm: N=%lld E=%d (E <= 256)", (long long)N, E);
-    hipLaunchKernelGGL(add_layernorm_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, b, w, bias, eps, y,
-                       xhat, rstd, N, E);
-    return check_launch("add_layernorm");
-}
-
-// gx = rstd (g w - mean(g w) - xhat mean(g w xhat));  gw += sum_rows g xhat;  gb += sum_rows g   (gw, gb: caller zero-fills;
-// per-workgroup partial sums in LDS, then one atomic per column and workgroup)
-__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ xhat,
-                                                            const float* __restrict__ rstd, const float* __restrict__ w,
-                                                            float* __restrict__ gx, float* __restrict__ gw, float* __restrict__ gb,
-                                                            int64_t N, int E, int rows_per_block) {
-    __shared__ float s_gw[4][256], s_gb[4][256];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    float pgw[4] = {0.f, 0.f, 0.f, 0.f}, pgb[4] = {0.f, 0.f, 0.f, 0.f};
-    const int64_t rbeg = (int64_t)blockIdx.x * rows_per_block;
-    int64_t rend = rbeg + rows_per_block;
-    if (rend > N) rend = N;
-    for (int64_t row = rbeg + wv; row < rend; row += 4) {
-        float g[4], xh[4];
-        float s1 = 0.0f, s2 = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = lane + 64 * i;
-            g[i] = e < E ? gy[(size_t)row * E + e] : 0.0f;
-            xh[i] = e < E ? xhat[(size_t)row * E + e] : 0.0f;
-            pgw[i] = lq_fma(g[i], xh[i], pgw[i]);
-            pgb[i] += g[i];
-            g[i] = e < E ? g[i] * w[e] : 0.0f;
-            s1 += g[i];
-            s2 = lq_fma(g[i], xh[i], s2);
-        }
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { s1 += __shfl_xor(s1, off, 64); s2 += __shfl_xor(s2, off, 64); }
-        const float m1 = s1 / (float)E, m2 = s2 / (float)E, rs = rstd[row];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = lane + 64 * i;
-            if (e < E) gx[(size_t)row * E + e] = rs * (g[i] - m1 - xh[i] * m2);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { s_gw[wv][lane + 64 * i] = pgw[i]; s_gb[wv][lane + 64 * i] = pgb[i]; }
-    __syncthreads();
-    const int e = threadIdx.x;
-    if (e < E) {
-        atomicAdd(&gw[e], ((s_gw[0][e] + s_gw[1][e]) + s_gw[2][e]) + s_gw[3][e]);
-        atomicAdd(&gb[e], ((s_gb[0][e] + s_gb[1][e]) + s_gb[2][e]) + s_gb[3][e]);
-    }
-}
-
-extern "C" int lipvq_layernorm_bwd_f32(const float* gy, const float* xhat, const float* rstd, const float* w, float* gx, float* gw,
-                                       float* gb, int64_t N, int E, void* stream) {
-    if (!gy || !xhat || !rstd || !w || !gx || !gw || !gb) return fail(LIPVQ_EINVAL, "layernorm_bwd: null pointer");
-    if (N <= 0 || E <= 0 || E > 256) return fail(LIPVQ_EUNSUPPORTED, "layernorm_bwd: N=%lld E=%d (E <= 256)", (long long)N, E);
-    const int rpb = N >= 65536 ? 256 : (N >= 1024 ? 32 : 4);
-    hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((unsigned)((N + rpb - 1) / rpb)), dim3(256), 0, (hipStream_t)stream, gy, xhat, rstd, w,
-                       gx, gw, gb, N, E, rpb);
-    return check_launch("layernorm_bwd");
 }

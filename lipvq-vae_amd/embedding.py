@@ -25,6 +25,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .nnfn import LinearFn
+from .ops import ACT_NONE
 from .tokenizer import _PackCache
 
 __all__ = ["ICLInputEmbedding", "sinusoidal_table"]
@@ -38,25 +40,6 @@ def sinusoidal_table(T: int, E: int, device) -> torch.Tensor:
     pe[:, 0::2] = torch.sin(t * div)
     pe[:, 1::2] = torch.cos(t * div)
     return pe
-
-
-class _LinearFn(torch.autograd.Function):
-    """y = x . W^T + b on lipvq_linear_f32; backward = one more Linear (gx) + the wgrad kernel (gW, gb)."""
-
-    @staticmethod
-    def forward(ctx, x, W, b):
-        ctx.save_for_backward(x, W)
-        return ops.linear(x, W, b)
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, W = ctx.saved_tensors
-        gy = gy.contiguous()
-        gx = ops.linear(gy, W.t().contiguous()) if ctx.needs_input_grad[0] else None
-        gW = gb = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            gW, gb = ops.wgrad(gy, x)
-        return gx, gW, gb
 
 
 class _EmbedStreamsFn(torch.autograd.Function):
@@ -144,7 +127,7 @@ class ICLInputEmbedding(nn.Module):
         lin = self.nets["embed_encoder"]
         codebook = codebook.detach()                        # z_latent is detached in the reference (v5:74)
         if torch.is_grad_enabled() and (lin.weight.requires_grad or lin.bias.requires_grad):
-            return _LinearFn.apply(codebook, lin.weight, lin.bias)
+            return LinearFn.apply(codebook, lin.weight, lin.bias, ACT_NONE)
         return self._table_cache.get((codebook, lin.weight, lin.bias),
                                      lambda: ops.linear(codebook, lin.weight.detach(), lin.bias.detach()))
 
@@ -153,7 +136,7 @@ class ICLInputEmbedding(nn.Module):
         B, T, Din = x3.shape
         if Din != self.input_dim:
             raise ValueError(f"expected inputs [..., {self.input_dim}], got {tuple(x3.shape)}")
-        return _LinearFn.apply(x3.reshape(B * T, Din), lin.weight, lin.bias)
+        return LinearFn.apply(x3.reshape(B * T, Din), lin.weight, lin.bias, ACT_NONE)
 
     def _embed(self, B, T, S, slots, idxs, srcs):
         ln = self.nets["embed_ln"]

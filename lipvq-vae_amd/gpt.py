@@ -33,39 +33,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from .nnfn import AddLayerNormFn, GraphedEval, LinearFn
 from .ops import ACT_GELU, ACT_NONE
 
 __all__ = ["GPTBackbone", "GraphedGPTBackbone"]
-
-
-class _LinearFn(torch.autograd.Function):
-    """act(x W^T + b) over the last dimension, b optional; backward = act' (elementwise), one more Linear (gx), the wgrad kernel."""
-
-    @staticmethod
-    def forward(ctx, x, W, b, act):
-        ctx.act, ctx.has_bias, ctx.shape = act, b is not None, x.shape
-        x2 = x.reshape(-1, x.shape[-1])
-        if act != ACT_NONE:
-            y, pre = ops.linear(x2, W, b, act=act, save_pre=True)
-            ctx.save_for_backward(x2, W, pre)
-        else:
-            y = ops.linear(x2, W, b)
-            ctx.save_for_backward(x2, W)
-        return y.view(*x.shape[:-1], W.shape[0])
-
-    @staticmethod
-    def backward(ctx, gy):
-        gy = gy.reshape(-1, gy.shape[-1]).contiguous()
-        if ctx.act != ACT_NONE:
-            x2, W, pre = ctx.saved_tensors
-            gy = ops.act_bwd(gy, pre, ctx.act)
-        else:
-            x2, W = ctx.saved_tensors
-        gx = ops.linear(gy, W.t().contiguous()).view(ctx.shape) if ctx.needs_input_grad[0] else None
-        gW = gb = None
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            gW, gb = ops.wgrad(gy, x2, want_bias=ctx.has_bias)
-        return gx, gW, gb, None
 
 
 class _AttentionFn(torch.autograd.Function):
@@ -81,30 +52,6 @@ class _AttentionFn(torch.autograd.Function):
         qkv, out, lse = ctx.saved_tensors
         return (ops.gpt_attention_bwd(qkv, out, gout.contiguous(), lse, ctx.nhead, ctx.causal, ctx.keep, ctx.keep_prob),
                 None, None, None, None)
-
-
-class _AddLayerNormFn(torch.autograd.Function):
-    """(s, y) = (a + b, LayerNorm(a + b) w + bias), b optional; s is None unless want_s (the closing LayerNorm discards it, and
-    without b the caller keeps using a).  Backward: the gradient of a and of b is LayerNorm's plus the gradient that arrives for
-    s (the residual stream), added inside the kernel."""
-
-    @staticmethod
-    def forward(ctx, a, b, w, bias, eps, want_s):
-        ctx.set_materialize_grads(False)
-        ctx.has_b = b is not None
-        if not any(ctx.needs_input_grad):                      # eval / no_grad: nothing is kept for a backward
-            return ops.gpt_layernorm(a, b, w, bias, eps, want_s=want_s)
-        s, y, xhat, rstd = ops.gpt_layernorm(a, b, w, bias, eps, want_s=want_s, save=True)
-        ctx.save_for_backward(xhat, rstd, w)
-        return s, y
-
-    @staticmethod
-    def backward(ctx, gs, gy):
-        if gy is None:
-            return gs, (gs if ctx.has_b else None), None, None, None, None
-        xhat, rstd, w = ctx.saved_tensors
-        g, gw, gb = ops.gpt_layernorm_bwd(gy.contiguous(), xhat, rstd, w, None if gs is None else gs.contiguous())
-        return g, (g if ctx.has_b else None), gw, gb, None, None
 
 
 class _SelfAttention(nn.Module):
@@ -198,26 +145,26 @@ class GPTBackbone(nn.Module):
                 keep = (torch.rand((B, H, L, L), device=x.device) >= p_att).to(torch.uint8)
                 keep_prob = 1.0 - p_att
             if b is None:                                      # first block: the stream is the input itself, nothing to add or copy
-                s, y = a, _AddLayerNormFn.apply(a, None, ln1.weight, ln1.bias, ln1.eps, False)[1]
+                s, y = a, AddLayerNormFn.apply(a, None, ln1.weight, ln1.bias, ln1.eps, False)[1]
             else:
-                s, y = _AddLayerNormFn.apply(a, b, ln1.weight, ln1.bias, ln1.eps, True)
-            qkv = _LinearFn.apply(y, att.nets["qkv"].weight, None, ACT_NONE)
+                s, y = AddLayerNormFn.apply(a, b, ln1.weight, ln1.bias, ln1.eps, True)
+            qkv = LinearFn.apply(y, att.nets["qkv"].weight, None, ACT_NONE)
             o = _AttentionFn.apply(qkv, H, bool(self.causal), keep, keep_prob)
-            o = _LinearFn.apply(o, att.nets["output"].weight, att.nets["output"].bias, ACT_NONE)
+            o = LinearFn.apply(o, att.nets["output"].weight, att.nets["output"].bias, ACT_NONE)
             if p_out > 0.0:
                 o = F.dropout(o, p_out, True)
-            s, y = _AddLayerNormFn.apply(s, o, ln2.weight, ln2.bias, ln2.eps, True)
-            f = _LinearFn.apply(y, mlp[0].weight, mlp[0].bias, ACT_GELU)
-            f = _LinearFn.apply(f, mlp[2].weight, mlp[2].bias, ACT_NONE)
+            s, y = AddLayerNormFn.apply(s, o, ln2.weight, ln2.bias, ln2.eps, True)
+            f = LinearFn.apply(y, mlp[0].weight, mlp[0].bias, ACT_GELU)
+            f = LinearFn.apply(f, mlp[2].weight, mlp[2].bias, ACT_NONE)
             if p_mlp > 0.0:
                 f = F.dropout(f, p_mlp, True)
             a, b = s, f
         ln = self.nets["output_ln"]
-        out = _AddLayerNormFn.apply(a, b, ln.weight, ln.bias, ln.eps, False)[1]
+        out = AddLayerNormFn.apply(a, b, ln.weight, ln.bias, ln.eps, False)[1]
         return out
 
 
-class GraphedGPTBackbone:
+class GraphedGPTBackbone(GraphedEval):
     """Eval-mode forward of a GPTBackbone captured in ONE HIP graph for a fixed [B, L, E] shape.
 
     The backbone is 6 small launches per block; at the ICRT step shape (B = 8, 240 rows) each is microseconds of GPU work, so
@@ -226,25 +173,3 @@ class GraphedGPTBackbone:
     their storage, so in-place updates (optimizer steps, load_state_dict) are seen; re-capture after anything that REPLACES a
     parameter tensor (.to(), .cuda()).  The returned tensor is the graph's own output buffer: copy it before the next call if
     it must survive."""
-
-    def __init__(self, net: GPTBackbone, example_inputs: torch.Tensor):
-        if net.training:
-            raise RuntimeError("GraphedGPTBackbone captures the eval-mode forward: call net.eval() first")
-        self.net = net
-        self._x = example_inputs.detach().contiguous().float().clone()
-        side = torch.cuda.Stream(device=self._x.device)
-        side.wait_stream(torch.cuda.current_stream(self._x.device))
-        with torch.no_grad(), torch.cuda.stream(side):            # first-use work stays out of the capture
-            for _ in range(3):
-                net(self._x)
-        torch.cuda.current_stream(self._x.device).wait_stream(side)
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self._graph):
-            self._y = net(self._x)
-
-    def __call__(self, inputs: torch.Tensor) -> torch.Tensor:
-        if inputs.shape != self._x.shape:
-            raise ValueError(f"captured for {tuple(self._x.shape)}, got {tuple(inputs.shape)}")
-        self._x.copy_(inputs)
-        self._graph.replay()
-        return self._y

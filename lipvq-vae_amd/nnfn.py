@@ -1,0 +1,93 @@
+"""What the transformer-style modules (embedding.py, default_branch.py, gpt.py) share: Linear and residual + LayerNorm as
+``torch.autograd.Function``s over the library's kernels, and the eval-forward HIP-graph wrapper."""
+from __future__ import annotations
+
+import torch
+
+from . import ops
+from .ops import ACT_NONE
+
+__all__ = ["LinearFn", "AddLayerNormFn", "GraphedEval"]
+
+
+class LinearFn(torch.autograd.Function):
+    """act(x W^T + b) over the last dimension, b optional; backward = act' (elementwise), one more Linear (gx), the wgrad kernel."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, act):
+        ctx.act, ctx.has_bias, ctx.shape = act, b is not None, x.shape
+        x2 = x if x.dim() == 2 else x.reshape(-1, x.shape[-1])      # (2-D callers: no view objects on their host-bound paths)
+        if act != ACT_NONE:
+            y, pre = ops.linear(x2, W, b, act=act, save_pre=True)
+            ctx.save_for_backward(x2, W, pre)
+        else:
+            y = ops.linear(x2, W, b)
+            ctx.save_for_backward(x2, W)
+        return y if x.dim() == 2 else y.view(*x.shape[:-1], W.shape[0])
+
+    @staticmethod
+    def backward(ctx, gy):
+        gy = gy.reshape(-1, gy.shape[-1]).contiguous()
+        if ctx.act != ACT_NONE:
+            x2, W, pre = ctx.saved_tensors
+            gy = ops.act_bwd(gy, pre, ctx.act)
+        else:
+            x2, W = ctx.saved_tensors
+        gx = ops.linear(gy, W.t().contiguous()).view(ctx.shape) if ctx.needs_input_grad[0] else None
+        gW = gb = None
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            gW, gb = ops.wgrad(gy, x2, want_bias=ctx.has_bias)
+        return gx, gW, gb, None
+
+
+class AddLayerNormFn(torch.autograd.Function):
+    """(s, y) = (a + b, LayerNorm(a + b) w + bias), b optional; s is None unless want_s (a post-norm residual and the closing
+    LayerNorm of a pre-norm stack discard it, and without b the caller keeps using a).  Backward: the gradient of a and of b is
+    LayerNorm's plus the gradient that arrives for s (the residual stream), added inside the kernel."""
+
+    @staticmethod
+    def forward(ctx, a, b, w, bias, eps, want_s):
+        ctx.set_materialize_grads(False)
+        ctx.has_b = b is not None
+        if not any(ctx.needs_input_grad):                      # eval / no_grad: nothing is kept for a backward
+            return ops.gpt_layernorm(a, b, w, bias, eps, want_s=want_s)
+        s, y, xhat, rstd = ops.gpt_layernorm(a, b, w, bias, eps, want_s=want_s, save=True)
+        ctx.save_for_backward(xhat, rstd, w)
+        return s, y
+
+    @staticmethod
+    def backward(ctx, gs, gy):
+        if gy is None:
+            return gs, (gs if ctx.has_b else None), None, None, None, None
+        xhat, rstd, w = ctx.saved_tensors
+        g, gw, gb = ops.gpt_layernorm_bwd(gy.contiguous(), xhat, rstd, w, None if gs is None else gs.contiguous())
+        return g, (g if ctx.has_b else None), gw, gb, None, None
+
+
+class GraphedEval:
+    """Eval-mode forward of ``net`` captured in ONE HIP graph for the shape of ``example``.  Parameters are read at replay time
+    through their storage, so in-place updates (optimizer steps, load_state_dict) are seen; re-capture after anything that
+    REPLACES a parameter tensor (.to(), .cuda()).  The returned tensor is the graph's own output buffer: copy it before the next
+    call if it must survive."""
+
+    def __init__(self, net: torch.nn.Module, example: torch.Tensor, /):
+        if net.training:
+            raise RuntimeError(f"{type(self).__name__} captures the eval-mode forward: call net.eval() first")
+        self.net = net
+        self._x = example.detach().contiguous().float().clone()
+        side = torch.cuda.Stream(device=self._x.device)
+        side.wait_stream(torch.cuda.current_stream(self._x.device))
+        with torch.no_grad(), torch.cuda.stream(side):            # first-use work (LDS reservations, lazy module state) stays out of the capture
+            for _ in range(3):
+                net(self._x)
+        torch.cuda.current_stream(self._x.device).wait_stream(side)
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(self._graph):
+            self._y = net(self._x)
+
+    def __call__(self, inputs: torch.Tensor, /) -> torch.Tensor:
+        if inputs.shape != self._x.shape:
+            raise ValueError(f"captured for {tuple(self._x.shape)}, got {tuple(inputs.shape)}")
+        self._x.copy_(inputs)
+        self._graph.replay()
+        return self._y

@@ -982,35 +982,6 @@ def attention_bwd(qkv, out, gout, lse, nhead: int, keep=None, keep_prob: float =
     return gqkv
 
 
-def add_layernorm(a, b, w, bias, eps: float, save: bool = False):
-    """LayerNorm(a + b) * w + bias over the last dimension (b may be None); save=True also returns (xhat, rstd)."""
-    a = _chk(a, "a")
-    if b is not None:
-        b = _chk(b, "b")
-        if b.shape != a.shape:
-            raise ValueError("add_layernorm: shapes differ")
-    N, E = a.shape
-    y = torch.empty_like(a)
-    xhat = torch.empty_like(a) if save else None
-    rstd = torch.empty(N, device=a.device, dtype=torch.float32) if save else None
-    with _on(a.device):
-        check(lib.lipvq_add_layernorm_f32(_ptr(a), _ptr(b), _ptr(_chk(w, "w")), _ptr(_chk(bias, "bias")), float(eps), _ptr(y),
-                                          _ptr(xhat), _ptr(rstd), N, E, _stream()), "lipvq_add_layernorm_f32")
-    return (y, xhat, rstd) if save else y
-
-
-def layernorm_bwd(gy, xhat, rstd, w):
-    gy, xhat = _chk(gy, "gy"), _chk(xhat, "xhat")
-    N, E = gy.shape
-    gx = torch.empty_like(gy)
-    gw = torch.zeros(E, device=gy.device, dtype=torch.float32)
-    gb = torch.zeros(E, device=gy.device, dtype=torch.float32)
-    with _on(gy.device):
-        check(lib.lipvq_layernorm_bwd_f32(_ptr(gy), _ptr(xhat), _ptr(_chk(rstd, "rstd")), _ptr(_chk(w, "w")), _ptr(gx), _ptr(gw),
-                                          _ptr(gb), N, E, _stream()), "lipvq_layernorm_bwd_f32")
-    return gx, gw, gb
-
-
 # ---------------------------------------------------------------------------------------------------
 # the transformer backbone (csrc/lipvq_gpt.hip; reference robomimic/models/transformers.py:80-439)
 # ---------------------------------------------------------------------------------------------------

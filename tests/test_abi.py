@@ -37,6 +37,9 @@ def test_ctypes_table_matches_header():
     import lipvq_vae_amd
     from lipvq_vae_amd import _capi
     assert sorted(_capi.SIGNATURES) == _declared()
+    # retired with the default branch's own LayerNorm kernels (it runs the lipvq_gpt_layernorm_* entry points)
+    for gone in ("lipvq_add_layernorm_f32", "lipvq_layernorm_bwd_f32"):
+        assert gone not in _capi.SIGNATURES and not hasattr(_capi.lib, gone)
     # pure host-side entry points are callable without a GPU
     assert _capi.lib.lipvq_mlp3_packed_floats(7, 64, 128, 64) == (2 * 4 * 64 + 64) + (4 * 32 * 64 + 128) + (2 * 64 * 64 + 64)
     assert _capi.lib.lipvq_mse_workspace_bytes() > 0

@@ -94,10 +94,12 @@ def test_add_layernorm_forward_backward(ops, N, E, with_b):
     ad, bd, wd, biasd = (t.double().requires_grad_(True) for t in (a, b, w, bias))
     ref = F.layer_norm(ad + bd if with_b else ad, (E,), wd, biasd, 1e-5)
     (ref * gy.double()).sum().backward()
-    y, xhat, rstd = ops.add_layernorm(a.cuda(), b.cuda() if with_b else None, w.cuda(), bias.cuda(), 1e-5, save=True)
-    assert _rel(y.cpu(), ref.detach()) <= 1e-5
-    gx, gw, gb = ops.layernorm_bwd(gy.cuda(), xhat, rstd, w.cuda())
+    s, y, xhat, rstd = ops.gpt_layernorm(a.cuda(), b.cuda() if with_b else None, w.cuda(), bias.cuda(), 1e-5, want_s=False, save=True)
+    assert s is None and _rel(y.cpu(), ref.detach()) <= 1e-5
+    gx, gw, gb = ops.gpt_layernorm_bwd(gy.cuda(), xhat, rstd, w.cuda(), gres=None)
     assert _rel(gx.cpu(), ad.grad) <= 1e-4 and _rel(gw.cpu(), wd.grad) <= 1e-4 and _rel(gb.cpu(), biasd.grad) <= 1e-4
+    _, gw2, gb2 = ops.gpt_layernorm_bwd(gy.cuda(), xhat, rstd, w.cuda(), gres=None)
+    assert torch.equal(gw2, gw) and torch.equal(gb2, gb)    # no atomics: the parameter gradients repeat bit for bit
 
 
 def _module(golden_dir, name):
