@@ -478,6 +478,47 @@ size_t lipvq_gpt_layernorm_bwd_workspace_bytes(int64_t N, int E);
 int lipvq_gpt_layernorm_bwd_f32(const float* gy, const float* xhat, const float* rstd, const float* w, const float* gres,
                                 float* gs, float* gw, float* gb, void* workspace, int64_t N, int E, void* stream);
 
+/* ---- the policy's GMM output head (pn = robomimic/models/policy_nets.py; ob:747-771 ObservationDecoder's three Linears
+ *      mean | scale | logits, pn:2545-2575 tanh / softplus + min_std / MixtureSameFamily, icl.py:947 log_prob, icl.py:966 the NLL,
+ *      pn:2599 sample).  lipvq-vae_amd/csrc/lipvq_gmm.hip, lipvq-vae_amd/gmm.py.
+ *      M = num_modes (1..16), A = ac_dim (1..64), P = M (2 A + 1) <= 512 columns mean [M][A] | scale [M][A] | logits [M];
+ *      E % 4 == 0, E <= 1024; outside these limits: LIPVQ_EUNSUPPORTED.  Row n = (b, t) = (n / T, n % T) of the input is read at
+ *      x + b bstride + t E floats (bstride % 4 == 0, x 16-byte aligned): the last T positions of a [B][3T][E] backbone output are
+ *      x = out + 2 T E, bstride = 3 T E; a dense [N][E] input is T = N.  N == 0: no-op. ---- */
+enum { LIPVQ_GMM_SOFTPLUS = 0, LIPVQ_GMM_EXP = 1, LIPVQ_GMM_LOW_NOISE = 2 };
+
+/* One launch: pre = x W^T + b for the three Linears (Wm, Ws [M A][E], Wl [M][E]; the k-ordered fp32 chain of
+ * lipvq_linear_act_f32, started from the bias), then per mode m and component a
+ *     mu = tanh(pre_mean),  sigma = softplus(pre_scale) + min_std  (F.softplus: beta 1, identity above 20; LIPVQ_GMM_EXP:
+ *     exp(pre_scale) + min_std; LIPVQ_GMM_LOW_NOISE: 1e-4, pn:2557),  l_m = sum_a [-(x_a - mu)^2 / (2 sigma^2) - log sigma - log(2 pi)/2],
+ *     log_prob = logsumexp_m(log_softmax(logits)_m + l_m)          (both max-subtracted)
+ * Every output may be NULL (not computed / not stored): log_prob [N] (needs actions [N][A]); pre [N][P] (kept for the backward);
+ * mean [N][M][A], scale [N][M][A], logits [N][M] (raw) for a distribution object; lp_sum [1] = sum_n log_prob[n], formed from
+ * per-workgroup partial sums in `workspace` (lipvq_gmm_workspace_bytes(N) bytes, any contents) by a second, one-workgroup launch
+ * in a fixed order: no float atomics, the same bits on every run. */
+size_t lipvq_gmm_workspace_bytes(int64_t N);
+int lipvq_gmm_head_f32(const float* x, int64_t bstride, const float* Wm, const float* bm, const float* Ws, const float* bs,
+                       const float* Wl, const float* bl, const float* actions, float* log_prob, float* pre, float* mean,
+                       float* scale, float* logits, float* lp_sum, void* workspace, int64_t N, int T, int E, int M, int A,
+                       int scale_mode, float min_std, void* stream);
+/* Its backward, one launch, no atomics: gpre [N][P] from the saved pre, the actions and the rows' upstream gradient
+ * g[n] + gsum[0] (g [N] = gradient of log_prob, gsum [1] = gradient of lp_sum; either may be NULL, not both).  With the
+ * responsibilities r_m = softmax_m(log pi_m + l_m):  d/dlogit_m = g (r_m - pi_m),  d/dpre_mean = g r_m (x - mu) / sigma^2 (1 - mu^2),
+ * d/dpre_scale = g r_m ((x - mu)^2 / sigma^3 - 1 / sigma) sigma'  (sigma' = sigmoid(p), 1 above 20; exp(p); 0 in low-noise mode).
+ * The Linear gradients are lipvq_wgrad_f32 (G = gpre) and lipvq_linear_act_f32 (gpre times the stacked weights). */
+int lipvq_gmm_head_bwd_f32(const float* pre, const float* actions, const float* g, const float* gsum, float* gpre, int64_t N,
+                           int M, int A, int scale_mode, float min_std, void* stream);
+/* Backward of the mean / scale / logits outputs: gpre [N][P] = gmean (1 - tanh(pre)^2) | gscale sigma' | glogits (a NULL
+ * gradient counts as zeros). */
+int lipvq_gmm_params_bwd_f32(const float* pre, const float* gmean, const float* gscale, const float* glogits, float* gpre,
+                             int64_t N, int M, int A, int scale_mode, void* stream);
+/* pn:2599 .sample() in one launch (the forward's product and tile, another epilogue): the mode of row n is the first m with
+ * u[n] < sum_{j <= m} softmax(logits)_j (the last mode if rounding leaves none), action [N][A] = mu_m + sigma_m eps[n][a].
+ * u [N] uniform in [0, 1), eps [N][A] standard normal; no [N][M][A] tensor is formed. */
+int lipvq_gmm_sample_f32(const float* x, int64_t bstride, const float* Wm, const float* bm, const float* Ws, const float* bs,
+                         const float* Wl, const float* bl, const float* u, const float* eps, float* action, int64_t N, int T,
+                         int E, int M, int A, int scale_mode, float min_std, void* stream);
+
 /* icl.py:885-889, :970  optim.AdamW(vq_vae_model.parameters(), lr=1e-3, weight_decay=1e-4).step() for a LIST of tensors in
  * two launches (torch's foreach form is 8-10): params / grads / exp_avg / exp_avg_sq / steps are HOST arrays of `count`
  * DEVICE pointers (count <= 32), numels their element counts; steps[i] is a float32 device scalar (torch's capturable layout),

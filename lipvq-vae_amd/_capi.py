@@ -107,6 +107,11 @@ SIGNATURES = {
     "lipvq_gpt_layernorm_f32": (_i, [_vp] * 4 + [C.c_float] + [_vp] * 4 + [_i64, _i, _vp]),
     "lipvq_gpt_layernorm_bwd_workspace_bytes": (_sz, [_i64, _i]),
     "lipvq_gpt_layernorm_bwd_f32": (_i, [_vp] * 9 + [_i64, _i, _vp]),
+    "lipvq_gmm_workspace_bytes": (_sz, [_i64]),
+    "lipvq_gmm_head_f32": (_i, [_vp, _i64] + [_vp] * 14 + [_i64] + [_i] * 5 + [C.c_float, _vp]),
+    "lipvq_gmm_head_bwd_f32": (_i, [_vp] * 5 + [_i64, _i, _i, _i, C.c_float, _vp]),
+    "lipvq_gmm_params_bwd_f32": (_i, [_vp] * 5 + [_i64, _i, _i, _i, _vp]),
+    "lipvq_gmm_sample_f32": (_i, [_vp, _i64] + [_vp] * 9 + [_i64] + [_i] * 5 + [C.c_float, _vp]),
     "lipvq_adamw_workspace_bytes": (_sz, []),
     "lipvq_adamw_f32": (_i, [_vp] * 6 + [_i] + [C.c_double] * 5 + [_vp, _vp]),
     "lipvq_ema_update_f32": (_i, [_vp] * 5 + [C.c_float, C.c_float, _i, _i, _vp, _vp]),

@@ -1061,3 +1061,129 @@ def gpt_layernorm_bwd(gy, xhat, rstd, w, gres=None):
         check(lib.lipvq_gpt_layernorm_bwd_f32(_ptr(gy), _ptr(xhat), _ptr(_chk(rstd, "rstd")), _ptr(_chk(w, "w")), _ptr(gres), _ptr(gs),
                                               _ptr(gw), _ptr(gb), _ptr(ws), N, E, _stream()), "lipvq_gpt_layernorm_bwd_f32")
     return gs, gw, gb
+
+
+# ---------------------------------------------------------------------------------------------------
+# the policy's GMM output head (csrc/lipvq_gmm.hip)
+# ---------------------------------------------------------------------------------------------------
+
+GMM_SOFTPLUS, GMM_EXP, GMM_LOW_NOISE = 0, 1, 2
+
+
+def _gmm_rows(feats):
+    """feats [B, T, E] (or [N, E]) -> (tensor, N, T, E, bstride): the tensor's own strides where the kernel can read them -- rows
+    of E contiguous floats, T consecutive rows per batch entry, a batch stride that is a multiple of 4 floats, as for the view
+    out[:, -T:] of a backbone output -- and a contiguous copy otherwise."""
+    if not isinstance(feats, torch.Tensor):
+        raise TypeError(f"feats: expected a tensor, got {type(feats).__name__}")
+    if not feats.is_cuda:
+        raise RuntimeError(f"feats: the GMM head runs on the HIP library only (got a {feats.device} tensor)")
+    if feats.dtype != torch.float32:
+        raise TypeError(f"feats: expected torch.float32, got {feats.dtype}")
+    if feats.dim() == 2:
+        feats = feats.unsqueeze(0)
+    if feats.dim() != 3:
+        raise ValueError(f"feats: expected [B, T, E], got {tuple(feats.shape)}")
+    B, T, E = feats.shape
+    if B * T == 0:
+        return feats, 0, max(T, 1), E, 0
+    ok = feats.stride(2) == 1 and (T == 1 or feats.stride(1) == E) and (B == 1 or feats.stride(0) % 4 == 0) and feats.data_ptr() % 16 == 0
+    if not ok:
+        feats = feats.contiguous()
+    return feats, B * T, T, E, (feats.stride(0) if B > 1 else T * E)
+
+
+def _gmm_params(params, M, A, E):
+    Wm, bm, Ws, bs, Wl, bl = (_chk(p, "gmm parameter") for p in params)
+    if Wm.shape != (M * A, E) or Ws.shape != (M * A, E) or Wl.shape != (M, E) or bm.shape != (M * A,) or bs.shape != (M * A,) or bl.shape != (M,):
+        raise ValueError(f"gmm head: parameter shapes do not match M={M} A={A} E={E}")
+    return Wm, bm, Ws, bs, Wl, bl
+
+
+def gmm_head(feats, params, M: int, A: int, actions=None, scale_mode: int = GMM_SOFTPLUS, min_std: float = 0.01,
+             want_pre: bool = False, want_params: bool = False, want_sum: bool = False):
+    """The GMM head in one launch (lipvq_gmm_head_f32).  feats [B, T, E] (its strides are passed on, see _gmm_rows); params =
+    (mean.weight, mean.bias, scale.weight, scale.bias, logits.weight, logits.bias); actions [B, T, A] or None.
+    Returns a dict with the outputs asked for: log_prob [N] (with actions), pre [N, P] (want_pre), mean / scale [N, M, A] and
+    logits [N, M] (want_params), sum [] (want_sum: the deterministic sum of log_prob)."""
+    feats, N, T, E, bstride = _gmm_rows(feats)
+    Wm, bm, Ws, bs, Wl, bl = _gmm_params(params, M, A, E)
+    dev = feats.device
+    P = M * (2 * A + 1)
+    out = {}
+    if actions is not None:
+        actions = _chk(actions, "actions")
+        if actions.numel() != N * A:
+            raise ValueError(f"gmm_head: actions {tuple(actions.shape)} do not match {N} rows of {A}")
+        out["log_prob"] = torch.empty(N, device=dev, dtype=torch.float32)
+    elif want_sum:
+        raise ValueError("gmm_head: the sum of log_prob needs actions")
+    if want_pre:
+        out["pre"] = torch.empty((N, P), device=dev, dtype=torch.float32)
+    if want_params:
+        out["mean"] = torch.empty((N, M, A), device=dev, dtype=torch.float32)
+        out["scale"] = torch.empty((N, M, A), device=dev, dtype=torch.float32)
+        out["logits"] = torch.empty((N, M), device=dev, dtype=torch.float32)
+    ws = None
+    if want_sum:
+        out["sum"] = torch.empty((), device=dev, dtype=torch.float32)
+        ws = torch.empty(max(1, lib.lipvq_gmm_workspace_bytes(N)), device=dev, dtype=torch.uint8)
+    with _on(dev):
+        check(lib.lipvq_gmm_head_f32(_ptr(feats), bstride, _ptr(Wm), _ptr(bm), _ptr(Ws), _ptr(bs), _ptr(Wl), _ptr(bl), _ptr(actions),
+                                     _ptr(out.get("log_prob")), _ptr(out.get("pre")), _ptr(out.get("mean")), _ptr(out.get("scale")),
+                                     _ptr(out.get("logits")), _ptr(out.get("sum")), _ptr(ws), N, T, E, int(M), int(A), int(scale_mode),
+                                     float(min_std), _stream()), "lipvq_gmm_head_f32")
+    return out
+
+
+def gmm_head_bwd(pre, actions, g, gsum, M: int, A: int, scale_mode: int = GMM_SOFTPLUS, min_std: float = 0.01):
+    """gpre [N, P] (lipvq_gmm_head_bwd_f32): g [N] = gradient of log_prob, gsum [] = gradient of the sum; either may be None."""
+    pre, actions = _chk(pre, "pre"), _chk(actions, "actions")
+    N, P = pre.shape
+    if P != M * (2 * A + 1) or actions.numel() != N * A:
+        raise ValueError("gmm_head_bwd: shapes do not match")
+    if g is None and gsum is None:
+        raise ValueError("gmm_head_bwd: no upstream gradient")
+    if g is not None:
+        g = _chk(g, "g")
+        if g.numel() != N:
+            raise ValueError("gmm_head_bwd: g must have one entry per row")
+    if gsum is not None:
+        gsum = _chk(gsum, "gsum")
+    gpre = torch.empty_like(pre)
+    with _on(pre.device):
+        check(lib.lipvq_gmm_head_bwd_f32(_ptr(pre), _ptr(actions), _ptr(g), _ptr(gsum), _ptr(gpre), N, int(M), int(A), int(scale_mode),
+                                         float(min_std), _stream()), "lipvq_gmm_head_bwd_f32")
+    return gpre
+
+
+def gmm_params_bwd(pre, gmean, gscale, glogits, M: int, A: int, scale_mode: int = GMM_SOFTPLUS):
+    """gpre [N, P] from the gradients of the head's mean / scale / logits outputs (lipvq_gmm_params_bwd_f32); None = zeros."""
+    pre = _chk(pre, "pre")
+    N, P = pre.shape
+    if P != M * (2 * A + 1):
+        raise ValueError("gmm_params_bwd: shapes do not match")
+    gmean, gscale, glogits = (None if t is None else _chk(t, "gradient") for t in (gmean, gscale, glogits))
+    for t, n in ((gmean, N * M * A), (gscale, N * M * A), (glogits, N * M)):
+        if t is not None and t.numel() != n:
+            raise ValueError("gmm_params_bwd: gradient shape")
+    gpre = torch.empty_like(pre)
+    with _on(pre.device):
+        check(lib.lipvq_gmm_params_bwd_f32(_ptr(pre), _ptr(gmean), _ptr(gscale), _ptr(glogits), _ptr(gpre), N, int(M), int(A),
+                                           int(scale_mode), _stream()), "lipvq_gmm_params_bwd_f32")
+    return gpre
+
+
+def gmm_sample(feats, params, M: int, A: int, u, eps, scale_mode: int = GMM_SOFTPLUS, min_std: float = 0.01):
+    """action [N, A] = mu_m + sigma_m eps with m drawn by inverse CDF from u (lipvq_gmm_sample_f32), one launch."""
+    feats, N, T, E, bstride = _gmm_rows(feats)
+    Wm, bm, Ws, bs, Wl, bl = _gmm_params(params, M, A, E)
+    u, eps = _chk(u, "u"), _chk(eps, "eps")
+    if u.numel() != N or eps.numel() != N * A:
+        raise ValueError(f"gmm_sample: u {tuple(u.shape)} / eps {tuple(eps.shape)} do not match {N} rows of {A}")
+    action = torch.empty((N, A), device=feats.device, dtype=torch.float32)
+    with _on(feats.device):
+        check(lib.lipvq_gmm_sample_f32(_ptr(feats), bstride, _ptr(Wm), _ptr(bm), _ptr(Ws), _ptr(bs), _ptr(Wl), _ptr(bl), _ptr(u), _ptr(eps),
+                                       _ptr(action), N, T, E, int(M), int(A), int(scale_mode), float(min_std), _stream()),
+              "lipvq_gmm_sample_f32")
+    return action
