@@ -331,7 +331,7 @@ extern "C" int lipvq_gpt_attention_bwd_f32(const float* qkv, const float* out, c
 
 // ---------------------------------------------------------------------------------------------------
 // s = a + b;  y = LayerNorm(s) * w + bias over rows of E <= 1024 floats, E % 4 == 0: one wave per row, up to four float4 per
-// lane, two-pass moments in registers.  With s_out == NULL this is the post-norm residual of the default action branch.
+// lane, two-pass moments in registers (the mean in two steps, see the kernel).  With s_out == NULL this is the post-norm residual of the default action branch.
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gpt_layernorm_kernel(const float4* __restrict__ a, const float4* __restrict__ b,
                                                             const float4* __restrict__ w, const float4* __restrict__ bias, float eps,
@@ -356,12 +356,26 @@ __global__ __launch_bounds__(256) void gpt_layernorm_kernel(const float4* __rest
     }
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off, 64);
+    // Centre twice.  The fp32 sum of a row around 1000 is off by ulps of E * 1000, its mean by ~1e-4: as large as the row's own
+    // spread allows unnoticed.  x - mean is exact for values within a factor 2 of the mean, so the mean of the centred values is
+    // that error, to fp32 accuracy at ITS size, and comes off too (0 for a row the first mean already centres).
     const float mean = s / (float)E;
-    float v = 0.0f;
+    float r = 0.0f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         if (lane + 64 * i < E4) {
             x[i].x -= mean; x[i].y -= mean; x[i].z -= mean; x[i].w -= mean;
+            r += (x[i].x + x[i].y) + (x[i].z + x[i].w);
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) r += __shfl_xor(r, off, 64);
+    const float rest = r / (float)E;
+    float v = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (lane + 64 * i < E4) {
+            x[i].x -= rest; x[i].y -= rest; x[i].z -= rest; x[i].w -= rest;
             v = lq_fma(x[i].x, x[i].x, v); v = lq_fma(x[i].y, x[i].y, v); v = lq_fma(x[i].z, x[i].z, v); v = lq_fma(x[i].w, x[i].w, v);
         }
     }

@@ -118,6 +118,8 @@ extern "C" int lipvq_spectral_norm_bwd_f32(const float* gWsn, const float* Wsn, 
 // 64-key LDS tile, keeps an online softmax (m, l, acc[dh]); the 16 partials are merged by xor-shuffles at the end.
 // keep [H][S][S] bytes (1 = keep) + inv_keep = 1 / (1 - p): the attention-probability dropout of nn.MultiheadAttention in
 // training mode (NULL in eval); the normaliser uses every key, the value sum only the kept ones.
+// A score is a float64 fma chain and stays float64 until its maximum is subtracted: an fp32 chain is off by ~1e-4 at |s| ~ 500
+// (q, k sixteen times unit-normal), which moves the weights of two nearly tied keys by as much; exp, l and the value sum are fp32.
 // ---------------------------------------------------------------------------------------------------
 #define XF_DH 32
 #define XF_QB 16
@@ -141,13 +143,15 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
     const int q = blockIdx.x * XF_QB + qi;
     const int qc = q < S ? q : S - 1;
     const float scale = 1.0f / lq_sqrt((float)dh);
-    float qr[DH], acc[DH];
+    double qr[DH];
+    float acc[DH];
 #pragma unroll
     for (int d = 0; d < DH; ++d) {
-        qr[d] = d < dh ? qkv[(size_t)qc * 3 * D + h * dh + d] * scale : 0.0f;
+        qr[d] = d < dh ? (double)qkv[(size_t)qc * 3 * D + h * dh + d] * scale : 0.0;
         acc[d] = 0.0f;
     }
-    float m = -INFINITY, l = 0.0f;
+    double m = -INFINITY;
+    float l = 0.0f;
     for (int k0 = 0; k0 < S; k0 += XF_KT) {
         __syncthreads();
         for (int i = tid; i < XF_KT * DH; i += 256) {
@@ -161,12 +165,12 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
         for (int jj = 0; jj < XF_KT / 16; ++jj) {
             const int j = p + 16 * jj;
             if (k0 + j < S) {
-                float s = 0.0f;
+                double s = 0.0;
 #pragma unroll
                 for (int d = 0; d < DH; ++d)
-                    s = lq_fma(qr[d], sk[j][d], s);
-                const float mn = fmaxf(m, s);
-                const float c = xf_exp(m - mn), e = xf_exp(s - mn);
+                    s = fma(qr[d], (double)sk[j][d], s);
+                const double mn = fmax(m, s);
+                const float c = xf_exp((float)(m - mn)), e = xf_exp((float)(s - mn));
                 l = lq_fma(l, c, e);
                 const float w = keep ? (keep[((size_t)h * S + qc) * S + k0 + j] ? e * inv_keep : 0.0f) : e;
 #pragma unroll
@@ -177,10 +181,10 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
         }
     }
     // merge the 16 key lanes of the query (lanes qi*16 .. qi*16+15 of the workgroup: 16 consecutive lanes of one wave)
-    float mall = m;
+    double mall = m;
 #pragma unroll
-    for (int off = 1; off < 16; off <<= 1) mall = fmaxf(mall, __shfl_xor(mall, off, 64));
-    const float c = (m == -INFINITY) ? 0.0f : xf_exp(m - mall);
+    for (int off = 1; off < 16; off <<= 1) mall = fmax(mall, __shfl_xor(mall, off, 64));
+    const float c = (m == -INFINITY) ? 0.0f : xf_exp((float)(m - mall));
     l *= c;
 #pragma unroll
     for (int off = 1; off < 16; off <<= 1) l += __shfl_xor(l, off, 64);
@@ -194,7 +198,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
     if (q < S) {
         const float inv = 1.0f / l;
         for (int d = p; d < dh; d += 16) out[(size_t)q * D + h * dh + d] = acc[d] * inv;       // (acc[d] is the same in all 16 lanes)
-        if (p == 0) lse[(size_t)h * S + q] = mall + __logf(l);
+        if (p == 0) lse[(size_t)h * S + q] = (float)(mall + (double)__logf(l));
     }
 }
 
@@ -248,11 +252,12 @@ __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const float* __res
         for (int jj = 0; jj < XF_KT / 16; ++jj) {
             const int j = p + 16 * jj;
             if (k0 + j < S) {
-                float s = 0.0f, dp = 0.0f;
+                double s = 0.0;
+                float dp = 0.0f;
 #pragma unroll
                 for (int d = 0; d < DH; ++d)
-                    { s = lq_fma(qr[d], sk[j][d], s); dp = lq_fma(gor[d], svv[j][d], dp); }
-                const float pr = xf_exp(s - ls);
+                    { s = fma((double)qr[d], (double)sk[j][d], s); dp = lq_fma(gor[d], svv[j][d], dp); }
+                const float pr = xf_exp((float)(s - (double)ls));
                 if (keep) dp = keep[((size_t)h * S + qc) * S + k0 + j] ? dp * inv_keep : 0.0f;
                 const float ds = pr * (dp - dl) * scale;
 #pragma unroll
@@ -309,11 +314,12 @@ __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const float* __re
         for (int jj = 0; jj < XF_KT / 16; ++jj) {
             const int j = p + 16 * jj;
             if (q0 + j < S) {
-                float s = 0.0f, dp = 0.0f;
+                double s = 0.0;
+                float dp = 0.0f;
 #pragma unroll
                 for (int d = 0; d < DH; ++d)
-                    { s = lq_fma(sq[j][d], kr[d], s); dp = lq_fma(sg[j][d], vr[d], dp); }
-                const float pr = xf_exp(s - sl[j]);
+                    { s = fma((double)sq[j][d], (double)kr[d], s); dp = lq_fma(sg[j][d], vr[d], dp); }
+                const float pr = xf_exp((float)(s - (double)sl[j]));
                 float kp = 1.0f;
                 if (keep) kp = keep[((size_t)h * S + q0 + j) * S + kc] ? inv_keep : 0.0f;
                 const float ds = pr * (dp * kp - sd[j]);          // (the forward's q was pre-scaled: dK_j = sum_i dS_ij (scale Q_i))

@@ -7,6 +7,7 @@ same op (tests/gpt_ref.py on .double() tensors), with the bounds tests/test_gpu_
 Whole module: GPTBackbone against the float64 columns of tests/golden/gpt_*.npz.  The bound is the larger of the per-kernel
 tolerance and 4 x the fp32 reference's own deviation from float64 stored in that fixture (a different but equally accurate
 summation order and erf over 6 x 4 GEMMs); every figure is printed before it is asserted.  This file reads tests/golden only.
+Every kernel input here is torch.randn; the non-random inputs, tile edges and fenced outputs are tests/test_gpu_xf_edges.py.
 """
 import numpy as np
 import pytest
