@@ -478,6 +478,34 @@ size_t lipvq_gpt_layernorm_bwd_workspace_bytes(int64_t N, int E);
 int lipvq_gpt_layernorm_bwd_f32(const float* gy, const float* xhat, const float* rstd, const float* w, const float* gres,
                                 float* gs, float* gw, float* gb, void* workspace, int64_t N, int E, void* stream);
 
+/* ---- the backbone's opt-in bf16 matrix-pipe mode (GPTBackbone.set_matmul_precision("bf16")): the three products of one
+ *      nn.Linear on the bf16 MFMAs.  lipvq-vae_amd/csrc/lipvq_gemm_bf16.hip.
+ *      Rounding rule: every tensor is fp32 in memory, as for the _f32 entry points; each element of the two MATRIX operands of
+ *      a product is rounded to bf16 with round-to-nearest-even as it is read (nothing is truncated, nothing is stored as bf16).
+ *      Accumulation: the bf16 x bf16 products are exact in fp32 and are accumulated in fp32 (v_mfma_f32_32x32x16_bf16); bias,
+ *      activation, the sums over row chunks and the bias gradient are fp32 and never see a rounded operand.
+ *      Determinism: no float atomics; the summation order depends on the shape alone, never on the device, its CU count or
+ *      the launch's timing, so repeated calls give bit-identical results.
+ *      Shapes: any N >= 0 (N == 0: no-op, returns 0); both Linear widths must be multiples of 8, else LIPVQ_EUNSUPPORTED.
+ *      Input tensors (and the workspace) 16-byte aligned, else LIPVQ_EINVAL; outputs need no alignment.  Sizes are checked
+ *      before pointers, pointers before any launch. ---- */
+
+/* y [N][E] = act(x [N][Kin] . W [E][Kin]^T + b): lipvq_linear_act_f32 in the bf16 mode.  b may be NULL; pre (may be NULL)
+ * receives the fp32 pre-activation; the activation is the fp32 function lipvq_linear_act_f32 applies (for GELU: the one whose
+ * derivative lipvq_act_bwd_f32 evaluates at pre). */
+int lipvq_linear_act_bf16(const float* x, const float* W, const float* b, float* y, float* pre, int64_t N, int Kin, int E,
+                          int act, void* stream);
+/* gx [N][K] = g [N][J] . W [J][K]: the input gradient of the Linear above with W read AS STORED (no transposed copy). */
+int lipvq_linear_nn_bf16(const float* g, const float* W, float* gx, int64_t N, int J, int K, void* stream);
+/* gW [J][K] = G [N][J]^T . H [N][K] (both rounded to bf16), gb [J] (may be NULL) = column sums of the UNROUNDED fp32 G.
+ * The N rows are cut into chunks of
+ *     chunk = max(64, 32 ceil(ceil(N / want) / 32)) rows,  want = max(1, floor(1024 / (ceil(J / 128) ceil(K / 128)))),
+ * one launch writes every chunk's partial gW and gb into the workspace and a second adds them in chunk order;
+ * lipvq_wgrad_bf16_workspace_bytes = ceil(N / chunk) (J K + J) 4 bytes (0 for N <= 0), a function of (N, J, K) only. */
+size_t lipvq_wgrad_bf16_workspace_bytes(int64_t N, int J, int K);
+int lipvq_wgrad_bf16(const float* G, const float* H, float* gW, float* gb, void* workspace, int64_t N, int J, int K,
+                     void* stream);
+
 /* ---- the policy's GMM output head (pn = robomimic/models/policy_nets.py; ob:747-771 ObservationDecoder's three Linears
  *      mean | scale | logits, pn:2545-2575 tanh / softplus + min_std / MixtureSameFamily, icl.py:947 log_prob, icl.py:966 the NLL,
  *      pn:2599 sample).  lipvq-vae_amd/csrc/lipvq_gmm.hip, lipvq-vae_amd/gmm.py.

@@ -93,6 +93,10 @@ SIGNATURES = {
     "lipvq_embed_rows_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _i64]),
     "lipvq_embed_rows_bwd_ws_f32": (_i, [_vp] * 11 + [_i64, _i, _i] + [_i64] * 4 + [_vp]),
     "lipvq_linear_act_f32": (_i, [_vp] * 5 + [_i64, _i, _i, _i, _vp]),
+    "lipvq_linear_act_bf16": (_i, [_vp] * 5 + [_i64, _i, _i, _i, _vp]),
+    "lipvq_linear_nn_bf16": (_i, [_vp] * 3 + [_i64, _i, _i, _vp]),
+    "lipvq_wgrad_bf16_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "lipvq_wgrad_bf16": (_i, [_vp] * 5 + [_i64, _i, _i, _vp]),
     "lipvq_bin_minmax_f32": (_i, [_vp] * 3 + [_i64, _i, _vp]),
     "lipvq_bin_discretize_f32": (_i, [_vp] * 4 + [_i64, _i, _i, _vp]),
     "lipvq_bin_boundaries_f32": (_i, [_vp] * 3 + [_i, _i, _vp]),

@@ -18,7 +18,9 @@ children are parameter CONTAINERS only: ``forward`` never calls them.  Per block
 and one more lipvq_gpt_layernorm_f32 closes the last residual and applies ``output_ln``: 6 launches per block, 37 for the ICRT
 model.  Every op is a ``torch.autograd.Function`` over the backward kernels (lipvq_gpt_attention_bwd_f32,
 lipvq_gpt_layernorm_bwd_f32 -- which folds the residual stream's incoming gradient in --, lipvq_act_bwd_f32, lipvq_wgrad_f32);
-none of them uses float atomics, so gradients repeat bit for bit.
+none of them uses float atomics, so gradients repeat bit for bit.  ``set_matmul_precision("bf16")`` moves the four Linears of
+every block -- forward, input gradient, weight gradient -- to lipvq_linear_act_bf16 / lipvq_linear_nn_bf16 / lipvq_wgrad_bf16
+(operands rounded to bf16 as they are read, fp32 accumulation, fp32 tensors, still no atomics); the default is fp32.
 
 Dropout (training mode, torch's RNG): the attention-probability mask is drawn here as ``keep`` bytes ``[B, H, L, L]`` and
 applied inside the attention kernel; the two block-output dropouts (transformers.py:205, :289) are applied BY TORCH
@@ -114,6 +116,23 @@ class GPTBackbone(nn.Module):
             for _ in range(num_layers)])
         self.nets["output_ln"] = nn.LayerNorm(embed_dim)
         self.apply(self._init_weights)
+        self._matmul_precision = "fp32"
+
+    @property
+    def matmul_precision(self) -> str:
+        """"fp32" (default) or "bf16": how the four Linears of every block multiply (set_matmul_precision)."""
+        return self._matmul_precision
+
+    def set_matmul_precision(self, precision: str) -> "GPTBackbone":
+        """"bf16": the four Linears of every block -- forward, input gradient and weight gradient -- run on the bf16 matrix
+        pipe: both operands of each product are rounded to bf16 (nearest even) as the kernel reads them, products are
+        accumulated in fp32, and every tensor (activations, saved tensors, gradients, parameters) stays fp32.  Attention,
+        LayerNorm, GELU and its derivative stay fp32.  "fp32" restores the default bit for bit.  Needs embed_dim % 8 == 0
+        (every supported head width gives that).  Not part of state_dict(); returns self."""
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f"GPTBackbone: matmul precision must be 'fp32' or 'bf16', got {precision!r}")
+        self._matmul_precision = precision
+        return self
 
     @staticmethod
     def _init_weights(module):
@@ -134,6 +153,7 @@ class GPTBackbone(nn.Module):
             raise RuntimeError("GPTBackbone runs on the HIP library only (no CPU path)")
         x = inputs.contiguous().float()
         B, L, H = x.shape[0], self.context_length, self.num_heads
+        prec = self._matmul_precision
         a, b = x, None
         for blk in self.nets["transformer"]:
             att, mlp, ln1, ln2 = blk.nets["attention"], blk.nets["mlp"], blk.nets["ln1"], blk.nets["ln2"]
@@ -148,14 +168,14 @@ class GPTBackbone(nn.Module):
                 s, y = a, AddLayerNormFn.apply(a, None, ln1.weight, ln1.bias, ln1.eps, False)[1]
             else:
                 s, y = AddLayerNormFn.apply(a, b, ln1.weight, ln1.bias, ln1.eps, True)
-            qkv = LinearFn.apply(y, att.nets["qkv"].weight, None, ACT_NONE)
+            qkv = LinearFn.apply(y, att.nets["qkv"].weight, None, ACT_NONE, prec)
             o = _AttentionFn.apply(qkv, H, bool(self.causal), keep, keep_prob)
-            o = LinearFn.apply(o, att.nets["output"].weight, att.nets["output"].bias, ACT_NONE)
+            o = LinearFn.apply(o, att.nets["output"].weight, att.nets["output"].bias, ACT_NONE, prec)
             if p_out > 0.0:
                 o = F.dropout(o, p_out, True)
             s, y = AddLayerNormFn.apply(s, o, ln2.weight, ln2.bias, ln2.eps, True)
-            f = LinearFn.apply(y, mlp[0].weight, mlp[0].bias, ACT_GELU)
-            f = LinearFn.apply(f, mlp[2].weight, mlp[2].bias, ACT_NONE)
+            f = LinearFn.apply(y, mlp[0].weight, mlp[0].bias, ACT_GELU, prec)
+            f = LinearFn.apply(f, mlp[2].weight, mlp[2].bias, ACT_NONE, prec)
             if p_mlp > 0.0:
                 f = F.dropout(f, p_mlp, True)
             a, b = s, f
@@ -171,5 +191,6 @@ class GraphedGPTBackbone(GraphedEval):
     an eager call is bound by Python + ctypes issue and a graph replay costs the GPU time alone.  Rollouts call the policy
     once per environment step with the same shape, which is what this serves.  Parameters are read at replay time through
     their storage, so in-place updates (optimizer steps, load_state_dict) are seen; re-capture after anything that REPLACES a
-    parameter tensor (.to(), .cuda()).  The returned tensor is the graph's own output buffer: copy it before the next call if
-    it must survive."""
+    parameter tensor (.to(), .cuda()).  The graph holds the kernels of the matmul precision that was set when it was captured:
+    re-capture after set_matmul_precision().  The returned tensor is the graph's own output buffer: copy it before the next call
+    if it must survive."""

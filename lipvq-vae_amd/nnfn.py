@@ -11,17 +11,22 @@ __all__ = ["LinearFn", "AddLayerNormFn", "GraphedEval"]
 
 
 class LinearFn(torch.autograd.Function):
-    """act(x W^T + b) over the last dimension, b optional; backward = act' (elementwise), one more Linear (gx), the wgrad kernel."""
+    """act(x W^T + b) over the last dimension, b optional; backward = act' (elementwise), one more Linear (gx), the wgrad kernel.
+    precision="bf16": the three matrix products run on the bf16 matrix pipe (ops.linear_bf16 / linear_nn_bf16 / wgrad_bf16:
+    operands rounded to bf16 as they are read, fp32 accumulation, fp32 tensors); act' stays the fp32 kernel."""
 
     @staticmethod
-    def forward(ctx, x, W, b, act):
-        ctx.act, ctx.has_bias, ctx.shape = act, b is not None, x.shape
+    def forward(ctx, x, W, b, act, precision="fp32"):
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f"LinearFn: precision must be 'fp32' or 'bf16', got {precision!r}")
+        ctx.act, ctx.has_bias, ctx.shape, ctx.bf16 = act, b is not None, x.shape, precision == "bf16"
+        linear = ops.linear_bf16 if ctx.bf16 else ops.linear
         x2 = x if x.dim() == 2 else x.reshape(-1, x.shape[-1])      # (2-D callers: no view objects on their host-bound paths)
         if act != ACT_NONE:
-            y, pre = ops.linear(x2, W, b, act=act, save_pre=True)
+            y, pre = linear(x2, W, b, act=act, save_pre=True)
             ctx.save_for_backward(x2, W, pre)
         else:
-            y = ops.linear(x2, W, b)
+            y = linear(x2, W, b)
             ctx.save_for_backward(x2, W)
         return y if x.dim() == 2 else y.view(*x.shape[:-1], W.shape[0])
 
@@ -33,11 +38,12 @@ class LinearFn(torch.autograd.Function):
             gy = ops.act_bwd(gy, pre, ctx.act)
         else:
             x2, W = ctx.saved_tensors
-        gx = ops.linear(gy, W.t().contiguous()).view(ctx.shape) if ctx.needs_input_grad[0] else None
-        gW = gb = None
+        gx = gW = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = (ops.linear_nn_bf16(gy, W) if ctx.bf16 else ops.linear(gy, W.t().contiguous())).view(ctx.shape)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            gW, gb = ops.wgrad(gy, x2, want_bias=ctx.has_bias)
-        return gx, gW, gb, None
+            gW, gb = (ops.wgrad_bf16 if ctx.bf16 else ops.wgrad)(gy, x2, want_bias=ctx.has_bias)
+        return gx, gW, gb, None, None
 
 
 class AddLayerNormFn(torch.autograd.Function):

@@ -696,6 +696,66 @@ def linear(x, W, b=None, act=ACT_NONE, save_pre=False):
     return (y, pre) if save_pre else y
 
 
+def _bf16_widths(what, Kin, E):
+    if Kin % 8 or E % 8:
+        raise ValueError(f"{what}: the bf16 mode needs both Linear widths to be multiples of 8 (got {Kin} -> {E})")
+
+
+def linear_bf16(x, W, b=None, act=ACT_NONE, save_pre=False):
+    """``linear`` in the bf16 matrix-pipe mode: x and W are rounded to bf16 (nearest even) as the kernel reads them, products
+    are accumulated in fp32, bias and activation are the fp32 epilogue of ``linear``; every tensor stays fp32."""
+    x, W = _chk(x, "x"), _chk(W, "W")
+    if x.dim() != 2 or W.dim() != 2 or W.shape[1] != x.shape[1]:
+        raise ValueError(f"linear_bf16: x {tuple(x.shape)} and W {tuple(W.shape)} do not match")
+    if b is not None:
+        b = _chk(b, "b")
+        if b.shape != (W.shape[0],):
+            raise ValueError("linear_bf16: bias shape")
+    N, Kin = x.shape
+    E = W.shape[0]
+    _bf16_widths("linear_bf16", Kin, E)
+    y = torch.empty((N, E), device=x.device, dtype=torch.float32)
+    pre = torch.empty_like(y) if save_pre else None
+    with _on(x.device):
+        check(lib.lipvq_linear_act_bf16(_ptr(x), _ptr(W), _ptr(b), _ptr(y), _ptr(pre), N, Kin, E, int(act), _stream()),
+              "lipvq_linear_act_bf16")
+    return (y, pre) if save_pre else y
+
+
+def linear_nn_bf16(g, W):
+    """gx = g . W in the bf16 mode (the input gradient of ``linear_bf16``): W [J, K] is read as stored, no transposed copy."""
+    g, W = _chk(g, "g"), _chk(W, "W")
+    if g.dim() != 2 or W.dim() != 2 or W.shape[0] != g.shape[1]:
+        raise ValueError(f"linear_nn_bf16: g {tuple(g.shape)} and W {tuple(W.shape)} do not match")
+    N, J = g.shape
+    K = W.shape[1]
+    _bf16_widths("linear_nn_bf16", K, J)
+    gx = torch.empty((N, K), device=g.device, dtype=torch.float32)
+    with _on(g.device):
+        check(lib.lipvq_linear_nn_bf16(_ptr(g), _ptr(W), _ptr(gx), N, J, K, _stream()), "lipvq_linear_nn_bf16")
+    return gx
+
+
+def wgrad_bf16(G, H, want_bias=True):
+    """(gW[J,K], gb[J]) of one Linear in the bf16 mode: gW = G^T . H on bf16-rounded operands with fp32 accumulation, gb = the
+    fp32 column sums of the unrounded G.  Row chunks are added in a fixed order: repeated calls give the same bits."""
+    G, H = _chk(G, "G"), _chk(H, "H")
+    if G.dim() != 2 or H.dim() != 2 or H.shape[0] != G.shape[0]:
+        raise ValueError("wgrad_bf16: G and H must be 2-D with the same number of rows")
+    N, J = G.shape
+    K = H.shape[1]
+    _bf16_widths("wgrad_bf16", K, J)
+    dev = G.device
+    if N == 0:
+        return torch.zeros((J, K), device=dev), (torch.zeros(J, device=dev) if want_bias else None)
+    gW = torch.empty((J, K), device=dev, dtype=torch.float32)
+    gb = torch.empty(J, device=dev, dtype=torch.float32) if want_bias else None
+    ws = torch.empty(lib.lipvq_wgrad_bf16_workspace_bytes(N, J, K), device=dev, dtype=torch.uint8)
+    with _on(dev):
+        check(lib.lipvq_wgrad_bf16(_ptr(G), _ptr(H), _ptr(gW), _ptr(gb), _ptr(ws), N, J, K, _stream()), "lipvq_wgrad_bf16")
+    return gW, gb
+
+
 def _embed_args(src, idx, pos, N, T, E):
     if src.dim() != 2 or src.shape[1] != E:
         raise ValueError(f"embed_rows: src {tuple(src.shape)} is not [rows, {E}]")

@@ -1,7 +1,11 @@
 """Dev measurement (GPU): GPTBackbone (lipvq-vae_amd/gpt.py) against the plain-torch restatement of the same op sequence
 (tests/gpt_ref.py: what the reference's eager GPT_Backbone issues), same parameters, same GPU, same process.
 
-    python scripts/bench_gpt.py [B ...]          (default: 8 and 4096 -- the ICRT step shape and a large batch; L = 30, E = 512, 6 layers)
+    python scripts/bench_gpt.py [--precision bf16] [B ...]   (default: 8 and 4096 -- the ICRT step shape and a large batch; L = 30,
+                                                              E = 512, 6 layers)
+
+--precision bf16 measures four sides instead of two: ours with set_matmul_precision("bf16"), ours in fp32 (the same build, the
+fp32 kernels), plain torch in fp32 and plain torch under torch.autocast(dtype=torch.bfloat16).
 
 Per shape: the eval forward and a training forward + backward (dropout 0.1: the attention mask drawn by torch.rand and the two
 block-output dropouts by F.dropout, on both sides), each eager
@@ -67,16 +71,18 @@ def window(fn, n):
     return a.elapsed_time(b) / n
 
 
-def alternate(fa, fb, n, rounds=5):
+def alternate(fns, n, rounds=5):
+    """Median per side of `rounds` rounds in which the sides take turns; also the clock and every side's min-max."""
     for _ in range(3):
-        fa(); fb()
+        for f in fns:
+            f()
     torch.cuda.synchronize()
-    ta, tb = [], []
+    t = [[] for _ in fns]
     for _ in range(rounds):
-        ta.append(window(fa, n))
-        tb.append(window(fb, n))
-    spread = f"[{min(ta):.3f}-{max(ta):.3f}] / [{min(tb):.3f}-{max(tb):.3f}]"
-    return statistics.median(ta), statistics.median(tb), f"{sclk()}   min-max {spread}"
+        for i, f in enumerate(fns):
+            t[i].append(window(f, n))
+    spread = " / ".join(f"[{min(v):.3f}-{max(v):.3f}]" for v in t)
+    return [statistics.median(v) for v in t], f"{sclk()}   min-max {spread}"
 
 
 def graphed_step(module, x):
@@ -96,40 +102,74 @@ def graphed_step(module, x):
 
 
 def main():
-    batches = [int(a) for a in sys.argv[1:]] or [8, 4096]
-    print(f"device {torch.cuda.get_device_name(0)}; L={L} E={E} heads={H} layers={LAYERS}; times in ms (ours / plain torch), median of alternating rounds")
+    args = sys.argv[1:]
+    bf16 = False
+    if "--precision" in args:
+        i = args.index("--precision")
+        if args[i + 1:i + 2] not in (["bf16"], ["fp32"]):
+            sys.exit("--precision takes fp32 or bf16")
+        bf16 = args[i + 1] == "bf16"
+        del args[i:i + 2]
+    batches = [int(a) for a in args] or [8, 4096]
+    names = ["ours-bf16", "ours-fp32", "torch-fp32", "torch-autocast-bf16"] if bf16 else ["ours", "plain torch"]
+    print(f"device {torch.cuda.get_device_name(0)}; L={L} E={E} heads={H} layers={LAYERS}; times in ms ({' / '.join(names)}), "
+          "median of alternating rounds")
+
+    def line(B, what, t, c, note=""):
+        print(f"B={B}: {what:<29s} {' / '.join(f'{v:9.3f}' for v in t)}   sclk {c}{note}")
+
     for B in batches:
         torch.manual_seed(0)
         ours = GPTBackbone(E, L).cuda()
         ref = TorchBackbone(ours)
+        mods = [ours, ref]                                              # the callables below, in the order of `names`
+        if bf16:
+            ours16 = GPTBackbone(E, L).cuda().set_matmul_precision("bf16")
+            ours16.load_state_dict(ours.state_dict())
+
+            def ref16(x):
+                with torch.autocast("cuda", dtype=torch.bfloat16):
+                    return ref(x).float()
+            ref16.zero_grad = ref.zero_grad
+            mods = [ours16, ours, ref, ref16]
         x = torch.randn(B, L, E, device="cuda")
         n = 300 if B <= 64 else 4
-        ours.eval(); ref.eval()
+        for m in (ours, ref) + ((ours16,) if bf16 else ()):
+            m.eval()
         with torch.no_grad():
-            d = ((ours(x) - ref(x)).abs().max() / ref(x).abs().max()).item()
-            t_o, t_r, c = alternate(lambda: ours(x), lambda: ref(x), n)
-            print(f"B={B}: eval forward, eager        {t_o:9.3f} / {t_r:9.3f}   ratio {t_r / t_o:5.2f}   sclk {c}   (max rel diff {d:.1e})")
-            g_o = GraphedGPTBackbone(ours, x)
-            gr = torch.cuda.CUDAGraph()
-            for _ in range(3):
-                ref(x)
-            torch.cuda.synchronize()
-            with torch.cuda.graph(gr):
-                ref(x)
-            same = torch.equal(g_o(x), ours(x))
-            t_o, t_r, c = alternate(lambda: g_o(x), gr.replay, n)
-            print(f"B={B}: eval forward, graph replay {t_o:9.3f} / {t_r:9.3f}   ratio {t_r / t_o:5.2f}   sclk {c}   (replay == eager: {same})")
-        ours.train(); ref.train()
+            base = ref(x)
+            d = [((m(x) - base).abs().max() / base.abs().max()).item() for m in mods]
+            t, c = alternate([lambda m=m: m(x) for m in mods], n)
+            line(B, "eval forward, eager", t, c, "   (max rel diff to torch-fp32: " + " / ".join(f"{v:.1e}" for v in d) + ")")
+            graphs = []
+            for m in mods:
+                if isinstance(m, GPTBackbone):
+                    g = GraphedGPTBackbone(m, x)
+                    graphs.append((lambda g=g: g(x), torch.equal(g(x), m(x))))
+                else:
+                    g = torch.cuda.CUDAGraph()
+                    for _ in range(3):
+                        m(x)
+                    torch.cuda.synchronize()
+                    with torch.cuda.graph(g):
+                        m(x)
+                    graphs.append((g.replay, None))
+            t, c = alternate([g for g, _ in graphs], n)
+            line(B, "eval forward, graph replay", t, c, f"   (replay == eager: {[s for _, s in graphs if s is not None]})")
+        for m in (ours, ref) + ((ours16,) if bf16 else ()):
+            m.train()
 
         def step(m):
             m.zero_grad(set_to_none=True)
             m(x).square().mean().backward()
-        t_o, t_r, c = alternate(lambda: step(ours), lambda: step(ref), max(2, n // 2))
-        print(f"B={B}: forward + backward, eager  {t_o:9.3f} / {t_r:9.3f}   ratio {t_r / t_o:5.2f}   sclk {c}")
-        r_o, r_r = graphed_step(ours, x), graphed_step(ref, x)
-        t_o, t_r, c = alternate(r_o, r_r, max(2, n // 2))
-        print(f"B={B}: forward + backward, graph  {t_o:9.3f} / {t_r:9.3f}   ratio {t_r / t_o:5.2f}   sclk {c}")
-        del ours, ref, x, r_o, r_r, g_o, gr
+        t, c = alternate([lambda m=m: step(m) for m in mods], max(2, n // 2))
+        line(B, "forward + backward, eager", t, c)
+        replays = [graphed_step(m, x) for m in mods]
+        t, c = alternate(replays, max(2, n // 2))
+        line(B, "forward + backward, graph", t, c)
+        del ours, ref, mods, x, replays, graphs, base
+        if bf16:
+            del ours16, ref16
         torch.cuda.empty_cache()
 
 
