@@ -24,6 +24,7 @@ import pytest
 import torch
 
 import xf_edge_inputs as X
+from fenced import PAD, SENTINEL, _Fenced  # noqa: F401  (the guard bands: sentinel word, pad length, fenced output)
 
 pytestmark = pytest.mark.gpu
 
@@ -208,34 +209,6 @@ def _constant_rows_are_exact(got, bias, sl):
 # ---------------------------------------------------------------------------------------------------
 # guard bands and full coverage of the outputs, through the C ABI
 # ---------------------------------------------------------------------------------------------------
-
-SENTINEL = 0x7FC0DEAD                   # a NaN with a payload: no arithmetic on finite inputs stores this word
-PAD = 1024                              # words (4 KiB) of sentinel before and after every output
-
-
-class _Fenced:
-    """An fp32 output of `shape` in the middle of a sentinel-filled int32 buffer."""
-
-    def __init__(self, what, *shape, offset_words=0):
-        self.what, self.n = what, int(np.prod(shape))
-        self.buf = torch.full((PAD + offset_words + self.n + PAD,), SENTINEL, dtype=torch.int32, device="cuda")
-        self.words = self.buf[PAD + offset_words:PAD + offset_words + self.n]
-        self.t = self.words.view(torch.float32).view(*shape)
-        assert self.t.data_ptr() % 16 == 4 * (offset_words % 4)
-
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def untouched(self):
-        return bool((self.buf == SENTINEL).all())
-
-    def check(self):
-        lo, hi = self.buf[:self.words.storage_offset()], self.buf[self.words.storage_offset() + self.n:]
-        assert lo.numel() >= PAD and hi.numel() >= PAD
-        assert bool((lo == SENTINEL).all()) and bool((hi == SENTINEL).all()), f"{self.what}: a word outside the output was written"
-        assert not bool((self.words == SENTINEL).any()), f"{self.what}: an output word was never written"
-        return self.t
-
 
 @pytest.mark.parametrize("L", [33, 127])
 @pytest.mark.parametrize("dh", X.GPT_DH)
