@@ -17,19 +17,24 @@
 
 // ---------------------------------------------------------------------------------------------------
 // bin:37-40  running_min = minimum(running_min, actions.min(0)), running_max likewise (in place, atomics on the
-// monotone integer image of the floats)
+// bit image of the floats; a NaN in a column makes both of its statistics NaN, for good)
 // ---------------------------------------------------------------------------------------------------
+// NaN rule (torch.minimum / torch.maximum and Tensor.min / max propagate NaN): a NaN candidate replaces a number, a NaN
+// statistic is never replaced.
+__device__ __forceinline__ bool takes_min(float v, float cur) { return v < cur || (v != v && cur == cur); }
+__device__ __forceinline__ bool takes_max(float v, float cur) { return v > cur || (v != v && cur == cur); }
+
 __device__ __forceinline__ void atomic_min_f32(float* addr, float v) {
     int* ia = reinterpret_cast<int*>(addr);
     int old = __atomic_load_n(ia, __ATOMIC_RELAXED);
-    while (v < __int_as_float(old)) {
+    while (takes_min(v, __int_as_float(old))) {
         if (__atomic_compare_exchange_n(ia, &old, __float_as_int(v), false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) break;
     }
 }
 __device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
     int* ia = reinterpret_cast<int*>(addr);
     int old = __atomic_load_n(ia, __ATOMIC_RELAXED);
-    while (v > __int_as_float(old)) {
+    while (takes_max(v, __int_as_float(old))) {
         if (__atomic_compare_exchange_n(ia, &old, __float_as_int(v), false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) break;
     }
 }
@@ -45,8 +50,8 @@ __global__ __launch_bounds__(256) void bin_minmax_kernel(const float* __restrict
     if (gtid < stride)
         for (int64_t i = gtid; i < total; i += stride) {
             const float v = x[i];
-            lo = v < lo ? v : lo;
-            hi = v > hi ? v : hi;
+            lo = takes_min(v, lo) ? v : lo;
+            hi = takes_max(v, hi) ? v : hi;
         }
     smin[threadIdx.x] = lo;
     smax[threadIdx.x] = hi;
@@ -57,11 +62,11 @@ __global__ __launch_bounds__(256) void bin_minmax_kernel(const float* __restrict
         const int first = (threadIdx.x - c0 + A) % A;               // first thread of this block in column threadIdx.x
         float l = INFINITY, h = -INFINITY;
         for (int t = first; t < 256; t += A) {
-            l = smin[t] < l ? smin[t] : l;
-            h = smax[t] > h ? smax[t] : h;
+            l = takes_min(smin[t], l) ? smin[t] : l;
+            h = takes_max(smax[t], h) ? smax[t] : h;
         }
-        if (l < INFINITY) atomic_min_f32(rmin + threadIdx.x, l);
-        if (h > -INFINITY) atomic_max_f32(rmax + threadIdx.x, h);
+        if (l != INFINITY) atomic_min_f32(rmin + threadIdx.x, l);           // true for NaN
+        if (h != -INFINITY) atomic_max_f32(rmax + threadIdx.x, h);
     }
 }
 
@@ -113,6 +118,11 @@ struct BinHiddenArgs {
 
 #define BINH_ROWS 4          // rows per wave step (independent gather chains in flight)
 
+// WIDE = false: A <= 64, lane i holds dimension i's offset for the whole row step.  WIDE = true: the offsets are formed per chunk
+// of 64 dimensions, inside the column loop (same order of additions: i ascending over all chunks).  The column loop is uniform --
+// every lane of the wave forms offsets and answers readlane in every trip; a lane past the slice's width reads the zero-filled
+// padding of the LDS slice (c < SW always) and is kept from b1 and from the stores.
+template <bool WIDE>
 __global__ __launch_bounds__(1024) void bin_hidden_kernel(const BinHiddenArgs a) {
     extern __shared__ float pl[];                                // [A * nb][SW]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -126,25 +136,35 @@ __global__ __launch_bounds__(1024) void bin_hidden_kernel(const BinHiddenArgs a)
     __syncthreads();
     const int64_t nw = (int64_t)gridDim.x * 16;
     for (int64_t n0 = ((int64_t)blockIdx.x * 16 + wave) * BINH_ROWS; n0 < a.N; n0 += nw * BINH_ROWS) {
-        // lane i < A holds the LDS row offset (i * nb + bin) * SW of dimension i for each of the step's rows
+        // lane i holds the LDS row offset (d * nb + bin) * SW of dimension d = i0 + i for each of the step's rows
         int off[BINH_ROWS];
+        auto offsets = [&](int i0) {                             // of dimensions i0 .. i0 + 63
 #pragma unroll
-        for (int r = 0; r < BINH_ROWS; ++r) {
-            off[r] = 0;
-            if (lane < a.A && n0 + r < a.N) off[r] = (lane * a.nb + (int)a.bins[(size_t)lane * a.N + n0 + r]) * a.SW;
-        }
-        for (int c = lane; c < sw; c += 64) {
-            const float b1 = a.b1[s0 + c];
+            for (int r = 0; r < BINH_ROWS; ++r) {
+                off[r] = 0;
+                const int i = i0 + lane;
+                if (i < a.A && n0 + r < a.N) off[r] = (i * a.nb + (int)a.bins[(size_t)i * a.N + n0 + r]) * a.SW;
+            }
+        };
+        if (!WIDE) offsets(0);
+        for (int c0 = 0; c0 < sw; c0 += 64) {
+            const int c = c0 + lane;
+            const bool live = c < sw;
+            const float b1 = live ? a.b1[s0 + c] : 0.0f;
             float acc[BINH_ROWS];
 #pragma unroll
             for (int r = 0; r < BINH_ROWS; ++r) acc[r] = b1;
-            for (int i = 0; i < a.A; ++i) {
+            for (int i0 = 0; i0 < (WIDE ? a.A : 1); i0 += 64) {
+                if (WIDE) offsets(i0);
+                const int cnt = (a.A - i0 < 64) ? (a.A - i0) : 64;
+                for (int i = 0; i < cnt; ++i) {
 #pragma unroll
-                for (int r = 0; r < BINH_ROWS; ++r) acc[r] = acc[r] + pl[__builtin_amdgcn_readlane(off[r], i) + c];
+                    for (int r = 0; r < BINH_ROWS; ++r) acc[r] = acc[r] + pl[__builtin_amdgcn_readlane(off[r], i) + c];
+                }
             }
 #pragma unroll
             for (int r = 0; r < BINH_ROWS; ++r) {
-                if (n0 + r < a.N) {
+                if (live && n0 + r < a.N) {
                     if (a.pre1) a.pre1[(size_t)(n0 + r) * a.H + s0 + c] = acc[r];
                     a.h[(size_t)(n0 + r) * a.H + s0 + c] = lq_gelu(acc[r]);
                 }
@@ -217,14 +237,17 @@ int lipvq_bin_hidden_f32(const int64_t* bins, const float* P, const float* b1, f
     if (SW > Hpad) SW = Hpad;
     const int slices = (int)((H + SW - 1) / SW);
     const size_t lds = (size_t)rowsP * SW * sizeof(float);
-    static LqLdsReserve reserved;               // per-device, thread-safe (lipvq_common.h)
-    if (int rc = lipvq_reserve_lds(reserved, (const void*)bin_hidden_kernel, 160 * 1024 - 64, "lipvq_bin_hidden_f32")) return rc;
+    const bool wide = A > 64;
+    static LqLdsReserve reserved[2];            // per-device, thread-safe (lipvq_common.h)
+    const void* kernel = wide ? (const void*)bin_hidden_kernel<true> : (const void*)bin_hidden_kernel<false>;
+    if (int rc = lipvq_reserve_lds(reserved[wide], kernel, 160 * 1024 - 64, "lipvq_bin_hidden_f32")) return rc;
     int gx = 512 / slices;                               // two 16-wave workgroups per CU
     if (gx < 1) gx = 1;
     const int64_t need = (N + 16 * BINH_ROWS - 1) / (16 * BINH_ROWS);
     if (gx > need) gx = (int)need;
     BinHiddenArgs a{bins, P, b1, h, pre1, N, A, num_bins, H, (int)SW};
-    hipLaunchKernelGGL(bin_hidden_kernel, dim3(gx, slices), dim3(1024), lds, (hipStream_t)stream, a);
+    if (wide) hipLaunchKernelGGL(bin_hidden_kernel<true>, dim3(gx, slices), dim3(1024), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(bin_hidden_kernel<false>, dim3(gx, slices), dim3(1024), lds, (hipStream_t)stream, a);
     return check_launch("bin_hidden_kernel");
 }
 

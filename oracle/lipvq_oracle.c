@@ -374,8 +374,9 @@ LQ_EXPORT void lq_ref_bin_minmax(const float* actions, float* rmin, float* rmax,
     for (int64_t n = 0; n < N; ++n)
         for (int i = 0; i < A; ++i) {
             const float v = actions[(size_t)n * A + i];
-            if (v < rmin[i]) rmin[i] = v;
-            if (v > rmax[i]) rmax[i] = v;
+            /* torch.minimum / maximum and Tensor.min / max propagate NaN: a NaN replaces a number, nothing replaces a NaN */
+            if (v < rmin[i] || (v != v && rmin[i] == rmin[i])) rmin[i] = v;
+            if (v > rmax[i] || (v != v && rmax[i] == rmax[i])) rmax[i] = v;
         }
 }
 

@@ -1,5 +1,6 @@
-"""Guard bands for the tests that call the C ABI on outputs of their own (tests/test_gpu_xf_edges.py, tests/test_gpu_gmm_edges.py):
-an fp32 output inside a sentinel-filled buffer.  No word outside the output may change, none inside may keep the sentinel."""
+"""Guard bands for the tests that call the C ABI on outputs of their own (tests/test_gpu_xf_edges.py, tests/test_gpu_gmm_edges.py,
+tests/test_gpu_bin_edges.py, tests/test_gpu_update_edges.py): an fp32 (or, for bin indices, int64) output inside a sentinel-filled
+buffer.  No word outside the output may change, none inside may keep the sentinel."""
 import numpy as np
 import torch
 
@@ -8,13 +9,16 @@ PAD = 1024                              # words (4 KiB) of sentinel before and a
 
 
 class _Fenced:
-    """An fp32 output of `shape` in the middle of a sentinel-filled int32 buffer."""
+    """An fp32 output of `shape` in the middle of a sentinel-filled int32 buffer; dtype=torch.int64: two words per element
+    (offset_words even), whose low and high words -- a small index and 0 -- are never the sentinel either."""
 
-    def __init__(self, what, *shape, offset_words=0):
-        self.what, self.n = what, int(np.prod(shape))
+    def __init__(self, what, *shape, offset_words=0, dtype=torch.float32):
+        wpe = {torch.float32: 1, torch.int64: 2}[dtype]
+        assert offset_words % wpe == 0
+        self.what, self.n = what, int(np.prod(shape)) * wpe
         self.buf = torch.full((PAD + offset_words + self.n + PAD,), SENTINEL, dtype=torch.int32, device="cuda")
         self.words = self.buf[PAD + offset_words:PAD + offset_words + self.n]
-        self.t = self.words.view(torch.float32).view(*shape)
+        self.t = self.words.view(dtype).view(*shape)
         assert self.t.data_ptr() % 16 == 4 * (offset_words % 4)
 
     def ptr(self):
