@@ -557,6 +557,38 @@ int lipvq_adamw_f32(float* const* params, const float* const* grads, float* cons
                     float* const* steps, const int64_t* numels, int count, double lr, double beta1, double beta2, double eps,
                     double weight_decay, void* workspace, void* stream);
 
+/* torch_utils.py:196-234 backprop_for_loss (called at icl.py:215-226): clip_grad_norm_ over the whole parameter list, the sum of
+ * p.grad.norm(2).pow(2) -- there one host synchronisation per parameter --, then optim.Adam.step() (icl_config.py:27,
+ * torch_utils.py:108-113: Adam with L2, not AdamW).  Here without a host synchronisation; tensor lists as above (HOST arrays of
+ * `count` <= 32 DEVICE pointers per call; a longer list takes several calls).
+ *
+ * Sum of squares: every element widened to double and squared (exact), summed in double into 64 slots per tensor, one per
+ * workgroup, of a double workspace sized lipvq_grad_sumsq_workspace_bytes(tensors) for the WHOLE list of `tensors` gradients.  A
+ * call covers list entries first ... first + count - 1 and writes their slots, all of them, so the workspace needs no
+ * initialisation.  No atomics; which elements meet in which slot depends on the sizes (and each pointer's offset from a 16-byte
+ * boundary) alone: the same bits on every run.  Any size >= 1, any 4-byte alignment; each gradient is read exactly once. */
+size_t lipvq_grad_sumsq_workspace_bytes(int64_t tensors);
+int lipvq_grad_sumsq_f32(const float* const* grads, const int64_t* numels, int count, int64_t first, int64_t tensors,
+                         void* workspace, void* stream);
+/* One small launch: sumsq = the slots of `tensors` gradients added in a fixed order, and the device record
+ *     stats[0] = total_norm = sqrt(sumsq)           stats[1] = clip_coef = min(1, max_norm / (total_norm + 1e-6))
+ *     stats[2] = sumsq                              stats[3] = sumsq_clipped = clip_coef^2 sumsq   (the reference's grad_norms)
+ * -- torch.nn.utils.clip_grad_norm_ with error_if_nonfinite=False: a NaN norm gives a NaN coefficient, an infinite norm 0.
+ * max_norm = +inf only reports (the coefficient is 1); negative or NaN: LIPVQ_EINVAL. */
+int lipvq_clip_coef_f64(const void* workspace, int64_t tensors, double max_norm, double* stats, void* stream);
+/* g *= (float)stats[1] in place for a list, the coefficient read on the device.  Always multiplies, as torch does (by 1.0f: exact). */
+int lipvq_grad_scale_f32(float* const* grads, const int64_t* numels, int count, const double* stats, void* stream);
+/* lipvq_adamw_f32's two launches (the same per-tensor step counters, the same bias-correction kernel, the same workspace) with
+ *   decoupled  1: AdamW, the arithmetic of lipvq_adamw_f32 bit for bit.  0: torch.optim.Adam -- g' = g' + weight_decay p in fp32
+ *              before the moments (not formed when weight_decay == 0), and no p *= 1 - lr weight_decay.
+ *   lr_dev     NULL: the host double `lr` is used as in lipvq_adamw_f32.  Else a float32 device scalar read by the kernel (`lr`
+ *              is ignored): a learning-rate schedule then reaches a step that was captured in a HIP graph.
+ *   stats      NULL, or the record above: each gradient is read as g' = g (float)clip_coef, rounded to fp32 once -- the value
+ *              lipvq_grad_scale_f32 would have stored; the gradient itself is left unscaled. */
+int lipvq_adam_f32(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                   float* const* steps, const int64_t* numels, int count, double lr, double beta1, double beta2, double eps,
+                   double weight_decay, int decoupled, const float* lr_dev, const double* stats, void* workspace, void* stream);
+
 /* ---- opt-in extension: EMA codebook update (not in the reference; named by BASELINE.json's north star) ----
  * cluster_size [K] and embed_sum [K][D] are the running statistics (updated in place), counts [K] int64 = this batch's
  * code usage (lipvq_nearest_f32 / lipvq_tokenize_f32 `usage`, summed over ranks), dw [K][D] = sum of the z_e rows mapped

@@ -118,6 +118,11 @@ SIGNATURES = {
     "lipvq_gmm_sample_f32": (_i, [_vp, _i64] + [_vp] * 9 + [_i64] + [_i] * 5 + [C.c_float, _vp]),
     "lipvq_adamw_workspace_bytes": (_sz, []),
     "lipvq_adamw_f32": (_i, [_vp] * 6 + [_i] + [C.c_double] * 5 + [_vp, _vp]),
+    "lipvq_grad_sumsq_workspace_bytes": (_sz, [_i64]),
+    "lipvq_grad_sumsq_f32": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _vp]),
+    "lipvq_clip_coef_f64": (_i, [_vp, _i64, C.c_double, _vp, _vp]),
+    "lipvq_grad_scale_f32": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "lipvq_adam_f32": (_i, [_vp] * 6 + [_i] + [C.c_double] * 5 + [_i, _vp, _vp, _vp, _vp]),
     "lipvq_ema_update_f32": (_i, [_vp] * 5 + [C.c_float, C.c_float, _i, _i, _vp, _vp]),
     "lipvq_kmeans_workspace_bytes": (_sz, [_i64, _i]),
     "lipvq_kmeans_seed_f32": (_i, [_vp] * 6 + [_i64, _i, _i, _i, _vp]),

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include "lipvq_common.h"
+#include "lipvq_optim.h"
 
 // rows per chunk: enough chunks that the (chunk x tile) grid fills the chip even for training-step batches -- with one
 // 2048-row chunk a 1024-row batch was ONE dependent chain of 512 load+MFMA steps per wave (248 us per call).
@@ -767,16 +768,7 @@ extern "C" int lipvq_ema_update_f32(float* cluster_size, float* embed_sum, const
 // `step` is a float32 device scalar PER TENSOR (torch's capturable layout: the optimizer state_dict stays interchangeable),
 // so the whole step is capturable in a HIP graph.
 // ---------------------------------------------------------------------------------------------------
-#define LIPVQ_ADAMW_MAX 32
-struct AdamwArgs {
-    float* p[LIPVQ_ADAMW_MAX];
-    const float* g[LIPVQ_ADAMW_MAX];
-    float* m[LIPVQ_ADAMW_MAX];
-    float* v[LIPVQ_ADAMW_MAX];
-    float* step[LIPVQ_ADAMW_MAX];
-    long long n[LIPVQ_ADAMW_MAX];
-    int count;
-};
+// AdamwArgs (the tensor list, LIPVQ_ADAMW_MAX = 32 per launch): lipvq_optim.h
 
 __global__ void adamw_steps_kernel(AdamwArgs a, double beta1, double beta2, float* __restrict__ bc) {
     const int t = threadIdx.x;
@@ -787,6 +779,10 @@ __global__ void adamw_steps_kernel(AdamwArgs a, double beta1, double beta2, floa
     // is far below the 1e-5 the fixtures are held to)
     bc[2 * t] = (float)(1.0 - pow(beta1, (double)s));
     bc[2 * t + 1] = (float)sqrt(1.0 - pow(beta2, (double)s));
+}
+
+void lipvq_adamw_launch_steps(const AdamwArgs& a, double beta1, double beta2, float* bc, hipStream_t st) {
+    hipLaunchKernelGGL(adamw_steps_kernel, dim3(1), dim3(64), 0, st, a, beta1, beta2, bc);
 }
 
 // the scalar constants are formed in double on the host, as torch forms them in Python, and rounded to fp32 once

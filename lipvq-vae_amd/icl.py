@@ -18,6 +18,7 @@
                              (robomimic/algo/icl.py:885-889 AdamW(lr=1e-3, wd=1e-4); :913-914 zero_grad;
                              :968-970 loss.backward(), step()), optionally data parallel
                              (``sharded.all_reduce_gradients``).
+* ``GraphedPolicyStep``    -- the policy's iteration (icl.py:215-226: forward, ``backprop_for_loss``) as one HIP graph.
 Pure plumbing: every number comes from the HIP library through ``LLFQVAE_V4``.
 """
 from __future__ import annotations
@@ -305,3 +306,96 @@ class GraphedTokenizerStep:
         if hasattr(self.model, "last_indices"):
             self.model.last_indices = self._static_last
         return self._z, self._loss
+
+
+class GraphedPolicyStep:
+    """The policy's training iteration (icl.py:215-226: ``backprop_for_loss`` after the forward pass) captured ONCE into a HIP
+    graph and replayed: ``zero_grad -> loss_fn(*static_inputs) -> backward -> optimizer.step()``, the step being one of
+    ``optim.Adam`` / ``optim.AdamW`` with its gradient clipping inside (``max_grad_norm``).  At the ICRT step shape every launch
+    is microseconds of GPU work and the eager iteration is host bound; a replay is one call, and nothing in it reads the device.
+
+    It follows torch's whole-network capture recipe: ``warmup`` real steps on a side stream (they make the one-time work happen:
+    optimizer state, workspaces, LDS reservations), ``zero_grad(set_to_none=True)``, then forward, backward and step inside the
+    capture, so that the gradients live in the graph's private pool and every replay rewrites them.
+
+    Construction does not train the model.  A captured graph refers to every buffer BY ADDRESS (see ``GraphedTokenizerStep``), so
+    the parameters, the optimizer's ``exp_avg`` / ``exp_avg_sq`` / ``step`` tensors and a tensor ``lr`` are snapshotted before the
+    warm-up and put back IN PLACE after it (state the warm-up created is zeroed: a fresh optimizer).  Replay ``k`` then equals eager
+    step ``k``.
+
+    The learning rate: a 0-dim CUDA tensor ``lr`` is read by the kernel at replay time, so a scheduler stepped between replays
+    (``LambdaLR`` fills the tensor in place) works as it does eagerly.  A host float ``lr`` is FROZEN at capture; an optimizer
+    that has a scheduler attached and a float ``lr`` is refused.  ``optimizer.max_grad_norm`` is frozen at capture as well.
+
+    ``loss_fn(*inputs)`` must return a scalar loss, be free of host synchronisation, and do the same work for every batch of the
+    captured shapes; ``example_inputs`` is a tensor or a sequence of tensors."""
+
+    def __init__(self, loss_fn, params, optimizer, example_inputs, warmup: int = 3):
+        if not isinstance(optimizer, (optim.Adam, optim.AdamW)):
+            raise TypeError("GraphedPolicyStep captures lipvq_vae_amd.optim.Adam / AdamW only (their step makes no host "
+                            f"synchronisation and keeps its counters on the device), got {type(optimizer).__name__}")
+        scheduled = hasattr(optimizer.step, "_wrapped_by_lr_sched") or any("initial_lr" in g for g in optimizer.param_groups)
+        if scheduled and not all(torch.is_tensor(g["lr"]) for g in optimizer.param_groups):
+            raise ValueError("GraphedPolicyStep: a scheduler is attached to the optimizer but its lr is a host float, which a "
+                             "captured graph freezes; construct the optimizer with lr=torch.tensor(lr, device='cuda')")
+        if isinstance(example_inputs, torch.Tensor):
+            example_inputs = (example_inputs,)
+        self.loss_fn, self.optimizer = loss_fn, optimizer
+        self.params = list(params)
+        self.static_inputs = tuple(x.detach().clone().contiguous() for x in example_inputs)
+        self.warmup_steps = int(warmup)
+        lrs = [g["lr"] for g in optimizer.param_groups if torch.is_tensor(g["lr"])]
+        owned = [p for g in optimizer.param_groups for p in g["params"]]
+        saved_params = [p.detach().clone() for p in self.params]
+        saved_lrs = [t.detach().clone() for t in lrs]
+        saved_state = {id(p): {k: v.detach().clone() for k, v in optimizer.state.get(p, {}).items() if torch.is_tensor(v)}
+                       for p in owned}
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(self.warmup_steps):
+                self._eager_step()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        with torch.no_grad():
+            for p, sp in zip(self.params, saved_params):
+                p.copy_(sp)
+            for t, s in zip(lrs, saved_lrs):
+                t.copy_(s)
+            for p in owned:
+                for k, v in optimizer.state.get(p, {}).items():
+                    if torch.is_tensor(v):
+                        old = saved_state[id(p)].get(k)
+                        if old is not None:
+                            v.copy_(old)
+                        else:
+                            v.zero_()
+        torch.cuda.synchronize()
+        optimizer.zero_grad(set_to_none=True)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._loss = self._eager_step()
+        self.grad_stats = optimizer.grad_stats
+
+    def _eager_step(self):
+        self.optimizer.zero_grad(set_to_none=True)
+        loss = self.loss_fn(*self.static_inputs)
+        loss.backward()
+        self.optimizer.step()
+        return loss.detach()
+
+    def step(self, *inputs):
+        """One training step on a batch of the captured shapes: (loss, grad_stats) -- static device tensors, valid until the next
+        step; ``grad_stats`` is None when the optimizer has no ``max_grad_norm``."""
+        if len(inputs) != len(self.static_inputs):
+            raise ValueError(f"graphed step was captured for {len(self.static_inputs)} inputs, got {len(inputs)}")
+        for x, s in zip(inputs, self.static_inputs):
+            if x.shape != s.shape:
+                raise ValueError(f"graphed step was captured for {[tuple(t.shape) for t in self.static_inputs]}, got {tuple(x.shape)}")
+        for x, s in zip(inputs, self.static_inputs):
+            s.copy_(x)
+        self.graph.replay()
+        # a replayed optimizer step does not bump Tensor._version: do it here, as the eager step does
+        for p in self.params:
+            torch.autograd.graph.increment_version(p)
+        return self._loss, self.grad_stats
