@@ -457,6 +457,16 @@ int lipvq_attention_bwd_f32(const float* qkv, const float* out, const float* gou
  * E/H is 16, 32 or 64; L <= 128 (longer: LIPVQ_EUNSUPPORTED); B == 0 or L == 0 is a no-op.  qkv and out 16-byte aligned. */
 int lipvq_gpt_attention_f32(const float* qkv, float* out, float* lse, const unsigned char* keep, float keep_prob, int64_t B,
                             int L, int E, int H, int causal, void* stream);
+/* The same causal forward for Lq NEW tokens behind P cached ones (a rollout step of a prompted policy: the prompt's keys and
+ * values do not change during an evaluation).  prefix_qkv [Bp][P][3E] is the qkv tensor of the prefix as the qkv Linear wrote
+ * it (q | k | v; only k and v are read), Bp == B or Bp == 1 (one prompt shared by every sequence); qkv [B][Lq][3E] and
+ * out [B][Lq][E] hold the new tokens alone.  Query iq is open to all P prefix keys and to the new keys jq <= iq.  out is, bit
+ * for bit, rows P .. P + Lq - 1 of lipvq_gpt_attention_f32 (causal, keep = NULL) on the concatenation [prefix | new] along L.
+ * Forward only: no dropout mask, no lse.  E/H is 16, 32 or 64; 0 <= P, 0 <= Lq, P + Lq <= 128 (longer: LIPVQ_EUNSUPPORTED);
+ * Bp other than B or 1: LIPVQ_EINVAL; B == 0 or Lq == 0 is a no-op; P == 0 (prefix_qkv may be NULL) is plain causal attention.
+ * prefix_qkv, qkv and out 16-byte aligned. */
+int lipvq_gpt_attention_prefix_f32(const float* prefix_qkv, const float* qkv, float* out, int64_t B, int64_t Bp, int P, int Lq,
+                                   int E, int H, void* stream);
 /* Its backward: gqkv [B][L][3E] from gout [B][L][E] and the forward's out, lse; delta [B][H][L] is scratch.  Two launches, no
  * atomics: the same bits on every run. */
 int lipvq_gpt_attention_bwd_f32(const float* qkv, const float* out, const float* gout, const float* lse, float* gqkv,

@@ -107,6 +107,7 @@ SIGNATURES = {
     "lipvq_attention_f32": (_i, [_vp] * 4 + [C.c_float, _i64, _i, _i, _vp]),
     "lipvq_attention_bwd_f32": (_i, [_vp] * 7 + [C.c_float, _i64, _i, _i, _vp]),
     "lipvq_gpt_attention_f32": (_i, [_vp] * 4 + [C.c_float, _i64, _i, _i, _i, _i, _vp]),
+    "lipvq_gpt_attention_prefix_f32": (_i, [_vp] * 3 + [_i64, _i64, _i, _i, _i, _i, _vp]),
     "lipvq_gpt_attention_bwd_f32": (_i, [_vp] * 7 + [C.c_float, _i64, _i, _i, _i, _i, _vp]),
     "lipvq_gpt_layernorm_f32": (_i, [_vp] * 4 + [C.c_float] + [_vp] * 4 + [_i64, _i, _vp]),
     "lipvq_gpt_layernorm_bwd_workspace_bytes": (_sz, [_i64, _i]),

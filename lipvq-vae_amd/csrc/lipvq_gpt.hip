@@ -3,6 +3,8 @@
 // Linears of lipvq_linear_act_f32 / lipvq_wgrad_f32:
 //   gpt_attention_kernel        softmax(mask(Q K^T / sqrt(dh))) V for every (batch, head) in one launch, head width 16 / 32 / 64,
 //                               sequence 1..128, fp32 MFMA (v_mfma_f32_32x32x2_f32) for both products, exact two-pass softmax
+//   gpt_attention_prefix_kernel the same forward for Lq new tokens over P cached prefix keys plus their own (P + Lq <= 128): the
+//                               rollout step behind a prompt cache, bit-equal to rows P.. of the kernel above (eval only)
 //   gpt_attention_bwd_q/kv      its backward in two passes (probabilities recomputed from the saved log-sum-exp), no atomics
 //   gpt_layernorm_kernel        s = a + b, y = LayerNorm(s) w + bias in one pass (pre-norm: the residual stream AND the next
 //                               sub-layer's input), rows of E <= 1024 floats
@@ -137,6 +139,92 @@ __global__ __launch_bounds__(64) void gpt_attention_kernel(const float* __restri
         gpt_store_t<DH, DT>(out + (b * L + i) * (size_t)E + (size_t)h * DH, o, hf, 1.0f);
         if (hf == 0) lse[bh * L + i] = m + lq_logf_ge1(l);         // (l >= 1: the row maximum contributes exp(0))
     }
+}
+
+// Causal attention of Lq NEW tokens over P cached prefix keys plus their own: the rollout step of a prompted policy, whose
+// prompt's keys and values are constants of the evaluation.  prefix [Bp][P][3E] is the qkv tensor of a prefill, read in place
+// (K at + E, V at + 2 E; pstride = 0 shares one prompt among all sequences); qkv [B][Lq][3E] and out [B][Lq][E] hold the new
+// tokens alone.  One wave per (b, h, 32-query tile of the new tokens).  Key tiles are tiles of the CONCATENATED key index
+// j = 0 .. P + Lq - 1 (j < P: prefix row j, else new row j - P), so query iq meets its keys in the tiles, registers and lane
+// halves in which gpt_attention_kernel hands them to row P + iq of the concatenated tensor, and both products are the same
+// chains: every output row carries that kernel's bits.  (A wave may run more trailing tiles for a row than that kernel does:
+// they are masked whole, add exp(-inf) = 0 to the sum and a 0 * v product to the value chain, and change nothing.)
+template <int DH, int NKT>
+__global__ __launch_bounds__(64) void gpt_attention_prefix_kernel(const float* __restrict__ prefix, const float* __restrict__ qkv,
+                                                                  float* __restrict__ out, size_t pstride, int P, int Lq, int E, int H,
+                                                                  int NQT) {
+    constexpr int DT = DH > 32 ? DH / 32 : 1;
+    const int lane = threadIdx.x, c = lane & 31, hf = lane >> 5;
+    const int qt = blockIdx.x % NQT;
+    const size_t bh = blockIdx.x / NQT;
+    const int h = (int)(bh % H);
+    const size_t b = bh / H;
+    const int L = P + Lq;
+    const float* __restrict__ pbase = prefix + b * pstride + (size_t)h * DH;             // (read for j < P only: may be NULL when P = 0)
+    const float* __restrict__ nbase = qkv + b * (size_t)Lq * 3 * E + (size_t)h * DH;
+    const int i = qt * 32 + c, ic = i < Lq ? i : Lq - 1;
+    const float scale = 1.0f / lq_sqrt((float)DH);
+    const int q_end = Lq < 32 * (qt + 1) ? Lq : 32 * (qt + 1);
+    const int kt_end = (P + q_end + 31) / 32;                       // (wave-uniform, <= NKT)
+    float q[DH / 2];
+    gpt_load_half<DH>(nbase + (size_t)ic * 3 * E, hf, q);
+    f32x16 s[NKT];
+    float m = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+        if (kt < kt_end) {
+            const int jr = kt * 32 + gpt_perm(c), jrc = jr < L ? jr : L - 1;
+            const float* __restrict__ krow = jrc < P ? pbase + (size_t)jrc * 3 * E : nbase + (size_t)(jrc - P) * 3 * E;
+            float k[DH / 2];
+            gpt_load_half<DH>(krow + E, hf, k);
+            const f32x16 acc = gpt_dot<DH>(k, q);
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                const int j = kt * 32 + 2 * g + hf;
+                const bool ok = j < L && j <= P + i;
+                const float v = ok ? acc[g] * scale : -INFINITY;
+                s[kt][g] = v;
+                m = fmaxf(m, v);
+            }
+        }
+    }
+    m = fmaxf(m, __shfl_xor(m, 32, 64));                            // (key 0 is open to every query: m is finite)
+    float l = 0.0f;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+        if (kt < kt_end) {
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                const float e = lq_expf(s[kt][g] - m);             // (masked: exp(-inf) = 0)
+                s[kt][g] = e;
+                l += e;
+            }
+        }
+    }
+    l += __shfl_xor(l, 32, 64);
+    const float inv = 1.0f / l;
+    f32x16 o[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) o[dt][g] = 0.0f;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+        if (kt < kt_end) {
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                const int j = kt * 32 + 2 * g + hf, jc = j < L ? j : L - 1;
+                const float* __restrict__ vrow = jc < P ? pbase + (size_t)jc * 3 * E : nbase + (size_t)(jc - P) * 3 * E;
+                const float p = s[kt][g] * inv;
+#pragma unroll
+                for (int dt = 0; dt < DT; ++dt) {
+                    const float a = (DH >= 32 || c < DH) ? vrow[2 * E + 32 * dt + c] : 0.0f;
+                    o[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, p, o[dt], 0, 0, 0);
+                }
+            }
+        }
+    }
+    if (i < Lq) gpt_store_t<DH, DT>(out + (b * Lq + i) * (size_t)E + (size_t)h * DH, o, hf, 1.0f);
 }
 
 // Backward.  delta[i] = sum_d dO[i][d] O[i][d];  P_ij = exp(s_ij - lse_i);  dP_ij = (keep_ij / keep_prob) dO_i . V_j;
@@ -308,6 +396,31 @@ extern "C" int lipvq_gpt_attention_f32(const float* qkv, float* out, float* lse,
     hipLaunchKernelGGL(kfn, dim3((unsigned)(B * H * NT)), dim3(64), 0, (hipStream_t)stream, qkv, out, lse, keep,
                        keep ? 1.0f / keep_prob : 1.0f, L, E, H, causal);
     return check_launch("gpt_attention");
+}
+
+extern "C" int lipvq_gpt_attention_prefix_f32(const float* prefix_qkv, const float* qkv, float* out, int64_t B, int64_t Bp, int P,
+                                              int Lq, int E, int H, void* stream) {
+    if (P < 0 || Lq < 0) return fail(LIPVQ_EINVAL, "gpt_attention_prefix: P=%d Lq=%d", P, Lq);
+    if (P + (int64_t)Lq > GPT_MAXL)
+        return fail(LIPVQ_EUNSUPPORTED, "gpt_attention_prefix: P + Lq = %d + %d keys (<= %d)", P, Lq, GPT_MAXL);
+    bool empty = false;
+    if (int rc = gpt_attention_args("gpt_attention_prefix", B, Lq, E, H, nullptr, 1.0f, &empty)) return rc;
+    if (Bp != B && Bp != 1)
+        return fail(LIPVQ_EINVAL, "gpt_attention_prefix: Bp=%lld prompts for B=%lld sequences (B, or 1 shared by all)", (long long)Bp, (long long)B);
+    if (empty) return 0;
+    if (!qkv || !out || (P > 0 && !prefix_qkv)) return fail(LIPVQ_EINVAL, "gpt_attention_prefix: null pointer");
+    if ((((uintptr_t)prefix_qkv | (uintptr_t)qkv | (uintptr_t)out) & 15) != 0)
+        return fail(LIPVQ_EINVAL, "gpt_attention_prefix: prefix_qkv / qkv / out must be 16-byte aligned");
+    typedef void (*fn_t)(const float*, const float*, float*, size_t, int, int, int, int, int);
+    const int dh = E / H, NQT = (Lq + 31) / 32, NKT = (P + Lq + 31) / 32;
+    fn_t kfn = nullptr;
+#define LQ_GA(DH_) if (dh == DH_) kfn = NKT == 1 ? (fn_t)gpt_attention_prefix_kernel<DH_, 1> : NKT == 2 ? (fn_t)gpt_attention_prefix_kernel<DH_, 2> \
+                                      : NKT == 3 ? (fn_t)gpt_attention_prefix_kernel<DH_, 3> : (fn_t)gpt_attention_prefix_kernel<DH_, 4>;
+    LQ_GA(16) LQ_GA(32) LQ_GA(64)
+#undef LQ_GA
+    const size_t pstride = Bp == 1 ? 0 : (size_t)P * 3 * E;
+    hipLaunchKernelGGL(kfn, dim3((unsigned)(B * H * NQT)), dim3(64), 0, (hipStream_t)stream, prefix_qkv, qkv, out, pstride, P, Lq, E, H, NQT);
+    return check_launch("gpt_attention_prefix");
 }
 
 extern "C" int lipvq_gpt_attention_bwd_f32(const float* qkv, const float* out, const float* gout, const float* lse, float* gqkv,

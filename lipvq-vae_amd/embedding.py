@@ -164,6 +164,13 @@ class ICLInputEmbedding(nn.Module):
         E = self.embed_dim
         if context_obs.shape != obs.shape:
             raise ValueError("obs and context_obs must have the same shape")
+        a_idx, a_src = self._action_stream(obs.shape, context_actions, action_indices, codebook)
+        slots = [(2 * E, 0), (2 * E, E), (E, 2 * T * E)]           # context_obs, context_actions, obs
+        return self._embed(B, T, 3 * T, slots, [None, a_idx, None], [self._dense(context_obs), a_src, self._dense(obs)])
+
+    def _action_stream(self, shape, context_actions, action_indices, codebook):
+        """(row indices or None, source rows) of the context-action stream, from dense rows or from indices + codebook."""
+        B, T, _ = shape
         if (action_indices is None) == (context_actions is None):
             raise ValueError("pass exactly one of context_actions / action_indices")
         if action_indices is not None:
@@ -171,10 +178,16 @@ class ICLInputEmbedding(nn.Module):
                 raise ValueError("action_indices needs the codebook")
             if tuple(action_indices.shape) != (B, T):
                 raise ValueError(f"action_indices must be [{B}, {T}]")
-            a_idx, a_src = action_indices.reshape(-1), self.code_table(codebook)
-        else:
-            if context_actions.shape != obs.shape:
-                raise ValueError("context_actions must have the same shape as obs")
-            a_idx, a_src = None, self._dense(context_actions)
-        slots = [(2 * E, 0), (2 * E, E), (E, 2 * T * E)]           # context_obs, context_actions, obs
-        return self._embed(B, T, 3 * T, slots, [None, a_idx, None], [self._dense(context_obs), a_src, self._dense(obs)])
+            return action_indices.reshape(-1), self.code_table(codebook)
+        if context_actions.shape != shape:
+            raise ValueError("context_actions must have the same shape as obs")
+        return None, self._dense(context_actions)
+
+    def prompt_embedding(self, context_obs, context_actions=None, *, action_indices=None, codebook=None):
+        """The first 2T positions of ``forward`` alone, [B, 2T, E]: context_obs at 2t, the context actions at 2t+1 -- the part
+        of the transformer input that a rollout does not change (``GPTBackbone.prefill`` takes it).  The remaining T positions
+        are ``input_embedding(obs)``: ``cat([prompt_embedding(...), input_embedding(obs)], 1)`` is ``forward(obs, ...)``."""
+        B, T, _ = context_obs.shape
+        E = self.embed_dim
+        a_idx, a_src = self._action_stream(context_obs.shape, context_actions, action_indices, codebook)
+        return self._embed(B, T, 2 * T, [(2 * E, 0), (2 * E, E)], [None, a_idx], [self._dense(context_obs), a_src])

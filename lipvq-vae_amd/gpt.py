@@ -22,6 +22,13 @@ none of them uses float atomics, so gradients repeat bit for bit.  ``set_matmul_
 every block -- forward, input gradient, weight gradient -- to lipvq_linear_act_bf16 / lipvq_linear_nn_bf16 / lipvq_wgrad_bf16
 (operands rounded to bf16 as they are read, fp32 accumulation, fp32 tensors, still no atomics); the default is fp32.
 
+Rollouts (``ICLTransformer.get_action``, icl.py:827-853) pass the same context for a whole evaluation, so the first 2T of the
+3T positions (obs_nets.py:2584-2596) and, the backbone being causal and adding no positional term of its own, every block's
+keys and values there are constants of it.  ``cache = prefill(prompt_embeddings)`` runs those rows once and keeps each block's
+qkv tensor; ``forward_cached(embeddings, cache)`` runs the same 6 launches per block on the new rows alone, with
+lipvq_gpt_attention_prefix_f32 in place of lipvq_gpt_attention_f32, and returns the bits ``forward`` gives for those rows
+(DESIGN.md 4.6.2).  Eval mode and causal backbones only; ``PromptedGPTBackbone`` wraps a (backbone, cache) pair for GraphedEval.
+
 Dropout (training mode, torch's RNG): the attention-probability mask is drawn here as ``keep`` bytes ``[B, H, L, L]`` and
 applied inside the attention kernel; the two block-output dropouts (transformers.py:205, :289) are applied BY TORCH
 (``F.dropout`` on the branch before the fused residual launch) -- they are elementwise over ``[B L, E]`` and vanish in eval.
@@ -38,7 +45,7 @@ from . import ops
 from .nnfn import AddLayerNormFn, GraphedEval, LinearFn
 from .ops import ACT_GELU, ACT_NONE
 
-__all__ = ["GPTBackbone", "GraphedGPTBackbone"]
+__all__ = ["GPTBackbone", "GraphedGPTBackbone", "PromptCache", "PromptedGPTBackbone"]
 
 
 class _AttentionFn(torch.autograd.Function):
@@ -182,6 +189,126 @@ class GPTBackbone(nn.Module):
         ln = self.nets["output_ln"]
         out = AddLayerNormFn.apply(a, b, ln.weight, ln.bias, ln.eps, False)[1]
         return out
+
+
+    # -- the prompt cache: a rollout's constant prefix is run once, every step runs its new tokens alone ---------------------
+    def _cacheable(self, what):
+        if self.training:
+            raise RuntimeError(f"GPTBackbone.{what} is an eval-mode path (no dropout, no backward): call eval() first")
+        if not self.causal:
+            raise ValueError(f"GPTBackbone.{what}: a non-causal prefix sees the tokens after it, so no cache of it is valid")
+
+    def _param_versions(self):
+        return tuple(p._version for p in self.parameters())
+
+    def _blocks_eval(self, x, prefix, record):
+        """The eval forward on the rows of x.  record (a list): plain causal attention, every block's qkv is appended and the
+        last block stops there (prefill).  Otherwise the attention of block i also sees the cached keys and values prefix[i]."""
+        H, prec = self.num_heads, self._matmul_precision
+        blocks = self.nets["transformer"]
+        a, b = x, None
+        for i, blk in enumerate(blocks):
+            att, mlp, ln1, ln2 = blk.nets["attention"], blk.nets["mlp"], blk.nets["ln1"], blk.nets["ln2"]
+            if b is None:
+                s, y = a, AddLayerNormFn.apply(a, None, ln1.weight, ln1.bias, ln1.eps, False)[1]
+            else:
+                s, y = AddLayerNormFn.apply(a, b, ln1.weight, ln1.bias, ln1.eps, True)
+            qkv = LinearFn.apply(y, att.nets["qkv"].weight, None, ACT_NONE, prec)
+            if record is not None:
+                record.append(qkv)
+                if i == len(blocks) - 1:                        # the prefix's own output is not needed
+                    return None
+                o = ops.gpt_attention(qkv, H, True)[0]
+            else:
+                o = ops.gpt_attention_prefix(prefix[i], qkv, H)
+            o = LinearFn.apply(o, att.nets["output"].weight, att.nets["output"].bias, ACT_NONE, prec)
+            s, y = AddLayerNormFn.apply(s, o, ln2.weight, ln2.bias, ln2.eps, True)
+            f = LinearFn.apply(y, mlp[0].weight, mlp[0].bias, ACT_GELU, prec)
+            f = LinearFn.apply(f, mlp[2].weight, mlp[2].bias, ACT_NONE, prec)
+            a, b = s, f
+        ln = self.nets["output_ln"]
+        return AddLayerNormFn.apply(a, b, ln.weight, ln.bias, ln.eps, False)[1]
+
+    @torch.no_grad()
+    def prefill(self, prompt_embeddings: torch.Tensor) -> "PromptCache":
+        """Run the constant prefix [Bp, P, E] of a rollout once and keep every block's qkv rows (``PromptCache``:
+        layers x Bp x P x 3E floats).  Blocks 0 .. n-2 run in full on the P rows, the last one up to its qkv Linear.  Eval mode,
+        causal backbones only.  The cache belongs to the parameters and the matmul precision it was made under."""
+        self._cacheable("prefill")
+        if prompt_embeddings.dim() != 3 or prompt_embeddings.shape[2] != self.embed_dim:
+            raise ValueError(f"GPTBackbone.prefill: prompt embeddings must be [Bp, P, {self.embed_dim}], got {tuple(prompt_embeddings.shape)}")
+        Bp, P, E = prompt_embeddings.shape
+        if P > self.context_length:
+            raise ValueError(f"GPTBackbone.prefill: P={P} exceeds context_length={self.context_length}")
+        if not prompt_embeddings.is_cuda:
+            raise RuntimeError("GPTBackbone runs on the HIP library only (no CPU path)")
+        x = prompt_embeddings.contiguous().float()
+        qkv = []
+        if Bp == 0 or P == 0:                                       # no rows: nothing to launch
+            qkv = [x.new_empty((Bp, P, 3 * E)) for _ in self.nets["transformer"]]
+        else:
+            self._blocks_eval(x, None, qkv)
+        return PromptCache(tuple(qkv), Bp, P, self._matmul_precision, self._param_versions())
+
+    @torch.no_grad()
+    def forward_cached(self, embeddings: torch.Tensor, cache: "PromptCache") -> torch.Tensor:
+        """[B, Lq, E] -> [B, Lq, E]: ``self(cat([prompt, embeddings], 1))[:, P:]`` from the Lq new rows and ``cache =
+        prefill(prompt)`` alone -- the same 6 launches per block and the closing LayerNorm, on Lq rows, with
+        lipvq_gpt_attention_prefix_f32 reading the cached keys and values.  P + Lq <= context_length; Bp == B or 1."""
+        self._cacheable("forward_cached")
+        if embeddings.dim() != 3 or embeddings.shape[2] != self.embed_dim:
+            raise ValueError(f"GPTBackbone.forward_cached: embeddings must be [B, Lq, {self.embed_dim}], got {tuple(embeddings.shape)}")
+        if not embeddings.is_cuda:
+            raise RuntimeError("GPTBackbone runs on the HIP library only (no CPU path)")
+        B, Lq = embeddings.shape[:2]
+        if cache.P + Lq > self.context_length:
+            raise ValueError(f"GPTBackbone.forward_cached: P + Lq = {cache.P} + {Lq} exceeds context_length={self.context_length}")
+        if cache.Bp not in (1, B):
+            raise ValueError(f"GPTBackbone.forward_cached: the cache holds {cache.Bp} prompts, the input {B} sequences (B, or 1 shared by all)")
+        if len(cache.qkv) != len(self.nets["transformer"]) or any(t.shape[2] != 3 * self.embed_dim or t.device != embeddings.device
+                                                                  for t in cache.qkv):
+            raise ValueError("GPTBackbone.forward_cached: the cache was made by another backbone or on another device")
+        if cache.precision != self._matmul_precision:
+            raise RuntimeError(f"GPTBackbone.forward_cached: the cache was made under matmul precision {cache.precision!r}, the "
+                               f"backbone is now {self._matmul_precision!r}: call prefill() again")
+        if cache.versions != self._param_versions():
+            raise RuntimeError("GPTBackbone.forward_cached: a parameter changed after the cache was made (an optimizer step, "
+                               "load_state_dict): the cached keys and values are stale, call prefill() again")
+        x = embeddings.contiguous().float()
+        if B == 0 or Lq == 0:
+            return torch.empty_like(x)
+        return self._blocks_eval(x, cache.qkv, None)
+
+
+class PromptCache:
+    """What ``GPTBackbone.prefill`` keeps of a prompt: ``qkv``, one [Bp, P, 3E] tensor per block exactly as the qkv Linear wrote it
+    (the attention kernel reads K and V in place), with ``Bp``, ``P``, the matmul ``precision`` and the ``_version`` of every
+    parameter at that moment, which ``forward_cached`` compares with the backbone's."""
+
+    __slots__ = ("qkv", "Bp", "P", "precision", "versions")
+
+    def __init__(self, qkv, Bp, P, precision, versions):
+        self.qkv, self.Bp, self.P, self.precision, self.versions = qkv, int(Bp), int(P), precision, versions
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.qkv)
+
+
+class PromptedGPTBackbone(nn.Module):
+    """``forward(embeddings) = backbone.forward_cached(embeddings, cache)``: a rollout step as a module, so that
+    ``nnfn.GraphedEval(PromptedGPTBackbone(net.eval(), cache), example)`` replays it as one HIP graph (a single chain of
+    launches on one stream).  The graph reads the cache by address and checks nothing at replay: after a parameter update or
+    set_matmul_precision(), prefill again and capture again."""
+
+    def __init__(self, backbone: GPTBackbone, cache: PromptCache):
+        super().__init__()
+        self.backbone = backbone
+        self.cache = cache
+        self.train(backbone.training)
+
+    def forward(self, embeddings: torch.Tensor) -> torch.Tensor:
+        return self.backbone.forward_cached(embeddings, self.cache)
 
 
 class GraphedGPTBackbone(GraphedEval):

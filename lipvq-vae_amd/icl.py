@@ -19,6 +19,8 @@
                              :968-970 loss.backward(), step()), optionally data parallel
                              (``sharded.all_reduce_gradients``).
 * ``GraphedPolicyStep``    -- the policy's iteration (icl.py:215-226: forward, ``backprop_for_loss``) as one HIP graph.
+* ``PromptedPolicy``       -- the rollout chain (icl.py:827-853) with the fixed context embedded and prefilled once
+                             (``GPTBackbone.prefill`` / ``forward_cached``): a step runs the T observation frames alone.
 Pure plumbing: every number comes from the HIP library through ``LLFQVAE_V4``.
 """
 from __future__ import annotations
@@ -399,3 +401,39 @@ class GraphedPolicyStep:
         for p in self.params:
             torch.autograd.graph.increment_version(p)
         return self._loss, self.grad_stats
+
+
+class PromptedPolicy:
+    """The policy chain of a rollout with the context held fixed (``ICLTransformer.get_action``, icl.py:827-853, passes the same
+    ``context_batch`` for a whole evaluation): ``set_prompt`` embeds the 2T context positions (``prompt_embedding``) and runs them
+    through the backbone ONCE (``GPTBackbone.prefill``); every step then embeds the T observation frames alone and runs
+    ``forward_cached`` on them.  ``embedding`` is an ``ICLInputEmbedding``, ``backbone`` a causal ``GPTBackbone``, ``head`` a
+    ``GMMActionHead`` (or any callable on [B, T, E] features); all in eval mode.  A context of batch 1 serves any number of
+    environments.  Call ``set_prompt`` again after the context, a parameter or the matmul precision changes (``forward_cached``
+    refuses a stale cache).  No kernels of its own."""
+
+    def __init__(self, embedding: nn.Module, backbone: nn.Module, head):
+        self.embedding, self.backbone, self.head = embedding, backbone, head
+        self.cache = None
+
+    def set_prompt(self, context_obs, context_actions=None, *, action_indices=None, codebook=None):
+        """Embed and prefill the context: context_obs [Bp, T, F] with dense context_actions [Bp, T, F] or action_indices [Bp, T] +
+        codebook (the tokenizer's).  Returns the ``PromptCache`` it keeps."""
+        if self.embedding.training:
+            raise RuntimeError("PromptedPolicy is an eval-mode path: call embedding.eval() first (its dropout would be cached)")
+        with torch.no_grad():
+            prompt = self.embedding.prompt_embedding(context_obs, context_actions, action_indices=action_indices, codebook=codebook)
+            self.cache = self.backbone.prefill(prompt)
+        return self.cache
+
+    def features(self, obs: torch.Tensor) -> torch.Tensor:
+        """[B, T, E]: the backbone's outputs at the T observation positions, what the head reads (obs_nets.py:2602-2605)."""
+        if self.cache is None:
+            raise RuntimeError("PromptedPolicy: call set_prompt() first")
+        if self.embedding.training:
+            raise RuntimeError("PromptedPolicy is an eval-mode path: call embedding.eval() first")
+        with torch.no_grad():
+            return self.backbone.forward_cached(self.embedding.input_embedding(obs), self.cache)
+
+    def __call__(self, obs: torch.Tensor):
+        return self.head(self.features(obs))

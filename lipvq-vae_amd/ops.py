@@ -1069,6 +1069,23 @@ def gpt_attention(qkv, nhead: int, causal: bool = True, keep=None, keep_prob: fl
     return out, lse
 
 
+def gpt_attention_prefix(prefix_qkv, qkv, nhead: int):
+    """out [B, Lq, E] of causal attention from the Lq new tokens of qkv [B, Lq, 3E] to the P cached keys and values of
+    prefix_qkv [Bp, P, 3E] (a prefill's qkv tensor; Bp == B, or 1 for one prompt shared by every sequence) plus their own:
+    the bits of gpt_attention(cat([prefix_qkv, qkv], 1), nhead, True)[0][:, P:].  Forward only."""
+    prefix_qkv, qkv = _chk(prefix_qkv, "prefix_qkv"), _chk(qkv, "qkv")
+    if qkv.dim() != 3 or qkv.shape[2] % 3 != 0 or prefix_qkv.dim() != 3 or prefix_qkv.shape[2] != qkv.shape[2]:
+        raise ValueError(f"gpt_attention_prefix: prefix_qkv {tuple(prefix_qkv.shape)}, qkv {tuple(qkv.shape)}")
+    if prefix_qkv.device != qkv.device:
+        raise ValueError("gpt_attention_prefix: prefix_qkv and qkv are on different devices")
+    B, Lq, E = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
+    out = torch.empty((B, Lq, E), device=qkv.device, dtype=torch.float32)
+    with _on(qkv.device):
+        check(lib.lipvq_gpt_attention_prefix_f32(_ptr(prefix_qkv), _ptr(qkv), _ptr(out), B, prefix_qkv.shape[0], prefix_qkv.shape[1],
+                                                 Lq, E, int(nhead), _stream()), "lipvq_gpt_attention_prefix_f32")
+    return out
+
+
 def gpt_attention_bwd(qkv, out, gout, lse, nhead: int, causal: bool = True, keep=None, keep_prob: float = 1.0):
     qkv, out, gout, lse = _chk(qkv, "qkv"), _chk(out, "out"), _chk(gout, "gout"), _chk(lse, "lse")
     B, L, E = out.shape
