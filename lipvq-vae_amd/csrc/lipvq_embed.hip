@@ -17,8 +17,12 @@
 //
 // Canonical LayerNorm (shared with oracle/lipvq_oracle.c, bit for bit): a row is owned by 16 lanes, lane l holding the
 // float4 groups q = l, l+16, ...;  lane sums run in that order and the 16 lane sums are combined by a butterfly with
-// partners l^1, l^2, l^7, l^15 (four DPP adds);  mean = s*(1/E), var = sum((v-mean)^2)*(1/E) (fmaf chain, same order),
-// rstd = 1/sqrt(var+eps), y = fmaf((v-mean)*rstd, w, b).
+// partners l^1, l^2, l^7, l^15 (four DPP adds).  The row is centred twice:  mean0 = s*(1/E), d = v-mean0,
+// rest = sum(d)*(1/E) (same lane order and butterfly), d = d-rest;  var = sum(d^2)*(1/E) (fmaf chain, same order),
+// rstd = 1/sqrt(var+eps), y = fmaf(d*rstd, w, b);  stats = (mean0+rest, rstd).  One centring is not enough: fl(1/E) is
+// inexact unless E is a power of two, so the mean of a constant row comes out an ulp off and rstd = 1/sqrt(eps) = 316
+// multiplies the residue (1e-4 of max|y| on rows of 3.0 at E = 252; tests/test_gpu_embed_edges.py).  stats keeps the
+// corrected mean, from which the backward kernels rebuild xhat = (v - mean) * rstd in one step.
 // ABI: include/lipvq.h.
 #include <stdlib.h>
 
@@ -275,13 +279,27 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(const EmbedRowsArgs a) 
                     s = s + c.x; s = s + c.y; s = s + c.z; s = s + c.w;
                 }
             }
-            const float mean = lq_row_allsum(s) * invE;
+            // Centre twice.  fl(1/E) is inexact for most E and the fp32 sum of a row around 1000 is ulps of 1000 E off, so the
+            // first mean misses by up to ~1e-4 -- which rstd = 316 blows up on a constant row.  v - mean0 is exact for values
+            // within a factor 2 of the mean: the mean of the centred values is that miss, to fp32 accuracy at ITS size.
+            const float mean0 = lq_row_allsum(s) * invE;
+            float rs = 0.0f;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+                if (l + 16 * j < E4) {
+                    float4 d = v[j];
+                    d.x = d.x - mean0; d.y = d.y - mean0; d.z = d.z - mean0; d.w = d.w - mean0;
+                    v[j] = d;
+                    rs = rs + d.x; rs = rs + d.y; rs = rs + d.z; rs = rs + d.w;
+                }
+            const float rest = lq_row_allsum(rs) * invE;
+            const float mean = mean0 + rest;                   // what stats keeps
             float ss = 0.0f;
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
                 if (l + 16 * j < E4) {
                     float4 d = v[j];
-                    d.x = d.x - mean; d.y = d.y - mean; d.z = d.z - mean; d.w = d.w - mean;
+                    d.x = d.x - rest; d.y = d.y - rest; d.z = d.z - rest; d.w = d.w - rest;
                     v[j] = d;
                     ss = lq_fma(d.x, d.x, ss); ss = lq_fma(d.y, d.y, ss);
                     ss = lq_fma(d.z, d.z, ss); ss = lq_fma(d.w, d.w, ss);

@@ -330,13 +330,27 @@ LQ_EXPORT void lq_ref_embed_rows(const float* src, const int64_t* idx, const flo
                     }
                 lane[l] = s;
             }
-            const float mean = row_allsum(lane) * invE;
+            /* centred twice: fl(1/E) and the fp32 row sum leave mean0 up to ~1e-4 off; the mean of the centred row is that miss */
+            const float mean0 = row_allsum(lane) * invE;
+            for (int l = 0; l < 16; ++l) {
+                float rs = 0.0f;
+                for (int q = l; q < E4; q += 16)
+                    for (int c = 0; c < 4; ++c) {
+                        const int e = 4 * q + c;
+                        const float d = v[e] - mean0;
+                        v[e] = d;
+                        rs = rs + d;
+                    }
+                lane[l] = rs;
+            }
+            const float rest = row_allsum(lane) * invE;
+            const float mean = mean0 + rest;
             for (int l = 0; l < 16; ++l) {
                 float ss = 0.0f;
                 for (int q = l; q < E4; q += 16)
                     for (int c = 0; c < 4; ++c) {
                         const int e = 4 * q + c;
-                        const float d = v[e] - mean;
+                        const float d = v[e] - rest;
                         v[e] = d;
                         ss = lq_fma(d, d, ss);
                     }
