@@ -557,6 +557,41 @@ int lipvq_gmm_sample_f32(const float* x, int64_t bstride, const float* Wm, const
                          const float* Wl, const float* bl, const float* u, const float* eps, float* action, int64_t N, int T,
                          int E, int M, int A, int scale_mode, float min_std, void* stream);
 
+/* ---- the deterministic policy's output head: what algo_factory (robomimic/algo/icl.py:41-75) builds when algo.gmm.enabled is
+ *      False (config/icl_config.py:63, the default) -- ICLTransformer: the ObservationDecoder's one Linear `action`
+ *      (obs_nets.py:747-771 with output_shapes = action (ac_dim,), pn:1683-1690), tanh (pn:1728-1731), and the losses of
+ *      ICL._compute_losses (icl.py:174-202, weights icl_config.py:43-45): MSELoss, SmoothL1Loss (beta 1), cosine_loss on the first
+ *      three components (utils/loss_utils.py:11-23) and their weighted sum.  lipvq-vae_amd/csrc/lipvq_action_head.hip,
+ *      lipvq-vae_amd/action_head.py.
+ *      A = ac_dim (1..64); E % 4 == 0, E <= 1024; outside these limits: LIPVQ_EUNSUPPORTED.  Rows are addressed as in the GMM
+ *      head: row n = (b, t) = (n / T, n % T) at x + b bstride + t E floats (bstride % 4 == 0, x and W 16-byte aligned).
+ *      Sizes are checked before pointers, pointers before any launch.  N == 0: no-op. ---- */
+
+/* One launch: pre = x W^T + b (W [A][E]; the GMM head's product stage: the k-ordered fp32 chain of lipvq_linear_act_f32 started
+ * from the bias, the reduction over E never split -- the same bits as lipvq_linear_act_f32), y = tanh(pre).  Every output may be
+ * NULL: actions [N][A] = y; pre [N][A] (kept for the backward); losses [4] (needs target [N][A] and `workspace`,
+ * lipvq_action_head_workspace_bytes(N) bytes, any contents) = with d = y - target, C = min(3, A), eps = 1e-8
+ *     losses[0] = l2  = sum d^2 / (N A)
+ *     losses[1] = l1  = sum smoothl1(d) / (N A)            smoothl1(d) = d^2 / 2 where |d| < 1, else |d| - 1/2
+ *     losses[2] = cos = sum_n (1 - sim_n) / N               sim = sum_{c < C} (y_c / max(|y|, eps)) (target_c / max(|target|, eps)),
+ *                                                           each norm over the first C components and clamped on its own
+ *                                                           (torch's nn.CosineSimilarity): -mean(sim - 1)
+ *     losses[3] = w2 l2 + w1 l1 + wc cos
+ * formed from per-workgroup partial sums (three floats per 32 rows, rows in order) by a second, one-workgroup launch that adds
+ * them in double in a fixed order: no float atomics, the same bits on every run. */
+size_t lipvq_action_head_workspace_bytes(int64_t N);
+int lipvq_action_head_f32(const float* x, int64_t bstride, const float* W, const float* b, const float* target, float* actions,
+                          float* pre, float* losses, void* workspace, int64_t N, int T, int E, int A, float w2, float w1,
+                          float wc, void* stream);
+/* Its backward, one elementwise launch: gpre [N][A] = (gL + gy) (1 - y^2) with y = tanh(pre).  g [4] is the upstream gradient of
+ * the four losses, a DEVICE tensor (needs target); with k2 = g[0] + g[3] w2, k1 = g[1] + g[3] w1, kc = g[2] + g[3] wc
+ *     gL = k2 2 d / (N A) + k1 smoothl1'(d) / (N A) - [c < C] kc / N  d sim / d y_c        smoothl1'(d) = d inside the band, sign(d) outside
+ *     d sim / d y_c = target_c / (n_y n_t) - [|y| > eps] sim y_c / |y|^2,   n = max(|.|, eps)
+ * gy [N][A] is a gradient arriving at the `actions` output.  Either of g, gy may be NULL (counts as zeros), not both.
+ * The Linear gradients are lipvq_wgrad_f32 (G = gpre) and lipvq_linear_act_f32 (gpre times the weight). */
+int lipvq_action_head_bwd_f32(const float* pre, const float* target, const float* g, const float* gy, float* gpre, int64_t N,
+                              int A, float w2, float w1, float wc, void* stream);
+
 /* icl.py:885-889, :970  optim.AdamW(vq_vae_model.parameters(), lr=1e-3, weight_decay=1e-4).step() for a LIST of tensors in
  * two launches (torch's foreach form is 8-10): params / grads / exp_avg / exp_avg_sq / steps are HOST arrays of `count`
  * DEVICE pointers (count <= 32), numels their element counts; steps[i] is a float32 device scalar (torch's capturable layout),

@@ -7,5 +7,6 @@ Importing this package loads the in-tree HIP library (``_lipvq_hip.so``) and fai
 if it is missing: the tokenizer path has no CPU or eager-PyTorch fallback.
 """
 from . import _capi, ops  # noqa: F401  (loads the shared object)
+from .action_head import ActionHead  # noqa: F401
 
-__all__ = ["ops"]
+__all__ = ["ops", "ActionHead"]

@@ -19,8 +19,9 @@
 #include <math.h>
 
 #include "lipvq_common.h"
+#include "lipvq_head_product.h"
 
-#define GMM_ROWS 32
+#define GMM_ROWS HEAD_ROWS
 #define GMM_MAXM 16
 #define GMM_MAXA 64
 #define GMM_MAXP 512
@@ -75,97 +76,38 @@ __device__ __forceinline__ float gmm_logz(const float* lg, int M) {
     return mx + logf(se);
 }
 
+// the P columns mean | scale | logits of the product (lipvq_head_product.h): a column picks its row of one of the three weights
+struct GmmCols {
+    const float* Wm; const float* Ws; const float* Wl;
+    const float* bm; const float* bs; const float* bl;
+    int MA, P, E;
+    __device__ __forceinline__ float bias(int c) const {
+        float b0 = 0.0f;
+        if (c < MA) b0 = bm[c];
+        else if (c < 2 * MA) b0 = bs[c - MA];
+        else if (c < P) b0 = bl[c - 2 * MA];
+        return b0;
+    }
+    __device__ __forceinline__ const float* wrow(int c) const {
+        return c < MA ? Wm + (size_t)c * E : c < 2 * MA ? Ws + (size_t)(c - MA) * E : c < P ? Wl + (size_t)(c - 2 * MA) * E : nullptr;
+    }
+};
+
 // ---------------------------------------------------------------------------------------------------
-// forward / sampling.  NT = column tiles per wave (P <= 128 NT), KC = input features staged per step.
-//   A operand: lane (m = lane & 31, kh = lane >> 5) = x[row0 + m][k0 + 2s + kh]
-//   B operand: lane (n = lane & 31, kh)             = W[column][k0 + 2s + kh]
-//   D[m][n]  : col n = lane & 31, row m = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+// forward / sampling.  NT = column tiles per wave (P <= 128 NT), KC = input features staged per step: the product stage of
+// lipvq_head_product.h, then the epilogues on its LDS tile.
 // dynamic LDS: max(staging [32 + 128 NT][KC + 1], tile [32][PS]) floats, then GMM_SIDE floats.
 // ---------------------------------------------------------------------------------------------------
 template <int NT, int KC>
 __global__ __launch_bounds__(256) void gmm_head_kernel(const GmmArgs a, int side_off) {
     extern __shared__ float gmm_lds[];
-    constexpr int WROWS = 128 * NT, KS = KC + 1, KC4 = KC / 4;
-    constexpr int WV = WROWS * KC4 / 256, WSTEP = 256 / KC4;      // float4 per thread and step; weight rows between two of them
-    float* xs = gmm_lds;                                            // [32][KS]
-    float* ws = gmm_lds + GMM_ROWS * KS;                            // [WROWS][KS]
     float* pt = gmm_lds;                                            // [32][PS], after the product
     float* s_ell = gmm_lds + side_off;                              // [32][17]
     float* s_lp = s_ell + 2 * GMM_ROWS * (GMM_MAXM + 1);            // [32]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, kh = lane >> 5;
+    const int tid = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * GMM_ROWS;
-    const int M = a.M, A = a.A, MA = a.M * a.A, P = a.P, PS = a.PS, E = a.E;
-
-    f32x16 acc[NT];
-    bool tile_ok[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int c = (j * 4 + wave) * 32 + li;
-        tile_ok[j] = (j * 4 + wave) * 32 < P;                      // wave-uniform
-        float b0 = 0.0f;
-        if (c < MA) b0 = a.bm[c];
-        else if (c < 2 * MA) b0 = a.bs[c - MA];
-        else if (c < P) b0 = a.bl[c - 2 * MA];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = b0;
-    }
-    // staging: thread -> (row sr (+ WSTEP i), 4 consecutive features at sk)
-    const int sr = tid / KC4, sk = 4 * (tid % KC4);
-    const float* xp = nullptr;
-    if (sr < GMM_ROWS && row0 + sr < a.N) {
-        const int64_t n = row0 + sr, b = n / a.T;
-        xp = a.x + b * a.bstride + (n - b * a.T) * (int64_t)E;
-    }
-    const float* wp[WV];
-#pragma unroll
-    for (int i = 0; i < WV; ++i) {
-        const int c = sr + WSTEP * i;
-        wp[i] = c < MA ? a.Wm + (size_t)c * E : c < 2 * MA ? a.Ws + (size_t)(c - MA) * E : c < P ? a.Wl + (size_t)(c - 2 * MA) * E : nullptr;
-    }
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 xr = zero4, wr[WV];
-    auto fetch = [&](int k0) {
-        const bool kin = k0 + sk < E;                               // E is a multiple of 4
-        xr = (xp && kin) ? *reinterpret_cast<const float4*>(xp + k0 + sk) : zero4;
-#pragma unroll
-        for (int i = 0; i < WV; ++i) wr[i] = (wp[i] && kin) ? *reinterpret_cast<const float4*>(wp[i] + k0 + sk) : zero4;
-    };
-    fetch(0);
-    for (int k0 = 0; k0 < E; k0 += KC) {
-        if (sr < GMM_ROWS) {
-            float* xd = xs + sr * KS + sk;
-            xd[0] = xr.x; xd[1] = xr.y; xd[2] = xr.z; xd[3] = xr.w;
-        }
-#pragma unroll
-        for (int i = 0; i < WV; ++i) {
-            float* wd = ws + (sr + WSTEP * i) * KS + sk;
-            wd[0] = wr[i].x; wd[1] = wr[i].y; wd[2] = wr[i].z; wd[3] = wr[i].w;
-        }
-        __syncthreads();
-        if (k0 + KC < E) fetch(k0 + KC);                            // uniform; in flight during the MFMAs below
-        const int kend = (E - k0 < KC) ? ((E - k0) >> 1) : (KC / 2);
-        for (int s = 0; s < kend; ++s) {
-            const float av = xs[li * KS + 2 * s + kh];
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-                if (tile_ok[j]) {
-                    const float bv = ws[((j * 4 + wave) * 32 + li) * KS + 2 * s + kh];
-                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[j], 0, 0, 0);
-                }
-        }
-        __syncthreads();
-    }
-    // the row tile's P pre-activations -> LDS (the staging buffers are dead: every wave has passed the loop's last barrier)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int c = (j * 4 + wave) * 32 + li;
-        if (c < P) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) pt[((r & 3) + 8 * (r >> 2) + 4 * kh) * PS + c] = acc[j][r];
-        }
-    }
-    __syncthreads();
+    const int M = a.M, A = a.A, MA = a.M * a.A, P = a.P, PS = a.PS;
+    lq_head_product<NT, KC, 1>(gmm_lds, a.x, a.bstride, a.N, a.T, a.E, P, PS, GmmCols{a.Wm, a.Ws, a.Wl, a.bm, a.bs, a.bl, MA, P, a.E});
     const int64_t live = (a.N - row0 < GMM_ROWS) ? (a.N - row0) : GMM_ROWS;      // rows of this tile that exist
     if (a.pre) {
         float* dst = a.pre + (size_t)row0 * P;
@@ -361,7 +303,7 @@ static int gmm_launch(const char* what, GmmArgs& a, hipStream_t st) {
     a.PS = a.P | 1;                                                 // odd row stride: the items of a wave differ in the row
     const int tiles = (a.P + 31) / 32, nt = (tiles + 3) / 4;
     const int NT = nt <= 1 ? 1 : (nt <= 2 ? 2 : 4), KC = NT == 4 ? 16 : 32;
-    const int stage = (GMM_ROWS + 128 * NT) * (KC + 1), tile = GMM_ROWS * a.PS;
+    const int stage = lq_head_stage_floats(NT, KC), tile = GMM_ROWS * a.PS;
     const int side_off = stage > tile ? stage : tile;
     const size_t lds = (size_t)(side_off + GMM_SIDE) * sizeof(float);
     typedef void (*fn_t)(const GmmArgs, int);

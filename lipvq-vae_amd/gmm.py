@@ -38,14 +38,8 @@ __all__ = ["GMMActionHead"]
 
 
 def _linear_grads(need_x, need_params, feats, gpre, Wm, Ws, Wl, MA):
-    """(gx in feats' shape, gWm, gbm, gWs, gbs, gWl, gbl) from gpre [N, P]: one wgrad over all P columns, one Linear for gx."""
-    gx = None
-    if need_x:
-        Wt = torch.cat((Wm, Ws, Wl), 0).t().contiguous()           # [E, P] -> gx = gpre . W
-        gx = ops.linear(gpre, Wt).view(feats.shape)
-    gW = gb = None
-    if need_params:
-        gW, gb = ops.wgrad(gpre, feats.reshape(-1, feats.shape[-1]))
+    """(gx in feats' shape, gWm, gbm, gWs, gbs, gWl, gbl) from gpre [N, P]: ops.head_linear_grads' results cut by rows."""
+    gx, gW, gb = ops.head_linear_grads(need_x, need_params, feats, gpre, (Wm, Ws, Wl))
     if gW is None:
         return (gx,) + (None,) * 6
     return gx, gW[:MA], gb[:MA], gW[MA:2 * MA], gb[MA:2 * MA], gW[2 * MA:], gb[2 * MA:]

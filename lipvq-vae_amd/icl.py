@@ -18,9 +18,12 @@
                              (robomimic/algo/icl.py:885-889 AdamW(lr=1e-3, wd=1e-4); :913-914 zero_grad;
                              :968-970 loss.backward(), step()), optionally data parallel
                              (``sharded.all_reduce_gradients``).
-* ``GraphedPolicyStep``    -- the policy's iteration (icl.py:215-226: forward, ``backprop_for_loss``) as one HIP graph.
+* ``GraphedPolicyStep``    -- the policy's iteration (icl.py:215-226: forward, ``backprop_for_loss``) as one HIP graph; its
+                             ``loss_fn`` ends in ``GMMActionHead.nll`` (``ICLTransformer_GMM``) or in
+                             ``ActionHead.losses(...)["action_loss"]`` (``ICLTransformer``, the default algorithm).
 * ``PromptedPolicy``       -- the rollout chain (icl.py:827-853) with the fixed context embedded and prefilled once
-                             (``GPTBackbone.prefill`` / ``forward_cached``): a step runs the T observation frames alone.
+                             (``GPTBackbone.prefill`` / ``forward_cached``): a step runs the T observation frames alone;
+                             ``head`` is a ``GMMActionHead`` (sampled actions) or an ``ActionHead`` (deterministic ones).
 Pure plumbing: every number comes from the HIP library through ``LLFQVAE_V4``.
 """
 from __future__ import annotations
@@ -330,7 +333,8 @@ class GraphedPolicyStep:
     that has a scheduler attached and a float ``lr`` is refused.  ``optimizer.max_grad_norm`` is frozen at capture as well.
 
     ``loss_fn(*inputs)`` must return a scalar loss, be free of host synchronisation, and do the same work for every batch of the
-    captured shapes; ``example_inputs`` is a tensor or a sequence of tensors."""
+    captured shapes (e.g. ``lambda x, a: head.nll(net(x)[:, -T:], a)`` with a ``GMMActionHead``, or
+    ``lambda x, a: head.losses(net(x)[:, -T:], a)["action_loss"]`` with an ``ActionHead``); ``example_inputs`` is a tensor or a sequence of tensors."""
 
     def __init__(self, loss_fn, params, optimizer, example_inputs, warmup: int = 3):
         if not isinstance(optimizer, (optim.Adam, optim.AdamW)):
@@ -408,7 +412,8 @@ class PromptedPolicy:
     ``context_batch`` for a whole evaluation): ``set_prompt`` embeds the 2T context positions (``prompt_embedding``) and runs them
     through the backbone ONCE (``GPTBackbone.prefill``); every step then embeds the T observation frames alone and runs
     ``forward_cached`` on them.  ``embedding`` is an ``ICLInputEmbedding``, ``backbone`` a causal ``GPTBackbone``, ``head`` a
-    ``GMMActionHead`` (or any callable on [B, T, E] features); all in eval mode.  A context of batch 1 serves any number of
+    ``GMMActionHead`` or an ``ActionHead`` (or any callable on [B, T, E] features; ``get_action``'s row pick, icl.py:845-851, is
+    the caller's ``policy(obs)[:, -1]``); all in eval mode.  A context of batch 1 serves any number of
     environments.  Call ``set_prompt`` again after the context, a parameter or the matmul precision changes (``forward_cached``
     refuses a stale cache).  No kernels of its own."""
 

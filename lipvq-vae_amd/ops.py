@@ -1147,14 +1147,14 @@ def gpt_layernorm_bwd(gy, xhat, rstd, w, gres=None):
 GMM_SOFTPLUS, GMM_EXP, GMM_LOW_NOISE = 0, 1, 2
 
 
-def _gmm_rows(feats):
+def _gmm_rows(feats, what="the GMM head"):
     """feats [B, T, E] (or [N, E]) -> (tensor, N, T, E, bstride): the tensor's own strides where the kernel can read them -- rows
     of E contiguous floats, T consecutive rows per batch entry, a batch stride that is a multiple of 4 floats, as for the view
     out[:, -T:] of a backbone output -- and a contiguous copy otherwise."""
     if not isinstance(feats, torch.Tensor):
         raise TypeError(f"feats: expected a tensor, got {type(feats).__name__}")
     if not feats.is_cuda:
-        raise RuntimeError(f"feats: the GMM head runs on the HIP library only (got a {feats.device} tensor)")
+        raise RuntimeError(f"feats: {what} runs on the HIP library only (got a {feats.device} tensor)")
     if feats.dtype != torch.float32:
         raise TypeError(f"feats: expected torch.float32, got {feats.dtype}")
     if feats.dim() == 2:
@@ -1168,6 +1168,19 @@ def _gmm_rows(feats):
     if not ok:
         feats = feats.contiguous()
     return feats, B * T, T, E, (feats.stride(0) if B > 1 else T * E)
+
+
+def head_linear_grads(need_x, need_params, feats, gpre, weights):
+    """The Linear gradients of an output head from gpre [N, P], the gradient of its pre-activations: (gx in feats' shape, gW [P, E],
+    gb [P]) -- one Linear for gx = gpre . W over the stacked `weights` (a tuple of [P_i, E] matrices, P = sum P_i), one wgrad over
+    all P columns; the caller cuts gW / gb by rows.  What is not needed is None."""
+    gx = gW = gb = None
+    if need_x:
+        Wt = torch.cat(tuple(weights), 0).t().contiguous()         # [E, P] -> gx = gpre . W
+        gx = linear(gpre, Wt).view(feats.shape)
+    if need_params:
+        gW, gb = wgrad(gpre, feats.reshape(-1, feats.shape[-1]))
+    return gx, gW, gb
 
 
 def _gmm_params(params, M, A, E):
@@ -1264,3 +1277,67 @@ def gmm_sample(feats, params, M: int, A: int, u, eps, scale_mode: int = GMM_SOFT
                                        _ptr(action), N, T, E, int(M), int(A), int(scale_mode), float(min_std), _stream()),
               "lipvq_gmm_sample_f32")
     return action
+
+
+# ---------------------------------------------------------------------------------------------------
+# the deterministic policy's output head (csrc/lipvq_action_head.hip)
+# ---------------------------------------------------------------------------------------------------
+
+def action_head(feats, W, b, target=None, weights=(1.0, 0.0, 0.0), want_actions: bool = True, want_pre: bool = False):
+    """The Linear + tanh head and its losses (lipvq_action_head_f32).  feats [B, T, E] (its strides are passed on, see _gmm_rows);
+    W [A, E], b [A]; target [B, T, A] or None; weights = (l2_weight, l1_weight, cos_weight).
+    Returns a dict with the outputs asked for: actions [N, A] (want_actions), pre [N, A] (want_pre), losses [4] = (l2, l1, cos,
+    action) (with a target: one more one-workgroup launch, a deterministic sum)."""
+    feats, N, T, E, bstride = _gmm_rows(feats, "the action head")
+    W, b = _chk(W, "W"), _chk(b, "b")
+    if W.dim() != 2 or W.shape[1] != E or b.shape != (W.shape[0],):
+        raise ValueError(f"action_head: W {tuple(W.shape)} / b {tuple(b.shape)} do not match E={E}")
+    A = W.shape[0]
+    dev = feats.device
+    out = {}
+    if want_actions:
+        out["actions"] = torch.empty((N, A), device=dev, dtype=torch.float32)
+    if want_pre:
+        out["pre"] = torch.empty((N, A), device=dev, dtype=torch.float32)
+    ws = None
+    if target is not None:
+        target = _chk(target, "target")
+        if target.numel() != N * A:
+            raise ValueError(f"action_head: target {tuple(target.shape)} does not match {N} rows of {A}")
+        out["losses"] = torch.empty(4, device=dev, dtype=torch.float32)
+        ws = torch.empty(max(1, lib.lipvq_action_head_workspace_bytes(N)), device=dev, dtype=torch.uint8)
+    w2, w1, wc = (float(w) for w in weights)
+    with _on(dev):
+        check(lib.lipvq_action_head_f32(_ptr(feats), bstride, _ptr(W), _ptr(b), _ptr(target), _ptr(out.get("actions")), _ptr(out.get("pre")),
+                                        _ptr(out.get("losses")), _ptr(ws), N, T, E, int(A), w2, w1, wc, _stream()), "lipvq_action_head_f32")
+    return out
+
+
+def action_head_bwd(pre, target=None, g=None, gy=None, weights=(1.0, 0.0, 0.0)):
+    """gpre [N, A] (lipvq_action_head_bwd_f32): g [4] = the gradient of (l2, l1, cos, action) -- a device tensor, with target
+    [N, A] --, gy [N, A] = a gradient arriving at the actions output; either may be None."""
+    pre = _chk(pre, "pre")
+    N, A = pre.shape
+    if g is None and gy is None:
+        raise ValueError("action_head_bwd: no upstream gradient")
+    if g is not None:
+        g = _chk(g, "g")
+        if g.numel() != 4:
+            raise ValueError("action_head_bwd: g must have the four losses' gradients")
+        if target is None:
+            raise ValueError("action_head_bwd: the losses' gradient needs the target")
+        target = _chk(target, "target")
+        if target.numel() != N * A:
+            raise ValueError("action_head_bwd: shapes do not match")
+    else:
+        target = None
+    if gy is not None:
+        gy = _chk(gy, "gy")
+        if gy.numel() != N * A:
+            raise ValueError("action_head_bwd: gy shape")
+    gpre = torch.empty_like(pre)
+    w2, w1, wc = (float(w) for w in weights)
+    with _on(pre.device):
+        check(lib.lipvq_action_head_bwd_f32(_ptr(pre), _ptr(target), _ptr(g), _ptr(gy), _ptr(gpre), N, int(A), w2, w1, wc, _stream()),
+              "lipvq_action_head_bwd_f32")
+    return gpre
