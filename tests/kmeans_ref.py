@@ -93,7 +93,10 @@ def revive(oracle, z, codebook, idx, counts, threshold, draws, dist, max_codes=N
     dead = [k for k in range(K) if counts[k] < threshold][: K if max_codes is None else max_codes]
     if not dead:
         return cb, picks, 0
-    d = oracle.distances(z, cb, dist)[np.arange(z.shape[0]), idx]
+    idx = np.asarray(idx, np.int64)
+    inside = np.nonzero((idx >= 0) & (idx < K))[0]             # an index outside [0, K) weighs 0
+    d = np.zeros(z.shape[0], np.float32)
+    d[inside] = oracle.distances(z, cb, dist)[inside, idx[inside]]
     e = scale_exponent(weights(d, dist).max(), z.shape[0])
     return cb, picks, _draw_loop(oracle, z, cb, d, dead, draws, dist, e, picks)
 
@@ -111,3 +114,48 @@ def lloyd_step(oracle, z, codebook, draws, dist):
     cb[live] = sums[live] / counts[live].astype(np.float32)[:, None]
     cb, _, _ = revive(oracle, z, cb, idx, counts, 1, draws, dist)
     return cb, idx, counts
+
+
+# ---- inputs of the edge suites (tests/test_kmeans_host.py, tests/test_gpu_kmeans_edges.py) ------------------------------------
+
+LAST = float(np.nextafter(1.0, 0.0))                           # the last double below 1
+EDGE_DRAWS = np.array([0.0, 0.3, 0.6, LAST, 0.0, 0.5])
+
+
+def scaled_rows(s, N=600, D=8, seed=0):
+    """randn * s: s = 1e-22 puts every squared distance into the fp32 subnormals, 1e-30 makes all rows equal under both rules,
+    1e15 / 1e18 push the scale exponent far below 0."""
+    return (np.random.default_rng(seed).standard_normal((N, D)) * s).astype(np.float32)
+
+
+def first_state(oracle, z, draws, dist):
+    """(r0, d, e) after code 0 of a seeding: its row, every row's comparison value to it, the scale exponent."""
+    N = z.shape[0]
+    r0 = min(N - 1, int(np.floor(np.float64(draws[0]) * np.float64(N))))
+    d = _dist_to(oracle, z, z[r0], dist)
+    return r0, d, scale_exponent(weights(d, dist).max(), N)
+
+
+def nonfinite_rows(N=600, D=8, seed=1):
+    """Rows 3, 200 and 599 hold a NaN, an inf and 3e19 (whose squared difference overflows fp32): they weigh 0 for ever."""
+    z = np.random.default_rng(seed).standard_normal((N, D)).astype(np.float32)
+    z[3, 2], z[200, 0], z[N - 1, D - 1] = np.nan, np.inf, 3e19
+    return z, (3, 200, N - 1)
+
+
+def boundary_draws(q, n):
+    """The two doubles next to c[n] / Q, c = cumsum(q): the draw below stops at row n, the one above at the next row that
+    weighs something."""
+    c = np.cumsum(q, dtype=np.uint64)
+    u = np.float64(c[n]) / np.float64(c[-1])
+    return float(np.nextafter(u, 0.0)), float(np.nextafter(u, 1.0))
+
+
+def zero_run_rows(N=1500, D=8, seed=2, r0=100):
+    """Rows 256..767 are copies of row r0: once r0 is a code, blocks 1 and 2 weigh nothing at all."""
+    z = np.random.default_rng(seed).standard_normal((N, D)).astype(np.float32)
+    z[256:768] = z[r0]
+    return z, r0
+
+
+ZERO_RUN_BOUNDARIES = (0, 99, 254, 255, 768, 1023, 1024, 1279, 1498)    # row 255: the next row that weighs something is 768
