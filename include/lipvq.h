@@ -56,7 +56,7 @@ const char* lipvq_last_error(void);
  *   tok_ze_rows       batch size up to which a fused launch stores z_e for its exact stage when nothing else asks for it
  *   tok_inplace       "0" | "1": the fused launch never / whenever possible lets its waves decide their uncertified rows in place
  *                     instead of listing them for a second kernel (default: whenever possible = K <= 2048 under the three-product
- *                     screen with z_e rows stored)
+ *                     screen; a parity launch of a latent width <= 64 whose caller wants no z_e then stores none)
  *   tok_defer_ze, tok_nt_ze   "0" | "1": the fused launch's two device-dependent schedule choices (the last z_e tile's stores issued
  *                     behind the screen's first stage copies; z_e rows stored nontemporal) -- overrides the defaults (0, 1) and
  *                     whatever lipvq_tokenize_tune_f32 found for the device */
@@ -193,7 +193,10 @@ int lipvq_tokenize_f32(const float* x, const float* packed, const float* const* 
  * rounds, minimum per combination -- and keeps the fastest as the current device's setting for every later lipvq_tokenize_* call of
  * the process.  SYNCHRONOUS (waits for the stream), not capturable; every launch writes idx / zq / ze_out and accumulates into usage
  * as lipvq_tokenize_f32 does.  choice (may be NULL): defer_ze | nt_ze << 1; ms4 (may be NULL): ms per launch of the four.
- * Latent widths above 64 have no such choice (their instances fix both): the call returns at once with choice = -1. */
+ * Latent widths above 64 have no such choice (their instances fix both): the call returns at once with choice = -1.
+ * A launch that stores no z_e at all has none either (width <= 64, at most 2048 codes under the three-product screen, ze_out NULL:
+ * its rows are decided in place from registers): the one launch is timed once, ms4 carries that time four times, choice is the
+ * library default and the device's setting stays as it was. */
 int lipvq_tokenize_tune_f32(const float* x, const float* packed, const float* const* raw6, const float* codebook,
                             const void* prep, int64_t* idx, float* zq, int64_t* usage, float* ze_out, void* workspace,
                             int64_t N, int A, int J0, int J1, int D, int K, void* stream, int launches, int* choice, float* ms4);

@@ -131,6 +131,7 @@ struct TokArgs {
     int nt_ze;                   // z_e rows are stored nontemporal                                                } same results: lq_schedule()
     int ze_ring;                 // ze_out is a RING: a wave's 32 rows of every row block go to the same 32 rows (in-place launches whose
                                  // caller wants no z_e: lq_ze_ring) -- the rows live in L2 until the wave has decided them
+    int keepz;                   // host side only: the KEEPZ instance runs (lq_keepz) -- ze_out, ze_ring, defer_ze and nt_ze are unused
 };
 
 // T0 = 2 (64 features), T1 = 4 (128 features): the reference's encoder widths (v5:54-59).
@@ -148,10 +149,15 @@ struct TokArgs {
 // latent itself) -- ReLU instead of GELU / GELU / sigmoid, no Lipschitz scale (the packed weights are the plain ones).  A ReLU
 // latent is unbounded, so the launch-wide fp16 scale of the sigmoid instance does not exist: the row keeps its centred latent
 // in fp32 until all tiles are finished and is then split with its OWN power of two, as the stand-alone screen does.
-template <int S, bool FAST, bool TRAIN, int WAVES, bool COARSE = false, bool VQ = false>
+// KEEPZ (S <= 4, parity, in-place decisions, caller wants no z_e): z_e is never stored.  A lane's post-sigmoid values of the wave's
+// 32 rows (T2 x 16 registers) stay in registers through phase B, and an uncertified row's two lanes hand them to the decision
+// through the wave's LDS slice (lq_screen_decide_inplace).  Same bits as the stored-and-re-read row, no z_e traffic at all; the
+// flag is compile-time so that only this instance carries the 32 live registers.
+template <int S, bool FAST, bool TRAIN, int WAVES, bool COARSE = false, bool VQ = false, bool KEEPZ = false>
 __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
     static_assert(!(FAST && TRAIN), "training uses the parity arithmetic");
     static_assert(!VQ || !FAST, "the ReLU instance: parity arithmetic");
+    static_assert(!KEEPZ || (S <= 4 && !FAST && !TRAIN && !COARSE && !VQ), "z_e kept in registers: the narrow parity instances, decided in place");
     constexpr int THREADS = WAVES * 64;
     // the one-product screen stages hi-only tiles (half the bytes): twice the tiles per stage in the same LDS, i.e. half the
     // stage hand-overs (vmcnt wait + workgroup barrier + DMA issue) per tile where a stage was ONE tile (S = 8)
@@ -196,6 +202,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
     // per-wave private slice of the (idle) ring: the decision's transposes (LQ_DECIDE_BYTES) and the z_q copy's staging (GP KiB)
     constexpr size_t WSLICE = (STAGES_BYTES >= (size_t)WAVES * 8192) ? 8192 : LQ_DECIDE_BYTES;
     static_assert(LQ_DECIDE_BYTES >= 4096 && WSLICE >= LQ_DECIDE_BYTES, "a slice holds the transposes and four staged KiB");
+    static_assert(!KEEPZ || WSLICE >= LQ_DECIDE_BYTES + 64 * S, "KEEPZ: one z_e row behind the decision scratch");
     unsigned* hist = reinterpret_cast<unsigned*>(stage0 + ((STAGES_BYTES + 63) & ~(size_t)63));
     const bool use_hist = a.usage && fused_hist_fits<S, FAST>(a.A, a.K);         // (the same rule sizes the launch's LDS)
 
@@ -396,13 +403,14 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
 #ifdef LQ_STAMPS
         st_prev = __builtin_amdgcn_s_memtime();
 #endif
-        ze_shift = a.ze_ring ? (blk - (int64_t)blockIdx.x) * (WAVES * 32) : 0;
+        ze_shift = (!KEEPZ && a.ze_ring) ? (blk - (int64_t)blockIdx.x) * (WAVES * 32) : 0;
         f16x8 ah[S], al[S];
         // z_e of the LAST layer-2 tile, stored behind the screen's first copies -- in the instances with registers to spare
         // (S <= 4: cfg2 0.4006 -> 0.3944 ms; at S = 13 the sixteen registers held across the end of layer 2 cost more than the
         // wait they remove: icrt 0.8945 -> 0.9149, profiles/r04_g_ze_store_placement.txt)
-        constexpr bool DEFER_ZE = S <= 4 && !TRAIN;
+        constexpr bool DEFER_ZE = S <= 4 && !TRAIN && !KEEPZ;
         f32x16 zdef;
+        f32x16 zkeep[KEEPZ ? T2 : 1];                        // KEEPZ: z_e of the wave's rows, register r of tile t = feature 32t + 2r + h of row ln
         float row_n2, row_a2, row_fz, row_fown;              // phase A's row statistics and scales (the VQ instance: the row's own)
       // ---- phase A: the wave's 32 rows through the encoder, split into the screen's fp16 fragments ----
       auto encode = [&]() {
@@ -471,7 +479,9 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
             // z_e rows for the exact stage (store_ze_tile).  The LAST tile's are not stored here: its sixteen values wait in zdef and
             // are stored behind the screen's first stage copies (lq_screen_core, DEFER) -- in front of them their write
             // acknowledgements stood between every wave and "stage 0 has landed" (vmcnt retires in order)
-            if (a.ze_out) {
+            if constexpr (KEEPZ) {
+                zkeep[t] = acc;                              // (no store, no transposes: the decision reads the registers)
+            } else if (a.ze_out) {
                 if (DEFER_ZE && a.defer_ze && t == T2 - 1) zdef = acc;
                 else store_ze_tile(row, t, acc);
             }
@@ -844,9 +854,15 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) znr[r] = 0.0f;
         }
-        const bool have_def = DEFER_ZE && a.defer_ze && a.ze_out != nullptr;
-        auto deferred_ze = [&]() { store_ze_tile((blk * WAVES + wave) * 32 + ln, T2 - 1, zdef); };
-        lq_screen_core<S, THREADS, TCF, NBF, PACKF, COARSE, 4, decltype(deferred_ze)>(ah, al, tiles, L.ntiles, stage0, tid, frow, znr, m1, m2, k1, have_def, deferred_ze);
+        if constexpr (KEEPZ) {
+            lq_screen_core<S, THREADS, TCF, NBF, PACKF, COARSE>(ah, al, tiles, L.ntiles, stage0, tid, frow, znr, m1, m2, k1);
+        } else {
+            const bool have_def = DEFER_ZE && a.defer_ze && a.ze_out != nullptr;
+            // the deferred stores sit under `row < N`: a wave without a valid row issues none, and its counted waits must not count them
+            const bool wave_def = __builtin_amdgcn_ballot_w64((blk * WAVES + wave) * 32 + ln < a.N) != 0ull;
+            auto deferred_ze = [&]() { store_ze_tile((blk * WAVES + wave) * 32 + ln, T2 - 1, zdef); };
+            lq_screen_core<S, THREADS, TCF, NBF, PACKF, COARSE, 4, decltype(deferred_ze)>(ah, al, tiles, L.ntiles, stage0, tid, frow, znr, m1, m2, k1, have_def, deferred_ze, wave_def);
+        }
         LQ_STAMP(4);
         const unsigned keep_mask = PACKF ? ~((1u << lq_pack_bits(L.ntiles)) - 1u) : 0xffffffffu;
         unsigned char* scratch = stage0 + (size_t)wave * WSLICE;
@@ -861,7 +877,10 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
         certified = certified && row_sane;
         // in place (round 4; small codebooks under the three-product screen): this wave decides its uncertified rows itself
         // (lq_screen_decide_inplace) and they go on as certified ones -- no list kernel behind the launch
-        if (!COARSE && a.inplace)
+        if constexpr (KEEPZ)
+            certified = lq_screen_decide_inplace<PACKF, 2 * S, LIPVQ_DIST_NORM, T2>(
+                dec, certified, row_sane, my_k, row0, row < a.N, a.amb_count, nullptr, a.cb, a.K, lane, keep_mask, scratch, zkeep);
+        else if (!COARSE && a.inplace)
             certified = lq_screen_decide_inplace<PACKF, 2 * S, VQ ? LIPVQ_DIST_SQSUM : LIPVQ_DIST_NORM>(
                 dec, certified, row_sane, my_k, row0 - ze_shift, row < a.N, a.amb_count, a.ze_out, a.cb, a.K, lane, keep_mask, scratch);
         else
@@ -902,13 +921,13 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
 }
 
 // two waves per SIMD (8 waves, 256 registers each) / one wave per SIMD (4 waves, the whole 512-register file each)
-template <int S, bool FAST, bool TRAIN = false, bool COARSE = false, bool VQ = false>
+template <int S, bool FAST, bool TRAIN = false, bool COARSE = false, bool VQ = false, bool KEEPZ = false>
 __global__ __launch_bounds__(FUSED_THREADS) void tokenize_kernel(TokArgs a) {
-    tokenize_body<S, FAST, TRAIN, FUSED_WAVES, COARSE, VQ>(a);
+    tokenize_body<S, FAST, TRAIN, FUSED_WAVES, COARSE, VQ, KEEPZ>(a);
 }
-template <int S, bool FAST, bool TRAIN, bool COARSE = false>
+template <int S, bool FAST, bool TRAIN, bool COARSE = false, bool KEEPZ = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void tokenize_kernel_w4(TokArgs a) {
-    tokenize_body<S, FAST, TRAIN, 4, COARSE>(a);
+    tokenize_body<S, FAST, TRAIN, 4, COARSE, false, KEEPZ>(a);
 }
 
 // fp16 MFMA fragments of the encoder stack for the fast mode: [layer][tile t][step s][lane][8 halfs] with
@@ -998,6 +1017,10 @@ static int lq_inplace(bool have_ze, int coarse, int K) {
 // MB per launch, HBM traffic 298 -> 270 MB: this L2 writes the rows through whether or not they are overwritten 50 us later), so the
 // gain is the read side of the in-place decisions and 118 MB of address range less, not the 134 MB of stores hoped for.
 static int lq_ze_ring(bool caller_wants_ze, int inplace) { return (!caller_wants_ze && inplace) ? 1 : 0; }
+// ... and where such a launch is a parity launch of a latent of at most 64 columns it stores no z_e at all: the KEEPZ instances
+// (tokenize_body) keep the rows in registers until they are decided.  What is left of the ring: the fast mode's launches of at
+// most 131 072 rows.
+static int lq_keepz(int ring, bool parity, int D) { return (ring && parity && lq_screen_S(D) <= 4) ? 1 : 0; }
 
 // Waves per workgroup of a parity launch (the fast, training and plain-VQVAE instances have 8 only).  Option tok_shape = w8rg1 | w4rg1,
 // read per launch so that a test can switch shapes in-process and honoured at any batch size; otherwise the size rule (round 4): a
@@ -1021,15 +1044,15 @@ __global__ void w2q_pack_kernel(const float* __restrict__ P2, float* __restrict_
 // One kernel instance's launch: its LDS reservation (one slot per instance, per device inside), for the streamed instance the
 // re-layout of layer 2's packed weights into the workspace (one small launch: the weights may have changed since the last call
 // and the library keeps no state), then one persistent workgroup per CU.
-template <int S, bool FAST, bool TRAIN, int WAVES, bool COARSE, bool VQ>
+template <int S, bool FAST, bool TRAIN, int WAVES, bool COARSE, bool VQ, bool KEEPZ = false>
 static int launch_tokenize_as(const TokArgs& a, hipStream_t st) {
     static_assert(WAVES == 8 || !VQ, "the plain VQVAE's instances have 8 waves");
     static LqLdsReserve reserved;
     const size_t lds = fused_lds_bytes<S, FAST>(a.A, a.K);
     if (lds > 160 * 1024) return fail(LIPVQ_EUNSUPPORTED, "tokenize: %zu B of LDS needed", lds);
     void (*kfn)(TokArgs);
-    if constexpr (WAVES == 4) kfn = tokenize_kernel_w4<S, FAST, TRAIN, COARSE>;
-    else kfn = tokenize_kernel<S, FAST, TRAIN, COARSE, VQ>;
+    if constexpr (WAVES == 4) kfn = tokenize_kernel_w4<S, FAST, TRAIN, COARSE, KEEPZ>;
+    else kfn = tokenize_kernel<S, FAST, TRAIN, COARSE, VQ, KEEPZ>;
     if (int rc = lipvq_reserve_lds(reserved, (const void*)kfn, lds, "tokenize")) return rc;
     if (a.w2q) {
         const PackedLayout PL = packed_layout(a.A, 64, 128, a.D);
@@ -1062,6 +1085,10 @@ static int launch_tokenize(const TokArgs& a, hipStream_t st) {
             if (a.coarse && waves == 4) return launch_tokenize_as<S, false, false, 4, true, false>(a, st);
         }
         if (a.coarse) return launch_tokenize_as<S, false, false, 8, true, false>(a, st);
+        if constexpr (S <= 4) {                 // (z_e kept in registers: lq_keepz)
+            if (a.keepz) return waves == 4 ? launch_tokenize_as<S, false, false, 4, false, false, true>(a, st)
+                                           : launch_tokenize_as<S, false, false, 8, false, false, true>(a, st);
+        }
         if (waves == 4) return launch_tokenize_as<S, false, false, 4, false, false>(a, st);
         return launch_tokenize_as<S, false, false, 8, false, false>(a, st);
     } else {                                    // the plain VQVAE's instances (ReLU encoder, per-row scales): both screens
@@ -1152,9 +1179,15 @@ static int tokenize_run(const char* who, bool vq, const float* x, const float* p
     a.coarse = coarse;
     a.inplace = lq_inplace(ze_buf != nullptr, coarse, K);
     a.ze_ring = lq_ze_ring(ze_out != nullptr, a.inplace);
-    const LqSchedule sc = lq_schedule(a.ze_ring);
-    a.defer_ze = sc.defer_ze;
-    a.nt_ze = sc.nt_ze;
+    a.keepz = lq_keepz(a.ze_ring, !vq && !pre0 && !packed16, D);
+    if (a.keepz) {
+        a.ze_out = nullptr;
+        a.ze_ring = 0;
+    } else {
+        const LqSchedule sc = lq_schedule(a.ze_ring);
+        a.defer_ze = sc.defer_ze;
+        a.nt_ze = sc.nt_ze;
+    }
     int rc = LIPVQ_OK;
     lq_dispatch<TOK_TRAIN, TOK_FAST, TOK_PARITY, TOK_VQ>(vq ? TOK_VQ : pre0 ? TOK_TRAIN : packed16 ? TOK_FAST : TOK_PARITY, [&](auto mode) {
         lq_dispatch<32, 64, 128, 208>(D, [&](auto d) { rc = launch_tokenize<(d() + 15) / 16, mode()>(a, st); });
@@ -1180,6 +1213,7 @@ extern "C" int lipvq_tokenize_f32(const float* x, const float* packed, const flo
 // fastest becomes this device's setting for every later lipvq_tokenize_* call of the process.  SYNCHRONOUS (it waits for the
 // stream) and not capturable.  Every launch writes idx / zq / ze_out and accumulates into usage like lipvq_tokenize_f32 -- all four
 // combinations write the same values.  choice (may be NULL): defer_ze | nt_ze << 1;  ms4 (may be NULL): the four times per launch.
+// What it is still for: the launches that store z_e at S <= 4 -- the caller wants z_e, K > LQ_LISTS_ALL_K, the one-product screen.
 extern "C" int lipvq_tokenize_tune_f32(const float* x, const float* packed, const float* const* raw6, const float* codebook,
                                        const void* prep, int64_t* idx, float* zq, int64_t* usage, float* ze_out, void* workspace,
                                        int64_t N, int A, int J0, int J1, int D, int K, void* stream, int launches, int* choice,
@@ -1206,6 +1240,22 @@ extern "C" int lipvq_tokenize_tune_f32(const float* x, const float* packed, cons
             rc = lipvq_tokenize_f32(x, packed, raw6, codebook, prep, idx, zq, usage, ze_out, workspace, N, A, J0, J1, D, K, stream);
     };
     run(launches);                                                       // the chip's clock and power state of a running job
+    // A launch that stores no z_e (KEEPZ) has no store schedule to choose: one timed pass of the one launch there is, reported
+    // under all four names (so that a caller's record keeps its fields), the library defaults as the choice, nothing kept.
+    if (lq_keepz(lq_ze_ring(ze_out != nullptr, lq_inplace(true, lq_screen_coarse(lq_screen_S(D), K), K)), true, D)) {
+        float ms = 0.0f;
+        (void)hipEventRecord(e0, st);
+        run(launches);
+        (void)hipEventRecord(e1, st);
+        if (!rc && hipEventSynchronize(e1) != hipSuccess) rc = fail(LIPVQ_EHIP, "tokenize_tune: hipEventSynchronize");
+        if (!rc && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = fail(LIPVQ_EHIP, "tokenize_tune: hipEventElapsedTime");
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        if (rc) return rc;
+        if (choice) *choice = LQ_DEFAULT_DEFER_ZE | (1 << 1);
+        if (ms4) for (int c = 0; c < 4; ++c) ms4[c] = ms / launches;
+        return LIPVQ_OK;
+    }
     for (int round = 0; round < 2 && !rc; ++round)
         for (int c = 0; c < 4 && !rc; ++c) {
             g_tuned[dev].store(1 + c, std::memory_order_relaxed);

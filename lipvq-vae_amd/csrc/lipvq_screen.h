@@ -213,7 +213,7 @@ __device__ __forceinline__ void lq_screen_core(const f16x8 (&ah)[S], const f16x8
                                                const unsigned char* __restrict__ tiles, int ntiles,
                                                unsigned char* stage0, int tid, const float (&frow)[16], const float (&znr)[16],
                                                float (&m1)[16], float (&m2)[16], int (&k1)[16],
-                                               bool have_def = false, DEFERRED deferred = DEFERRED()) {
+                                               bool have_def = false, DEFERRED deferred = DEFERRED(), bool wave_def = true) {
     using C = ScreenCfg<S, TC_, COARSE>;
     // NB = 2 is NOT a ring this loop can run: with one stage in flight (PD = 1) stage st+1 is only ISSUED at the hand-over in the
     // middle of stage st, and nothing waits for it before the read-ahead crosses into it.  (An experiment build with 2 x 4 tiles
@@ -267,8 +267,12 @@ __device__ __forceinline__ void lq_screen_core(const f16x8 (&ah)[S], const f16x8
 #pragma unroll
     for (int p = 0; p < PD; ++p) stage_dma(p, p);
     static_assert((PD - 1) * CPW + NDEF < 64, "vmcnt immediate");
-    if (NDEF > 0 && have_def) {                   // (launch-uniform)
-        deferred();
+    // wave_def (wave-uniform): this wave's deferred() really issues its NDEF stores -- the caller's sit under a row bound, and a
+    // wave whose rows are all past the end issues none: counting them, its wait would let NDEF of its own stage copies fly on
+    // into the barrier, and the other waves would read stages 0 and 1 before those pieces have landed
+    const bool count_def = NDEF > 0 && have_def && wave_def;
+    if (NDEF > 0 && have_def) deferred();         // (launch-uniform)
+    if (count_def) {
         lq_wait_vmcnt<(PD - 1) * CPW + NDEF>();
     } else {
         lq_wait_vmcnt<(PD - 1) * CPW>();
@@ -310,7 +314,7 @@ __device__ __forceinline__ void lq_screen_core(const f16x8 (&ah)[S], const f16x8
                 // ---- mid-stage hand-over: stage st+1 has landed everywhere (the PD-2 younger stages may still fly); everyone has
                 // left stage st-1, whose buffer is the one stage st+PD goes to
                 // (the first hand-over of a pass with deferred stores: they are younger than stage 1's copy and need not be done)
-                if (NDEF > 0 && have_def && st == 0) lq_wait_vmcnt<(PD >= 2 ? (PD - 2) * CPW : 0) + (PD >= 2 ? NDEF : 0)>();
+                if (count_def && st == 0) lq_wait_vmcnt<(PD >= 2 ? (PD - 2) * CPW : 0) + (PD >= 2 ? NDEF : 0)>();
                 else lq_wait_vmcnt<(PD >= 2 ? (PD - 2) * CPW : 0)>();
                 lq_wg_barrier();
                 int b = buf + PD; b = b >= NB ? b - NB : b;
@@ -839,11 +843,16 @@ __device__ __forceinline__ int lq_lists_row(ZLOAD zload, const float* __restrict
 // certified one (index, usage, z_q gather), so the call has no list kernel behind it: one launch less per call (6 us of a 65 us
 // launch at 65 536 rows).  The number of rows decided this way is still counted into the live word and published as before
 // (LLFQVAE_V4.last_exact_rows, the screen monitor).
-template <bool PACK, int DCH, int DIST>
+// NKEEP > 0 (the fused launch's KEEPZ instances): nothing was stored.  zkeep[t][r] is feature 32 t + 2 r + h of the row this lane
+// screened (row ln: lanes ln and ln + 32 hold it between them); for each row to decide, its two lanes write their NKEEP x 16
+// values to a row buffer of 8 DCH floats behind the LQ_DECIDE_BYTES of scratch, and lq_lists_row reads the row there: the values
+// the stores would have written, in the order the loads would have returned them -- and no global load but the candidates' codes.
+template <bool PACK, int DCH, int DIST, int NKEEP = 0>
 __device__ __forceinline__ bool lq_screen_decide_inplace(const LqDecision& dec, bool certified, bool lists_ok, int& my_k, int64_t row0,
                                                          bool row_valid, int* __restrict__ amb_count, const float* __restrict__ z,
                                                          const float* __restrict__ cb, int K, int lane, unsigned keep_mask,
-                                                         unsigned char* wave_lds) {
+                                                         unsigned char* wave_lds /* NKEEP: LQ_DECIDE_BYTES + 32 DCH bytes */,
+                                                         const f32x16* zkeep = nullptr) {
     const bool need = row_valid && !certified;                          // the same in both halves of the row
     if (__builtin_amdgcn_ballot_w64(need) == 0ull) return certified;    // wave-uniform: most waves have nothing to decide
     const int ln = lane & 31, h = lane >> 5;
@@ -868,9 +877,25 @@ __device__ __forceinline__ bool lq_screen_decide_inplace(const LqDecision& dec, 
     while (lm) {                                                        // wave-uniform
         const int r = __builtin_ctzll(lm);
         lm &= lm - 1ull;
-        const float* zr = z + (size_t)(row0 + r) * D;
-        const int bk = lq_lists_row<DCH, DIST>([&](int f) { return __hip_atomic_load(zr + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
-                                               cb, K, parts + r * 16, lane, true);
+        int bk;
+        if constexpr (NKEEP > 0) {
+            static_assert(NKEEP * 32 == D, "the kept tiles are the row");
+            float* zrow = reinterpret_cast<float*>(wave_lds + LQ_DECIDE_BYTES);
+            if (ln == r) {
+#pragma unroll
+                for (int t = 0; t < NKEEP; ++t)
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) zrow[32 * t + 2 * q + h] = zkeep[t][q];
+            }
+            __builtin_amdgcn_s_waitcnt(0xC07F);                         // lgkmcnt(0): the row has landed
+            __builtin_amdgcn_wave_barrier();
+            bk = lq_lists_row<DCH, DIST>([&](int f) { return zrow[f]; }, cb, K, parts + r * 16, lane, true);
+            __builtin_amdgcn_wave_barrier();                            // the row has been read before the next one is written
+        } else {
+            const float* zr = z + (size_t)(row0 + r) * D;
+            bk = lq_lists_row<DCH, DIST>([&](int f) { return __hip_atomic_load(zr + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
+                                         cb, K, parts + r * 16, lane, true);
+        }
         if (ln == r) { my_k = bk; certified = true; }
     }
     __builtin_amdgcn_wave_barrier();                                    // the parts have been read before the scratch's next use
