@@ -1,4 +1,4 @@
-"""torch.autograd.Function wrappers: the reference's forward()/backward() contract on the HIP path.
+"""torch.autograd.Function wrapper: the reference's forward()/backward() contract on the HIP path.
 
 Forward value flow (LLFQVAE_V4, reference backbone_lfqvae_v5.py:70-84):
     x --mlp3(gelu,gelu,sigmoid; W2 = Lipschitz-normalised)--> z_e --nearest--> (idx, z_q)
@@ -9,17 +9,19 @@ Gradient routing (no straight-through estimator in this variant):
     codebook  -> codebook
     commit    -> to_latent.{W,b,ci}, encoder
 The two latent mse terms have the same VALUE; the library computes it once.
+
+The plain VQVAE (reference backbone.py:38-76) runs the same function: ReLU stacks, the decoder on the straight-through value
+z_st = z_e + (z_q - z_e), loss = m0 + (m1 + commitment_cost m1).  What differs is class data of the two modules (tokenizer.py).
 """
 from __future__ import annotations
 
 import torch
 
 from . import ops
-from .ops import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, DIST_NORM, DIST_SQSUM
+from .tokenizer import LLFQVAE_V4, VQVAE
 
-_ENC_ACTS = (ACT_GELU, ACT_GELU, ACT_SIGMOID)
-_DEC_ACTS = (ACT_GELU, ACT_GELU, ACT_NONE)
-_RELU3 = (ACT_RELU, ACT_RELU, ACT_RELU)
+# (the triples are defined on the tokenizer classes; these names are kept for tests and measurement scripts)
+_ENC_ACTS, _DEC_ACTS, _RELU3 = LLFQVAE_V4._ENC_ACTS, LLFQVAE_V4._DEC_ACTS, VQVAE._ENC_ACTS
 
 
 def _check_versions(ctx, params):
@@ -33,166 +35,67 @@ def _check_versions(ctx, params):
                                f"backward (version {v} -> {p._version}); the gradient would be computed with the new weights")
 
 
-class _LLFQFn(torch.autograd.Function):
-    """(z_latent, loss) = f(x, 14 parameters).  z_latent is non-differentiable (v5:74)."""
+class _TokenizerFn(torch.autograd.Function):
+    """(z_latent, loss) = f(x, the module's parameters in module._params() order).  z_latent is non-differentiable (v5:74)."""
 
     @staticmethod
     def forward(ctx, module, x, *params):
         # (the engine would otherwise hand backward() a materialised [N, D] zero tensor for the non-differentiable z_latent: a 134 MB
         # fill per step at the metric's batch)
         ctx.set_materialize_grads(False)
-        enc_packed, scale, Wn = module._packed_encoder()
-        dec_packed = module._packed_decoder()
-        codebook = module.quantizer.codebook.detach()
+        m = module
+        enc = m._packed_encoder()                        # LLFQVAE_V4: (packed, scale, W_norm) -- its backward reads the last two
+        enc_packed, lipschitz = (enc[0], enc[1:]) if isinstance(enc, tuple) else (enc, ())
+        dec_packed = m._packed_decoder()
+        codebook = m._codebook().detach()
         need_grad = any(ctx.needs_input_grad[2:])
-        screen = module.screen_pays(x.shape[0])          # one routing decision per call (tokenizer._ScreenMonitor)
-        fused_ok = x.shape[0] > module.EXACT_ROWS_MAX and screen and module.fused_shape()
-        if need_grad and fused_ok:
-            # large training batches: encoder + quantizer + everything the backward needs in ONE launch (lipvq_tokenize_train_f32)
-            # instead of mlp3 (saved pre-activations) + the stand-alone screen over z_e
-            idx, z_q, z_e, pre_e = module._tokenize_fused(x, module.code_usage, want_pre=True)
-        elif need_grad:
-            z_e, pre_e = ops.mlp3(x, enc_packed, _ENC_ACTS, save_pre=True)
-            idx, z_q = module._quantize(z_e, module.code_usage, screen=screen)
-        elif fused_ok:
-            # no autograd (rollouts under no_grad, bulk evaluation): the fused encode + quantize launch, z_e written for the loss
-            idx, z_q, z_e = module._tokenize_fused(x, module.code_usage, want_ze=True)
-            pre_e = None
+        # ask the plan (one routing decision per call) and run its route: large batches encoder + quantizer + everything the
+        # backward needs in ONE launch (lipvq_tokenize_train_f32; without autograd lipvq_tokenize_f32, z_e written for the loss),
+        # otherwise mlp3 (saved pre-activations) + one of the three quantizer routes
+        plan = m._plan(x.shape[0], "forward", need_grad, decoder=dec_packed)
+        idx, z_q, z_e, pre_e = m._encode_quantize(x, m.code_usage, plan, enc_packed)
+        w = m._loss_weight
+        if plan.fold_loss:
+            # large batches: the decoder launch sums both squared errors itself (its input rows ARE z_q, its output x_rec); with
+            # ste it forms z_st = z_e + (z_q - z_e) (vq:74) from codebook[idx] and z_e itself, runs on it and stores it -- no
+            # separate straight-through and mse passes over the [N, D] operands
+            out = ops.mlp3_loss(codebook, dec_packed, m._DEC_ACTS, idx, x, z_e, w, m._LOSS, save_pre=need_grad, ste=m._STE)
+            x_rec, pre_d, l3 = out[:3]
+            z_st = out[3] if m._STE else None
         else:
-            z_e, pre_e = ops.mlp3(x, enc_packed, _ENC_ACTS), None
-            idx, z_q = module._quantize(z_e, module.code_usage, screen=screen)
-        # recon + 0.25*commit + 0.25*codebook, left to right (v5:83): (m0 + q) + q with q = 0.25 m1, evaluated on the device
-        if ops.mlp3_loss_supported(x.shape[0], dec_packed):
-            # large batches: the decoder launch sums both squared errors itself (its input rows ARE z_q, its output x_rec)
-            x_rec, pre_d, l3 = ops.mlp3_loss(codebook, dec_packed, _DEC_ACTS, idx, x, z_e, 0.25, ops.LOSS_LLFQ, save_pre=need_grad)
-            loss = l3[2]
-        else:
+            z_st = ops.ste(z_e, z_q) if m._STE else None                                   # vq:74
+            src, gather = (codebook, idx) if z_st is None else (z_st, None)
             if need_grad:
-                x_rec, pre_d = ops.mlp3(codebook, dec_packed, _DEC_ACTS, gather_idx=idx, save_pre=True)
+                x_rec, pre_d = ops.mlp3(src, dec_packed, m._DEC_ACTS, gather_idx=gather, save_pre=True)
             else:
-                x_rec, pre_d = ops.mlp3(codebook, dec_packed, _DEC_ACTS, gather_idx=idx), None
-            loss = ops.mse_pair_loss(x_rec, x, z_q, z_e, 0.25, ops.LOSS_LLFQ)[2]
-        module.last_indices = idx
-        ctx.module = module
+                x_rec, pre_d = ops.mlp3(src, dec_packed, m._DEC_ACTS, gather_idx=gather), None
+            l3 = ops.mse_pair_loss(x_rec, x, z_q, z_e, w, m._LOSS)
+        latent = z_q if z_st is None else z_st
+        m.last_indices = idx
+        ctx.module = m
         if need_grad:
-            ctx.save_for_backward(x, z_e, z_q, idx, x_rec, Wn, scale, *pre_e, *pre_d)
+            ctx.save_for_backward(x, z_e, z_q, idx, x_rec, *lipschitz, *(() if z_st is None else (z_st,)), *pre_e, *pre_d)
             # backward() re-reads the module's live weights (decoder, codebook, encoder, to_latent): remember their versions, so
             # that a parameter update between forward and backward raises, as torch's saved-tensor check would
             ctx.param_versions = tuple(p._version for p in params)
-        ctx.mark_non_differentiable(z_q)
-        return z_q, loss
+        ctx.mark_non_differentiable(latent)
+        return latent, l3[2]
 
     @staticmethod
     def backward(ctx, _g_latent, g_loss):
-        from .backward import llfq_backward
         m = ctx.module
-        _check_versions(ctx, (*m._enc_params(), m.quantizer.codebook, *m._dec_params()))
+        _check_versions(ctx, m._params())
         if g_loss is None:                               # the loss took no part in what is being differentiated
             return (None,) * len(ctx.needs_input_grad)
-        grads = llfq_backward(m, ctx.saved_tensors, g_loss)
-        return (None, None) + tuple(grads)
+        return (None, None) + tuple(m._backward(ctx.saved_tensors, g_loss))
 
 
-def llfq_forward(module, x):
-    params = (*module._enc_params(), module.quantizer.codebook, *module._dec_params())
-    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-        z_latent, loss = _LLFQFn.apply(module, x, *params)
-    else:
-        with torch.no_grad():
-            z_latent, loss = _LLFQFn.forward(_NoCtx(len(params)), module, x, *params)
-    return z_latent, loss
+class _Ctx:
+    """Stand-in for the autograd context where the engine is not used: the no-grad path (rollouts, tokenisation; nothing is
+    saved) and forward_backward() (need_grad: the saved tensors are kept for the backward launches)."""
 
-
-class _NoCtx:
-    """Stand-in for the autograd context on the no-grad path (rollouts, tokenisation)."""
-
-    def __init__(self, n):
-        self.needs_input_grad = (False,) * (n + 2)
-
-    def save_for_backward(self, *a):
-        pass
-
-    def mark_non_differentiable(self, *a):
-        pass
-
-    def set_materialize_grads(self, flag):
-        pass
-
-
-class _VQFn(torch.autograd.Function):
-    """(z_latent, loss) of the plain VQVAE (reference backbone.py:38-76)."""
-
-    @staticmethod
-    def forward(ctx, module, x, *params):
-        ctx.set_materialize_grads(False)                 # (see _LLFQFn.forward)
-        enc_packed = module._packed_encoder()
-        dec_packed = module._packed_decoder()
-        E = module.embedding.weight.detach()
-        need_grad = any(ctx.needs_input_grad[2:])
-        big = x.shape[0] > module.EXACT_ROWS_MAX and module.num_embeddings >= module.FUSED_MIN_CODES
-        screen = module._screen_monitor.use_screen() if big else None          # one routing decision per call
-        if need_grad and big and screen and module.fused_shape():
-            # large training batches: encoder + quantizer + the saved pre-activations in ONE launch (lipvq_vq_tokenize_train_f32)
-            idx, z_q, z_e, pre_e = module._tokenize_fused(x, module.code_usage, want_pre=True)
-        elif need_grad:
-            z_e, pre_e = ops.mlp3(x, enc_packed, _RELU3, save_pre=True)
-            idx, z_q = module._quantize(z_e, module.code_usage, screen=screen)  # vq:57-66 (screened / exact rows / all-pairs: same results)
-        elif big and screen and module.fused_shape():
-            # no autograd (rollouts, bulk evaluation): encoder + quantizer in ONE launch (lipvq_vq_tokenize_f32)
-            idx, z_q, z_e = module._tokenize_fused(x, module.code_usage)
-            pre_e = None
-        else:
-            z_e, pre_e = ops.mlp3(x, enc_packed, _RELU3), None
-            idx, z_q = module._quantize(z_e, module.code_usage, screen=screen)
-        # q_loss = m1 + commitment_cost m1 (vq:69-71); loss = m0 + q_loss (vq:50-51): evaluated on the device
-        if ops.mlp3_loss_supported(x.shape[0], dec_packed):
-            # large batches: the decoder launch forms z_st = z_e + (z_q - z_e) (vq:74) from E[idx] and z_e itself, runs on it, stores
-            # it, and sums both squared errors -- no separate straight-through and mse passes over the [N, D] operands
-            x_rec, pre_d, l3, z_st = ops.mlp3_loss(E, dec_packed, _RELU3, idx, x, z_e, float(module.commitment_cost), ops.LOSS_VQ,
-                                                   save_pre=need_grad, ste=True)
-            loss = l3[2]
-        else:
-            z_st = ops.ste(z_e, z_q)                                   # vq:74
-            if need_grad:
-                x_rec, pre_d = ops.mlp3(z_st, dec_packed, _RELU3, save_pre=True)
-            else:
-                x_rec, pre_d = ops.mlp3(z_st, dec_packed, _RELU3), None
-            loss = ops.mse_pair_loss(x_rec, x, z_q, z_e, float(module.commitment_cost), ops.LOSS_VQ)[2]
-        module.last_indices = idx
-        ctx.module = module
-        if need_grad:
-            ctx.save_for_backward(x, z_e, z_q, z_st, idx, x_rec, *pre_e, *pre_d)
-            ctx.param_versions = tuple(p._version for p in params)
-        ctx.mark_non_differentiable(z_st)
-        return z_st, loss
-
-    @staticmethod
-    def backward(ctx, _g_latent, g_loss):
-        from .backward import vq_backward
-        m = ctx.module
-        _check_versions(ctx, (*m._enc_params(), *m._dec_params(), m.embedding.weight))
-        if g_loss is None:
-            return (None,) * len(ctx.needs_input_grad)
-        grads = vq_backward(m, ctx.saved_tensors, g_loss)
-        return (None, None) + tuple(grads)
-
-
-def vq_forward(module, x):
-    params = (*module._enc_params(), *module._dec_params(), module.embedding.weight)
-    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-        return _VQFn.apply(module, x, *params)
-    with torch.no_grad():
-        return _VQFn.forward(_NoCtx(len(params)), module, x, *params)
-
-
-# ---------------------------------------------------------------------------------------------------
-# engine-free forward + backward (used under HIP-graph capture, where the autograd engine's per-parameter
-# AccumulateGrad nodes -- bound to whatever stream first produced a gradient -- must stay out of the way)
-# ---------------------------------------------------------------------------------------------------
-
-class _ManualCtx:
-    def __init__(self, n):
-        self.needs_input_grad = (False, False) + (True,) * n
+    def __init__(self, n_params, need_grad):
+        self.needs_input_grad = (False, False) + (need_grad,) * n_params
         self.saved_tensors = ()
         self.module = None
         self.param_versions = None
@@ -207,20 +110,25 @@ class _ManualCtx:
         pass
 
 
+def tokenizer_forward(module, x):
+    params = module._params()
+    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        return _TokenizerFn.apply(module, x, *params)
+    with torch.no_grad():
+        return _TokenizerFn.forward(_Ctx(len(params), False), module, x, *params)
+
+
+llfq_forward = vq_forward = tokenizer_forward
+
+
 def forward_backward(module, x):
     """(z_latent, loss, params, grads) with grads = dloss/dparams computed by the library's backward kernels,
-    without touching torch.autograd.  params are in the order of the returned gradients."""
-    from .backward import llfq_backward, vq_backward
-    from .tokenizer import LLFQVAE_V4
+    without touching torch.autograd.  params are in the order of the returned gradients.  Engine-free: used under HIP-graph
+    capture, where the autograd engine's per-parameter AccumulateGrad nodes -- bound to whatever stream first produced a
+    gradient -- must stay out of the way."""
     with torch.no_grad():
-        if isinstance(module, LLFQVAE_V4):
-            params = (*module._enc_params(), module.quantizer.codebook, *module._dec_params())
-            ctx = _ManualCtx(len(params))
-            z, loss = _LLFQFn.forward(ctx, module, x, *params)
-            grads = llfq_backward(module, ctx.saved_tensors, torch.ones((), device=x.device, dtype=x.dtype))
-        else:
-            params = (*module._enc_params(), *module._dec_params(), module.embedding.weight)
-            ctx = _ManualCtx(len(params))
-            z, loss = _VQFn.forward(ctx, module, x, *params)
-            grads = vq_backward(module, ctx.saved_tensors, torch.ones((), device=x.device, dtype=x.dtype))
+        params = module._params()
+        ctx = _Ctx(len(params), True)
+        z, loss = _TokenizerFn.forward(ctx, module, x, *params)
+        grads = module._backward(ctx.saved_tensors, torch.ones((), device=x.device, dtype=x.dtype))
     return z, loss, params, grads

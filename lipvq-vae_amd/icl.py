@@ -279,7 +279,7 @@ class GraphedTokenizerStep:
             vq_vae_model.last_indices = saved_last
         mon = getattr(vq_vae_model, "_screen_monitor", None)
         if mon is not None:
-            mon.__init__()
+            mon.reset()
         torch.cuda.synchronize()
         self.model.invalidate_caches()
         self.graph = torch.cuda.CUDAGraph()

@@ -20,11 +20,9 @@ import torch
 
 from . import ops
 from .ops import DIST_NORM
+from .tokenizer import _TokenizerBase
 
 __all__ = ["kmeans", "lloyd_step", "assign", "draws"]
-
-# rows up to which assign() takes the small-batch exact kernel (the tokenizers' EXACT_ROWS_MAX)
-_ROWS_MAX = 2048
 
 
 def draws(n: int, generator=None, device=None) -> torch.Tensor:
@@ -36,7 +34,7 @@ def draws(n: int, generator=None, device=None) -> torch.Tensor:
 
 def assign(z, codebook, dist: int = DIST_NORM, usage=None):
     """Exact nearest-code indices of the rows of z (the tokenizers' decision, first minimum); usage [K] int64 is accumulated."""
-    if z.shape[0] <= _ROWS_MAX:
+    if z.shape[0] <= _TokenizerBase.EXACT_ROWS_MAX:     # the small-batch exact kernel up to the tokenizers' own threshold
         return ops.nearest_rows(z, codebook, usage=usage, want_zq=False, dist=dist)[0]
     return ops.nearest(z, codebook, dist, usage=usage, want_zq=False)[0]
 

@@ -336,6 +336,18 @@ def wgrad(G, H, h_act=ACT_NONE, hidx=None, want_bias=True):
     return gW, gb
 
 
+def _scatter_route(N, K, D, deterministic=None):
+    """THE rule of scatter_add / scatter_add_vq: "sequential_sorted" | "sequential_scan" where the sums must be in ascending row
+    order (deterministic=None follows torch.are_deterministic_algorithms_enabled()), otherwise "sorted" -- the counting sort,
+    for the shapes it takes from 65 536 rows on -- or "atomics"."""
+    if deterministic is None:
+        deterministic = torch.are_deterministic_algorithms_enabled()
+    sortable = bool(lib.lipvq_scatter_add_sorted_supported(N, K, D))
+    if deterministic:
+        return "sequential_sorted" if sortable else "sequential_scan"
+    return "sorted" if (sortable and N >= 65536) else "atomics"
+
+
 def scatter_add(g, idx, K, deterministic=None, route=None):
     """gC[k] = sum of the rows of g whose idx is k (the gather's backward / index_add_).  deterministic=None follows
     torch.are_deterministic_algorithms_enabled(): strictly ascending row order per code, bit-identical to a sequential fp32
@@ -345,14 +357,8 @@ def scatter_add(g, idx, K, deterministic=None, route=None):
     route = "atomics" | "sorted" | "sequential_sorted" | "sequential_scan" forces one (tests, measurements)."""
     g, idx = _chk(g, "g"), _chk(idx, "idx", torch.int64)
     N, D = g.shape
-    if deterministic is None:
-        deterministic = torch.are_deterministic_algorithms_enabled()
     if route is None:
-        sortable = bool(lib.lipvq_scatter_add_sorted_supported(N, K, D))
-        if deterministic:
-            route = "sequential_sorted" if sortable else "sequential_scan"
-        else:
-            route = "sorted" if (sortable and N >= 65536) else "atomics"
+        route = _scatter_route(N, K, D, deterministic)
     gC = torch.zeros((K, D), device=g.device, dtype=torch.float32)
     with _on(g.device):
         if route == "sequential_scan":
@@ -380,17 +386,14 @@ def scatter_add_vq(g, ze, table, idx, alpha, gscale=None, zq=None, deterministic
     K = table.shape[0]
     if gscale is not None:
         gscale = _chk(gscale.reshape(1), "gscale")
-    if deterministic is None:
-        deterministic = torch.are_deterministic_algorithms_enabled()
-    sortable = bool(lib.lipvq_scatter_add_sorted_supported(N, K, D))
-    if not sortable or (not deterministic and N < 65536):
-        return scatter_add(scaled_diff(zq if zq is not None else table[idx], ze, alpha, gscale=gscale, c=g), idx, K,
-                           deterministic=deterministic)
+    route = _scatter_route(N, K, D, deterministic)
+    if route in ("sequential_scan", "atomics"):
+        return scatter_add(scaled_diff(zq if zq is not None else table[idx], ze, alpha, gscale=gscale, c=g), idx, K, route=route)
     gC = torch.zeros((K, D), device=ze.device, dtype=torch.float32)
     ws = torch.empty(lib.lipvq_scatter_add_sorted_workspace_bytes(N, K, D), device=ze.device, dtype=torch.uint8)
     with _on(ze.device):
         check(lib.lipvq_scatter_add_sorted_vq_f32(_ptr(g), _ptr(ze), _ptr(table), float(alpha), _ptr(gscale), _ptr(idx), _ptr(gC),
-                                                  _ptr(ws), N, K, D, 1 if deterministic else 0, _stream()),
+                                                  _ptr(ws), N, K, D, 1 if route == "sequential_sorted" else 0, _stream()),
               "lipvq_scatter_add_sorted_vq_f32")
     return gC
 

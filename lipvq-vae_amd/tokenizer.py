@@ -11,7 +11,7 @@
 The ``nn.Linear`` / container sub-modules exist only to own the parameters under the
 reference's names; they are never called.  All arithmetic is issued through
 ``lipvq_vae_amd.ops`` (C ABI -> hand-written gfx950 kernels).  Gradients are produced by the
-library's backward kernels through one ``torch.autograd.Function`` per variant, so
+library's backward kernels through one ``torch.autograd.Function`` for both variants, so
 ``loss.backward(); AdamW.step()`` in the ICRT loop (robomimic/algo/icl.py:885-889,968-970)
 works unchanged.
 
@@ -22,10 +22,13 @@ only: the BASELINE metric's path) and ``perplexity()``; opt-in, never called by 
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 import torch.nn as nn
 
 from . import ops
+from .backward import llfq_backward, vq_backward
 from .ops import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, DIST_NORM, DIST_SQSUM
 
 __all__ = ["LLFQVAE_V4", "VQVAE", "LipschitzMLP", "LFQQuantizer"]
@@ -103,6 +106,10 @@ class _ScreenMonitor:
     PROBE_EVERY = 16
 
     def __init__(self):
+        self.reset()
+
+    def reset(self):
+        """Forget every reading (a new codebook; a graph capture that must not inherit its warm-up steps' readings)."""
         self._pending = None
         self.bypass_calls = 0
         self.last_fraction = None
@@ -138,7 +145,34 @@ class _ScreenMonitor:
         self._pending = (ev, host, int(n), bool(coarse))
 
 
+# The encoder + quantizer routes of a call (identical results on every one):
+FUSED = "fused"            # encoder + screen in ONE persistent launch (csrc/lipvq_fused.hip), z_e never re-read
+ROWS = "rows"              # mlp3, then the exact kernel on every row (no prepared codebook)
+SCREENED = "screened"      # mlp3, then the stand-alone MFMA screen + exact re-scoring of the rows it cannot certify
+ALL_PAIRS = "all_pairs"    # mlp3, then the all-pairs exact kernel
+
+
+class _Plan(NamedTuple):
+    """What _TokenizerBase._plan decided for one call."""
+    route: str             # FUSED | ROWS | SCREENED | ALL_PAIRS
+    keep: str | None       # what the encoder stage hands back besides (idx, z_q): "pre" (z_e + the three pre-activations a
+    #                        training step saves), "ze" (z_e, for the loss) or None
+    fast: bool             # the fused launch runs the encoder's GEMMs on fp16 MFMAs (tokenize(mode="fast"))
+    fold_loss: bool        # the decoder launch sums both squared errors itself (mlp3_loss) instead of mlp3 + mse_pair_loss
+
+
 class _TokenizerBase(nn.Module):
+    """What the two tokenizers share: derived buffers, codebook maintenance and the ROUTING POLICY (_plan), with everything that
+    differs between them as class data: _DIST, the activation triples, the loss form, the thresholds below."""
+
+    # rows up to which every row is decided by the exact kernel, without a prepared codebook or a screen launch: measured
+    # (scripts/measure_quantize_small.py, K = 1024) exact rows vs screen [+ codebook preparation]: D = 208: 36 vs 75 [+69] us at
+    # N = 80, 74 vs 122 [+69] at 2048, 143 vs 89 [+69] at 4096
+    EXACT_ROWS_MAX = 2048
+    SCREEN_MIN_CODES = 0          # codebook size from which the stand-alone screen is a route at all
+    FUSED_MIN_CODES = 0           # ... and the fused launch
+    FUSED_SMALL_TOKENIZE = False  # tokenize() takes the fused launch up to EXACT_ROWS_MAX rows too (forward() never does)
+
     def _init_extras(self, K):
         self._screen_monitor = _ScreenMonitor()
         self.register_buffer("code_usage", torch.zeros(K, dtype=torch.int64), persistent=False)
@@ -178,6 +212,14 @@ class _TokenizerBase(nn.Module):
             self.invalidate_caches()
         return out
 
+    def _packed_decoder(self):
+        return self._dec_cache.get(self._dec_params(), lambda: ops.mlp3_pack(*(t.detach() for t in self._dec_params())))
+
+    def _enc_packed(self):
+        """The packed encoder stack alone (LLFQVAE_V4._packed_encoder returns the Lipschitz scale and W_norm with it)."""
+        p = self._packed_encoder()
+        return p[0] if isinstance(p, tuple) else p
+
     # -- opt-in codebook maintenance (extensions, not reference behaviour: kmeans.py) -------------------
     def _codebook_written(self):
         """After an in-place write through a raw pointer: bump the version (autograd's saved-tensor checks), drop the prepared
@@ -185,7 +227,7 @@ class _TokenizerBase(nn.Module):
         its all-pairs bypass)."""
         torch.autograd.graph.increment_version(self._codebook())
         self.invalidate_caches()
-        self._screen_monitor = _ScreenMonitor()
+        self._screen_monitor.reset()
 
     @torch.no_grad()
     def init_codebook_(self, x, iters: int = 10, generator=None, seed_rows=None):
@@ -236,6 +278,121 @@ class _TokenizerBase(nn.Module):
             raise TypeError(f"expected float32 actions, got {x.dtype}")
         return x.contiguous()
 
+    # -- which launches a call runs -------------------------------------------------
+    def fused_shape(self) -> bool:
+        K, D = self._codebook().shape
+        return ops.tokenize_supported(self.feature_dim, 64, self.hidden_dim, D, K)
+
+    def _plan(self, n, entry, need_grad=False, mode="parity", screen=None, decoder=None) -> _Plan:
+        """THE routing policy: which encoder + quantizer route a call of n rows runs, and whether its decoder folds the loss.
+        entry = "tokenize" | "forward" | "quantize" (_quantize called on its own: z_e exists, no fused launch); decoder = the
+        packed decoder stack of a forward.  The screen monitor is consulted at most ONCE, only for a batch above EXACT_ROWS_MAX
+        (the exact kernel copes with all the rows of a smaller one) and only where a screened route exists; screen = an answer
+        the caller already has.  The one difference between the entry points: tokenize() takes the fused launch at small batches as
+        well where FUSED_SMALL_TOKENIZE says so (the metric's path; its small launch has its own workgroup shape), a small forward()
+        keeps mlp3 + exact rows, which hands it the pre-activations or z_e it saves."""
+        K, D = self._codebook().shape
+        if mode != "parity":
+            if mode != "fast":
+                raise ValueError(f"unknown tokenize mode {mode!r}")
+            if not ops.tokenize_fast_supported(self.feature_dim, 64, self.hidden_dim, D, K):
+                raise RuntimeError("tokenize(mode='fast') needs the fast kernel's shapes (hidden 64/128, D in {32, 64, 128})")
+        keep = "pre" if need_grad else ("ze" if entry == "forward" else None)
+        fold = decoder is not None and ops.mlp3_loss_supported(n, decoder)
+        fusable = entry != "quantize" and K >= self.FUSED_MIN_CODES            # (... and fused_shape(), asked where it matters)
+        if n == 0:
+            route = ALL_PAIRS
+        elif self._small(n):
+            # training-step batches: the exact kernel on every row beats preparing the codebook + one screen launch
+            if fusable and entry == "tokenize" and self.FUSED_SMALL_TOKENIZE and self.fused_shape():
+                route = FUSED
+            else:
+                route = ROWS if self._screenable(K, D) else ALL_PAIRS
+        else:
+            fusable = fusable and self.fused_shape()
+            if (fusable or self._screenable(K, D)) and (self.screen_pays(n) if screen is None else screen):
+                route = FUSED if fusable else SCREENED
+            else:
+                route = ALL_PAIRS
+        return _Plan(route, keep, mode == "fast", fold)
+
+    def _screenable(self, K, D):
+        return K >= self.SCREEN_MIN_CODES and ops.nearest_screen_supported(K, D)
+
+    def _small(self, n_rows):
+        return n_rows <= self.EXACT_ROWS_MAX
+
+    def screen_pays(self, n_rows: int) -> bool:
+        """Small batches never consult the monitor (the exact kernel copes with all of their rows); large ones ask it whether the
+        screen has been certifying its rows (see _ScreenMonitor)."""
+        return self._small(n_rows) or self._screen_monitor.use_screen()
+
+    def _quantize(self, z_e, usage, screen=None, route=None):
+        """(idx, z_q) of v5:37-48 / vq:57-66 (``self._DIST``; first minimum) on one of the three unfused routes: exact rows, MFMA
+        screen + exact re-scoring where the latent width has a screening instance and the codebook is large enough to pay for
+        it, the all-pairs exact kernel otherwise.  Identical results on every route."""
+        cb = self._codebook().detach()
+        if route is None:
+            route = self._plan(z_e.shape[0], "quantize", screen=screen).route
+        if route == SCREENED:
+            idx, zq, ws = ops.nearest_screened(z_e, cb, self._prepared(cb), usage=usage, return_workspace=True, dist=self._DIST)
+            self._screened(ws, z_e.shape[0], ops.screen_is_coarse(*cb.shape))
+            return idx, zq
+        self.last_exact_rows = None
+        if route == ROWS:
+            return ops.nearest_rows(z_e, cb, usage=usage, dist=self._DIST)
+        idx, zq, _ = ops.nearest(z_e, cb, self._DIST, usage=usage)
+        return idx, zq
+
+    def _encode_quantize(self, x, usage, plan, packed=None):
+        """(idx, z_q, z_e, pre) on the plan's route; z_e / pre are None where the plan does not keep them (fused launch)."""
+        if plan.route == FUSED:
+            out = self._tokenize_fused(x, usage, want_ze=plan.keep == "ze", fast=plan.fast, want_pre=plan.keep == "pre")
+            return out if plan.keep == "pre" else (*out, None)
+        if packed is None:
+            packed = self._enc_packed()
+        if plan.keep == "pre":
+            z_e, pre = ops.mlp3(x, packed, self._ENC_ACTS, save_pre=True)
+        else:
+            z_e, pre = ops.mlp3(x, packed, self._ENC_ACTS), None
+        idx, zq = self._quantize(z_e, usage, route=plan.route)
+        return idx, zq, z_e, pre
+
+    # prologue and epilogue of a screened launch (fused or stand-alone)
+    def _prepared(self, cb):
+        return self._cb_cache.get((self._codebook(),), lambda: ops.nearest_prepare(cb))
+
+    def _fused_operands(self, x):
+        """(codebook, prepared codebook, workspace) of a fused launch; the workspace (row list) is reused across calls."""
+        cb = self._codebook().detach()
+        prep = self._prepared(cb)
+        key = (x.shape[0], x.device)
+        if self._tok_ws_key != key:
+            self._tok_ws, self._tok_ws_key = ops.tokenize_workspace(x.shape[0], cb.shape[1], x.device), key
+        return cb, prep, self._tok_ws
+
+    def _screened(self, ws, n, coarse):
+        self.last_exact_rows = ws
+        self._screen_monitor.record(ws, n, coarse)
+
+    # -- the metric's path ------------------------------------------------------------------
+    @torch.no_grad()
+    def encode(self, x):
+        """z_e = to_latent(encoder(x))   (v5:71-72; vq:38-43)."""
+        return ops.mlp3(self._as_rows(x), self._enc_packed(), self._ENC_ACTS)
+
+    def _tokenize(self, x, count_usage, mode="parity"):
+        x = self._as_rows(x)
+        plan = self._plan(x.shape[0], "tokenize", mode=mode)
+        idx, zq, z_e, _ = self._encode_quantize(x, self.code_usage if count_usage else None, plan)
+        self.last_indices = idx
+        return idx, zq, z_e
+
+    # -- reference forward ------------------------------------------------------------------
+    def forward(self, x):
+        from .autograd import tokenizer_forward
+        return tokenizer_forward(self, self._as_rows(x))
+
 
 class LLFQVAE_V4(_TokenizerBase):
     def __init__(self, feature_dim, latent_dim, num_codes=1024, hidden_dim=128):
@@ -252,6 +409,14 @@ class LLFQVAE_V4(_TokenizerBase):
         self._init_extras(num_codes)
 
     _DIST = DIST_NORM
+    _ENC_ACTS = (ACT_GELU, ACT_GELU, ACT_SIGMOID)
+    _DEC_ACTS = (ACT_GELU, ACT_GELU, ACT_NONE)
+    # recon + 0.25*commit + 0.25*codebook, left to right (v5:83): (m0 + q) + q with q = 0.25 m1, evaluated on the device
+    _LOSS = ops.LOSS_LLFQ
+    _loss_weight = 0.25
+    _STE = False                  # the decoder runs on codebook[idx] (no straight-through estimator, v5:74-81); z_latent = z_q
+    _backward = llfq_backward
+    FUSED_SMALL_TOKENIZE = True
 
     def _codebook(self):
         return self.quantizer.codebook
@@ -265,6 +430,9 @@ class LLFQVAE_V4(_TokenizerBase):
         return (self.decoder[0].weight, self.decoder[0].bias, self.decoder[2].weight, self.decoder[2].bias,
                 self.to_output.weight, self.to_output.bias)
 
+    def _params(self):
+        return (*self._enc_params(), self.quantizer.codebook, *self._dec_params())
+
     def _packed_encoder(self):
         def build():
             w0, b0, w1, b1, W, b, ci = (t.detach() for t in self._enc_params())
@@ -272,75 +440,26 @@ class LLFQVAE_V4(_TokenizerBase):
             return ops.mlp3_pack(w0, b0, w1, b1, Wn, b), scale, Wn
         return self._enc_cache.get(self._enc_params(), build)
 
-    def _packed_decoder(self):
-        def build():
-            return ops.mlp3_pack(*(t.detach() for t in self._dec_params()))
-        return self._dec_cache.get(self._dec_params(), build)
-
-    # rows up to which _quantize skips the screen: measured (scripts/measure_quantize_small.py, K = 1024) exact rows vs
-    # screen [+ codebook preparation]: D = 208: 36 vs 75 [+69] us at N = 80, 74 vs 122 [+69] at 2048, 143 vs 89 [+69] at 4096
-    EXACT_ROWS_MAX = 2048
-
-    def screen_pays(self, n_rows: int) -> bool:
-        """ONE routing decision per call: small batches never consult the monitor (the exact kernel copes with all of their rows);
-        large ones ask it whether the screen has been certifying its rows (see _ScreenMonitor)."""
-        return n_rows <= self.EXACT_ROWS_MAX or self._screen_monitor.use_screen()
-
-    def _quantize(self, z_e, usage, screen=None):
-        """(idx, z_q) of v5:37-48: MFMA screen + exact re-scoring where the latent width has a
-        screening instance, the all-pairs exact kernel otherwise.  Identical results either way."""
-        cb = self.quantizer.codebook.detach()
-        if screen is None:
-            screen = self.screen_pays(z_e.shape[0])
-        if ops.nearest_screen_supported(cb.shape[0], cb.shape[1]) and 0 < z_e.shape[0] <= self.EXACT_ROWS_MAX:
-            # training-step batches: the exact kernel on every row beats preparing the codebook + one screen launch
-            self.last_exact_rows = None
-            return ops.nearest_rows(z_e, cb, usage=usage)
-        if ops.nearest_screen_supported(cb.shape[0], cb.shape[1]) and z_e.shape[0] > 0 and screen:
-            prep = self._cb_cache.get((self.quantizer.codebook,), lambda: ops.nearest_prepare(cb))
-            idx, zq, ws = ops.nearest_screened(z_e, cb, prep, usage=usage, return_workspace=True)
-            self.last_exact_rows = ws
-            self._screen_monitor.record(ws, z_e.shape[0], ops.screen_is_coarse(cb.shape[0], cb.shape[1]))
-            return idx, zq
-        self.last_exact_rows = None
-        idx, zq, _ = ops.nearest(z_e, cb, DIST_NORM, usage=usage)
-        return idx, zq
-
-    # -- the metric's path ------------------------------------------------------------------
-    @torch.no_grad()
-    def encode(self, x):
-        """z_e = to_latent(encoder(x))   (v5:71-72)."""
-        packed, _, _ = self._packed_encoder()
-        return ops.mlp3(self._as_rows(x), packed, (ACT_GELU, ACT_GELU, ACT_SIGMOID))
+    def _fused_inputs(self, x):
+        """(packed encoder, its six raw tensors -- the exact stage re-encodes uncertified rows with them --, codebook, prepared
+        codebook, workspace) of the fused launch and of its tuner."""
+        packed, _, Wn = self._packed_encoder()
+        w0, b0, w1, b1, _, b2, _ = (t.detach() for t in self._enc_params())
+        return (packed, (w0, b0, w1, b1, Wn, b2), *self._fused_operands(x))
 
     def _tokenize_fused(self, x, usage, want_ze=False, fast=False, want_pre=False):
         """(idx, z_q, z_e | None) from ONE persistent launch: z_e never leaves registers unless asked for
-        (csrc/lipvq_fused.hip).  Caller checks ops.tokenize_supported()."""
-        cb = self.quantizer.codebook.detach()
-        packed, _, Wn = self._packed_encoder()
-        w0, b0, w1, b1, _, b2, _ = (t.detach() for t in self._enc_params())
-        prep = self._cb_cache.get((self.quantizer.codebook,), lambda: ops.nearest_prepare(cb))
-        key = (x.shape[0], x.device)
-        if self._tok_ws_key != key:                          # the scratch (row list) is reused across calls
-            self._tok_ws, self._tok_ws_key = ops.tokenize_workspace(x.shape[0], self.latent_dim, x.device), key
+        (csrc/lipvq_fused.hip).  want_pre (training forward): (idx, z_q, z_e, pre) with the three pre-activations as well.
+        Caller checks fused_shape()."""
+        packed, raw, cb, prep, ws = self._fused_inputs(x)
         packed16 = None
         if fast:
-            packed16 = self._enc16_cache.get((w0, w1, self.to_latent.W, self.to_latent.ci),
-                                             lambda: ops.mlp3_pack_f16(w0, w1, Wn))
-        if want_pre:                                         # training forward: z_e and the three pre-activations as well
-            idx, zq, ze, ws, pre = ops.tokenize(x, packed, (w0, b0, w1, b1, Wn, b2), cb, prep, usage=usage, workspace=self._tok_ws,
-                                                want_pre=True)
-            self.last_exact_rows = ws
-            self._screen_monitor.record(ws, x.shape[0], ops.screen_is_coarse(self.num_codes, self.latent_dim))
-            return idx, zq, ze, pre
-        idx, zq, ze, ws = ops.tokenize(x, packed, (w0, b0, w1, b1, Wn, b2), cb, prep, usage=usage, want_ze=want_ze,
-                                       workspace=self._tok_ws, packed16=packed16)
-        self.last_exact_rows = ws
-        self._screen_monitor.record(ws, x.shape[0], (not fast) and ops.screen_is_coarse(self.num_codes, self.latent_dim))
-        return idx, zq, ze
-
-    def fused_shape(self) -> bool:
-        return ops.tokenize_supported(self.feature_dim, 64, self.hidden_dim, self.latent_dim, self.num_codes)
+            packed16 = self._enc16_cache.get((raw[0], raw[2], self.to_latent.W, self.to_latent.ci),
+                                             lambda: ops.mlp3_pack_f16(raw[0], raw[2], raw[4]))
+        out = ops.tokenize(x, packed, raw, cb, prep, usage=usage, want_ze=want_ze, workspace=ws, packed16=packed16,
+                           want_pre=want_pre)
+        self._screened(out[3], x.shape[0], (not fast) and ops.screen_is_coarse(*cb.shape))
+        return (*out[:3], out[4]) if want_pre else out[:3]
 
     @torch.no_grad()
     def tune(self, x, launches=150):
@@ -351,11 +470,8 @@ class LLFQVAE_V4(_TokenizerBase):
         x = self._as_rows(x)
         if x.shape[0] == 0 or not self.fused_shape():
             return None
-        cb = self.quantizer.codebook.detach()
-        packed, _, Wn = self._packed_encoder()
-        w0, b0, w1, b1, _, b2, _ = (t.detach() for t in self._enc_params())
-        prep = self._cb_cache.get((self.quantizer.codebook,), lambda: ops.nearest_prepare(cb))
-        choice, ms = ops.tokenize_tune(x, packed, (w0, b0, w1, b1, Wn, b2), cb, prep, launches=launches)
+        packed, raw, cb, prep, ws = self._fused_inputs(x)
+        choice, ms = ops.tokenize_tune(x, packed, raw, cb, prep, workspace=ws, launches=launches)
         if choice < 0:                                       # latent widths above 64: nothing device-dependent to choose
             return None
         return {"choice": {"defer_ze": choice & 1, "nt_ze": (choice >> 1) & 1},
@@ -368,31 +484,12 @@ class LLFQVAE_V4(_TokenizerBase):
         mode="parity" (default): fp32 everywhere, indices bit-identical to the CPU oracle / the reference.
         mode="fast": the encoder's GEMMs on fp16 MFMAs (fp32 accumulation) -- SURVEY section 7's throughput mode; a
         fraction of a percent of the indices differ from parity mode, always between near-equidistant codes."""
-        if mode not in ("parity", "fast"):
-            raise ValueError(f"unknown tokenize mode {mode!r}")
-        x = self._as_rows(x)
-        usage = self.code_usage if count_usage else None
-        shape = (self.feature_dim, 64, self.hidden_dim, self.latent_dim, self.num_codes)
-        if mode == "fast" and not ops.tokenize_fast_supported(*shape):
-            raise RuntimeError("tokenize(mode='fast') needs the fast kernel's shapes (hidden 64/128, D in {32, 64, 128})")
-        screen = self.screen_pays(x.shape[0])
-        if x.shape[0] > 0 and screen and self.fused_shape():
-            idx, zq, _ = self._tokenize_fused(x, usage, fast=(mode == "fast"))
-        else:
-            idx, zq = self._quantize(self.encode(x), usage, screen=screen)
-        self.last_indices = idx
-        return idx, zq
+        return self._tokenize(x, count_usage, mode)[:2]
 
     @torch.no_grad()
     def decode(self, indices):
         """x_recon = to_output(decoder(codebook[indices]))   (v5:75-76)."""
-        return ops.mlp3(self.quantizer.codebook.detach(), self._packed_decoder(), (ACT_GELU, ACT_GELU, ACT_NONE),
-                        gather_idx=indices)
-
-    # -- reference forward ------------------------------------------------------------------
-    def forward(self, x):
-        from .autograd import llfq_forward
-        return llfq_forward(self, self._as_rows(x))
+        return ops.mlp3(self.quantizer.codebook.detach(), self._packed_decoder(), self._DEC_ACTS, gather_idx=indices)
 
 
 class VQVAE(_TokenizerBase):
@@ -411,6 +508,18 @@ class VQVAE(_TokenizerBase):
         self._init_extras(num_embeddings)
 
     _DIST = DIST_SQSUM
+    _ENC_ACTS = _DEC_ACTS = (ACT_RELU, ACT_RELU, ACT_RELU)
+    # q_loss = m1 + commitment_cost m1 (vq:69-71); loss = m0 + q_loss (vq:50-51): evaluated on the device
+    _LOSS = ops.LOSS_VQ
+    _loss_weight = property(lambda self: float(self.commitment_cost))
+    _STE = True                   # the decoder runs on z_st = z_e + (z_q - z_e) (vq:74), which is also the returned latent
+    _backward = vq_backward
+    hidden_dim = 128              # (the encoder's second width, fixed in the reference: vq:20)
+    # the all-pairs kernel stays the route for small codebooks: at K = 128 (the reference's default, vq:7) it runs at its VALU
+    # bound in 0.4 ms per 524 288 rows, where a screen launch + its uncertified rows would gain nothing
+    SCREEN_MIN_CODES = 256
+    # ... but the FUSED launch (encoder + screen in one kernel, z_e never re-read) beats encoder + all-pairs from far fewer codes on
+    FUSED_MIN_CODES = 64
 
     def _codebook(self):
         return self.embedding.weight
@@ -423,87 +532,26 @@ class VQVAE(_TokenizerBase):
         d = self.decoder
         return (d[0].weight, d[0].bias, d[2].weight, d[2].bias, d[4].weight, d[4].bias)
 
+    def _params(self):
+        return (*self._enc_params(), *self._dec_params(), self.embedding.weight)
+
     def _packed_encoder(self):
         return self._enc_cache.get(self._enc_params(),
                                    lambda: ops.mlp3_pack(*(t.detach() for t in self._enc_params())))
 
-    def _packed_decoder(self):
-        return self._dec_cache.get(self._dec_params(),
-                                   lambda: ops.mlp3_pack(*(t.detach() for t in self._dec_params())))
-
-    @torch.no_grad()
-    def encode(self, x):
-        return ops.mlp3(self._as_rows(x), self._packed_encoder(), (ACT_RELU, ACT_RELU, ACT_RELU))
-
-    # rows up to which the exact re-scoring kernel decides every row (no codebook preparation), as in LLFQVAE_V4._quantize
-    EXACT_ROWS_MAX = 2048
-    # the all-pairs kernel stays the route for small codebooks: at K = 128 (the reference's default, vq:7) it runs at its VALU
-    # bound in 0.4 ms per 524 288 rows, where a screen launch + its uncertified rows would gain nothing
-    SCREEN_MIN_CODES = 256
-    # ... but the FUSED launch (encoder + screen in one kernel, z_e never re-read) beats encoder + all-pairs from far fewer codes on
-    FUSED_MIN_CODES = 64
-
-    def _quantize(self, z_e, usage, screen=None):
-        """(idx, z_q) of vq:57-66 (`pow(2).sum(-1)`, argmin, embedding lookup): MFMA screen + exact re-scoring where the latent
-        width has a screening instance and the codebook is large enough to pay for it, the all-pairs exact kernel otherwise.
-        Identical results on every route."""
-        cb = self.embedding.weight.detach()
-        K, D = cb.shape
-        n = z_e.shape[0]
-        if ops.nearest_screen_supported(K, D) and K >= self.SCREEN_MIN_CODES and n > 0:
-            if n <= self.EXACT_ROWS_MAX:
-                self.last_exact_rows = None
-                return ops.nearest_rows(z_e, cb, usage=usage, dist=DIST_SQSUM)
-            if screen is None:
-                screen = self._screen_monitor.use_screen()
-            if screen:
-                prep = self._cb_cache.get((self.embedding.weight,), lambda: ops.nearest_prepare(cb))
-                idx, zq, ws = ops.nearest_screened(z_e, cb, prep, usage=usage, return_workspace=True, dist=DIST_SQSUM)
-                self.last_exact_rows = ws
-                self._screen_monitor.record(ws, n, ops.screen_is_coarse(K, D))
-                return idx, zq
-        self.last_exact_rows = None
-        idx, zq, _ = ops.nearest(z_e, cb, DIST_SQSUM, usage=usage)
-        return idx, zq
-
-    def fused_shape(self) -> bool:
-        return ops.tokenize_supported(self.feature_dim, 64, 128, self.latent_dim, self.num_embeddings)
-
-    def _tokenize_fused(self, x, usage, want_pre=False):
+    def _tokenize_fused(self, x, usage, want_ze=True, fast=False, want_pre=False):
         """(idx, z_q, z_e) from ONE persistent launch (lipvq_vq_tokenize_f32: the fused kernel's ReLU instance, per-row fp16
-        scales): encoder + screen, then the exact stage for the rows the screen leaves.  want_pre: (idx, z_q, z_e, pre) with the
-        three pre-activations a training step saves (lipvq_vq_tokenize_train_f32)."""
-        cb = self.embedding.weight.detach()
-        prep = self._cb_cache.get((self.embedding.weight,), lambda: ops.nearest_prepare(cb))
-        key = (x.shape[0], x.device)
-        if self._tok_ws_key != key:
-            self._tok_ws, self._tok_ws_key = ops.tokenize_workspace(x.shape[0], self.latent_dim, x.device), key
-        pre = None
-        if want_pre:
-            idx, zq, ze, pre, ws = ops.vq_tokenize(x, self._packed_encoder(), cb, prep, usage=usage, workspace=self._tok_ws, want_pre=True)
-        else:
-            idx, zq, ze, ws = ops.vq_tokenize(x, self._packed_encoder(), cb, prep, usage=usage, workspace=self._tok_ws)
-        self.last_exact_rows = ws
-        self._screen_monitor.record(ws, x.shape[0], ops.screen_is_coarse(cb.shape[0], cb.shape[1]))
-        return (idx, zq, ze, pre) if want_pre else (idx, zq, ze)
+        scales): encoder + screen, then the exact stage for the rows the screen leaves.  z_e is always returned (the
+        straight-through value needs it).  want_pre: (idx, z_q, z_e, pre) with the three pre-activations a training step saves
+        (lipvq_vq_tokenize_train_f32)."""
+        if fast:
+            raise ValueError("the plain VQVAE has no fast mode")
+        cb, prep, ws = self._fused_operands(x)
+        out = ops.vq_tokenize(x, self._packed_encoder(), cb, prep, usage=usage, workspace=ws, want_pre=want_pre)
+        self._screened(out[-1], x.shape[0], ops.screen_is_coarse(*cb.shape))
+        return out[:-1]
 
     @torch.no_grad()
     def tokenize(self, x, count_usage=True):
-        x = self._as_rows(x)
-        usage = self.code_usage if count_usage else None
-        n = x.shape[0]
-        # the fused launch from the codebook size on where a screen pays at all (below, the all-pairs kernel at its VALU bound);
-        # ONE routing decision per call (see _ScreenMonitor)
-        big = n > self.EXACT_ROWS_MAX and self.num_embeddings >= self.FUSED_MIN_CODES
-        screen = self._screen_monitor.use_screen() if big else None
-        if big and screen and self.fused_shape():
-            idx, zq, z_e = self._tokenize_fused(x, usage)
-        else:
-            z_e = self.encode(x)
-            idx, zq = self._quantize(z_e, usage, screen=screen)
-        self.last_indices = idx
+        idx, zq, z_e = self._tokenize(x, count_usage)
         return idx, ops.ste(z_e, zq)
-
-    def forward(self, x):
-        from .autograd import vq_forward
-        return vq_forward(self, self._as_rows(x))
