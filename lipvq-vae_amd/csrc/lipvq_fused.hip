@@ -233,23 +233,51 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
     const bool x_pref = !FAST && a.A <= 2 * XPF;
     float xq[XPF];
     constexpr int LANE_W_MIN_S = 8;      // the instances that re-form lane-dependent addresses per use; at S = 4 nothing spills
+    // The XPF loads of a call are issued back to back: nothing between them consumes a result, and the `k < A` select is applied where
+    // layer 0 consumes xq (x_masked), not here -- with the select at load time hipcc emitted load / s_waitcnt vmcnt(0) / v_cndmask
+    // eight times in a row in the block loop: one HBM miss and seven dependent cache hits in series per wave and row block.
+    // Addresses: ONE wave-uniform base (the wave's first row, clamped into the array) plus the lane's 32-bit byte offset, clamped
+    // to the array's last float -- always valid; what a clamp redirects is masked at use (k >= A) or belongs to a row past N.
+    // (S >= 8 keeps the first form, select at load time: those instances spill xq itself, every load is followed by its
+    // `s_waitcnt vmcnt(0)` and scratch store whichever way it is written, and the batched form made their prologue's loads wait too)
+    constexpr bool X_BATCHED = S < LANE_W_MIN_S;
     auto load_x = [&](int64_t blk_, float (&out)[XPF]) {
-        int64_t r_ = (blk_ * WAVES + wave) * 32 + ln;
-        r_ = r_ < a.N ? r_ : a.N - 1;
-        const int64_t last = a.N * a.A - 1;
-        // (S >= 8: the lane half is opaque here -- hipcc had hoisted the XPF partial addresses `x + 4 k` out of the block loop and
-        // spilled them; each reload's `vmcnt(0)` sat behind the x load issued just before it: XPF global loads in series per block)
-        int h_x = h;
-        if constexpr (S >= LANE_W_MIN_S) asm volatile("" : "+v"(h_x));
+        if constexpr (!X_BATCHED) {
+            int64_t r_ = (blk_ * WAVES + wave) * 32 + ln;
+            r_ = r_ < a.N ? r_ : a.N - 1;
+            const int64_t last = a.N * a.A - 1;
+            // (the lane half is opaque here -- hipcc had hoisted the XPF partial addresses `x + 4 k` out of the block loop and
+            // spilled them; each reload's `vmcnt(0)` sat behind the x load issued just before it: XPF global loads in series per block)
+            int h_x = h;
+            asm volatile("" : "+v"(h_x));
+#pragma unroll
+            for (int q = 0; q < XPF; ++q) {
+                const int k = 2 * q + h_x;
+                int64_t i_ = r_ * a.A + k;
+                i_ = i_ < last ? i_ : last;                      // always a valid address; masked below (no divergent branch)
+                const float v = a.x[i_];
+                out[q] = (k < a.A) ? v : 0.0f;
+            }
+            return;
+        }
+        int64_t row0_ = (blk_ * WAVES + wave) * 32;
+        row0_ = row0_ < a.N ? row0_ : a.N - 1;
+        const int64_t left64 = a.N - 1 - row0_;                  // rows behind the wave's first one
+        const int left = left64 < 31 ? (int)left64 : 31;
+        const unsigned char* xb = reinterpret_cast<const unsigned char*>(a.x + row0_ * a.A);
+        const int64_t end64 = ((a.N - row0_) * a.A - 1) * 4;     // byte offset of the array's last float
+        const unsigned end = end64 < (int64_t)(32 * 2 * XPF * 4) ? (unsigned)end64 : 32u * 2 * XPF * 4;      // (beyond every offset of a wave)
+        const unsigned off0 = (unsigned)((ln < left ? ln : left) * a.A + h) * 4u;
 #pragma unroll
         for (int q = 0; q < XPF; ++q) {
-            const int k = 2 * q + h_x;
-            int64_t i_ = r_ * a.A + k;
-            i_ = i_ < last ? i_ : last;                      // always a valid address; masked below (no divergent branch)
-            const float v = a.x[i_];
-            out[q] = (k < a.A) ? v : 0.0f;
+            unsigned o = off0 + 8u * q;                          // k = 2 q + h
+            o = o < end ? o : end;
+            out[q] = *reinterpret_cast<const float*>(xb + o);
         }
     };
+    // xq[i] as layer 0 consumes it: inputs past the fan-in are zeros (a select, not a product: the loaded value may be anything)
+    const int x_kmax = a.A - h;
+    auto x_masked = [&](int i, const float (&v)[XPF]) { return (!X_BATCHED || 2 * i < x_kmax) ? v[i] : 0.0f; };
     if (x_pref) load_x(blockIdx.x, xq);
     lq_ws_begin(a.amb_count);
     // ---- once per workgroup: weights (re-laid out 4 k-steps per 16-byte LDS read), biases, mu --------
@@ -536,7 +564,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                             for (int t = 0; t < T0; ++t) av[t] = *reinterpret_cast<const float4*>(w_P0 + ((t * S0q + sq) * 64 + lane_w) * 4);
 #pragma unroll
                             for (int q = 0; q < 4; ++q) {
-                                const float bv = xq[4 * sq + q];
+                                const float bv = x_masked(4 * sq + q, xq);
 #pragma unroll
                                 for (int t = 0; t < T0; ++t) {
                                     const float aq = q == 0 ? av[t].x : q == 1 ? av[t].y : q == 2 ? av[t].z : av[t].w;
@@ -843,7 +871,12 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) { m1[r] = INFINITY; m2[r] = INFINITY; k1[r] = 0; }
         LQ_STAMP(3);
-        if (x_pref) load_x(blk + gridDim.x < nblk ? blk + gridDim.x : blk, xq);      // next row block's inputs: a whole phase ahead
+        // next row block's inputs, a whole phase ahead.  The narrow parity instances issue the loads BEHIND the screen's prologue
+        // copies (lq_screen_core's deferred hook): vmcnt retires in order, and in front of the copies the loads' HBM miss stood
+        // between every wave and "stage 0 has landed", as the z_e stores' acknowledgements once did
+        constexpr bool DEFER_X = S <= 4 && !FAST && !TRAIN && !COARSE && !VQ;
+        const int64_t blk_next = blk + gridDim.x < nblk ? blk + gridDim.x : blk;
+        if (!DEFER_X && x_pref) load_x(blk_next, xq);
         // (S = 13: 104 registers of A fragments leave no room for an index array; COARSE: the packed index's perturbation is far
         // below the one-product margin at any S)
         constexpr bool PACKF = S <= 4 || S > 8 || COARSE;
@@ -855,13 +888,19 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
             for (int r = 0; r < 16; ++r) znr[r] = 0.0f;
         }
         if constexpr (KEEPZ) {
-            lq_screen_core<S, THREADS, TCF, NBF, PACKF, COARSE>(ah, al, tiles, L.ntiles, stage0, tid, frow, znr, m1, m2, k1);
+            auto deferred_x = [&]() { load_x(blk_next, xq); };
+            lq_screen_core<S, THREADS, TCF, NBF, PACKF, COARSE, 0, decltype(deferred_x), DEFER_X ? XPF : 0>(
+                ah, al, tiles, L.ntiles, stage0, tid, frow, znr, m1, m2, k1, false, deferred_x, true, DEFER_X && x_pref);
         } else {
             const bool have_def = DEFER_ZE && a.defer_ze && a.ze_out != nullptr;
             // the deferred stores sit under `row < N`: a wave without a valid row issues none, and its counted waits must not count them
             const bool wave_def = __builtin_amdgcn_ballot_w64((blk * WAVES + wave) * 32 + ln < a.N) != 0ull;
-            auto deferred_ze = [&]() { store_ze_tile((blk * WAVES + wave) * 32 + ln, T2 - 1, zdef); };
-            lq_screen_core<S, THREADS, TCF, NBF, PACKF, COARSE, 4, decltype(deferred_ze)>(ah, al, tiles, L.ntiles, stage0, tid, frow, znr, m1, m2, k1, have_def, deferred_ze, wave_def);
+            auto deferred_ze = [&]() {                           // (stores first, then the loads: either may be absent)
+                if (have_def) store_ze_tile((blk * WAVES + wave) * 32 + ln, T2 - 1, zdef);
+                if (DEFER_X && x_pref) load_x(blk_next, xq);
+            };
+            lq_screen_core<S, THREADS, TCF, NBF, PACKF, COARSE, 4, decltype(deferred_ze), DEFER_X ? XPF : 0>(
+                ah, al, tiles, L.ntiles, stage0, tid, frow, znr, m1, m2, k1, have_def, deferred_ze, wave_def, DEFER_X && x_pref);
         }
         LQ_STAMP(4);
         const unsigned keep_mask = PACKF ? ~((1u << lq_pack_bits(L.ntiles)) - 1u) : 0xffffffffu;

@@ -206,14 +206,27 @@ __host__ __device__ static inline int lq_pack_bits(int ntiles) { int b = 1; whil
 // front of them.  vmcnt retires in order: issued in front, their write acknowledgements (microseconds) stood between every wave
 // and "stage 0 has landed" -- 3.5 % of the cfg2 launch (profiles/r04_g_ze_store_placement.txt).  Behind the copies, the prologue's
 // wait and the first hand-over simply leave NDEF more operations outstanding.
+// The same hook carries the caller's prefetch of the next row block's inputs (NPF loads per wave when `have_pf`, issued by
+// `deferred()` behind its stores): in front of the copies, the loads' HBM miss stood between every wave and "stage 0 has landed" in
+// the same way.  The loads are unconditional, so every wave counts them; the stores stay under `wave_def`.
 struct LqNoDeferred { __device__ __forceinline__ void operator()() const {} };
+// all but the BASE youngest operations are done, not counting this wave's deferred stores (cd) and prefetch loads (cp) either
+template <int BASE, int NDEF, int NPF>
+__device__ __forceinline__ void lq_wait_vmcnt_deferred(bool cd, bool cp) {
+    static_assert(BASE + NDEF + NPF < 64, "vmcnt immediate");
+    if (NDEF > 0 && NPF > 0 && cd && cp) lq_wait_vmcnt<BASE + NDEF + NPF>();
+    else if (NDEF > 0 && cd) lq_wait_vmcnt<BASE + NDEF>();
+    else if (NPF > 0 && cp) lq_wait_vmcnt<BASE + NPF>();
+    else lq_wait_vmcnt<BASE>();
+}
 template <int S, int NT, int TC_ = screen_default_tc(S), int NB = 4, bool PACK = false, bool COARSE = false, int NDEF = 0,
-          typename DEFERRED = LqNoDeferred>
+          typename DEFERRED = LqNoDeferred, int NPF = 0>
 __device__ __forceinline__ void lq_screen_core(const f16x8 (&ah)[S], const f16x8 (&al)[S],
                                                const unsigned char* __restrict__ tiles, int ntiles,
                                                unsigned char* stage0, int tid, const float (&frow)[16], const float (&znr)[16],
                                                float (&m1)[16], float (&m2)[16], int (&k1)[16],
-                                               bool have_def = false, DEFERRED deferred = DEFERRED(), bool wave_def = true) {
+                                               bool have_def = false, DEFERRED deferred = DEFERRED(), bool wave_def = true,
+                                               bool have_pf = false) {
     using C = ScreenCfg<S, TC_, COARSE>;
     // NB = 2 is NOT a ring this loop can run: with one stage in flight (PD = 1) stage st+1 is only ISSUED at the hand-over in the
     // middle of stage st, and nothing waits for it before the read-ahead crosses into it.  (An experiment build with 2 x 4 tiles
@@ -266,17 +279,14 @@ __device__ __forceinline__ void lq_screen_core(const f16x8 (&ah)[S], const f16x8
     // prologue: stages 0 .. PD-1 in flight, stage 0 landed
 #pragma unroll
     for (int p = 0; p < PD; ++p) stage_dma(p, p);
-    static_assert((PD - 1) * CPW + NDEF < 64, "vmcnt immediate");
+    static_assert((PD - 1) * CPW + NDEF + NPF < 64, "vmcnt immediate");
     // wave_def (wave-uniform): this wave's deferred() really issues its NDEF stores -- the caller's sit under a row bound, and a
     // wave whose rows are all past the end issues none: counting them, its wait would let NDEF of its own stage copies fly on
     // into the barrier, and the other waves would read stages 0 and 1 before those pieces have landed
     const bool count_def = NDEF > 0 && have_def && wave_def;
-    if (NDEF > 0 && have_def) deferred();         // (launch-uniform)
-    if (count_def) {
-        lq_wait_vmcnt<(PD - 1) * CPW + NDEF>();
-    } else {
-        lq_wait_vmcnt<(PD - 1) * CPW>();
-    }
+    const bool count_pf = NPF > 0 && have_pf;     // (launch-uniform)
+    if ((NDEF > 0 && have_def) || count_pf) deferred();         // (launch-uniform)
+    lq_wait_vmcnt_deferred<(PD - 1) * CPW, NDEF, NPF>(count_def, count_pf);
     lq_wg_barrier();
 
     // two named accumulators: the chain of tile i runs into one while the other (tile i-1) is booked
@@ -313,8 +323,8 @@ __device__ __forceinline__ void lq_screen_core(const f16x8 (&ah)[S], const f16x8
             if (g == MID) {
                 // ---- mid-stage hand-over: stage st+1 has landed everywhere (the PD-2 younger stages may still fly); everyone has
                 // left stage st-1, whose buffer is the one stage st+PD goes to
-                // (the first hand-over of a pass with deferred stores: they are younger than stage 1's copy and need not be done)
-                if (count_def && st == 0) lq_wait_vmcnt<(PD >= 2 ? (PD - 2) * CPW : 0) + (PD >= 2 ? NDEF : 0)>();
+                // (the first hand-over of a pass with deferred operations: they are younger than stage 1's copy and need not be done)
+                if ((count_def || count_pf) && st == 0) lq_wait_vmcnt_deferred<(PD >= 2 ? (PD - 2) * CPW : 0), (PD >= 2 ? NDEF : 0), (PD >= 2 ? NPF : 0)>(count_def, count_pf);
                 else lq_wait_vmcnt<(PD >= 2 ? (PD - 2) * CPW : 0)>();
                 lq_wg_barrier();
                 int b = buf + PD; b = b >= NB ? b - NB : b;
