@@ -101,15 +101,20 @@ struct StandaloneScreen {
 // smallest value carries its own code and no index array is kept: med3 + min on the packed floats (3 instructions + the fma
 // instead of 4 + the fma, and 16 registers less).  The perturbation, below 2^(TB-23) of the value's own magnitude, is part of
 // the certification margin (lq_screen_decide, pack_eps).  id = the code (unpacked) or the tile index (packed).
+__device__ __forceinline__ float lq_pack_key(float v, int id, unsigned keep_mask) {
+    // one instruction.  Plain C: with the tile index kept in a vector register by the caller, hipcc selects v_and_or_b32 itself
+    // (it splits the and/or only when both constants sit in scalar registers) -- and, unlike the result of an asm statement, a
+    // value it defined itself gets no wait state in front of the v_med3_f32 that reads it
+    return __uint_as_float((__float_as_uint(v) & keep_mask) | (unsigned)id);
+}
 template <bool PACK>
 __device__ __forceinline__ void lq_track_one(float v, int id, unsigned keep_mask, float& m1, float& m2, int& k1) {
     if constexpr (PACK) {
-        // one instruction each (hipcc splits the and/or when both constants sit in scalar registers, and wraps fminf in two
-        // NaN-canonicalising v_max): the tile index is kept in a vector register by the caller
-        float key;
-        asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(key) : "v"(v), "s"(keep_mask), "v"(id));
-        m2 = __builtin_amdgcn_fmed3f(key, m1, m2);
-        asm("v_min_f32 %0, %1, %2" : "=v"(m1) : "v"(key), "v"(m1));
+        // `v` is the packed key (lq_pack_key).  The minimum stays an asm v_min_f32: fminf brings two NaN-canonicalising v_max, and
+        // v_med3_f32(key, m1, -inf) would book -inf where v_min_f32 keeps m1 once a key is a NaN (med3 with a NaN operand returns
+        // min3).  Its input is hipcc's own definition and its result is next read a tile later: no wait state on either side.
+        m2 = __builtin_amdgcn_fmed3f(v, m1, m2);
+        asm("v_min_f32 %0, %1, %2" : "=v"(m1) : "v"(v), "v"(m1));
     } else {
         const bool lt = v < m1;                 // one compare feeds both selects (fminf would cost two
         k1 = lt ? id : k1;                      // NaN-canonicalising v_max as well)
@@ -145,24 +150,40 @@ __device__ __forceinline__ void lq_track_part(const f32x16& acc, float e2, float
     for (int r = LO; r < HI; ++r) {
         // COARSE: the chain started from |e'|^2 f - w (lq_screen_core seeds it), the accumulator IS the booked value
         const float v = COARSE ? acc[r] : lq_fma(e2, frow[r], acc[r]);
-        lq_track_one<PACK>(v, id, keep_mask, m1[r], m2[r], k1[r]);
+        lq_track_one<PACK>(PACK ? lq_pack_key(v, id, keep_mask) : v, id, keep_mask, m1[r], m2[r], k1[r]);
     }
 }
 
-// the pending tile's registers that are booked behind MFMA j of the NM MFMAs of the running tile (NM = 3 S, or S for the
-// one-product chain): [16 j / NM, 16 (j + 1) / NM)   (j a compile-time constant after unrolling)
-template <int S, bool PACK, bool COARSE = false>
-__device__ __forceinline__ void lq_track_after_mfma(int j, const f32x16& acc, float e2, float en, const float (&frow)[16],
+// the pending tile's registers that are booked in gap q of the NG MFMA gaps of the running tile that take bookkeeping:
+// [16 q / NG, 16 (q + 1) / NG)   (q a compile-time constant after unrolling).  Packed three-product chains: the gap's elements are
+// booked in LOCKSTEP -- every value, every key, then med3 and min per element: an in-order wave cannot issue an instruction in the
+// slot right behind the one whose result it reads, and with two elements side by side no instruction of the gap does.  Per
+// register nothing changes: it is booked once per tile, in the same order of tiles.
+template <int NG, bool PACK, bool COARSE = false>
+__device__ __forceinline__ void lq_track_after_mfma(int q, const f32x16& acc, float e2, float en, const float (&frow)[16],
                                                     const float (&znr)[16], int id, unsigned keep_mask, float (&m1)[16],
                                                     float (&m2)[16], int (&k1)[16]) {
-    constexpr int NM = COARSE ? S : 3 * S;
-    const int lo = (16 * j) / NM, hi = (16 * (j + 1)) / NM;
+    const int lo = (16 * q) / NG, hi = (16 * (q + 1)) / NG;
+    if constexpr (PACK && !COARSE) {
+        float key[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r)
-        if (r >= lo && r < hi) {
-            const float v = COARSE ? acc[r] : lq_fma(e2, frow[r], acc[r]);
-            lq_track_one<PACK>(v, id, keep_mask, m1[r], m2[r], k1[r]);
-        }
+        for (int r = 0; r < 16; ++r)
+            if (r >= lo && r < hi) key[r] = lq_fma(e2, frow[r], acc[r]);
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (r >= lo && r < hi) key[r] = lq_pack_key(key[r], id, keep_mask);
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (r >= lo && r < hi) lq_track_one<PACK>(key[r], id, keep_mask, m1[r], m2[r], k1[r]);
+    } else {
+        // (one element after the other: written in lockstep, the one-product S = 8 instances spill ten times the scalar registers)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (r >= lo && r < hi) {
+                const float v = COARSE ? acc[r] : lq_fma(e2, frow[r], acc[r]);
+                lq_track_one<PACK>(PACK ? lq_pack_key(v, id, keep_mask) : v, id, keep_mask, m1[r], m2[r], k1[r]);
+            }
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -241,13 +262,19 @@ __device__ __forceinline__ void lq_screen_core(const f16x8 (&ah)[S], const f16x8
     constexpr int MID = (C::TC >= 2) ? (C::TC / 2) * S : S / 2;       // the k-step in front of which the mid-stage hand-over sits
     constexpr int FR = 2;                                             // fragment ring slots; reads run FR - 1 k-steps ahead
     constexpr int FD = FR - 1;
+    // S <= 4 three-product chains: the gap behind a k-step's first MFMA holds the LDS read-ahead and no bookkeeping; the 16 registers
+    // of the pending tile go to the other 2 S gaps, two or more to each, so that they are booked in lockstep (lq_track_after_mfma)
+    constexpr bool BOOK2 = PACK && !COARSE && S <= 4;
+    // the same instances, where ntiles' multiple of 8 makes the stage count a multiple of the ring's length: the stage loop is
+    // unrolled over one pass of the ring, and every ring position is a compile-time constant
+    constexpr bool RING_STATIC = BOOK2 && (8 / C::TC) % NB == 0;
     constexpr int PERIOD = ((C::TC & 1) || (NSTEP % FR)) ? 2 : 1;     // stages per loop trip: an even number of tiles, whole fragment rings
     static_assert(C::STAGE_BYTES >= 1024 && C::STAGE_BYTES % 16 == 0, "stage copies are whole KiB pieces");
     static_assert(NSTEP - FD >= MID, "next-stage fragments are read after the hand-over");
     static_assert(CPW * PD < 64, "vmcnt immediate");
     const int lane = tid & 63, ln = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // provably wave-uniform: DMA addresses stay scalar base + lane offset
-    const int nstage = ntiles / C::TC;                              // ntiles is a multiple of 8: nstage % PERIOD == 0
+    const int nstage = __builtin_amdgcn_readfirstlane(ntiles / C::TC);     // ntiles is a multiple of 8: nstage % PERIOD == 0
     unsigned char* dummy = stage0 + (size_t)NB * C::STAGE_BYTES;    // 1 KiB nobody reads
     // Stage copies go global -> LDS directly (global_load_lds_dwordx4: no VGPR round trip, no ds_write issue).  One
     // wave-instruction moves 64 x 16 B to a wave-uniform LDS base + lane*16.  Wave w copies KiB pieces w, w + NW, ...; the
@@ -257,28 +284,51 @@ __device__ __forceinline__ void lq_screen_core(const f16x8 (&ah)[S], const f16x8
     // body has no branch and the counted waits below mean the same thing in every wave at every stage.
     typedef __attribute__((address_space(3))) void* lds_ptr_t;
     typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-    auto stage_dma = [&](int st, int buf) {
-        const bool real = st < nstage;
-        const unsigned char* src = tiles + (real ? (size_t)st * C::STAGE_BYTES : (size_t)0);
-        unsigned char* dst = stage0 + (size_t)buf * C::STAGE_BYTES;
+    // What a hand-over's copy needs is carried, not recomputed: the pieces' places in a stage (poff: constants of the wave), the
+    // stage's byte offset into the tiles (advanced by STAGE_BYTES) and `past` = stage - nstage, negative for a real stage (advanced
+    // by one).  The "past the end" rule is arithmetic on the sign of `past` -- source offset and ring offset ANDed with it -- where
+    // a select per copy re-tested the condition in front of every M0 write (the adds in between clobber SCC).
+    int poff[CPW];
+#pragma unroll
+    for (int j = 0; j < CPW; ++j) {
+        int chunk = wave + j * NW;
+        chunk = chunk < CHUNKS ? chunk : CHUNKS - 1;
+        const int off = chunk * 1024;
+        poff[j] = off + 1024 <= C::STAGE_BYTES ? off : C::STAGE_BYTES - 1024;
+    }
+    const unsigned lane16 = (unsigned)lane * 16u;
+    auto stage_dma = [&](int past, size_t src_off, int rp) {
+        // all ones: a real stage; 0: one past the end (readfirstlane keeps it a mask: hipcc would turn the ANDs back into selects)
+        const int real = __builtin_amdgcn_readfirstlane(past >> 31);
+        const size_t real64 = ((size_t)(unsigned)real << 32) | (unsigned)real;
+        const unsigned char* src = tiles + (src_off & real64);
+        unsigned char* dbase = dummy - ((NB - rp) * C::STAGE_BYTES & real);     // the stage's place in the ring, or the dummy KiB
 #pragma unroll
         for (int j = 0; j < CPW; ++j) {
-            int chunk = wave + j * NW;
-            chunk = chunk < CHUNKS ? chunk : CHUNKS - 1;
-            int off = chunk * 1024;
-            off = off + 1024 <= C::STAGE_BYTES ? off : C::STAGE_BYTES - 1024;
-            unsigned char* d = real ? dst + off : dummy;
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + off + lane * 16), (lds_ptr_t)d, 16, 0, 0);
+            unsigned char* d = dbase + (poff[j] & real);
+            __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + poff[j] + lane16), (lds_ptr_t)d, 16, 0, 0);
         }
     };
+    // The lane's reads of a tile at `tb`: its |e'|^2 (extra = 128: |e'|) and its fragment of k-step s.  RING_STATIC: the lane's
+    // places in the ring's FIRST tile are kept as two opaque LDS addresses, and every read is one of them + an immediate (the ring
+    // ends just past 64 KiB) -- left alone, hipcc keeps an address register per tile of the ring and per ring position, twelve in
+    // all, which the 256 registers of the S = 4 instances do not have
+    typedef const __attribute__((address_space(3))) float* lds_cfloat_t;
+    typedef const __attribute__((address_space(3))) f16x8* lds_cfrag_t;
+    unsigned norm_lane = (unsigned)(uintptr_t)(lds_ptr_t)(stage0 + C::FRAG_BYTES + ln * 4);
+    unsigned frag_lane = (unsigned)(uintptr_t)(lds_ptr_t)(stage0 + lane * 16);
+    if constexpr (RING_STATIC) asm volatile("" : "+v"(norm_lane), "+v"(frag_lane));
+    auto norm_at = [&](const unsigned char* tb, int extra) {
+        return *(lds_cfloat_t)(uintptr_t)(norm_lane + (unsigned)(tb - stage0) + (unsigned)extra);
+    };
     auto frag = [&](const unsigned char* tb, int s, int hl) {
-        return COARSE ? *reinterpret_cast<const f16x8*>(tb + ((size_t)s * 64 + lane) * 16)          // hi-only tiles
-                      : *reinterpret_cast<const f16x8*>(tb + (((size_t)s * 2 + hl) * 64 + lane) * 16);
+        const int piece = COARSE ? s : s * 2 + hl;                   // (hi-only tiles: one KiB per k-step)
+        return *(lds_cfrag_t)(uintptr_t)(frag_lane + (unsigned)(tb - stage0) + (unsigned)piece * 1024u);
     };
     lq_wg_barrier();                              // earlier users of the stage buffers (previous row block) are done
     // prologue: stages 0 .. PD-1 in flight, stage 0 landed
 #pragma unroll
-    for (int p = 0; p < PD; ++p) stage_dma(p, p);
+    for (int p = 0; p < PD; ++p) stage_dma(p - nstage, (size_t)p * C::STAGE_BYTES, p);
     static_assert((PD - 1) * CPW + NDEF + NPF < 64, "vmcnt immediate");
     // wave_def (wave-uniform): this wave's deferred() really issues its NDEF stores -- the caller's sit under a row bound, and a
     // wave whose rows are all past the end issues none: counting them, its wait would let NDEF of its own stage copies fly on
@@ -307,16 +357,23 @@ __device__ __forceinline__ void lq_screen_core(const f16x8 (&ah)[S], const f16x8
         fh[g] = frag(stage0, g, 0);
         if constexpr (!COARSE) fl[g] = frag(stage0, g, 1);
     }
-    e2q[0] = reinterpret_cast<const float*>(stage0 + C::FRAG_BYTES)[ln];
-    if constexpr (COARSE) enq[0] = reinterpret_cast<const float*>(stage0 + C::FRAG_BYTES + 128)[ln];
+    e2q[0] = norm_at(stage0, 0);
+    if constexpr (COARSE) enq[0] = norm_at(stage0, 128);
     static_assert(FD <= S, "prologue reads stay in tile 0");
-    int buf = 0;                                  // ring position of stage st
-    auto do_stage = [&](auto POS, int st) {
+    int buf = 0;                                  // ring position of stage st (!RING_STATIC)
+    int past = PD - nstage;                       // the stage the next hand-over copies (stage_dma): its number - nstage,
+    size_t src_off = (size_t)PD * C::STAGE_BYTES; // its place in the tiles
+    // RP: the stage's ring position -- a constant of the unrolled loop (RING_STATIC: every LDS address of the stage is then the
+    // lane's base + an immediate), otherwise `buf`; FIRST: stage 0 -- a constant likewise (the first pass of the ring is peeled: as
+    // a test inside the unrolled loop it split stage 0 into two basic blocks, and hipcc sank sixteen v_med3_f32 of the first
+    // block's bookkeeping behind the hand-over in a lump), otherwise `st == 0`
+    auto do_stage = [&](auto POS, auto RP, auto FIRST, int st) {
         constexpr int par = (decltype(POS)::value * C::TC) & 1;    // 0: the stage's first tile runs into accA, 1: into accB
         constexpr int so = (decltype(POS)::value * NSTEP) % FR;    // fragment slot of the stage's k-step 0
-        const unsigned char* sb = stage0 + (size_t)buf * C::STAGE_BYTES;
-        int nbuf = buf + 1; nbuf = nbuf == NB ? 0 : nbuf;
-        const unsigned char* nsb = stage0 + (size_t)nbuf * C::STAGE_BYTES;
+        const int rp = RP;
+        const unsigned char* sb = stage0 + (size_t)rp * C::STAGE_BYTES;
+        int nrp = rp + 1; nrp = nrp == NB ? 0 : nrp;
+        const unsigned char* nsb = stage0 + (size_t)nrp * C::STAGE_BYTES;
 #pragma unroll
         for (int g = 0; g < NSTEP; ++g) {
             const int c = g / S, s = g % S;
@@ -324,11 +381,13 @@ __device__ __forceinline__ void lq_screen_core(const f16x8 (&ah)[S], const f16x8
                 // ---- mid-stage hand-over: stage st+1 has landed everywhere (the PD-2 younger stages may still fly); everyone has
                 // left stage st-1, whose buffer is the one stage st+PD goes to
                 // (the first hand-over of a pass with deferred operations: they are younger than stage 1's copy and need not be done)
-                if ((count_def || count_pf) && st == 0) lq_wait_vmcnt_deferred<(PD >= 2 ? (PD - 2) * CPW : 0), (PD >= 2 ? NDEF : 0), (PD >= 2 ? NPF : 0)>(count_def, count_pf);
+                if ((count_def || count_pf) && FIRST) lq_wait_vmcnt_deferred<(PD >= 2 ? (PD - 2) * CPW : 0), (PD >= 2 ? NDEF : 0), (PD >= 2 ? NPF : 0)>(count_def, count_pf);
                 else lq_wait_vmcnt<(PD >= 2 ? (PD - 2) * CPW : 0)>();
                 lq_wg_barrier();
-                int b = buf + PD; b = b >= NB ? b - NB : b;
-                stage_dma(st + PD, b);
+                int b = rp + PD; b = b >= NB ? b - NB : b;
+                stage_dma(past, src_off, b);
+                past += 1;
+                src_off += C::STAGE_BYTES;
             }
             f32x16& acc = (((c + par) & 1) == 0) ? accA : accB;
             const f32x16& prev = (((c + par) & 1) == 0) ? accB : accA;
@@ -357,8 +416,8 @@ __device__ __forceinline__ void lq_screen_core(const f16x8 (&ah)[S], const f16x8
                 fh[(g1 + so) % FR] = frag(tb, gg % S, 0);
                 if constexpr (!COARSE) fl[(g1 + so) % FR] = frag(tb, gg % S, 1);
                 if (gg % S == 0) {
-                    e2q[(g1 / S + par) & 1] = reinterpret_cast<const float*>(tb + C::FRAG_BYTES)[ln];   // g1 / S >= TC: next stage
-                    if constexpr (COARSE) enq[(g1 / S + par) & 1] = reinterpret_cast<const float*>(tb + C::FRAG_BYTES + 128)[ln];
+                    e2q[(g1 / S + par) & 1] = norm_at(tb, 0);                   // g1 / S >= TC: next stage
+                    if constexpr (COARSE) enq[(g1 / S + par) & 1] = norm_at(tb, 128);
                 }
             };
             // pinned order: first MFMA, the read-ahead, then (its share of the pending tile's bookkeeping, MFMA) x 2 -- left alone, hipcc
@@ -371,22 +430,38 @@ __device__ __forceinline__ void lq_screen_core(const f16x8 (&ah)[S], const f16x8
             __builtin_amdgcn_sched_barrier(0);
             read_ahead();
             __builtin_amdgcn_sched_barrier(0);
-            lq_track_after_mfma<S, PACK, COARSE>(COARSE ? s : 3 * s + 0, prev, e2_prev, en_prev, frow, znr, code_prev, keep_mask, m1, m2, k1);
+            if constexpr (!BOOK2) lq_track_after_mfma<COARSE ? S : 3 * S, PACK, COARSE>(COARSE ? s : 3 * s + 0, prev, e2_prev, en_prev, frow, znr, code_prev, keep_mask, m1, m2, k1);
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (!COARSE) {
+                constexpr int NG = BOOK2 ? 2 * S : 3 * S;
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s], bh, acc, 0, 0, 0);
-                lq_track_after_mfma<S, PACK>(3 * s + 1, prev, e2_prev, en_prev, frow, znr, code_prev, keep_mask, m1, m2, k1);
+                lq_track_after_mfma<NG, PACK>(BOOK2 ? 2 * s + 0 : 3 * s + 1, prev, e2_prev, en_prev, frow, znr, code_prev, keep_mask, m1, m2, k1);
                 __builtin_amdgcn_sched_barrier(0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bl, acc, 0, 0, 0);
-                lq_track_after_mfma<S, PACK>(3 * s + 2, prev, e2_prev, en_prev, frow, znr, code_prev, keep_mask, m1, m2, k1);
+                lq_track_after_mfma<NG, PACK>(BOOK2 ? 2 * s + 1 : 3 * s + 2, prev, e2_prev, en_prev, frow, znr, code_prev, keep_mask, m1, m2, k1);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        buf = nbuf;
     };
-    for (int st = 0; st < nstage; st += PERIOD) {
-        do_stage(std::integral_constant<int, 0>{}, st);
-        if constexpr (PERIOD == 2) do_stage(std::integral_constant<int, 1>{}, st + 1);
+    if constexpr (RING_STATIC) {
+        static_assert(NB == 4 && NB % PERIOD == 0, "one trip = one pass of the ring");
+        auto ring_pass = [&](auto FIRST, int st) {
+            do_stage(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, FIRST, st);
+            do_stage(std::integral_constant<int, 1 % PERIOD>{}, std::integral_constant<int, 1>{}, std::false_type{}, st + 1);
+            do_stage(std::integral_constant<int, 2 % PERIOD>{}, std::integral_constant<int, 2>{}, std::false_type{}, st + 2);
+            do_stage(std::integral_constant<int, 3 % PERIOD>{}, std::integral_constant<int, 3>{}, std::false_type{}, st + 3);
+        };
+        ring_pass(std::true_type{}, 0);
+        for (int st = NB; st < nstage; st += NB) ring_pass(std::false_type{}, st);      // nstage is a multiple of 8 / TC, so of NB
+    } else {
+        for (int st = 0; st < nstage; st += PERIOD) {
+            do_stage(std::integral_constant<int, 0>{}, buf, st == 0, st);
+            buf = buf + 1 == NB ? 0 : buf + 1;
+            if constexpr (PERIOD == 2) {
+                do_stage(std::integral_constant<int, 1>{}, buf, false, st + 1);
+                buf = buf + 1 == NB ? 0 : buf + 1;
+            }
+        }
     }
     // the last tile's chain: ntiles is even, so it ran into accB
     lq_track_part<0, 16, PACK, COARSE>(accB, e2B, enB, frow, znr, codeB, keep_mask, m1, m2, k1);
