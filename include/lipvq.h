@@ -171,7 +171,7 @@ int lipvq_screen_debug_f32(const float* z, const float* codebook, const void* pr
  * z_e stays in registers.  packed = lipvq_mlp3_pack_f32 of the encoder stack (A -> J0 -> J1 -> D, W2 already
  * Lipschitz-normalised); prep = lipvq_nearest_prepare_f32 of the codebook.  Supported: J0 = 64, J1 = 128
  * (the reference's widths), D in {32, 64, 128, 208} (208 = the width the reference itself runs, v5:89-92 / obs_nets.py:1225-1227:
- * its 112 KB of Lipschitz-layer weights are streamed through LDS), A <= 64.  raw6 = host array of the six device pointers {W0, b0, W1, b1,
+ * its 112 KB of Lipschitz-layer weights are streamed through LDS), A <= 64 (D = 128, whose layer 2 stays in LDS: A <= 40).  raw6 = host array of the six device pointers {W0, b0, W1, b1,
  * W2 (normalised), b2}: the exact kernel re-encodes the few uncertified rows from x with them, so z_e is written to
  * HBM only when ze_out is given.  After the call the first int of `workspace` holds the number of rows the screen left to an
  * exact decision.  WORKSPACE CONTRACT (round 4): the first 64 bytes are a header whose counters are zero between calls -- zero a

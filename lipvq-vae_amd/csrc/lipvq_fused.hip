@@ -1009,13 +1009,22 @@ extern "C" int lipvq_mlp3_pack_f16_f32(const float* W0, const float* W1, const f
     return check_launch("mlp3_pack_f16");
 }
 
-extern "C" int lipvq_tokenize_supported(int A, int J0, int J1, int D, int K) {
-    return (A > 0 && A <= 64 && J0 == 64 && J1 == 128 && K > 0 && (D == 32 || D == 64 || D == 128 || D == 208)) ? 1 : 0;
+// The shapes with an instance -- whose weights, biases and stage ring also fit the 160 KiB of LDS (launch_tokenize_as refuses what
+// does not): layer 0's fragments grow with the fan-in, and beside D = 128's resident layer-2 weights they fit up to A = 40 (the
+// other widths up to 64; D = 208 streams layer 2).  A caller that asks first (fused_shape) takes the unfused route for the rest.
+template <bool FAST>
+static int tokenize_shape_fits(int A, int J0, int J1, int D, int K) {
+    if (!(A > 0 && A <= 64 && J0 == 64 && J1 == 128 && K > 0)) return 0;
+    size_t lds = 0;
+    if (!lq_dispatch<32, 64, 128, 208>(D, [&](auto d) { lds = fused_lds_bytes_nohist<(d() + 15) / 16, FAST>(A); })) return 0;
+    return lds <= (size_t)160 * 1024 ? 1 : 0;
 }
+
+extern "C" int lipvq_tokenize_supported(int A, int J0, int J1, int D, int K) { return tokenize_shape_fits<false>(A, J0, J1, D, K); }
 
 // the fast mode has no D = 208 instance (its fp16 weights would fit, but the mode exists for BASELINE config 2's shapes)
 extern "C" int lipvq_tokenize_fast_supported(int A, int J0, int J1, int D, int K) {
-    return (lipvq_tokenize_supported(A, J0, J1, D, K) && D != 208) ? 1 : 0;
+    return D != 208 ? tokenize_shape_fits<true>(A, J0, J1, D, K) : 0;
 }
 
 // Schedule choices of the fused launch with IDENTICAL results whose better setting depends on the DEVICE (round 4,
@@ -1170,7 +1179,7 @@ static int tokenize_run(const char* who, bool vq, const float* x, const float* p
     if (!x || !packed || !codebook || !prep || !idx || !workspace || (vq ? !ze_out : !raw6)) return fail(LIPVQ_EINVAL, "%s: null pointer", who);
     for (int i = 0; !vq && i < 6; ++i)
         if (!raw6[i]) return fail(LIPVQ_EINVAL, "%s: raw encoder weight %d is null", who, i);
-    if (!lipvq_tokenize_supported(A, J0, J1, D, K))
+    if (!lipvq_tokenize_supported(A, J0, J1, D, K) && !(packed16 && lipvq_tokenize_fast_supported(A, J0, J1, D, K)))
         return fail(LIPVQ_EUNSUPPORTED, "%s: unsupported shape A=%d J0=%d J1=%d D=%d K=%d", who, A, J0, J1, D, K);
     if (N > 2147483647LL) return fail(LIPVQ_EUNSUPPORTED, "%s: N too large", who);
     if ((((uintptr_t)codebook | (uintptr_t)zq | (uintptr_t)ze_out | (uintptr_t)workspace | (uintptr_t)packed16 | (uintptr_t)pre0 |
