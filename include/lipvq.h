@@ -18,7 +18,10 @@
  *     returns a thread-local message.  Nothing throws across the ABI.
  *   - stateless and re-entrant; one process per GPU.
  *   - arithmetic: "canonical fp32" (lipvq-vae_amd/csrc/lipvq_math.h): every forward tensor is
- *     bit-identical to oracle/lipvq_oracle.c on the same inputs.
+ *     bit-identical to oracle/lipvq_oracle.c on the same inputs.  That includes denormals -- nothing is
+ *     flushed, neither by the vector ALU nor by the fp32 MFMA chains of the three-layer stacks, operands
+ *     and results alike (measured on gfx950: tests/test_gpu_mlp3_edges.py) -- and NaN / infinite
+ *     inputs, which stay in their own row.
  */
 #ifndef LIPVQ_H_
 #define LIPVQ_H_

@@ -20,8 +20,8 @@ def ops():
 
 
 def test_math_device_equals_host(ops, oracle):
-    """lq_gelu/lq_sigmoid evaluated on the GPU (through a 1-layer-wide MLP is awkward; use the
-    Lipschitz kernel for softplus and the MLP with identity-like weights for gelu/sigmoid)."""
+    """lq_softplus and the IEEE division evaluated on the GPU, through the Lipschitz kernel, equal the host's over a dense sweep
+    of ci.  (lq_gelu / lq_sigmoid / ReLU on the device: tests/test_gpu_mlp3_edges.py::test_activations_on_the_device.)"""
     # softplus + division via lipschitz_scale: W = 1 row of H ones -> scale = min(1, softplus(ci)/H)
     ci = np.linspace(-30, 30, 4001).astype(np.float32)
     W = np.ones((ci.size, 4), np.float32)
