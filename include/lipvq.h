@@ -501,7 +501,13 @@ int lipvq_gpt_layernorm_bwd_f32(const float* gy, const float* xhat, const float*
  *      Accumulation: the bf16 x bf16 products are exact in fp32 and are accumulated in fp32 (v_mfma_f32_32x32x16_bf16); bias,
  *      activation, the sums over row chunks and the bias gradient are fp32 and never see a rounded operand.
  *      Determinism: no float atomics; the summation order depends on the shape alone, never on the device, its CU count or
- *      the launch's timing, so repeated calls give bit-identical results.
+ *      the launch's timing, so repeated calls give bit-identical results.  A row of y or gx has one chain over the reduction
+ *      in the same order at every tile (lipvq_gemm_bf16_tile), so its bits depend neither on its position nor on the number
+ *      of rows or output columns of the launch (tests/test_gpu_gemm_bf16_tiles.py compares the three tiles bit for bit).
+ *      Special values: the rounding is IEEE -- ties to even, -0 stays -0, denormal operands are kept, NaN and +-Inf pass and
+ *      reach only their own row (or column) of the result -- and it can OVERFLOW: an |element| from the bit pattern 0x7f7f8000
+ *      (about 3.396e38) up, FLT_MAX among them, rounds to +-Inf in bf16, so an output is +-Inf or NaN here where the _f32
+ *      entry point's is finite.
  *      Shapes: any N >= 0 (N == 0: no-op, returns 0); both Linear widths must be multiples of 8, else LIPVQ_EUNSUPPORTED.
  *      Input tensors (and the workspace) 16-byte aligned, else LIPVQ_EINVAL; outputs need no alignment.  Sizes are checked
  *      before pointers, pointers before any launch. ---- */
@@ -519,6 +525,15 @@ int lipvq_linear_nn_bf16(const float* g, const float* W, float* gx, int64_t N, i
  * one launch writes every chunk's partial gW and gb into the workspace and a second adds them in chunk order;
  * lipvq_wgrad_bf16_workspace_bytes = ceil(N / chunk) (J K + J) 4 bytes (0 for N <= 0), a function of (N, J, K) only. */
 size_t lipvq_wgrad_bf16_workspace_bytes(int64_t N, int J, int K);
+/* The tile of the launch that computes an [M][Nc] result in `chunks` row chunks (1 for the forward and the input gradient;
+ * ceil(N / chunk) for the weight gradient, whose result is gW: M = J, Nc = K), chosen from the shape alone:
+ *     128 (128 x 128, 2 x 2 waves of 64 x 64) when the 128^2-grid (x row chunks), ceil(M / 128) ceil(Nc / 128) chunks, has
+ *         >= 256 workgroups,
+ *     64 (64 x 64, 2 x 2 waves of 32 x 32) else, if the 64^2-grid has >= 256,
+ *     32 (32 x 32, one wave) else.
+ * lipvq_linear_act_bf16, lipvq_linear_nn_bf16 and lipvq_wgrad_bf16 take their tile from this function.  Returns 0 for a non-positive argument.  Pure host
+ * arithmetic: launches nothing, needs no device. */
+int lipvq_gemm_bf16_tile(int64_t M, int Nc, int64_t chunks);
 int lipvq_wgrad_bf16(const float* G, const float* H, float* gW, float* gb, void* workspace, int64_t N, int J, int K,
                      void* stream);
 

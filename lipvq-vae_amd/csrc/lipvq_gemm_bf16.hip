@@ -271,12 +271,12 @@ __global__ __launch_bounds__(256) void wgrad_bf16_reduce_kernel(const float* __r
     if (w) gW[i] = s; else gb[i - JK] = s;
 }
 
-// Tile choice from the shape alone: 128 x 128 (2 x 2 waves of 64 x 64) once that gives the chip a workgroup per CU, else
-// 64 x 64 (2 x 2 waves of 32 x 32), else one wave per 32 x 32 tile (the 240-row step shape: 8 x 16 .. 8 x 64 workgroups).
+// Tile choice from the shape alone (lipvq_gemm_bf16_tile below, the rule of include/lipvq.h): 128 x 128 (2 x 2 waves of
+// 64 x 64) once that gives the chip a workgroup per CU, else 64 x 64 (2 x 2 waves of 32 x 32), else one wave per 32 x 32 tile
+// (the 240-row step shape: 8 x 16 .. 8 x 64 workgroups).
 template <bool AS, bool BS>
 static int launch_gemm(const char* what, const GemmArgs& a, int64_t nchunks, hipStream_t st) {
-    auto wgs = [&](int64_t t) { return ((a.M + t - 1) / t) * ((a.Nc + t - 1) / t) * nchunks; };
-    const int t = wgs(128) >= 256 ? 128 : (wgs(64) >= 256 ? 64 : 32);
+    const int t = lipvq_gemm_bf16_tile(a.M, a.Nc, nchunks);
     const int64_t gx = (a.M + t - 1) / t, gy = (a.Nc + t - 1) / t;
     if (gx > 0x7fffffffLL || gy > 65535 || nchunks > 65535) return fail(LIPVQ_EUNSUPPORTED, "%s: too large", what);
     const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)nchunks);
@@ -328,6 +328,12 @@ int lipvq_linear_nn_bf16(const float* g, const float* W, float* gx, int64_t N, i
     if (misaligned(g) || misaligned(W)) return fail(LIPVQ_EINVAL, "lipvq_linear_nn_bf16: g and W must be 16-byte aligned");
     GemmArgs a = {g, W, nullptr, gx, nullptr, nullptr, N, K, J, J, LIPVQ_ACT_NONE};
     return launch_gemm<false, true>("lipvq_linear_nn_bf16", a, 1, (hipStream_t)stream);
+}
+
+int lipvq_gemm_bf16_tile(int64_t M, int Nc, int64_t chunks) {
+    if (M <= 0 || Nc <= 0 || chunks <= 0) return 0;
+    auto wgs = [&](int64_t t) { return ((M + t - 1) / t) * ((Nc + t - 1) / t) * chunks; };
+    return wgs(128) >= 256 ? 128 : (wgs(64) >= 256 ? 64 : 32);
 }
 
 size_t lipvq_wgrad_bf16_workspace_bytes(int64_t N, int J, int K) {

@@ -18,53 +18,18 @@ import torch.nn.functional as F
 
 import gpt_bf16_ref
 import gpt_ref
+from gemm_bf16_cases import EPS, case as _case, ratio as _ratio, rb as _rb   # shared with test_gpu_gemm_bf16_tiles.py
 
 pytestmark = pytest.mark.gpu
 
-EPS = 2.0 ** -24
 NS = (1, 33, 130, 240)
 KJ = ((16, 8), (72, 24), (512, 136), (2048, 512))
-
-
-def _rb(t):
-    return t.bfloat16().double()
 
 
 @pytest.fixture(scope="module")
 def ops():
     import lipvq_vae_amd
     return lipvq_vae_amd.ops
-
-
-_cases = {}
-
-
-def _case(N, K, J):
-    """Inputs and float64 references of one shape, computed once and shared (never modified)."""
-    key = (N, K, J)
-    if key not in _cases:
-        torch.manual_seed(10000 * N + 10 * K + J)
-        x, W, b, g = torch.randn(N, K), torch.randn(J, K) / K ** 0.5, torch.randn(J), torch.randn(N, J)
-        for t in (x, W, g):
-            changed = float((t.bfloat16().float() != t).float().mean())
-            assert changed > 0.9, f"only {changed:.2f} of the elements change under bf16 rounding"
-        xr, Wr, gr = _rb(x), _rb(W), _rb(g)
-        c = dict(x=x, W=W, b=b, g=g)
-        c["y"], c["Ry"] = xr @ Wr.t(), xr.abs() @ Wr.abs().t()                   # forward: reduction K
-        c["y_exact"], c["Ry_exact"] = x.double() @ W.double().t(), x.double().abs() @ W.double().abs().t()
-        c["gx"], c["Rgx"] = gr @ Wr, gr.abs() @ Wr.abs()                         # input gradient: reduction J
-        c["gW"], c["RgW"] = gr.t() @ xr, gr.abs().t() @ xr.abs()                 # weight gradient: reduction N
-        c["gb"], c["Rgb"] = g.double().sum(0), g.double().abs().sum(0)
-        _cases[key] = c
-    return _cases[key]
-
-
-def _ratio(what, got, want, R, length):
-    """Largest |got - want| / ((length + 1) 2^-24 R): <= 1 is any-order round-to-nearest accumulation."""
-    rn = (length + 1) * EPS * R
-    ratio = float(((got.cpu().double() - want).abs() / rn.clamp_min(1e-300)).max())
-    print(f"{what}: error / RN bound = {ratio:.3f}")
-    return ratio
 
 
 @pytest.mark.parametrize("K,J", KJ)

@@ -237,7 +237,8 @@ def test_one_cache_serves_many_suffixes_and_many_sequences(golden_dir, name, P):
 def test_cached_forward_in_bf16_mode(golden_dir):
     """The bound of tests/test_gpu_gemm_bf16.py for the module's output: 2 e0, e0 = the distance of the float64 emulation of the
     mode from the float64 fixture -- here for the distance of the cached bf16 rows from the full bf16 forward's, and from the
-    fixture's."""
+    fixture's.  The cached rows also have the full forward's BITS; every Linear of this fixture runs the 32 tile
+    on both sides -- tests/test_gpu_gemm_bf16_tiles.py repeats the comparison where the two sides use different tiles."""
     net, g, cfg = _module(golden_dir, "gpt_small")
     P = 8
     out64 = torch.from_numpy(g["out64"])
@@ -257,6 +258,7 @@ def test_cached_forward_in_bf16_mode(golden_dir):
     print(f"gpt_small bf16 P={P}: |cached - full bf16| = {d:.3e}, cached error to float64 {e:.3e}, e0 = {e0:.3e} (bound 2 e0); "
           f"cached == full bf16 in bits: {torch.equal(out, full[:, P:])}")
     assert not torch.equal(out, fp32), "the cached path ignored the matmul precision"
+    assert torch.equal(out, full[:, P:])        # a bf16 Linear row does not depend on the rows around it
     assert d <= 2 * e0
     assert e <= 2 * e0
 
