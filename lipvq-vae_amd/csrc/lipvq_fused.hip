@@ -18,26 +18,10 @@
 
 #include "lipvq_mlp.h"
 #include "lipvq_screen.h"
+#include "lipvq_fused_lds.h"
 
 #define FUSED_WAVES 8
 #define FUSED_THREADS (FUSED_WAVES * 64)
-// LDS budget: the D = 128 instance holds 105 KB of weights, so its codebook stages are one tile deep
-#define FUSED_HIST_MAX 2048
-// stage ring of the fused kernel (LDS left beside the encoder weights): S <= 4: four buffers of two/four tiles; S = 8: the
-// weights take 98 KB, three buffers of one tile
-// The Lipschitz layer's weights are STREAMED through the stage ring (instead of living in LDS) from this many k-steps on:
-// 13 (D = 208) has no choice -- 112 KB of A operands; for 8 (D = 128) it is a trade measured in round 3: 64 KB of LDS go from
-// a phase that is a twentieth of the work at K = 8192 to the codebook ring of the phase that is the rest.
-// (LQ_STREAM2_MIN_S = 9 lives in lipvq_screen.h: it also sizes the streamed weights' region of the workspace)
-#define LQ_RING8_TC 1
-#define LQ_RING8_NB 3
-#define LQ_RING13_NB 3
-constexpr int fused_ring_tc(int S) { return (S <= 2) ? 4 : (S <= 4) ? 2 : (S == 8) ? LQ_RING8_TC : 1; }
-constexpr int fused_ring_nb(int S) { return (S <= 4) ? 4 : (S == 8) ? LQ_RING8_NB : LQ_RING13_NB; }
-#define LQ_COARSE_TC_WIDE 2       /* tiles per stage of the one-product S = 8 instance */
-// S = 8 (cfg3): 1.610 -> 1.555 ms, same box.  Not S = 13: with two tiles per stage that instance runs 10 ms instead of 0.9 (its
-// 26-k-step stage body no longer fits the registers it has left beside 104 of row fragments) -- profiles/r04_f_coarse_ring_ab.txt
-constexpr int fused_ring_tc_coarse(int S) { return S == 8 ? LQ_COARSE_TC_WIDE * fused_ring_tc(S) : fused_ring_tc(S); }
 
 // lq_gelu_poly2 (two elements per instruction: v_pk_fma_f32), cut into four stages so that one stage can follow each MFMA of a
 // 4-MFMA group (same operations in the same order as lq_gelu_poly: bit-identical values)
@@ -82,29 +66,11 @@ struct ActStage<true> {
     __device__ __forceinline__ void stage3(float& o0, float& o1) { o0 = a_ > 0.0f ? a_ : 0.0f; o1 = b_ > 0.0f ? b_ : 0.0f; }
 };
 
+// the launch's LDS (FusedLds, lipvq_fused_lds.h), as the host asks for it
 template <int S, bool FAST>
-__host__ __device__ static size_t fused_lds_bytes_nohist(int A) {
-    constexpr int T0 = 2, T1 = 4, T2 = (S + 1) / 2;
-    const int S0q = ((A + 1) / 2 + 3) / 4;
-    const int S0h = (A + 15) / 16;
-    size_t fl = FAST ? (size_t)T0 * S0h * 256 + (size_t)T1 * (2 * T0) * 256 + (size_t)T2 * (2 * T1) * 256
-                     : (size_t)T0 * S0q * 256 + (size_t)T1 * 8 * 256 + (S >= LQ_STREAM2_MIN_S ? (size_t)0 : (size_t)T2 * 16 * 256);
-    fl += 32 * T0 + 32 * T1 + 32 * T2 + 16 * S;
-    // (one size for both screens' instances: the larger ring)
-    constexpr size_t ring_fine = (size_t)fused_ring_nb(S) * ScreenCfg<S, fused_ring_tc(S), false>::STAGE_BYTES + 1024;
-    constexpr size_t ring_coarse = (size_t)fused_ring_nb(S) * ScreenCfg<S, fused_ring_tc_coarse(S), true>::STAGE_BYTES + 1024;
-    const size_t ring = ((ring_fine > ring_coarse ? ring_fine : ring_coarse) + 63) & ~(size_t)63;
-    return fl * sizeof(float) + ring;
-}
-// the per-workgroup usage histogram: codebooks of up to FUSED_HIST_MAX codes, where the LDS has room for it
+static size_t fused_lds_bytes_nohist(int A) { return FusedLds<S, FAST>(A).bytes_nohist(); }
 template <int S, bool FAST>
-__host__ __device__ static bool fused_hist_fits(int A, int K) {
-    return K <= FUSED_HIST_MAX && fused_lds_bytes_nohist<S, FAST>(A) + (size_t)K * 4 <= (size_t)160 * 1024;
-}
-template <int S, bool FAST>
-static size_t fused_lds_bytes(int A, int K) {
-    return fused_lds_bytes_nohist<S, FAST>(A) + (fused_hist_fits<S, FAST>(A, K) ? (size_t)K * 4 : 0);
-}
+static size_t fused_lds_bytes(int A, int K) { return FusedLds<S, FAST>::bytes(A, K); }
 
 struct TokArgs {
     const float* x;              // [N][A]
@@ -134,6 +100,260 @@ struct TokArgs {
     int keepz;                   // host side only: the KEEPZ instance runs (lq_keepz) -- ze_out, ze_ring, defer_ze and nt_ze are unused
 };
 
+// Diagnostic build only (-DLQ_STAMPS, scripts/stamps.py): per-wave cycles per segment, accumulated over the row blocks and written to
+// the unused upper half of the row list; no output value depends on them.  Without the flag every one of these is empty.  (Macros: as
+// a small type with empty methods the stamps changed the code of builds WITHOUT the flag -- the calls reorder what the inliner
+// leaves in the 4-wave instances -- and as a type with state that of builds with it.)
+#ifdef LQ_STAMPS
+// kernel entry: the prologue is [st_top, st_begin); st_top_rt: 100 MHz, the same clock on every CU
+#define LQ_STAMPS_ENTER()                                                                                            \
+    const long long st_top = __builtin_amdgcn_s_memtime();                                                           \
+    const long long st_top_rt = (long long)__builtin_amdgcn_s_memrealtime()
+#define LQ_STAMPS_PROLOGUE_DONE()                                                                                    \
+    long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev;                                                         \
+    const long long st_begin = __builtin_amdgcn_s_memtime()
+#define LQ_STAMPS_BEGIN_BLOCK() st_prev = __builtin_amdgcn_s_memtime()
+#define LQ_STAMP(i) do { const long long t_ = __builtin_amdgcn_s_memtime(); st_acc[i] += t_ - st_prev; st_prev = t_; } while (0)
+// (dbg[11]: 100 MHz wall clock at this wave's end)
+#define LQ_STAMPS_FLUSH(a, lane, wave, WAVES)                                                                        \
+    if (lane == 0) {                                                                                                 \
+        long long* dbg = LqWorkspace::from_lists(a.amb_list, a.N).stamps() + ((size_t)blockIdx.x * WAVES + wave) * 16;   \
+        for (int i = 0; i < 7; ++i) dbg[i] = st_acc[i];                                                              \
+        dbg[7] = 0;                                                                                                  \
+        dbg[8] = __builtin_amdgcn_s_memtime() - st_begin;                                                            \
+        dbg[9] = st_begin;                                                                                           \
+        dbg[10] = st_begin - st_top;                                                                                 \
+        dbg[11] = (long long)__builtin_amdgcn_s_memrealtime();                                                       \
+        dbg[12] = st_top_rt;                                                                                         \
+    }
+#else
+#define LQ_STAMPS_ENTER() do { } while (0)
+#define LQ_STAMPS_PROLOGUE_DONE() do { } while (0)
+#define LQ_STAMPS_BEGIN_BLOCK() do { } while (0)
+#define LQ_STAMP(i) do { } while (0)
+#define LQ_STAMPS_FLUSH(a, lane, wave, WAVES) do { } while (0)
+#endif
+
+// z_e row store of one finished 32-feature tile.  Lane (n, h) holds features 32t + 2r + h (r = 0..15) of row n: the even ones in
+// the low half-wave, the odd ones in the high half.  One v_permlane32_swap per register pair (low half's r >= 8 <-> high
+// half's r < 8) leaves the low lane with features 32t .. 32t+15 and the high lane with 32t+16 .. 32t+31, i.e. four 16-byte
+// stores of consecutive floats per lane (64 contiguous bytes per lane) instead of sixteen 4-byte stores scattered over the row.
+// ze_shift: ring mode, rows of this row block are stored ze_shift rows lower.  Issues four vector stores where `row < N`, waits for none.
+template <int S, bool TRAIN>
+__device__ __forceinline__ void tok_store_ze_tile(const TokArgs& a, const int h, const int64_t ze_shift, const int64_t row, const int t,
+                                                  const f32x16& acc) {
+    float lo8[8], hi8[8];                 // after the swaps: lo8[j] = feature base + 2j, hi8[j] = base + 2j + 1
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        // vdst = low half's register r = 8 + j (goes up), src = high half's register r = j (comes down)
+        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[j]), __float_as_uint(acc[8 + j]), false, false);
+        // sw[0]: lanes 0-31 keep acc[j] (own even features 2j), lanes 32-63 receive low half's acc[8+j]
+        // sw[1]: lanes 0-31 receive high half's acc[j] (odd features 2j+1), lanes 32-63 keep acc[8+j]
+        lo8[j] = __uint_as_float(sw[0]);
+        hi8[j] = __uint_as_float(sw[1]);
+    }
+    // low lanes : lo8[j] = feat 2j (own, even), hi8[j] = feat 2j+1 (from the high lane)        -> base 32t
+    // high lanes: lo8[j] = feat 16+2j (from the low lane, even), hi8[j] = feat 16+2j+1 (own) -> base 32t+16
+    if (row < a.N && 2 * t + h < S) {                // (the high lanes' 16 features of a half-used last tile do not exist)
+        float4* dst = reinterpret_cast<float4*>(a.ze_out + (size_t)(row - ze_shift) * a.D + 32 * t + 16 * h);
+        // nontemporal (round 4): written once, read back for a fraction of a percent of the rows -- the stream should not
+        // displace the codebook tiles and weights every workgroup re-reads from L2 (with the z_q rows the same way:
+        // cfg2 -2.4 %, icrt -2.9 %, same box, profiles/r04_e_nt_stores_ab.txt)
+        typedef float lq_f4v __attribute__((ext_vector_type(4)));
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (S > 4 || TRAIN || a.nt_ze) __builtin_nontemporal_store((lq_f4v){lo8[2 * q], hi8[2 * q], lo8[2 * q + 1], hi8[2 * q + 1]}, reinterpret_cast<lq_f4v*>(dst) + q);
+            else reinterpret_cast<lq_f4v*>(dst)[q] = (lq_f4v){lo8[2 * q], hi8[2 * q], lo8[2 * q + 1], hi8[2 * q + 1]};   // (launch-uniform: TokArgs; S > 4 and the training instances: always nontemporal -- nothing to choose there, and the second copy of the stores cost icrt 1.4 %)
+    }
+}
+
+// largest |pre| of the tile by v_max3 (half an instruction per element instead of a multiply and a compare), the rare
+// |x| >= sqrt(18) elements of `out` (the GELU polynomial of `pre`) replaced behind a wave-uniform branch;
+// a NaN is skipped by max3, but the polynomial has already turned it into a NaN, as the tail would
+__device__ __forceinline__ void tok_gelu_fixup(f32x16& out, const f32x16& pre) {
+    float mx = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(mx) : "v"(mx), "v"(pre[r]), "v"(pre[r + 1]));
+    if (__builtin_amdgcn_ballot_w64(!(mx * mx < 18.0f)) != 0ull) {          // wave-uniform, practically never taken
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (!(pre[r] * pre[r] < 18.0f)) out[r] = lq_gelu_tail(pre[r]);
+    }
+}
+// the lane's 16 bias values of tile t (see the bias re-layout in tokenize_body's prologue): four 16-byte LDS reads
+__device__ __forceinline__ f32x16 tok_bias16(const float* wb, int t, int h) {
+    f32x16 b;
+    const float4* p4 = reinterpret_cast<const float4*>(wb + (2 * t + h) * 16);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { const float4 v = p4[q]; b[4 * q] = v.x; b[4 * q + 1] = v.y; b[4 * q + 2] = v.z; b[4 * q + 3] = v.w; }
+    return b;
+}
+// global -> LDS in 16-byte pieces, four loads in flight per thread and round (the element loop was one L2 round trip per float)
+template <int THREADS>
+__device__ __forceinline__ void tok_copy16(float* dst, const float* from, int nfl, int tid) {
+    const float4* s4 = reinterpret_cast<const float4*>(from);
+    float4* d4 = reinterpret_cast<float4*>(dst);
+    const int nv = nfl / 4;
+    for (int v0 = tid; v0 < nv; v0 += 4 * THREADS) {
+        float4 r[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { const int v = v0 + q * THREADS; r[q] = s4[v < nv ? v : nv - 1]; }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { const int v = v0 + q * THREADS; if (v < nv) d4[v] = r[q]; }
+    }
+}
+
+// x prefetch: this lane's inputs of a row block (k = 2 q + h, q < XPF).  Reads a.x; leaves XPF loads in flight into `out` and waits for
+// none of them.
+// The XPF loads of a call are issued back to back: nothing between them consumes a result, and the `k < A` select is applied where
+// layer 0 consumes xq (x_masked), not here -- with the select at load time hipcc emitted load / s_waitcnt vmcnt(0) / v_cndmask
+// eight times in a row in the block loop: one HBM miss and seven dependent cache hits in series per wave and row block.
+// Addresses: ONE wave-uniform base (the wave's first row, clamped into the array) plus the lane's 32-bit byte offset, clamped
+// to the array's last float -- always valid; what a clamp redirects is masked at use (k >= A) or belongs to a row past N.
+// (S >= 8 keeps the first form, select at load time: those instances spill xq itself, every load is followed by its
+// `s_waitcnt vmcnt(0)` and scratch store whichever way it is written, and the batched form made their prologue's loads wait too)
+template <int WAVES, int XPF, bool X_BATCHED>
+__device__ __forceinline__ void tok_load_x(const TokArgs& a, const int wave, const int ln, const int h, int64_t blk_, float (&out)[XPF]) {
+    if constexpr (!X_BATCHED) {
+        int64_t r_ = (blk_ * WAVES + wave) * 32 + ln;
+        r_ = r_ < a.N ? r_ : a.N - 1;
+        const int64_t last = a.N * a.A - 1;
+        // (the lane half is opaque here -- hipcc had hoisted the XPF partial addresses `x + 4 k` out of the block loop and
+        // spilled them; each reload's `vmcnt(0)` sat behind the x load issued just before it: XPF global loads in series per block)
+        int h_x = h;
+        asm volatile("" : "+v"(h_x));
+#pragma unroll
+        for (int q = 0; q < XPF; ++q) {
+            const int k = 2 * q + h_x;
+            int64_t i_ = r_ * a.A + k;
+            i_ = i_ < last ? i_ : last;                      // always a valid address; masked below (no divergent branch)
+            const float v = a.x[i_];
+            out[q] = (k < a.A) ? v : 0.0f;
+        }
+        return;
+    }
+    int64_t row0_ = (blk_ * WAVES + wave) * 32;
+    row0_ = row0_ < a.N ? row0_ : a.N - 1;
+    const int64_t left64 = a.N - 1 - row0_;                  // rows behind the wave's first one
+    const int left = left64 < 31 ? (int)left64 : 31;
+    const unsigned char* xb = reinterpret_cast<const unsigned char*>(a.x + row0_ * a.A);
+    const int64_t end64 = ((a.N - row0_) * a.A - 1) * 4;     // byte offset of the array's last float
+    const unsigned end = end64 < (int64_t)(32 * 2 * XPF * 4) ? (unsigned)end64 : 32u * 2 * XPF * 4;      // (beyond every offset of a wave)
+    const unsigned off0 = (unsigned)((ln < left ? ln : left) * a.A + h) * 4u;
+#pragma unroll
+    for (int q = 0; q < XPF; ++q) {
+        unsigned o = off0 + 8u * q;                          // k = 2 q + h
+        o = o < end ? o : end;
+        out[q] = *reinterpret_cast<const float*>(xb + o);
+    }
+}
+// xq[i] as layer 0 consumes it: inputs past the fan-in are zeros (a select, not a product: the loaded value may be anything).
+// x_kmax = A - h.
+template <bool X_BATCHED, int XPF>
+__device__ __forceinline__ float tok_x_masked(const int x_kmax, int i, const float (&v)[XPF]) { return (!X_BATCHED || 2 * i < x_kmax) ? v[i] : 0.0f; }
+
+// Prologue of the FAST instances: the three fp16 fragment blocks, global -> LDS as they are (n0: the floats of layer 0's block,
+// FusedLds::n_P0).  Reads a.packed16; issues and completes its own loads; the caller owns the barrier behind the prologue.
+template <class Lds, int THREADS>
+__device__ __forceinline__ void tok_prologue_weights_f16(const TokArgs& a, const int n0, const int tid, float* w_P0, float* w_P1, float* w_P2) {
+    // packed16 = [P0h | P1h | P2h], each already [t][s][lane][8 halfs] = 4 floats per (t, s, lane)
+    const float* src = reinterpret_cast<const float*>(a.packed16);
+    const int n1 = Lds::N_P1, n2 = Lds::N_P2;
+    tok_copy16<THREADS>(w_P0, src, n0, tid);
+    tok_copy16<THREADS>(w_P1, src + n0, n1, tid);
+    tok_copy16<THREADS>(w_P2, src + n0 + n1, n2, tid);
+}
+
+// Phase A of the FAST instances: the wave's 32 rows through the three layers, each finished output tile handed to finish_tile(t, acc).
+// ---- fast mode: fp16 operands, fp32 accumulation.  k index of (step s, lane half h, element j) = 16 s + 2 j + h,
+// i.e. the B operand of step s is registers 8 (s & 1) .. +7 of tile s >> 1 of the previous layer as they stand.
+// Reads x (row rowc) and the fp16 weight blocks and biases in LDS; no waits or barriers of its own.
+template <int T0, int T1, int T2, typename FinishTile>
+__device__ __forceinline__ void tok_encode_fast(const TokArgs& a, const float* w_P0, const float* w_B0, const float* w_P1, const float* w_B1,
+                                                const float* w_P2, const float* w_B2, const int S0h, const int64_t rowc, const int lane,
+                                                const int h, FinishTile& finish_tile) {
+    const _Float16* wh0 = reinterpret_cast<const _Float16*>(w_P0);
+    const _Float16* wh1 = reinterpret_cast<const _Float16*>(w_P1);
+    const _Float16* wh2 = reinterpret_cast<const _Float16*>(w_P2);
+    const float* xr = a.x + (size_t)rowc * a.A;
+    f32x16 h0[T0];
+#pragma unroll
+    for (int t = 0; t < T0; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) h0[t][r] = w_B0[(2 * t + h) * 16 + r];
+    for (int s2 = 0; s2 < S0h; ++s2) {
+        f16x8 bx;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = 16 * s2 + 2 * j + h;
+            bx[j] = (_Float16)((k < a.A) ? xr[k] : 0.0f);
+        }
+#pragma unroll
+        for (int t = 0; t < T0; ++t) {
+            const f16x8 av = *reinterpret_cast<const f16x8*>(wh0 + ((size_t)(t * S0h + s2) * 64 + lane) * 8);
+            h0[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bx, h0[t], 0, 0, 0);
+        }
+    }
+    f16x8 b0[2 * T0];
+#pragma unroll
+    for (int t = 0; t < T0; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) b0[2 * t + (r >> 3)][r & 7] = (_Float16)lq_gelu(h0[t][r]);
+    f16x8 b1[2 * T1];
+#pragma unroll
+    for (int t = 0; t < T1; ++t) {
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = w_B1[(2 * t + h) * 16 + r];
+#pragma unroll
+        for (int s2 = 0; s2 < 2 * T0; ++s2) {
+            const f16x8 av = *reinterpret_cast<const f16x8*>(wh1 + ((size_t)(t * (2 * T0) + s2) * 64 + lane) * 8);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, b0[s2], acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) b1[2 * t + (r >> 3)][r & 7] = (_Float16)lq_gelu(acc[r]);
+    }
+#pragma unroll
+    for (int t = 0; t < T2; ++t) {
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = w_B2[(2 * t + h) * 16 + r];
+#pragma unroll
+        for (int s2 = 0; s2 < 2 * T1; ++s2) {
+            const f16x8 av = *reinterpret_cast<const f16x8*>(wh2 + ((size_t)(t * (2 * T1) + s2) * 64 + lane) * 8);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, b1[s2], acc, 0, 0, 0);
+        }
+        finish_tile(t, acc);
+    }
+}
+
+// STREAM2: one 16 KB output-tile slab of layer 2 (slab t_ of a.w2q) into ring buffer buf_, 2 KiB per wave.  Issues LDS-DMA copies
+// and waits for none: which read needs which copy is layer 2's protocol (counted lq_wait_vmcnt + barrier).
+template <int G2, int WAVES, size_t SLAB_STRIDE>
+__device__ __forceinline__ void tok_slab_dma(const TokArgs& a, unsigned char* stage0, const int lane, const int wave, int t_, int buf_) {
+    const unsigned char* src = reinterpret_cast<const unsigned char*>(a.w2q) + (size_t)t_ * (G2 * 1024);
+    unsigned char* dst = stage0 + (size_t)buf_ * SLAB_STRIDE;
+    // the lane offset is made opaque HERE: the 14 source addresses of a row block's slabs do not change from block to
+    // block, hipcc hoisted them out of the block loop as 64-bit VGPR pairs and (S = 13: 190 spilled registers) spilled
+    // eleven of them -- each DMA then sat behind `scratch_load; s_waitcnt vmcnt(0)`, and vmcnt(0) also waits for every
+    // slab copy in flight: the ring ran one memory round trip per KiB.  Two adds per copy instead.
+    unsigned lane16 = (unsigned)lane * 16u;
+    asm volatile("" : "+v"(lane16));
+#pragma unroll
+    for (int j = 0; j < G2 * 1024 / 1024 / WAVES; ++j) {
+        const int off = (wave + j * WAVES) * 1024;
+        // issued as inline asm: behind the builtin hipcc guards the tile's first LDS read of the slab ring with
+        // `s_waitcnt vmcnt(0)` (a DS read may alias an LDS-DMA write) -- the copy of slab t+2, issued two instructions
+        // earlier, had to LAND before tile t could start: a memory round trip per tile.  Which read needs which copy
+        // is this loop's own protocol (counted lq_wait_vmcnt + barrier above).
+        const unsigned long long gaddr = (unsigned long long)(uintptr_t)(src + off) + lane16;
+        const unsigned ldsaddr = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(dst + off));
+        unsigned m0_keep;                                   // (m0 is handed back: hipcc does not accept it as a clobber)
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(m0_keep) : "v"(gaddr), "s"(ldsaddr) : "memory");
+    }
+}
+
 // T0 = 2 (64 features), T1 = 4 (128 features): the reference's encoder widths (v5:54-59).
 // FAST: the encoder's three GEMMs as fp16 MFMAs (v_mfma_f32_32x32x16_f16, fp32 accumulation) -- the "fast" mode
 // of SURVEY section 7 / BASELINE config 2's half-precision encoder: NOT bit-identical to the oracle (a fraction of a
@@ -153,6 +373,32 @@ struct TokArgs {
 // 32 rows (T2 x 16 registers) stay in registers through phase B, and an uncertified row's two lanes hand them to the decision
 // through the wave's LDS slice (lq_screen_decide_inplace).  Same bits as the stored-and-re-read row, no z_e traffic at all; the
 // flag is compile-time so that only this instance carries the 32 live registers.
+//
+// What is a named unit above and what is still in this body was decided by the device assembly of all instances (scripts/dev/asm_diff.sh
+// against the parent commit): a piece was moved out only where not one instruction changed.  Out: the LDS layout (FusedLds), the stamps,
+// tok_store_ze_tile, tok_gelu_fixup, tok_bias16, tok_copy16, tok_load_x / tok_x_masked, the fast prologue and the fast encoder,
+// tok_slab_dma.  Where a thin `[&]` lambda forwards to such a function (load_x, bias16, store_ze_tile, slab_dma), the direct call
+// changed some instance: the closure is part of what the inliner sees.  Tried and NOT kept, with what differed:
+//  * the parity prologue as a function (direct and behind a forwarding lambda): the LDS stores of layer 1's block moved in front of the
+//    layer-0 loop in every parity instance;
+//  * the per-row-block values (ah, al, zdef, zkeep, row_n2 .. row_fown) as ONE struct, with or without encode's own n2 / a2lo / amax /
+//    zt: the loop header's phis changed order, a handful of scalar moves with them (8-wave S = 2, 4-wave S = 4 KEEPZ, S = 8 VQ);
+//  * layer 1 and layer 2 of the fp32 encoder as functions taking wread / slab_dma / finish_tile as callables (forced inline, plain
+//    inline, behind a forwarding lambda): S = 13 and the VQ training instances changed block order and register allocation;
+//  * finish_tile whole (a function taking the individual references behind a forwarding lambda -- forced and plain inline, scalars by
+//    value and by reference, zt as array reference and as pointer -- and a hand-written closure struct with an inline operator()): the
+//    loop header's phis changed order in every VQ instance and in no other; its sigmoid / centre / split half alone as a function
+//    left 44 instances identical and changed the S = 13 training instance (8 000 lines: register allocation);
+//  * layer 0, with its z_q gather rounds and without them (direct and behind a forwarding lambda, forced and plain inline, every
+//    parameter by value and by reference): the LDS addresses of its weight reads were formed differently (the lane's `| 256` folded into
+//    another base) and register allocation followed, thousands of lines in the parity instances; with pend_* by value also the phis;
+//  * phase B's decision and booking (lq_screen_decide .. the z_q hand-over) as one function: by value thousands of lines; by reference
+//    two instructions of lq_usage_add's count changed places in every instance; with the usage count and the hand-over left in the body
+//    the default build was identical and the -DLQ_STAMPS build was not (registers around the stamp behind it, 8-wave S = 2 and S = 13);
+//    behind a forwarding lambda, or the decision alone returning (certified, my_k): hundreds of lines.  So phase B stays in the loop;
+//  * the VQ instance's rescale-and-split and the epilogue's publish + histogram flush as functions: one instance each changed;
+//  * the stamps as a small type: empty methods changed the 4-wave instances of builds WITHOUT the flag (see LQ_STAMP);
+//  * `row0` / `row` once per block for encode and phase B together: the VQ training instance changed; phase B computes its own once.
 template <int S, bool FAST, bool TRAIN, int WAVES, bool COARSE = false, bool VQ = false, bool KEEPZ = false>
 __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
     static_assert(!(FAST && TRAIN), "training uses the parity arithmetic");
@@ -162,49 +408,39 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
     // the one-product screen stages hi-only tiles (half the bytes): twice the tiles per stage in the same LDS, i.e. half the
     // stage hand-overs (vmcnt wait + workgroup barrier + DMA issue) per tile where a stage was ONE tile (S = 8)
     constexpr int TCF = COARSE ? fused_ring_tc_coarse(S) : fused_ring_tc(S), NBF = fused_ring_nb(S);
-    using RingCfg = ScreenCfg<S, TCF, COARSE>;
-    constexpr size_t SLAB_STRIDE = ScreenCfg<S, fused_ring_tc(S), false>::STAGE_BYTES;   // the streamed layer-2 slabs' three buffers (either screen)
-    constexpr int T0 = 2, T1 = 4, T2 = (S + 1) / 2;         // S odd (D = 208): the last 32-feature tile is half used
-    constexpr int S1 = 16 * T0, S2 = 16 * T1;               // k-steps (pairs) of layers 1 and 2
-    // STREAM2: the Lipschitz layer's weights (T2 x 16 KB of fp32 MFMA A operands: 112 KB at D = 208) do not fit beside the stage
-    // ring, so they are streamed, one 16 KB output-tile slab at a time, through that ring -- which is idle during the encoder
-    // phase -- by the same LDS-DMA + counted-vmcnt mechanism as the codebook (all eight waves work on the same tile).
-    constexpr bool STREAM2 = !FAST && S >= LQ_STREAM2_MIN_S;
+    using Lds = FusedLds<S, FAST>;                           // the workgroup's LDS, as the host sized it (lipvq_fused_lds.h)
+    static_assert(Lds::template slices_fit<WAVES, COARSE, KEEPZ>(), "the per-wave slices of the stage ring");
+    constexpr size_t SLAB_STRIDE = Lds::SLAB_STRIDE;         // the streamed layer-2 slabs' three buffers (either screen)
+    constexpr int T0 = Lds::T0, T1 = Lds::T1, T2 = Lds::T2; // 32-feature tiles per layer; S odd (D = 208): the last one is half used
+    constexpr int S1 = Lds::S1, S2 = Lds::S2;               // k-steps (pairs) of layers 1 and 2
+    constexpr bool STREAM2 = Lds::STREAM2;                   // the Lipschitz layer's weights are streamed through the stage ring
     static_assert(!FAST || (S % 2 == 0 && S <= 8), "fast mode: D in {32, 64, 128}");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-#ifdef LQ_STAMPS
-    const long long st_top = __builtin_amdgcn_s_memtime();            // kernel entry: the prologue is [st_top, st_begin)
-    const long long st_top_rt = (long long)__builtin_amdgcn_s_memrealtime();      // (100 MHz, the same clock on every CU)
-#endif
+    LQ_STAMPS_ENTER();
 
     const PackedLayout PL = packed_layout(a.A, 32 * T0, 32 * T1, 16 * S);
     const PrepLayout L = prep_layout(a.K, a.D);
     const int S0 = PL.S0;
     const int S0q = (S0 + 3) / 4;
-    // LDS carve (floats unless noted).  FAST: the three weight blocks are fp16 MFMA fragments instead:
-    // [T][k-steps of 16][64 lanes][8 halfs]
     const int S0h = (a.A + 15) / 16;                                   // fp16 k-steps of layer 0
-    float* w_P0 = reinterpret_cast<float*>(lds);                       // [T0][S0q][64][4]
-    float* w_B0 = w_P0 + (FAST ? T0 * S0h * 256 : T0 * S0q * 256);     // [32*T0]
-    float* w_P1 = w_B0 + 32 * T0;                                      // [T1][S1/4][64][4]
-    float* w_B1 = w_P1 + (FAST ? T1 * (2 * T0) * 256 : T1 * (S1 / 4) * 256);
-    float* w_P2 = w_B1 + 32 * T1;                                      // [T2][S2/4][64][4]
-    float* w_B2 = w_P2 + (FAST ? T2 * (2 * T1) * 256 : STREAM2 ? 0 : T2 * (S2 / 4) * 256);
-    float* w_mu = w_B2 + 32 * T2;                                      // [16*S]
-    unsigned char* stage0 = reinterpret_cast<unsigned char*>(w_mu + 16 * S);   // 2 stage buffers (also the
-                                                                                // per-wave transpose slices of the decision)
+    // LDS carve (FusedLds: floats unless noted; FAST: the three weight blocks are fp16 MFMA fragments instead)
+    const Lds lay(a.A);
+    // (written out here, block after block as FusedLds orders them: as a member function returning the pointers the chain left the
+    // parity instances' code as it was and changed the fast instances' -- there layer 0's block size is also the prologue's copy length)
+    float* const w_P0 = reinterpret_cast<float*>(lds);                 // [T0][S0q][64][4]
+    float* const w_B0 = w_P0 + lay.template n_P0<int>();               // [32*T0]
+    float* const w_P1 = w_B0 + Lds::N_B0;                              // [T1][S1/4][64][4]
+    float* const w_B1 = w_P1 + Lds::N_P1;                              // [32*T1]
+    float* const w_P2 = w_B1 + Lds::N_B1;                              // [T2][S2/4][64][4]
+    float* const w_B2 = w_P2 + Lds::N_P2;                              // [32*T2]
+    float* const w_mu = w_B2 + Lds::N_B2;                              // [16*S]
+    unsigned char* const stage0 = reinterpret_cast<unsigned char*>(w_mu + Lds::N_MU);   // the stage ring (also the per-wave transpose slices of the decision)
+    unsigned* const hist = reinterpret_cast<unsigned*>(stage0 + Lds::template hist_in_ring<COARSE>());
+    constexpr size_t STAGES_BYTES = Lds::template stages_bytes<COARSE>(), WSLICE = Lds::template wslice<WAVES, COARSE>();
     // per-workgroup usage histogram (K <= FUSED_HIST_MAX): LDS atomics per row, ONE global atomic per non-empty
     // bin at the end of this persistent workgroup -- skewed code distributions would otherwise serialise on a
     // few global addresses (see lq_usage_add)
-    constexpr size_t RING_OWN = (size_t)NBF * RingCfg::STAGE_BYTES + 1024, RING_FINE = lq_ring_bytes<S, fused_ring_tc(S), NBF>();
-    constexpr size_t STAGES_BYTES = RING_OWN > RING_FINE ? RING_OWN : RING_FINE;      // the ring + its dummy KiB (one LDS carve for both screens)
-    static_assert(STAGES_BYTES >= (size_t)WAVES * LQ_DECIDE_BYTES, "the decision's per-wave transposes live in the stage ring");
-    // per-wave private slice of the (idle) ring: the decision's transposes (LQ_DECIDE_BYTES) and the z_q copy's staging (GP KiB)
-    constexpr size_t WSLICE = (STAGES_BYTES >= (size_t)WAVES * 8192) ? 8192 : LQ_DECIDE_BYTES;
-    static_assert(LQ_DECIDE_BYTES >= 4096 && WSLICE >= LQ_DECIDE_BYTES, "a slice holds the transposes and four staged KiB");
-    static_assert(!KEEPZ || WSLICE >= LQ_DECIDE_BYTES + 64 * S, "KEEPZ: one z_e row behind the decision scratch");
-    unsigned* hist = reinterpret_cast<unsigned*>(stage0 + ((STAGES_BYTES + 63) & ~(size_t)63));
-    const bool use_hist = a.usage && fused_hist_fits<S, FAST>(a.A, a.K);         // (the same rule sizes the launch's LDS)
+    const bool use_hist = a.usage && Lds::hist_fits(a.A, a.K);         // (the same rule sizes the launch's LDS)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // provably wave-uniform (scalar row/address arithmetic)
@@ -233,51 +469,9 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
     const bool x_pref = !FAST && a.A <= 2 * XPF;
     float xq[XPF];
     constexpr int LANE_W_MIN_S = 8;      // the instances that re-form lane-dependent addresses per use; at S = 4 nothing spills
-    // The XPF loads of a call are issued back to back: nothing between them consumes a result, and the `k < A` select is applied where
-    // layer 0 consumes xq (x_masked), not here -- with the select at load time hipcc emitted load / s_waitcnt vmcnt(0) / v_cndmask
-    // eight times in a row in the block loop: one HBM miss and seven dependent cache hits in series per wave and row block.
-    // Addresses: ONE wave-uniform base (the wave's first row, clamped into the array) plus the lane's 32-bit byte offset, clamped
-    // to the array's last float -- always valid; what a clamp redirects is masked at use (k >= A) or belongs to a row past N.
-    // (S >= 8 keeps the first form, select at load time: those instances spill xq itself, every load is followed by its
-    // `s_waitcnt vmcnt(0)` and scratch store whichever way it is written, and the batched form made their prologue's loads wait too)
-    constexpr bool X_BATCHED = S < LANE_W_MIN_S;
-    auto load_x = [&](int64_t blk_, float (&out)[XPF]) {
-        if constexpr (!X_BATCHED) {
-            int64_t r_ = (blk_ * WAVES + wave) * 32 + ln;
-            r_ = r_ < a.N ? r_ : a.N - 1;
-            const int64_t last = a.N * a.A - 1;
-            // (the lane half is opaque here -- hipcc had hoisted the XPF partial addresses `x + 4 k` out of the block loop and
-            // spilled them; each reload's `vmcnt(0)` sat behind the x load issued just before it: XPF global loads in series per block)
-            int h_x = h;
-            asm volatile("" : "+v"(h_x));
-#pragma unroll
-            for (int q = 0; q < XPF; ++q) {
-                const int k = 2 * q + h_x;
-                int64_t i_ = r_ * a.A + k;
-                i_ = i_ < last ? i_ : last;                      // always a valid address; masked below (no divergent branch)
-                const float v = a.x[i_];
-                out[q] = (k < a.A) ? v : 0.0f;
-            }
-            return;
-        }
-        int64_t row0_ = (blk_ * WAVES + wave) * 32;
-        row0_ = row0_ < a.N ? row0_ : a.N - 1;
-        const int64_t left64 = a.N - 1 - row0_;                  // rows behind the wave's first one
-        const int left = left64 < 31 ? (int)left64 : 31;
-        const unsigned char* xb = reinterpret_cast<const unsigned char*>(a.x + row0_ * a.A);
-        const int64_t end64 = ((a.N - row0_) * a.A - 1) * 4;     // byte offset of the array's last float
-        const unsigned end = end64 < (int64_t)(32 * 2 * XPF * 4) ? (unsigned)end64 : 32u * 2 * XPF * 4;      // (beyond every offset of a wave)
-        const unsigned off0 = (unsigned)((ln < left ? ln : left) * a.A + h) * 4u;
-#pragma unroll
-        for (int q = 0; q < XPF; ++q) {
-            unsigned o = off0 + 8u * q;                          // k = 2 q + h
-            o = o < end ? o : end;
-            out[q] = *reinterpret_cast<const float*>(xb + o);
-        }
-    };
-    // xq[i] as layer 0 consumes it: inputs past the fan-in are zeros (a select, not a product: the loaded value may be anything)
+    constexpr bool X_BATCHED = S < LANE_W_MIN_S;      // (tok_load_x)
+    auto load_x = [&](int64_t blk_, float (&out)[XPF]) { tok_load_x<WAVES, XPF, X_BATCHED>(a, wave, ln, h, blk_, out); };
     const int x_kmax = a.A - h;
-    auto x_masked = [&](int i, const float (&v)[XPF]) { return (!X_BATCHED || 2 * i < x_kmax) ? v[i] : 0.0f; };
     if (x_pref) load_x(blockIdx.x, xq);
     lq_ws_begin(a.amb_count);
     // ---- once per workgroup: weights (re-laid out 4 k-steps per 16-byte LDS read), biases, mu --------
@@ -290,25 +484,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
         const float vb0 = bias_src(PL.oB0, 32 * T0), vb1 = bias_src(PL.oB1, 32 * T1), vb2 = bias_src(PL.oB2, 32 * T2);
         const float vmu = mu[tid < 16 * S ? tid : 16 * S - 1];
         if (FAST) {
-            // packed16 = [P0h | P1h | P2h], each already [t][s][lane][8 halfs] = 4 floats per (t, s, lane)
-            const float* src = reinterpret_cast<const float*>(a.packed16);
-            const int n0 = T0 * S0h * 256, n1 = T1 * (2 * T0) * 256, n2 = T2 * (2 * T1) * 256;
-            // 16-byte pieces, four loads in flight per thread and round (the element loop was one L2 round trip per float)
-            auto copy16 = [&](float* dst, const float* from, int nfl) {
-                const float4* s4 = reinterpret_cast<const float4*>(from);
-                float4* d4 = reinterpret_cast<float4*>(dst);
-                const int nv = nfl / 4;
-                for (int v0 = tid; v0 < nv; v0 += 4 * THREADS) {
-                    float4 r[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { const int v = v0 + q * THREADS; r[q] = s4[v < nv ? v : nv - 1]; }
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { const int v = v0 + q * THREADS; if (v < nv) d4[v] = r[q]; }
-                }
-            };
-            copy16(w_P0, src, n0);
-            copy16(w_P1, src + n0, n1);
-            copy16(w_P2, src + n0 + n1, n2);
+            tok_prologue_weights_f16<Lds, THREADS>(a, lay.template n_P0<int>(), tid, w_P0, w_P1, w_P2);
         } else {
             // Round 4: every load of the prologue is issued before the first LDS store.  The first version copied element by
             // element (`w[i] = P[..]`: hipcc emits load, s_waitcnt vmcnt(0), ds_write_b32 per iteration -- 16 + 16 dependent L2
@@ -379,15 +555,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
     }
     __syncthreads();
 
-#ifdef LQ_STAMPS
-    // diagnostic build only (scripts/stamps.py): per-wave cycles per segment, accumulated over the row blocks and written to
-    // the unused upper half of the row list; no output value depends on them
-    long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev;
-    const long long st_begin = __builtin_amdgcn_s_memtime();
-#define LQ_STAMP(i) do { const long long t_ = __builtin_amdgcn_s_memtime(); st_acc[i] += t_ - st_prev; st_prev = t_; } while (0)
-#else
-#define LQ_STAMP(i) do { } while (0)
-#endif
+    LQ_STAMPS_PROLOGUE_DONE();
     // the z_q copy of a row block is deferred to the start of the NEXT block (parity kernel) and routed through LDS (lq_gather_dma):
     // its first round overlaps layer 0, further rounds (wider latents) follow
     constexpr bool DEFER_GATHER = !FAST;
@@ -395,42 +563,10 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
     bool pend_ok = false;
     int64_t pend_row0 = 0;
     bool have_pend = false;
-    // z_e row store of one finished 32-feature tile.  Lane (n, h) holds features 32t + 2r + h (r = 0..15) of row n: the even ones in
-    // the low half-wave, the odd ones in the high half.  One v_permlane32_swap per register pair (low half's r >= 8 <-> high
-    // half's r < 8) leaves the low lane with features 32t .. 32t+15 and the high lane with 32t+16 .. 32t+31, i.e. four 16-byte
-    // stores of consecutive floats per lane (64 contiguous bytes per lane) instead of sixteen 4-byte stores scattered over the row.
     int64_t ze_shift = 0;          // ring mode: rows of row block blk are stored ze_shift rows lower (set per block)
-    auto store_ze_tile = [&](const int64_t row, const int t, const f32x16& acc) {
-            {
-                float lo8[8], hi8[8];                 // after the swaps: lo8[j] = feature base + 2j, hi8[j] = base + 2j + 1
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    // vdst = low half's register r = 8 + j (goes up), src = high half's register r = j (comes down)
-                    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[j]), __float_as_uint(acc[8 + j]), false, false);
-                    // sw[0]: lanes 0-31 keep acc[j] (own even features 2j), lanes 32-63 receive low half's acc[8+j]
-                    // sw[1]: lanes 0-31 receive high half's acc[j] (odd features 2j+1), lanes 32-63 keep acc[8+j]
-                    lo8[j] = __uint_as_float(sw[0]);
-                    hi8[j] = __uint_as_float(sw[1]);
-                }
-                // low lanes : lo8[j] = feat 2j (own, even), hi8[j] = feat 2j+1 (from the high lane)        -> base 32t
-                // high lanes: lo8[j] = feat 16+2j (from the low lane, even), hi8[j] = feat 16+2j+1 (own) -> base 32t+16
-                if (row < a.N && 2 * t + h < S) {                // (the high lanes' 16 features of a half-used last tile do not exist)
-                    float4* dst = reinterpret_cast<float4*>(a.ze_out + (size_t)(row - ze_shift) * a.D + 32 * t + 16 * h);
-                    // nontemporal (round 4): written once, read back for a fraction of a percent of the rows -- the stream should not
-                    // displace the codebook tiles and weights every workgroup re-reads from L2 (with the z_q rows the same way:
-                    // cfg2 -2.4 %, icrt -2.9 %, same box, profiles/r04_e_nt_stores_ab.txt)
-                    typedef float lq_f4v __attribute__((ext_vector_type(4)));
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (S > 4 || TRAIN || a.nt_ze) __builtin_nontemporal_store((lq_f4v){lo8[2 * q], hi8[2 * q], lo8[2 * q + 1], hi8[2 * q + 1]}, reinterpret_cast<lq_f4v*>(dst) + q);
-                        else reinterpret_cast<lq_f4v*>(dst)[q] = (lq_f4v){lo8[2 * q], hi8[2 * q], lo8[2 * q + 1], hi8[2 * q + 1]};   // (launch-uniform: TokArgs; S > 4 and the training instances: always nontemporal -- nothing to choose there, and the second copy of the stores cost icrt 1.4 %)
-                }
-            }
-    };
+    auto store_ze_tile = [&](const int64_t row, const int t, const f32x16& acc) { tok_store_ze_tile<S, TRAIN>(a, h, ze_shift, row, t, acc); };
     for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-#ifdef LQ_STAMPS
-        st_prev = __builtin_amdgcn_s_memtime();
-#endif
+        LQ_STAMPS_BEGIN_BLOCK();
         ze_shift = (!KEEPZ && a.ze_ring) ? (blk - (int64_t)blockIdx.x) * (WAVES * 32) : 0;
         f16x8 ah[S], al[S];
         // z_e of the LAST layer-2 tile, stored behind the screen's first copies -- in the instances with registers to spare
@@ -440,425 +576,329 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
         f32x16 zdef;
         f32x16 zkeep[KEEPZ ? T2 : 1];                        // KEEPZ: z_e of the wave's rows, register r of tile t = feature 32t + 2r + h of row ln
         float row_n2, row_a2, row_fz, row_fown;              // phase A's row statistics and scales (the VQ instance: the row's own)
-      // ---- phase A: the wave's 32 rows through the encoder, split into the screen's fp16 fragments ----
-      auto encode = [&]() {
-        // the lane index the LDS weight reads are addressed with, opaque per row block in the instances that spill (S >= 8): as loop
-        // invariants hipcc kept the lanes' LDS addresses in registers from the kernel's first lines and spilled them -- a reload is a
-        // vector-memory load, and `s_waitcnt vmcnt(0)` in front of its use also waits for every store and copy in flight
-        int lane_w = lane;
-        if constexpr (S >= LANE_W_MIN_S) asm volatile("" : "+v"(lane_w));
-        const int h_w = lane_w >> 5;                         // (the centring vector's LDS reads: not hoisted out of the block loop either)
-        const int64_t row0 = (blk * WAVES + wave) * 32;
-        const int64_t row = row0 + ln;
-        const int64_t rowc = row < a.N ? row : a.N - 1;
-        float n2 = 0.0f, a2lo = 0.0f, amax = 0.0f;
-        float zt[VQ ? T2 : 1][16];                           // VQ: the centred latent in fp32 until the row's scale is known
-        // sigmoid, centring, row statistics and the optional z_e store of one finished 32-feature tile
-        auto finish_tile = [&](const int t, f32x16& acc) {
-            if constexpr (TRAIN) lq_tile_store16(a.pre2, a.D, row, row < a.N, t, h, acc, a.D, true);
-          if constexpr (VQ) {
+        // ---- phase A: the wave's 32 rows through the encoder, split into the screen's fp16 fragments ----
+        auto encode = [&]() {
+            // the lane index the LDS weight reads are addressed with, opaque per row block in the instances that spill (S >= 8): as loop
+            // invariants hipcc kept the lanes' LDS addresses in registers from the kernel's first lines and spilled them -- a reload is a
+            // vector-memory load, and `s_waitcnt vmcnt(0)` in front of its use also waits for every store and copy in flight
+            int lane_w = lane;
+            if constexpr (S >= LANE_W_MIN_S) asm volatile("" : "+v"(lane_w));
+            const int h_w = lane_w >> 5;                         // (the centring vector's LDS reads: not hoisted out of the block loop either)
+            const int64_t row0 = (blk * WAVES + wave) * 32;
+            const int64_t row = row0 + ln;
+            const int64_t rowc = row < a.N ? row : a.N - 1;
+            float n2 = 0.0f, a2lo = 0.0f, amax = 0.0f;
+            float zt[VQ ? T2 : 1][16];                           // VQ: the centred latent in fp32 until the row's scale is known
+            // sigmoid, centring, row statistics and the optional z_e store of one finished 32-feature tile
+            auto finish_tile = [&](const int t, f32x16& acc) {
+                if constexpr (TRAIN) lq_tile_store16(a.pre2, a.D, row, row < a.N, t, h, acc, a.D, true);
+                if constexpr (VQ) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                if (2 * t + (r >> 3) >= S) { zt[t][r] = 0.0f; continue; }
-                const float zv = acc[r] > 0.0f ? acc[r] : 0.0f;      // the canonical ReLU (lq_act_apply)
-                acc[r] = zv;
-                const float v = zv - w_mu[32 * t + 2 * r + h_w];
-                zt[t][r] = v;
-                n2 = lq_fma(v, v, n2);
-                amax = fmaxf(amax, lq_abs(v));
-            }
-          } else {
-            if constexpr (!FAST) {
-                // the canonical sigmoid, two elements per instruction; a tile that holds a NaN or an infinity (wave-uniform test,
-                // practically never true) takes the one-element form, whose clamps propagate NaN
-                lq_v2f chk = lq_bc2(0.0f);
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) chk = lq_nonfinite_acc2((lq_v2f){acc[r], acc[r + 1]}, chk);
-                if (__builtin_amdgcn_ballot_w64(!(chk.x == 0.0f && chk.y == 0.0f)) != 0ull) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[r] = lq_sigmoid(acc[r]);
+                    for (int r = 0; r < 16; ++r) {
+                        if (2 * t + (r >> 3) >= S) { zt[t][r] = 0.0f; continue; }
+                        const float zv = acc[r] > 0.0f ? acc[r] : 0.0f;      // the canonical ReLU (lq_act_apply)
+                        acc[r] = zv;
+                        const float v = zv - w_mu[32 * t + 2 * r + h_w];
+                        zt[t][r] = v;
+                        n2 = lq_fma(v, v, n2);
+                        amax = fmaxf(amax, lq_abs(v));
+                    }
                 } else {
+                    if constexpr (!FAST) {
+                        // the canonical sigmoid, two elements per instruction; a tile that holds a NaN or an infinity (wave-uniform test,
+                        // practically never true) takes the one-element form, whose clamps propagate NaN
+                        lq_v2f chk = lq_bc2(0.0f);
 #pragma unroll
-                    for (int r = 0; r < 16; r += 2) {
-                        if (2 * t + (r >> 3) >= S) continue;
-                        const lq_v2f z2 = lq_sigmoid2_finite((lq_v2f){acc[r], acc[r + 1]});
-                        acc[r] = z2.x; acc[r + 1] = z2.y;
+                        for (int r = 0; r < 16; r += 2) chk = lq_nonfinite_acc2((lq_v2f){acc[r], acc[r + 1]}, chk);
+                        if (__builtin_amdgcn_ballot_w64(!(chk.x == 0.0f && chk.y == 0.0f)) != 0ull) {
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) acc[r] = lq_sigmoid(acc[r]);
+                        } else {
+#pragma unroll
+                            for (int r = 0; r < 16; r += 2) {
+                                if (2 * t + (r >> 3) >= S) continue;
+                                const lq_v2f z2 = lq_sigmoid2_finite((lq_v2f){acc[r], acc[r + 1]});
+                                acc[r] = z2.x; acc[r + 1] = z2.y;
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        if (2 * t + (r >> 3) >= S) continue;             // S odd: features past D in the last tile (zero weights) are not z_e
+                        // fast mode: hardware exp2 / rcp (1 ulp each) instead of the canonical exp polynomial + IEEE division
+                        const float zv = FAST ? __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(acc[r] * -1.44269504088896341f)) : acc[r];
+                        acc[r] = zv;
+                        const float v = zv - w_mu[32 * t + 2 * r + h_w];
+                        n2 = lq_fma(v, v, n2);
+                        // register r of tile t is feature 32t + 2r + h = screen slot (step 2t + (r >> 3), element r & 7): scaled by the
+                        // kernel-wide power of two fz and split into fp16 hi + lo right here (nothing of z_e is kept in fp32)
+                        const float vs = v * fz;
+                        const _Float16 vh = (_Float16)vs;
+                        const float rs = vs - (float)vh;                       // exact: the one-product screen's row-side residual
+                        ah[2 * t + (r >> 3)][r & 7] = vh;
+                        al[2 * t + (r >> 3)][r & 7] = (_Float16)rs;
+                        if constexpr (COARSE) a2lo = lq_fma(rs, rs, a2lo);
                     }
                 }
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                if (2 * t + (r >> 3) >= S) continue;             // S odd: features past D in the last tile (zero weights) are not z_e
-                // fast mode: hardware exp2 / rcp (1 ulp each) instead of the canonical exp polynomial + IEEE division
-                const float zv = FAST ? __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(acc[r] * -1.44269504088896341f)) : acc[r];
-                acc[r] = zv;
-                const float v = zv - w_mu[32 * t + 2 * r + h_w];
-                n2 = lq_fma(v, v, n2);
-                // register r of tile t is feature 32t + 2r + h = screen slot (step 2t + (r >> 3), element r & 7): scaled by the
-                // kernel-wide power of two fz and split into fp16 hi + lo right here (nothing of z_e is kept in fp32)
-                const float vs = v * fz;
-                const _Float16 vh = (_Float16)vs;
-                const float rs = vs - (float)vh;                       // exact: the one-product screen's row-side residual
-                ah[2 * t + (r >> 3)][r & 7] = vh;
-                al[2 * t + (r >> 3)][r & 7] = (_Float16)rs;
-                if constexpr (COARSE) a2lo = lq_fma(rs, rs, a2lo);
-            }
-          }
-            // z_e rows for the exact stage (store_ze_tile).  The LAST tile's are not stored here: its sixteen values wait in zdef and
-            // are stored behind the screen's first stage copies (lq_screen_core, DEFER) -- in front of them their write
-            // acknowledgements stood between every wave and "stage 0 has landed" (vmcnt retires in order)
-            if constexpr (KEEPZ) {
-                zkeep[t] = acc;                              // (no store, no transposes: the decision reads the registers)
-            } else if (a.ze_out) {
-                if (DEFER_ZE && a.defer_ze && t == T2 - 1) zdef = acc;
-                else store_ze_tile(row, t, acc);
-            }
-        };
-
-        if constexpr (!FAST) {
-            // ================= phase A: encoder + Lipschitz layer, fp32 MFMA ====================
-            // An fp32 MFMA blocks its own wave's vector instructions for its whole duration (scripts/probe/probe_pipes2.hip:
-            // 64 + 8 + 4.4 n cycles for an MFMA followed by n independent v_fma), so GELU / sigmoid work cannot hide under
-            // the chain; what CAN be hidden is latency: the LDS reads of the weights (16 bytes per lane feed four MFMAs) and
-            // of the biases are issued one group ahead of the MFMAs that use them (sched_barrier keeps hipcc from sinking them
-            // back in front of their use, where it waits for each LDS round trip), and x comes from the prefetch above.
-            auto gelu_fixup = [&](f32x16& out, const f32x16& pre) {
-                // largest |pre| of the tile by v_max3 (half an instruction per element instead of a multiply and a compare);
-                // a NaN is skipped by max3, but the polynomial has already turned it into a NaN, as the tail would
-                float mx = 0.0f;
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(mx) : "v"(mx), "v"(pre[r]), "v"(pre[r + 1]));
-                if (__builtin_amdgcn_ballot_w64(!(mx * mx < 18.0f)) != 0ull) {          // wave-uniform, practically never taken
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        if (!(pre[r] * pre[r] < 18.0f)) out[r] = lq_gelu_tail(pre[r]);
+                // z_e rows for the exact stage (store_ze_tile).  The LAST tile's are not stored here: its sixteen values wait in zdef and
+                // are stored behind the screen's first stage copies (lq_screen_core, DEFER) -- in front of them their write
+                // acknowledgements stood between every wave and "stage 0 has landed" (vmcnt retires in order)
+                if constexpr (KEEPZ) {
+                    zkeep[t] = acc;                              // (no store, no transposes: the decision reads the registers)
+                } else if (a.ze_out) {
+                    if (DEFER_ZE && a.defer_ze && t == T2 - 1) zdef = acc;
+                    else store_ze_tile(row, t, acc);
                 }
             };
-            auto bias16 = [&](const float* wb, int t) {                   // the lane's 16 bias values of tile t (see the LDS fill)
-                f32x16 b;
-                const float4* p4 = reinterpret_cast<const float4*>(wb + (2 * t + h) * 16);
+
+            if constexpr (!FAST) {
+                // ================= phase A: encoder + Lipschitz layer, fp32 MFMA ====================
+                // An fp32 MFMA blocks its own wave's vector instructions for its whole duration (scripts/probe/probe_pipes2.hip:
+                // 64 + 8 + 4.4 n cycles for an MFMA followed by n independent v_fma), so GELU / sigmoid work cannot hide under
+                // the chain; what CAN be hidden is latency: the LDS reads of the weights (16 bytes per lane feed four MFMAs) and
+                // of the biases are issued one group ahead of the MFMAs that use them (sched_barrier keeps hipcc from sinking them
+                // back in front of their use, where it waits for each LDS round trip), and x comes from the prefetch above.
+                auto bias16 = [&](const float* wb, int t) { return tok_bias16(wb, t, h); };     // the lane's 16 bias values of tile t
+                f32x16 h0[T0];
+                // the previous block's z_q rows: round 0 of the copy travels codebook -> LDS staging while layer 0 runs
+                constexpr int NTRIP = (16 * S + 63) / 64;                    // 64 floats of every row per gather trip
+                constexpr int GP = (STAGES_BYTES >= (size_t)WAVES * 8192) ? 8 : 4;      // passes (KiB per wave) per round
+                constexpr int NROUND = NTRIP * (8 / GP);
+                // every wave's staging area and its decision scratch are ONE private slice of the ring (stride WSLICE): a wave may start
+                // the copy while the others are still deciding the previous block -- no workgroup barrier in front of it (round 4; the
+                // staging areas used to overlap other waves' scratch: every block began by waiting for its slowest wave)
+                unsigned char* gstage = stage0 + (size_t)wave * WSLICE;
+                const bool gnow = DEFER_GATHER && have_pend && a.zq;         // wave-uniform
+                if (gnow) lq_gather_dma<GP>(gstage, a.cb, pend_k, pend_ok, pend_row0, a.N, a.D, lane, 0, 0);
+                {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) { const float4 v = p4[q]; b[4 * q] = v.x; b[4 * q + 1] = v.y; b[4 * q + 2] = v.z; b[4 * q + 3] = v.w; }
-                return b;
-            };
-            f32x16 h0[T0];
-            // the previous block's z_q rows: round 0 of the copy travels codebook -> LDS staging while layer 0 runs
-            constexpr int NTRIP = (16 * S + 63) / 64;                    // 64 floats of every row per gather trip
-            constexpr int GP = (STAGES_BYTES >= (size_t)WAVES * 8192) ? 8 : 4;      // passes (KiB per wave) per round
-            constexpr int NROUND = NTRIP * (8 / GP);
-            // every wave's staging area and its decision scratch are ONE private slice of the ring (stride WSLICE): a wave may start
-            // the copy while the others are still deciding the previous block -- no workgroup barrier in front of it (round 4; the
-            // staging areas used to overlap other waves' scratch: every block began by waiting for its slowest wave)
-            unsigned char* gstage = stage0 + (size_t)wave * WSLICE;
-            const bool gnow = DEFER_GATHER && have_pend && a.zq;         // wave-uniform
-            if (gnow) lq_gather_dma<GP>(gstage, a.cb, pend_k, pend_ok, pend_row0, a.N, a.D, lane, 0, 0);
-            {
+                    for (int t = 0; t < T0; ++t) h0[t] = bias16(w_B0, t);
+                    if (x_pref) {
 #pragma unroll
-                for (int t = 0; t < T0; ++t) h0[t] = bias16(w_B0, t);
-                if (x_pref) {
+                        for (int sq = 0; sq < XPF / 4; ++sq) {
+                            if (sq < S0q) {                                    // wave-uniform
+                                float4 av[T0];
 #pragma unroll
-                    for (int sq = 0; sq < XPF / 4; ++sq) {
-                        if (sq < S0q) {                                    // wave-uniform
+                                for (int t = 0; t < T0; ++t) av[t] = *reinterpret_cast<const float4*>(w_P0 + ((t * S0q + sq) * 64 + lane_w) * 4);
+#pragma unroll
+                                for (int q = 0; q < 4; ++q) {
+                                    const float bv = tok_x_masked<X_BATCHED, XPF>(x_kmax, 4 * sq + q, xq);
+#pragma unroll
+                                    for (int t = 0; t < T0; ++t) {
+                                        const float aq = q == 0 ? av[t].x : q == 1 ? av[t].y : q == 2 ? av[t].z : av[t].w;
+                                        // padded k-steps (s >= S0) multiply zeros: acc + 0*0 = acc (oracle pads odd fan-in the same way)
+                                        h0[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq, bv, h0[t], 0, 0, 0);
+                                    }
+                                }
+                            }
+                        }
+                    } else {
+                        const float* xr = a.x + (size_t)rowc * a.A;
+                        for (int sq = 0; sq < S0q; ++sq) {
                             float4 av[T0];
+                            float bvv[4];
 #pragma unroll
                             for (int t = 0; t < T0; ++t) av[t] = *reinterpret_cast<const float4*>(w_P0 + ((t * S0q + sq) * 64 + lane_w) * 4);
 #pragma unroll
                             for (int q = 0; q < 4; ++q) {
-                                const float bv = x_masked(4 * sq + q, xq);
+                                const int k = 2 * (4 * sq + q) + h;
+                                bvv[q] = (k < a.A) ? xr[k] : 0.0f;
+                            }
+#pragma unroll
+                            for (int q = 0; q < 4; ++q)
 #pragma unroll
                                 for (int t = 0; t < T0; ++t) {
                                     const float aq = q == 0 ? av[t].x : q == 1 ? av[t].y : q == 2 ? av[t].z : av[t].w;
-                                    // padded k-steps (s >= S0) multiply zeros: acc + 0*0 = acc (oracle pads odd fan-in the same way)
-                                    h0[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq, bv, h0[t], 0, 0, 0);
+                                    h0[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq, bvv[q], h0[t], 0, 0, 0);
                                 }
-                            }
                         }
                     }
-                } else {
-                    const float* xr = a.x + (size_t)rowc * a.A;
-                    for (int sq = 0; sq < S0q; ++sq) {
-                        float4 av[T0];
-                        float bvv[4];
+                    // GELU: the straight-line polynomial on every element, the rare |x| >= sqrt(18) ones fixed up behind a wave-uniform
+                    // branch (lq_gelu's per-element branch cost a divergent-branch sequence per value)
 #pragma unroll
-                        for (int t = 0; t < T0; ++t) av[t] = *reinterpret_cast<const float4*>(w_P0 + ((t * S0q + sq) * 64 + lane_w) * 4);
+                    for (int t = 0; t < T0; ++t) {
+                        const f32x16 pre = h0[t];
+                        if constexpr (TRAIN) lq_tile_store16(a.pre0, 32 * T0, row, row < a.N, t, h, pre, 32 * T0, true);
+                        if constexpr (VQ) {
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const int k = 2 * (4 * sq + q) + h;
-                            bvv[q] = (k < a.A) ? xr[k] : 0.0f;
-                        }
+                            for (int r = 0; r < 16; ++r) h0[t][r] = pre[r] > 0.0f ? pre[r] : 0.0f;
+                        } else {
 #pragma unroll
-                        for (int q = 0; q < 4; ++q)
-#pragma unroll
-                            for (int t = 0; t < T0; ++t) {
-                                const float aq = q == 0 ? av[t].x : q == 1 ? av[t].y : q == 2 ? av[t].z : av[t].w;
-                                h0[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq, bvv[q], h0[t], 0, 0, 0);
+                            for (int r = 0; r < 16; r += 2) {
+                                const lq_v2f g2 = lq_gelu_poly2((lq_v2f){pre[r], pre[r + 1]});
+                                h0[t][r] = g2.x; h0[t][r + 1] = g2.y;
                             }
+                            tok_gelu_fixup(h0[t], pre);
+                        }
                     }
                 }
-                // GELU: the straight-line polynomial on every element, the rare |x| >= sqrt(18) ones fixed up behind a wave-uniform
-                // branch (lq_gelu's per-element branch cost a divergent-branch sequence per value)
+                if (gnow) {
 #pragma unroll
-                for (int t = 0; t < T0; ++t) {
-                    const f32x16 pre = h0[t];
-                    if constexpr (TRAIN) lq_tile_store16(a.pre0, 32 * T0, row, row < a.N, t, h, pre, 32 * T0, true);
-                    if constexpr (VQ) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) h0[t][r] = pre[r] > 0.0f ? pre[r] : 0.0f;
-                    } else {
-#pragma unroll
-                    for (int r = 0; r < 16; r += 2) {
-                        const lq_v2f g2 = lq_gelu_poly2((lq_v2f){pre[r], pre[r + 1]});
-                        h0[t][r] = g2.x; h0[t][r + 1] = g2.y;
-                    }
-                    gelu_fixup(h0[t], pre);
+                    for (int rd = 0; rd < NROUND; ++rd) {                    // round rd = (trip rd / (8 / GP), passes GP (rd % (8 / GP)) ...)
+                        lq_wait_vmcnt<0>();
+                        lq_gather_flush<GP>(gstage, a.zq, pend_ok, pend_row0, a.N, a.D, lane, rd / (8 / GP), GP * (rd % (8 / GP)));
+                        if (rd + 1 < NROUND) {
+                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // my staging reads are done before it is refilled
+                            lq_gather_dma<GP>(gstage, a.cb, pend_k, pend_ok, pend_row0, a.N, a.D, lane, (rd + 1) / (8 / GP),
+                                              GP * ((rd + 1) % (8 / GP)));
+                        }
                     }
                 }
-            }
-            if (gnow) {
-#pragma unroll
-                for (int rd = 0; rd < NROUND; ++rd) {                    // round rd = (trip rd / (8 / GP), passes GP (rd % (8 / GP)) ...)
-                    lq_wait_vmcnt<0>();
-                    lq_gather_flush<GP>(gstage, a.zq, pend_ok, pend_row0, a.N, a.D, lane, rd / (8 / GP), GP * (rd % (8 / GP)));
-                    if (rd + 1 < NROUND) {
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // my staging reads are done before it is refilled
-                        lq_gather_dma<GP>(gstage, a.cb, pend_k, pend_ok, pend_row0, a.N, a.D, lane, (rd + 1) / (8 / GP),
-                                          GP * ((rd + 1) % (8 / GP)));
-                    }
-                }
-            }
-            LQ_STAMP(0);
-            // ---- layers 1 and 2: one stream of 16-byte weight reads (T1 S1/4 of layer 1, then T2 S2/4 of layer 2), each read
-            // issued one 4-MFMA group ahead of its use.  The GELU of tile t-1 is written between the MFMAs of tile t (two
-            // elements per group): it cannot overlap the MFMAs (see above), but it keeps the polynomial out of a lumped
-            // 16 x 17-instruction block behind each chain.
-            f32x16 h1[T1];
-            f32x16 pend;                      // pre-activations of the previous tile, GELU pending
-            // LUMPED (round 4): a tile's GELU as ONE block behind its MFMA chain instead of staged between the MFMAs of the next
-            // tile's chain (rounds 2-3).  scripts/probe/probe_roles.hip: fp32 MFMAs and fp32 vector work share the SIMD's lanes -- a
-            // pair of tiles on a SIMD's two waves takes the SUM of both (5 340 cycles) however the instructions are arranged -- but
-            // the interleaved stream loses another 9 % to issue arbitration between the two waves (5 843).  Same values either way:
-            // cfg2 0.4095 -> 0.3997 ms per launch, same box (profiles/r04_b_lumped_gelu_ab.txt).  Not where every output tile of
-            // layer 2 waits at a workgroup barrier for its streamed weights (S = 13: 0.934 -> 1.00 ms lumped) -- there the staging stays.
-            constexpr bool LUMPED = !VQ && !STREAM2;
-            constexpr int G1 = S1 / 4, G2 = S2 / 4;             // groups per tile
-            auto wread = [&](int gidx) {                        // group gidx of the stream (compile-time after unrolling)
-                if (STREAM2 && gidx >= T1 * G1) gidx = T1 * G1 - 1;             // streamed layer 2: its groups are read from the slab ring
-                return (gidx < T1 * G1) ? *reinterpret_cast<const float4*>(w_P1 + (gidx * 64 + lane_w) * 4)
-                                        : *reinterpret_cast<const float4*>(w_P2 + ((gidx - T1 * G1) * 64 + lane_w) * 4);
-            };
-            auto slab_dma = [&](int t_, int buf_) {             // one 16 KB output-tile slab of layer 2 into a ring buffer: 2 KiB per wave
-                const unsigned char* src = reinterpret_cast<const unsigned char*>(a.w2q) + (size_t)t_ * (G2 * 1024);
-                unsigned char* dst = stage0 + (size_t)buf_ * SLAB_STRIDE;
-                // the lane offset is made opaque HERE: the 14 source addresses of a row block's slabs do not change from block to
-                // block, hipcc hoisted them out of the block loop as 64-bit VGPR pairs and (S = 13: 190 spilled registers) spilled
-                // eleven of them -- each DMA then sat behind `scratch_load; s_waitcnt vmcnt(0)`, and vmcnt(0) also waits for every
-                // slab copy in flight: the ring ran one memory round trip per KiB.  Two adds per copy instead.
-                unsigned lane16 = (unsigned)lane * 16u;
-                asm volatile("" : "+v"(lane16));
-#pragma unroll
-                for (int j = 0; j < G2 * 1024 / 1024 / WAVES; ++j) {
-                    const int off = (wave + j * WAVES) * 1024;
-                    // issued as inline asm: behind the builtin hipcc guards the tile's first LDS read of the slab ring with
-                    // `s_waitcnt vmcnt(0)` (a DS read may alias an LDS-DMA write) -- the copy of slab t+2, issued two instructions
-                    // earlier, had to LAND before tile t could start: a memory round trip per tile.  Which read needs which copy
-                    // is this loop's own protocol (counted lq_wait_vmcnt + barrier above).
-                    const unsigned long long gaddr = (unsigned long long)(uintptr_t)(src + off) + lane16;
-                    const unsigned ldsaddr = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(dst + off));
-                    unsigned m0_keep;                                   // (m0 is handed back: hipcc does not accept it as a clobber)
-                    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                                 : "=&s"(m0_keep) : "v"(gaddr), "s"(ldsaddr) : "memory");
-                }
-            };
-            if constexpr (STREAM2) {
-                // everyone is past the previous row block's decision scratch (it lives in ring buffers 0 and 1), then the first two
-                // slabs start: they have the whole of layer 1 to land
-                lq_wg_barrier();
-                slab_dma(0, 0);
-                slab_dma(1, 1);
-            }
-            float4 wn = wread(0);
-            f32x16 bnext = bias16(w_B1, 0);
-#pragma unroll
-            for (int t = 0; t < T1; ++t) {
-                f32x16 acc = bnext;
-#pragma unroll
-                for (int sq = 0; sq < G1; ++sq) {
-                    const float4 av = wn;
-                    wn = wread(t * G1 + sq + 1);                 // the next group's weights (layer 2's first group after the last)
-                    if (sq == G1 - 1 && (t + 1 < T1 || !STREAM2)) bnext = (t + 1 < T1) ? bias16(w_B1, t + 1) : bias16(w_B2, 0);
-                    __builtin_amdgcn_sched_barrier(0x6);         // reads stay in front of this group's MFMAs (VALU/SALU may move)
-                    ActStage<VQ> g;
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, h0[(4 * sq + 0) / 16][(4 * sq + 0) % 16], acc, 0, 0, 0);
-                    if (t > 0 && !LUMPED) g.stage0(pend[2 * sq], pend[2 * sq + 1]);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, h0[(4 * sq + 1) / 16][(4 * sq + 1) % 16], acc, 0, 0, 0);
-                    if (t > 0 && !LUMPED) g.stage1();
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, h0[(4 * sq + 2) / 16][(4 * sq + 2) % 16], acc, 0, 0, 0);
-                    if (t > 0 && !LUMPED) g.stage2();
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, h0[(4 * sq + 3) / 16][(4 * sq + 3) % 16], acc, 0, 0, 0);
-                    if (t > 0 && !LUMPED) {
-                        float o0, o1;
-                        g.stage3(o0, o1);
-                        h1[t - 1][2 * sq] = o0; h1[t - 1][2 * sq + 1] = o1;
-                    }
-                    __builtin_amdgcn_sched_barrier(0x6);
-                }
-                if constexpr (!VQ) { if (t > 0 && !LUMPED) gelu_fixup(h1[t - 1], pend); }
-                if constexpr (LUMPED) {
-#pragma unroll
-                    for (int r = 0; r < 16; r += 2) {
-                        const lq_v2f g2 = lq_gelu_poly2((lq_v2f){acc[r], acc[r + 1]});
-                        h1[t][r] = g2.x; h1[t][r + 1] = g2.y;
-                    }
-                    gelu_fixup(h1[t], acc);
-                }
-                pend = acc;
-                if constexpr (TRAIN) lq_tile_store16(a.pre1, 32 * T1, row, row < a.N, t, h, acc, 32 * T1, true);
-            }
-            LQ_STAMP(1);
-            // the last tile's GELU runs inside the first layer-2 chain: steps 0 .. 47 of that chain only read h1[0..2]
-            constexpr int SLAB_BYTES = G2 * 1024;                          // one output tile's A operands: 16 KB
-            constexpr int SLAB_CPW = SLAB_BYTES / 1024 / WAVES;
-            static_assert(!STREAM2 || (SLAB_BYTES % (1024 * WAVES) == 0 && SLAB_BYTES <= SLAB_STRIDE && 3 * SLAB_STRIDE <= STAGES_BYTES),
-                          "slabs ride in the stage ring");
-#pragma unroll
-            for (int t = 0; t < T2; ++t) {
-                const float* wslab = w_P2;
+                LQ_STAMP(0);
+                // ---- layers 1 and 2: one stream of 16-byte weight reads (T1 S1/4 of layer 1, then T2 S2/4 of layer 2), each read
+                // issued one 4-MFMA group ahead of its use.  The GELU of tile t-1 is written between the MFMAs of tile t (two
+                // elements per group): it cannot overlap the MFMAs (see above), but it keeps the polynomial out of a lumped
+                // 16 x 17-instruction block behind each chain.
+                f32x16 h1[T1];
+                f32x16 pend;                      // pre-activations of the previous tile, GELU pending
+                // LUMPED (round 4): a tile's GELU as ONE block behind its MFMA chain instead of staged between the MFMAs of the next
+                // tile's chain (rounds 2-3).  scripts/probe/probe_roles.hip: fp32 MFMAs and fp32 vector work share the SIMD's lanes -- a
+                // pair of tiles on a SIMD's two waves takes the SUM of both (5 340 cycles) however the instructions are arranged -- but
+                // the interleaved stream loses another 9 % to issue arbitration between the two waves (5 843).  Same values either way:
+                // cfg2 0.4095 -> 0.3997 ms per launch, same box (profiles/r04_b_lumped_gelu_ab.txt).  Not where every output tile of
+                // layer 2 waits at a workgroup barrier for its streamed weights (S = 13: 0.934 -> 1.00 ms lumped) -- there the staging stays.
+                constexpr bool LUMPED = !VQ && !STREAM2;
+                constexpr int G1 = S1 / 4, G2 = S2 / 4;             // groups per tile
+                auto wread = [&](int gidx) {                        // group gidx of the stream (compile-time after unrolling)
+                    if (STREAM2 && gidx >= T1 * G1) gidx = T1 * G1 - 1;             // streamed layer 2: its groups are read from the slab ring
+                    return (gidx < T1 * G1) ? *reinterpret_cast<const float4*>(w_P1 + (gidx * 64 + lane_w) * 4)
+                                            : *reinterpret_cast<const float4*>(w_P2 + ((gidx - T1 * G1) * 64 + lane_w) * 4);
+                };
+                auto slab_dma = [&](int t_, int buf_) { tok_slab_dma<G2, WAVES, SLAB_STRIDE>(a, stage0, lane, wave, t_, buf_); };
                 if constexpr (STREAM2) {
-                    // slab t has landed in every wave's part (slab t+1 may still fly); everyone has left tile t-1, whose buffer
-                    // slab t+2 goes to.  (Slabs 0 and 1 were issued in front of layer 1.)
-                    // (round 4, not kept: counting the previous tile's four z_e stores out of this wait -- they are younger than slab t --
-                    // made icrt slower, 0.886 -> 0.908 ms: profiles/r04_g_ze_store_placement.txt)
-                    if (t + 1 < T2) lq_wait_vmcnt<SLAB_CPW>(); else lq_wait_vmcnt<0>();
+                    // everyone is past the previous row block's decision scratch (it lives in ring buffers 0 and 1), then the first two
+                    // slabs start: they have the whole of layer 1 to land
                     lq_wg_barrier();
-                    if (t + 2 < T2) slab_dma(t + 2, (t + 2) % 3);
-                    // the lane's LDS address is formed per tile from an opaque lane offset: as a loop invariant hipcc kept it in a
-                    // register from the kernel's first lines and (S = 13) spilled it -- its reload in front of the tile's reads is a
-                    // vector-memory load, and waiting for it (`vmcnt(0)`) waits for the slab copy just issued as well
-                    unsigned lane4 = (unsigned)lane * 4u;
-                    asm volatile("" : "+v"(lane4));
-                    wslab = reinterpret_cast<const float*>(stage0 + (size_t)(t % 3) * SLAB_STRIDE) + lane4;
-                    wn = *reinterpret_cast<const float4*>(wslab);                     // the tile's first group (read after the barrier)
-                    bnext = bias16(w_B2, t);                                            // (no bias prefetch here: registers)
+                    slab_dma(0, 0);
+                    slab_dma(1, 1);
                 }
-                f32x16 acc = bnext;
+                float4 wn = wread(0);
+                f32x16 bnext = bias16(w_B1, 0);
 #pragma unroll
-                for (int sq = 0; sq < G2; ++sq) {
-                    if (t == 0 && sq == 3 * (S2 / 16)) {
-                        // h1[T1-1] is needed from here on (k-steps 48..63 of a 128-wide layer): finish its GELU
-                        if constexpr (!VQ && !LUMPED) gelu_fixup(h1[T1 - 1], pend);
+                for (int t = 0; t < T1; ++t) {
+                    f32x16 acc = bnext;
+#pragma unroll
+                    for (int sq = 0; sq < G1; ++sq) {
+                        const float4 av = wn;
+                        wn = wread(t * G1 + sq + 1);                 // the next group's weights (layer 2's first group after the last)
+                        if (sq == G1 - 1 && (t + 1 < T1 || !STREAM2)) bnext = (t + 1 < T1) ? bias16(w_B1, t + 1) : bias16(w_B2, 0);
+                        __builtin_amdgcn_sched_barrier(0x6);         // reads stay in front of this group's MFMAs (VALU/SALU may move)
+                        ActStage<VQ> g;
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, h0[(4 * sq + 0) / 16][(4 * sq + 0) % 16], acc, 0, 0, 0);
+                        if (t > 0 && !LUMPED) g.stage0(pend[2 * sq], pend[2 * sq + 1]);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, h0[(4 * sq + 1) / 16][(4 * sq + 1) % 16], acc, 0, 0, 0);
+                        if (t > 0 && !LUMPED) g.stage1();
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, h0[(4 * sq + 2) / 16][(4 * sq + 2) % 16], acc, 0, 0, 0);
+                        if (t > 0 && !LUMPED) g.stage2();
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, h0[(4 * sq + 3) / 16][(4 * sq + 3) % 16], acc, 0, 0, 0);
+                        if (t > 0 && !LUMPED) {
+                            float o0, o1;
+                            g.stage3(o0, o1);
+                            h1[t - 1][2 * sq] = o0; h1[t - 1][2 * sq + 1] = o1;
+                        }
+                        __builtin_amdgcn_sched_barrier(0x6);
                     }
-                    const float4 av = wn;
+                    if constexpr (!VQ) { if (t > 0 && !LUMPED) tok_gelu_fixup(h1[t - 1], pend); }
+                    if constexpr (LUMPED) {
+#pragma unroll
+                        for (int r = 0; r < 16; r += 2) {
+                            const lq_v2f g2 = lq_gelu_poly2((lq_v2f){acc[r], acc[r + 1]});
+                            h1[t][r] = g2.x; h1[t][r + 1] = g2.y;
+                        }
+                        tok_gelu_fixup(h1[t], acc);
+                    }
+                    pend = acc;
+                    if constexpr (TRAIN) lq_tile_store16(a.pre1, 32 * T1, row, row < a.N, t, h, acc, 32 * T1, true);
+                }
+                LQ_STAMP(1);
+                // the last tile's GELU runs inside the first layer-2 chain: steps 0 .. 47 of that chain only read h1[0..2]
+                constexpr int SLAB_CPW = Lds::SLAB_BYTES / 1024 / WAVES;       // a slab's copies per wave
+#pragma unroll
+                for (int t = 0; t < T2; ++t) {
+                    const float* wslab = w_P2;
                     if constexpr (STREAM2) {
-                        if (sq + 1 < G2) wn = *reinterpret_cast<const float4*>(wslab + (sq + 1) * 256);
-                    } else {
-                        if (t * G2 + sq + 1 < T2 * G2) wn = wread(T1 * G1 + t * G2 + sq + 1);
+                        // slab t has landed in every wave's part (slab t+1 may still fly); everyone has left tile t-1, whose buffer
+                        // slab t+2 goes to.  (Slabs 0 and 1 were issued in front of layer 1.)
+                        // (round 4, not kept: counting the previous tile's four z_e stores out of this wait -- they are younger than slab t --
+                        // made icrt slower, 0.886 -> 0.908 ms: profiles/r04_g_ze_store_placement.txt)
+                        if (t + 1 < T2) lq_wait_vmcnt<SLAB_CPW>(); else lq_wait_vmcnt<0>();
+                        lq_wg_barrier();
+                        if (t + 2 < T2) slab_dma(t + 2, (t + 2) % 3);
+                        // the lane's LDS address is formed per tile from an opaque lane offset: as a loop invariant hipcc kept it in a
+                        // register from the kernel's first lines and (S = 13) spilled it -- its reload in front of the tile's reads is a
+                        // vector-memory load, and waiting for it (`vmcnt(0)`) waits for the slab copy just issued as well
+                        unsigned lane4 = (unsigned)lane * 4u;
+                        asm volatile("" : "+v"(lane4));
+                        wslab = reinterpret_cast<const float*>(stage0 + (size_t)(t % 3) * SLAB_STRIDE) + lane4;
+                        wn = *reinterpret_cast<const float4*>(wslab);                     // the tile's first group (read after the barrier)
+                        bnext = bias16(w_B2, t);                                            // (no bias prefetch here: registers)
                     }
-                    if (!STREAM2 && sq == G2 - 1 && t + 1 < T2) bnext = bias16(w_B2, t + 1);
-                    __builtin_amdgcn_sched_barrier(0x6);
-                    const bool pg = (t == 0 && sq < 8 && !LUMPED);   // the 16 pending GELUs ride on groups 0..7 (< 12: they only read h1[0..2])
-                    ActStage<VQ> g;
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, h1[(4 * sq + 0) / 16][(4 * sq + 0) % 16], acc, 0, 0, 0);
-                    if (pg) g.stage0(pend[(2 * sq) & 15], pend[(2 * sq + 1) & 15]);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, h1[(4 * sq + 1) / 16][(4 * sq + 1) % 16], acc, 0, 0, 0);
-                    if (pg) g.stage1();
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, h1[(4 * sq + 2) / 16][(4 * sq + 2) % 16], acc, 0, 0, 0);
-                    if (pg) g.stage2();
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, h1[(4 * sq + 3) / 16][(4 * sq + 3) % 16], acc, 0, 0, 0);
-                    if (pg) {
-                        float o0, o1;
-                        g.stage3(o0, o1);
-                        h1[T1 - 1][(2 * sq) & 15] = o0; h1[T1 - 1][(2 * sq + 1) & 15] = o1;
+                    f32x16 acc = bnext;
+#pragma unroll
+                    for (int sq = 0; sq < G2; ++sq) {
+                        if (t == 0 && sq == 3 * (S2 / 16)) {
+                            // h1[T1-1] is needed from here on (k-steps 48..63 of a 128-wide layer): finish its GELU
+                            if constexpr (!VQ && !LUMPED) tok_gelu_fixup(h1[T1 - 1], pend);
+                        }
+                        const float4 av = wn;
+                        if constexpr (STREAM2) {
+                            if (sq + 1 < G2) wn = *reinterpret_cast<const float4*>(wslab + (sq + 1) * 256);
+                        } else {
+                            if (t * G2 + sq + 1 < T2 * G2) wn = wread(T1 * G1 + t * G2 + sq + 1);
+                        }
+                        if (!STREAM2 && sq == G2 - 1 && t + 1 < T2) bnext = bias16(w_B2, t + 1);
+                        __builtin_amdgcn_sched_barrier(0x6);
+                        const bool pg = (t == 0 && sq < 8 && !LUMPED);   // the 16 pending GELUs ride on groups 0..7 (< 12: they only read h1[0..2])
+                        ActStage<VQ> g;
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, h1[(4 * sq + 0) / 16][(4 * sq + 0) % 16], acc, 0, 0, 0);
+                        if (pg) g.stage0(pend[(2 * sq) & 15], pend[(2 * sq + 1) & 15]);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, h1[(4 * sq + 1) / 16][(4 * sq + 1) % 16], acc, 0, 0, 0);
+                        if (pg) g.stage1();
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, h1[(4 * sq + 2) / 16][(4 * sq + 2) % 16], acc, 0, 0, 0);
+                        if (pg) g.stage2();
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, h1[(4 * sq + 3) / 16][(4 * sq + 3) % 16], acc, 0, 0, 0);
+                        if (pg) {
+                            float o0, o1;
+                            g.stage3(o0, o1);
+                            h1[T1 - 1][(2 * sq) & 15] = o0; h1[T1 - 1][(2 * sq + 1) & 15] = o1;
+                        }
+                        __builtin_amdgcn_sched_barrier(0x6);
                     }
-                    __builtin_amdgcn_sched_barrier(0x6);
+                    finish_tile(t, acc);
                 }
-                finish_tile(t, acc);
+            } else {
+                tok_encode_fast<T0, T1, T2>(a, w_P0, w_B0, w_P1, w_B1, w_P2, w_B2, S0h, rowc, lane, h, finish_tile);
             }
-        } else {
-            // ---- fast mode: fp16 operands, fp32 accumulation.  k index of (step s, lane half h, element j) = 16 s + 2 j + h,
-            // i.e. the B operand of step s is registers 8 (s & 1) .. +7 of tile s >> 1 of the previous layer as they stand.
-            const _Float16* wh0 = reinterpret_cast<const _Float16*>(w_P0);
-            const _Float16* wh1 = reinterpret_cast<const _Float16*>(w_P1);
-            const _Float16* wh2 = reinterpret_cast<const _Float16*>(w_P2);
-            const float* xr = a.x + (size_t)rowc * a.A;
-            f32x16 h0[T0];
+            LQ_STAMP(2);
+            n2 += __shfl_xor(n2, 32, 64);
+            row_n2 = n2;
+            row_fz = fz;
+            row_fown = fown;
+            if constexpr (VQ) {
+                // the row's own scale (block floating point, lipvq_screen.h): its largest |z'| lands in [2^13, 2^14)
+                amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+                const int szr = lq_scale_exp(amax);
+                const float fzr = lq_pow2f(szr);
+                row_fz = fzr;
+                row_fown = lq_pow2f(szr + (int)hdr[3]);
 #pragma unroll
-            for (int t = 0; t < T0; ++t)
+                for (int t = 0; t < T2; ++t)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) h0[t][r] = w_B0[(2 * t + h) * 16 + r];
-            for (int s2 = 0; s2 < S0h; ++s2) {
-                f16x8 bx;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int k = 16 * s2 + 2 * j + h;
-                    bx[j] = (_Float16)((k < a.A) ? xr[k] : 0.0f);
-                }
-#pragma unroll
-                for (int t = 0; t < T0; ++t) {
-                    const f16x8 av = *reinterpret_cast<const f16x8*>(wh0 + ((size_t)(t * S0h + s2) * 64 + lane) * 8);
-                    h0[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bx, h0[t], 0, 0, 0);
-                }
+                    for (int r = 0; r < 16; ++r) {
+                        if (2 * t + (r >> 3) >= S) continue;
+                        const float vs = zt[t][r] * fzr;
+                        const _Float16 vh = (_Float16)vs;
+                        const float rs = vs - (float)vh;
+                        ah[2 * t + (r >> 3)][r & 7] = vh;
+                        al[2 * t + (r >> 3)][r & 7] = (_Float16)rs;
+                        if constexpr (COARSE) a2lo = lq_fma(rs, rs, a2lo);
+                    }
             }
-            f16x8 b0[2 * T0];
-#pragma unroll
-            for (int t = 0; t < T0; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) b0[2 * t + (r >> 3)][r & 7] = (_Float16)lq_gelu(h0[t][r]);
-            f16x8 b1[2 * T1];
-#pragma unroll
-            for (int t = 0; t < T1; ++t) {
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = w_B1[(2 * t + h) * 16 + r];
-#pragma unroll
-                for (int s2 = 0; s2 < 2 * T0; ++s2) {
-                    const f16x8 av = *reinterpret_cast<const f16x8*>(wh1 + ((size_t)(t * (2 * T0) + s2) * 64 + lane) * 8);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, b0[s2], acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) b1[2 * t + (r >> 3)][r & 7] = (_Float16)lq_gelu(acc[r]);
-            }
-#pragma unroll
-            for (int t = 0; t < T2; ++t) {
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = w_B2[(2 * t + h) * 16 + r];
-#pragma unroll
-                for (int s2 = 0; s2 < 2 * T1; ++s2) {
-                    const f16x8 av = *reinterpret_cast<const f16x8*>(wh2 + ((size_t)(t * (2 * T1) + s2) * 64 + lane) * 8);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, b1[s2], acc, 0, 0, 0);
-                }
-                finish_tile(t, acc);
-            }
-        }
-        LQ_STAMP(2);
-        n2 += __shfl_xor(n2, 32, 64);
-        row_n2 = n2;
-        row_fz = fz;
-        row_fown = fown;
-        if constexpr (VQ) {
-            // the row's own scale (block floating point, lipvq_screen.h): its largest |z'| lands in [2^13, 2^14)
-            amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-            const int szr = lq_scale_exp(amax);
-            const float fzr = lq_pow2f(szr);
-            row_fz = fzr;
-            row_fown = lq_pow2f(szr + (int)hdr[3]);
-#pragma unroll
-            for (int t = 0; t < T2; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    if (2 * t + (r >> 3) >= S) continue;
-                    const float vs = zt[t][r] * fzr;
-                    const _Float16 vh = (_Float16)vs;
-                    const float rs = vs - (float)vh;
-                    ah[2 * t + (r >> 3)][r & 7] = vh;
-                    al[2 * t + (r >> 3)][r & 7] = (_Float16)rs;
-                    if constexpr (COARSE) a2lo = lq_fma(rs, rs, a2lo);
-                }
-        }
-        if constexpr (COARSE) a2lo += __shfl_xor(a2lo, 32, 64);
-        row_a2 = a2lo;
-      };
+            if constexpr (COARSE) a2lo += __shfl_xor(a2lo, 32, 64);
+            row_a2 = a2lo;
+        };
         encode();
+        const int64_t row0 = (blk * WAVES + wave) * 32, row = row0 + ln;      // (phase B's: this wave's first row of the block, this lane's row)
         float frow[16];                                       // one scale for every row here (see fz): a single register
         if constexpr (VQ) lq_row_factors(row_fown, lane, frow);  // (the ReLU instance: every row its own)
         else {
@@ -894,9 +934,9 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
         } else {
             const bool have_def = DEFER_ZE && a.defer_ze && a.ze_out != nullptr;
             // the deferred stores sit under `row < N`: a wave without a valid row issues none, and its counted waits must not count them
-            const bool wave_def = __builtin_amdgcn_ballot_w64((blk * WAVES + wave) * 32 + ln < a.N) != 0ull;
+            const bool wave_def = __builtin_amdgcn_ballot_w64(row < a.N) != 0ull;
             auto deferred_ze = [&]() {                           // (stores first, then the loads: either may be absent)
-                if (have_def) store_ze_tile((blk * WAVES + wave) * 32 + ln, T2 - 1, zdef);
+                if (have_def) store_ze_tile(row, T2 - 1, zdef);
                 if (DEFER_X && x_pref) load_x(blk_next, xq);
             };
             lq_screen_core<S, THREADS, TCF, NBF, PACKF, COARSE, 4, decltype(deferred_ze), DEFER_X ? XPF : 0>(
@@ -905,8 +945,6 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
         LQ_STAMP(4);
         const unsigned keep_mask = PACKF ? ~((1u << lq_pack_bits(L.ntiles)) - 1u) : 0xffffffffu;
         unsigned char* scratch = stage0 + (size_t)wave * WSLICE;
-        const int64_t row0 = (blk * WAVES + wave) * 32;
-        const int64_t row = row0 + ln;
         int my_k;
         LqDecision dec;
         bool certified = lq_screen_decide<PACKF, COARSE>(m1, m2, k1, scratch, hdr, row_n2, row_fown, a.gamma, a.K, a.D, lane,
@@ -936,18 +974,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
         LQ_STAMP(6);
     }
     if (DEFER_GATHER && have_pend && a.zq) lq_screen_gather(a.cb, a.zq, pend_k, pend_ok, pend_row0, a.N, a.D, lane);   // the last block's
-#ifdef LQ_STAMPS
-    if (lane == 0) {
-        long long* dbg = LqWorkspace::from_lists(a.amb_list, a.N).stamps() + ((size_t)blockIdx.x * WAVES + wave) * 16;
-        for (int i = 0; i < 7; ++i) dbg[i] = st_acc[i];
-        dbg[7] = 0;
-        dbg[8] = __builtin_amdgcn_s_memtime() - st_begin;
-        dbg[9] = st_begin;
-        dbg[10] = st_begin - st_top;
-        dbg[11] = (long long)__builtin_amdgcn_s_memrealtime();          // 100 MHz wall clock at this wave's end
-        dbg[12] = st_top_rt;
-    }
-#endif
+    LQ_STAMPS_FLUSH(a, lane, wave, WAVES);
     // the grid's last workgroup publishes the number of listed rows and zeroes the live counters (lipvq_screen.h); its barrier is
     // the one the histogram flush needs, and the arrival's round trip flies beside the flush's atomics
     lq_ws_publish(a.amb_count);
@@ -1017,7 +1044,7 @@ static int tokenize_shape_fits(int A, int J0, int J1, int D, int K) {
     if (!(A > 0 && A <= 64 && J0 == 64 && J1 == 128 && K > 0)) return 0;
     size_t lds = 0;
     if (!lq_dispatch<32, 64, 128, 208>(D, [&](auto d) { lds = fused_lds_bytes_nohist<(d() + 15) / 16, FAST>(A); })) return 0;
-    return lds <= (size_t)160 * 1024 ? 1 : 0;
+    return lds <= FUSED_LDS_MAX ? 1 : 0;
 }
 
 extern "C" int lipvq_tokenize_supported(int A, int J0, int J1, int D, int K) { return tokenize_shape_fits<false>(A, J0, J1, D, K); }
@@ -1097,7 +1124,7 @@ static int launch_tokenize_as(const TokArgs& a, hipStream_t st) {
     static_assert(WAVES == 8 || !VQ, "the plain VQVAE's instances have 8 waves");
     static LqLdsReserve reserved;
     const size_t lds = fused_lds_bytes<S, FAST>(a.A, a.K);
-    if (lds > 160 * 1024) return fail(LIPVQ_EUNSUPPORTED, "tokenize: %zu B of LDS needed", lds);
+    if (lds > FUSED_LDS_MAX) return fail(LIPVQ_EUNSUPPORTED, "tokenize: %zu B of LDS needed", lds);
     void (*kfn)(TokArgs);
     if constexpr (WAVES == 4) kfn = tokenize_kernel_w4<S, FAST, TRAIN, COARSE, KEEPZ>;
     else kfn = tokenize_kernel<S, FAST, TRAIN, COARSE, VQ, KEEPZ>;
