@@ -18,6 +18,7 @@ from oracle import lipvq_oracle as O
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import backward_ref as R  # noqa: E402
+from backward_edge_cases import mlp3_inputs as _mlp3_inputs  # noqa: E402  (the draws, shared with tests/test_gpu_backward_extent.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -107,32 +108,6 @@ MLP3_CASES += [(333, 12, j0, j1, 37, MIX, True) for j0, j1 in ((32, 32), (64, 12
 MLP3_CASES += [(100, k0, 64, 128, 16, DEC, True) for k0 in (1, 3, 7, 12, 33, 64, 208, 209, 512)]
 # forward J2: the chain's input width (odd widths exercise the (J2 + 1) / 2 k-pair padding of the staged gy)
 MLP3_CASES += [(100, 9, 64, 128, j2, ENC, True) for j2 in (1, 5, 7, 12, 64, 208, 300, 512)]
-
-
-def _plant(t, salt):
-    """backward_ref.PLANTED (+-0, +-9, +-40, +-100) at scattered positions of a pre-activation tensor; returns the flat positions."""
-    flat = t.view(-1)
-    pos = [(salt + 37 * k) % flat.numel() for k in range(len(R.PLANTED))]
-    for q, v in zip(pos, R.PLANTED):
-        flat[q] = float(v)
-    return pos
-
-
-def _mlp3_inputs(N, K0, J0, J1, J2, acts, seed):
-    g = torch.Generator().manual_seed(seed)
-    W0 = torch.randn(J0, K0, generator=g) * 0.3
-    W1 = torch.randn(J1, J0, generator=g) * 0.2
-    W2 = torch.randn(J2, J1, generator=g) * 0.2
-    gy = torch.randn(N, J2, generator=g)
-    pre = [torch.randn(N, J, generator=g) * 2.0 for J in (J0, J1, J2)]
-    for i, p in enumerate(pre):
-        _plant(p, 3 + i)
-    zero_row = N // 2 if N >= 3 else None                   # one row of all zeros in gy (its gradients must be exactly 0)
-    if zero_row is not None:
-        gy[zero_row] = 0.0
-    if acts[2] == O.ACT_NONE:
-        pre[2] = None
-    return W0, W1, W2, gy, pre, zero_row
 
 
 def _check_chain(out, gy, pre, W0, W1, W2, acts, want_gx, zero_row, g2_checked=False):
