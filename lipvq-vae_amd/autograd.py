@@ -29,10 +29,10 @@ def _check_versions(ctx, params):
     saved = getattr(ctx, "param_versions", None)
     if saved is None:
         return
-    for i, (p, v) in enumerate(zip(params, saved)):
-        if p._version != v:
-            raise RuntimeError(f"lipvq: parameter #{i} (shape {tuple(p.shape)}) was modified in place between forward and "
-                               f"backward (version {v} -> {p._version}); the gradient would be computed with the new weights")
+    for i, (p, (ptr, v)) in enumerate(zip(params, saved)):
+        if p._version != v or p.data_ptr() != ptr:           # (``p.data = new`` and ``.to()`` keep the version, not the address)
+            raise RuntimeError(f"lipvq: parameter #{i} (shape {tuple(p.shape)}) was modified in place or replaced between forward "
+                               f"and backward (version {v} -> {p._version}); the gradient would be computed with the new weights")
 
 
 class _TokenizerFn(torch.autograd.Function):
@@ -77,7 +77,7 @@ class _TokenizerFn(torch.autograd.Function):
             ctx.save_for_backward(x, z_e, z_q, idx, x_rec, *lipschitz, *(() if z_st is None else (z_st,)), *pre_e, *pre_d)
             # backward() re-reads the module's live weights (decoder, codebook, encoder, to_latent): remember their versions, so
             # that a parameter update between forward and backward raises, as torch's saved-tensor check would
-            ctx.param_versions = tuple(p._version for p in params)
+            ctx.param_versions = tuple((p.data_ptr(), p._version) for p in params)
         ctx.mark_non_differentiable(latent)
         return latent, l3[2]
 

@@ -92,6 +92,11 @@ class AdaptiveBinActionEmbedding(nn.Module):
         self._table_cache = _PackCache()
         self.last_bins = None                  # [A, N] int64 of the most recent forward
 
+    def invalidate_caches(self):
+        """Drop the [A, num_bins, H] table of the eval forward; the next no-grad call rebuilds it.  Needed after a write the
+        version counter does not see (``p.data.add_()``; see tokenizer._PackCache)."""
+        self._table_cache.invalidate()
+
     # -- the reference's methods ---------------------------------------------------------------------
     def update_running_stats(self, actions):
         """bin:37-40 (in place on the two buffers)."""

@@ -105,6 +105,11 @@ class ICLInputEmbedding(nn.Module):
         self._table_cache = _PackCache()
         self._sin_cache = {}
 
+    def invalidate_caches(self):
+        """Drop the [K, E] code table; the next no-grad call rebuilds it.  Needed after a write the version counter does not see
+        (``p.data.add_()`` on the embed_encoder or on the codebook; see tokenizer._PackCache)."""
+        self._table_cache.invalidate()
+
     # -- pieces ------------------------------------------------------------------------------------
     def time_table(self, T: int) -> torch.Tensor:
         """[T, E] rows added to timesteps 0..T-1 (ob:2485-2523)."""

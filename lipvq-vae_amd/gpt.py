@@ -37,6 +37,8 @@ dropout kernel).  ``activation="geglu"`` is not implemented (the ICRT configurat
 """
 from __future__ import annotations
 
+import weakref
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -45,7 +47,11 @@ from . import ops
 from .nnfn import AddLayerNormFn, GraphedEval, LinearFn
 from .ops import ACT_GELU, ACT_NONE
 
-__all__ = ["GPTBackbone", "GraphedGPTBackbone", "PromptCache", "PromptedGPTBackbone"]
+__all__ = ["GPTBackbone", "GraphedGPTBackbone", "PromptCache", "PromptedGPTBackbone", "StalePromptCache"]
+
+
+class StalePromptCache(RuntimeError):
+    """forward_cached: the cache no longer belongs to the backbone's parameters or matmul precision; prefill() again."""
 
 
 class _AttentionFn(torch.autograd.Function):
@@ -199,7 +205,8 @@ class GPTBackbone(nn.Module):
             raise ValueError(f"GPTBackbone.{what}: a non-causal prefix sees the tokens after it, so no cache of it is valid")
 
     def _param_versions(self):
-        return tuple(p._version for p in self.parameters())
+        """(data_ptr, _version) of every parameter: an in-place write moves the version, ``p.data = new`` / ``.to()`` the address."""
+        return tuple((p.data_ptr(), p._version) for p in self.parameters())
 
     def _blocks_eval(self, x, prefix, record):
         """The eval forward on the rows of x.  record (a list): plain causal attention, every block's qkv is appended and the
@@ -248,7 +255,7 @@ class GPTBackbone(nn.Module):
             qkv = [x.new_empty((Bp, P, 3 * E)) for _ in self.nets["transformer"]]
         else:
             self._blocks_eval(x, None, qkv)
-        return PromptCache(tuple(qkv), Bp, P, self._matmul_precision, self._param_versions())
+        return PromptCache(tuple(qkv), Bp, P, self._matmul_precision, self._param_versions(), weakref.ref(self))
 
     @torch.no_grad()
     def forward_cached(self, embeddings: torch.Tensor, cache: "PromptCache") -> torch.Tensor:
@@ -268,12 +275,16 @@ class GPTBackbone(nn.Module):
         if len(cache.qkv) != len(self.nets["transformer"]) or any(t.shape[2] != 3 * self.embed_dim or t.device != embeddings.device
                                                                   for t in cache.qkv):
             raise ValueError("GPTBackbone.forward_cached: the cache was made by another backbone or on another device")
+        if cache.owner is not None and cache.owner() is not self:      # (same shapes and versions do not make it this one's)
+            raise ValueError("GPTBackbone.forward_cached: the cache was made by another backbone (or a copy of this one): call "
+                             "prefill() on this backbone")
         if cache.precision != self._matmul_precision:
-            raise RuntimeError(f"GPTBackbone.forward_cached: the cache was made under matmul precision {cache.precision!r}, the "
-                               f"backbone is now {self._matmul_precision!r}: call prefill() again")
+            raise StalePromptCache(f"GPTBackbone.forward_cached: the cache was made under matmul precision {cache.precision!r}, "
+                                   f"the backbone is now {self._matmul_precision!r}: call prefill() again")
         if cache.versions != self._param_versions():
-            raise RuntimeError("GPTBackbone.forward_cached: a parameter changed after the cache was made (an optimizer step, "
-                               "load_state_dict): the cached keys and values are stale, call prefill() again")
+            raise StalePromptCache("GPTBackbone.forward_cached: a parameter changed or was replaced after the cache was made (an "
+                                   "optimizer step, load_state_dict, p.data = ..., .to()): the cached keys and values are stale, "
+                                   "call prefill() again")
         x = embeddings.contiguous().float()
         if B == 0 or Lq == 0:
             return torch.empty_like(x)
@@ -282,13 +293,15 @@ class GPTBackbone(nn.Module):
 
 class PromptCache:
     """What ``GPTBackbone.prefill`` keeps of a prompt: ``qkv``, one [Bp, P, 3E] tensor per block exactly as the qkv Linear wrote it
-    (the attention kernel reads K and V in place), with ``Bp``, ``P``, the matmul ``precision`` and the ``_version`` of every
-    parameter at that moment, which ``forward_cached`` compares with the backbone's."""
+    (the attention kernel reads K and V in place), with ``Bp``, ``P``, the matmul ``precision``, the ``(data_ptr, _version)`` of
+    every parameter at that moment and a weak reference to the backbone that made it, all of which ``forward_cached`` compares
+    with its own.  A write that moves neither a version nor an address (``p.data.add_()``) is invisible: prefill again."""
 
-    __slots__ = ("qkv", "Bp", "P", "precision", "versions")
+    __slots__ = ("qkv", "Bp", "P", "precision", "versions", "owner")
 
-    def __init__(self, qkv, Bp, P, precision, versions):
+    def __init__(self, qkv, Bp, P, precision, versions, owner=None):
         self.qkv, self.Bp, self.P, self.precision, self.versions = qkv, int(Bp), int(P), precision, versions
+        self.owner = owner
 
     @property
     def nbytes(self) -> int:

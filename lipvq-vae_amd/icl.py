@@ -34,6 +34,7 @@ import torch.nn as nn
 from . import optim, sharded
 from .binning import AdaptiveBinActionEmbedding
 from .default_branch import DefaultActionNetwork
+from .gpt import StalePromptCache
 from .tokenizer import LLFQVAE_V4, VQVAE
 
 
@@ -216,8 +217,10 @@ class GraphedTokenizerStep:
         ``capturable`` (its step counter lives on the device);
       * warm-up steps (real training steps, on a side stream) run before the capture, so that lazy one-time work -- the
         per-device LDS reservations (hipFuncSetAttribute), AdamW's state -- is not issued while capturing;
-      * ``invalidate_caches()`` runs again after the capture and after every replay: a replayed optimizer step does not
-        bump ``Tensor._version``, so eager code must never trust caches that predate it.
+      * ``invalidate_caches()`` runs again after the capture and after every replay, and every replay bumps the version of
+        every parameter (``increment_version``), as the eager optimizer step does: a replayed step does not, and eager code must
+        never trust what predates it -- neither the model's own caches nor what OTHERS keyed on a parameter's version
+        (``ICLInputEmbedding.code_table`` of the codebook, the backward of an eager forward that ran before the replay).
     The input is copied into a static buffer; shapes are fixed at construction."""
 
     def __init__(self, vq_vae_model: nn.Module, example_actions: torch.Tensor, lr: float = 1e-3, weight_decay: float = 1e-4,
@@ -248,7 +251,7 @@ class GraphedTokenizerStep:
         # snapshotted here and put back IN PLACE after the warm-up -- in place, because the capture below records the state
         # tensors' addresses and must find them allocated: state created by the warm-up is zeroed (= a fresh AdamW), state that
         # came with `optimizer_state` gets its values back.  Replay k then equals eager step k.
-        params = list(vq_vae_model.parameters())
+        params = self._params = list(vq_vae_model.parameters())
         saved_params = [p.detach().clone() for p in params]
         saved_state = {id(p): {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in self.vq_optimizer.state.get(p, {}).items()}
                        for p in params}
@@ -307,6 +310,9 @@ class GraphedTokenizerStep:
             raise ValueError(f"graphed step was captured for {tuple(self.static_x.shape)}, got {tuple(prompt_actions.shape)}")
         self.static_x.copy_(prompt_actions)
         self.graph.replay()
+        # a replayed optimizer step does not bump Tensor._version: do it here, as the eager step does
+        for p in self._params:
+            torch.autograd.graph.increment_version(p)
         self.model.invalidate_caches()
         if hasattr(self.model, "last_indices"):
             self.model.last_indices = self._static_last
@@ -414,12 +420,23 @@ class PromptedPolicy:
     ``forward_cached`` on them.  ``embedding`` is an ``ICLInputEmbedding``, ``backbone`` a causal ``GPTBackbone``, ``head`` a
     ``GMMActionHead`` or an ``ActionHead`` (or any callable on [B, T, E] features; ``get_action``'s row pick, icl.py:845-851, is
     the caller's ``policy(obs)[:, -1]``); all in eval mode.  A context of batch 1 serves any number of
-    environments.  Call ``set_prompt`` again after the context, a parameter or the matmul precision changes (``forward_cached``
-    refuses a stale cache).  No kernels of its own."""
+    environments.  Call ``set_prompt`` again after the context, a parameter or the matmul precision changes.  ``features``
+    refuses a stale prompt (``RuntimeError``) after any write it can see: ``set_prompt`` records the ``(data_ptr, _version)`` of
+    every embedding parameter and of the codebook it embedded, ``GPTBackbone.forward_cached`` checks the backbone's parameters
+    and precision.  What no version counter sees (``p.data.add_()``, a raw-pointer writer) it cannot refuse: call ``set_prompt``
+    yourself.  No kernels of its own."""
 
     def __init__(self, embedding: nn.Module, backbone: nn.Module, head):
         self.embedding, self.backbone, self.head = embedding, backbone, head
         self.cache = None
+        self._codebook, self._embedded = None, None
+
+    def _embedded_key(self):
+        """(data_ptr, _version) of everything set_prompt's embedding read: the embedding's parameters, the codebook if any."""
+        ts = list(self.embedding.parameters())
+        if self._codebook is not None:
+            ts.append(self._codebook)
+        return tuple((t.data_ptr(), t._version) for t in ts)
 
     def set_prompt(self, context_obs, context_actions=None, *, action_indices=None, codebook=None):
         """Embed and prefill the context: context_obs [Bp, T, F] with dense context_actions [Bp, T, F] or action_indices [Bp, T] +
@@ -429,6 +446,8 @@ class PromptedPolicy:
         with torch.no_grad():
             prompt = self.embedding.prompt_embedding(context_obs, context_actions, action_indices=action_indices, codebook=codebook)
             self.cache = self.backbone.prefill(prompt)
+        self._codebook = codebook if action_indices is not None else None
+        self._embedded = self._embedded_key()
         return self.cache
 
     def features(self, obs: torch.Tensor) -> torch.Tensor:
@@ -437,8 +456,15 @@ class PromptedPolicy:
             raise RuntimeError("PromptedPolicy: call set_prompt() first")
         if self.embedding.training:
             raise RuntimeError("PromptedPolicy is an eval-mode path: call embedding.eval() first")
+        if self._embedded != self._embedded_key():
+            raise RuntimeError("PromptedPolicy.features: a parameter of the embedding, or the codebook, changed after the prompt "
+                               "was embedded (an optimizer step, load_state_dict, .to()): the cached prompt is stale, call "
+                               "set_prompt() again")
         with torch.no_grad():
-            return self.backbone.forward_cached(self.embedding.input_embedding(obs), self.cache)
+            try:
+                return self.backbone.forward_cached(self.embedding.input_embedding(obs), self.cache)
+            except StalePromptCache as e:
+                raise RuntimeError(f"PromptedPolicy.features: call set_prompt() again ({e})") from e
 
     def __call__(self, obs: torch.Tensor):
         return self.head(self.features(obs))

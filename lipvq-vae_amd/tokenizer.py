@@ -58,6 +58,9 @@ class _PackCache:
         self._key = None
         self._val = None
 
+    def __deepcopy__(self, memo):
+        return type(self)()          # a copied module builds its own: the key holds the ORIGINAL's addresses
+
 
 class LipschitzMLP(nn.Module):
     """Parameter holder of the Lipschitz latent layer (reference v5:15-24): W ~ N(0,1), b = 0, ci = 1."""
@@ -113,6 +116,9 @@ class _ScreenMonitor:
         self._pending = None
         self.bypass_calls = 0
         self.last_fraction = None
+
+    def __deepcopy__(self, memo):
+        return type(self)()          # (a pending reading holds an event, which cannot be copied, and is the original's anyway)
 
     ENABLED = True                # tests / measurements: False = always the screen (class attribute; no environment variable)
 
