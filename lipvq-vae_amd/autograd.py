@@ -18,6 +18,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from .derived import stamp
 from .tokenizer import LLFQVAE_V4, VQVAE
 
 # (the triples are defined on the tokenizer classes; these names are kept for tests and measurement scripts)
@@ -25,14 +26,12 @@ _ENC_ACTS, _DEC_ACTS, _RELU3 = LLFQVAE_V4._ENC_ACTS, LLFQVAE_V4._DEC_ACTS, VQVAE
 
 
 def _check_versions(ctx, params):
-    """The backward kernels read the module's LIVE weights; refuse to run if one was modified in place since the forward."""
-    saved = getattr(ctx, "param_versions", None)
-    if saved is None:
-        return
-    for i, (p, (ptr, v)) in enumerate(zip(params, saved)):
-        if p._version != v or p.data_ptr() != ptr:           # (``p.data = new`` and ``.to()`` keep the version, not the address)
+    """The backward kernels read the module's LIVE weights; refuse to run if one was modified in place or replaced since (``stamp``)."""
+    saved = getattr(ctx, "param_versions", None) or ()       # (None: the forward kept nothing for a backward)
+    for i, (p, was, now) in enumerate(zip(params, saved, stamp(params))):
+        if now != was:
             raise RuntimeError(f"lipvq: parameter #{i} (shape {tuple(p.shape)}) was modified in place or replaced between forward "
-                               f"and backward (version {v} -> {p._version}); the gradient would be computed with the new weights")
+                               f"and backward (version {was[1]} -> {now[1]}); the gradient would be computed with the new weights")
 
 
 class _TokenizerFn(torch.autograd.Function):
@@ -77,7 +76,7 @@ class _TokenizerFn(torch.autograd.Function):
             ctx.save_for_backward(x, z_e, z_q, idx, x_rec, *lipschitz, *(() if z_st is None else (z_st,)), *pre_e, *pre_d)
             # backward() re-reads the module's live weights (decoder, codebook, encoder, to_latent): remember their versions, so
             # that a parameter update between forward and backward raises, as torch's saved-tensor check would
-            ctx.param_versions = tuple((p.data_ptr(), p._version) for p in params)
+            ctx.param_versions = stamp(params)
         ctx.mark_non_differentiable(latent)
         return latent, l3[2]
 

@@ -94,7 +94,7 @@ class AdaptiveBinActionEmbedding(nn.Module):
 
     def invalidate_caches(self):
         """Drop the [A, num_bins, H] table of the eval forward; the next no-grad call rebuilds it.  Needed after a write the
-        version counter does not see (``p.data.add_()``; see tokenizer._PackCache)."""
+        version counter does not see (``p.data.add_()``; see derived.stamp)."""
         self._table_cache.invalidate()
 
     # -- the reference's methods ---------------------------------------------------------------------

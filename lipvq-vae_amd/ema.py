@@ -11,6 +11,7 @@ from __future__ import annotations
 import torch
 
 from . import ops, sharded
+from .derived import mark_written
 
 __all__ = ["EMACodebook"]
 
@@ -41,7 +42,7 @@ class EMACodebook:
         ops.ema_update(self.cluster_size, self.embed_sum, counts, dw, cb, self.decay, self.eps)
         # the kernel wrote through a raw pointer: tell torch, so that version-keyed caches (the tokenizer's prepared
         # codebook, autograd's saved-tensor checks) see the change
-        torch.autograd.graph.increment_version(self.codebook)
+        mark_written((self.codebook,))
         return counts
 
     @torch.no_grad()

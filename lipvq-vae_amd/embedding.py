@@ -107,7 +107,7 @@ class ICLInputEmbedding(nn.Module):
 
     def invalidate_caches(self):
         """Drop the [K, E] code table; the next no-grad call rebuilds it.  Needed after a write the version counter does not see
-        (``p.data.add_()`` on the embed_encoder or on the codebook; see tokenizer._PackCache)."""
+        (``p.data.add_()`` on the embed_encoder or on the codebook; see derived.stamp)."""
         self._table_cache.invalidate()
 
     # -- pieces ------------------------------------------------------------------------------------

@@ -44,6 +44,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from .derived import stamp
 from .nnfn import AddLayerNormFn, GraphedEval, LinearFn
 from .ops import ACT_GELU, ACT_NONE
 
@@ -205,8 +206,8 @@ class GPTBackbone(nn.Module):
             raise ValueError(f"GPTBackbone.{what}: a non-causal prefix sees the tokens after it, so no cache of it is valid")
 
     def _param_versions(self):
-        """(data_ptr, _version) of every parameter: an in-place write moves the version, ``p.data = new`` / ``.to()`` the address."""
-        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+        """``derived.stamp`` of every parameter: an in-place write moves the version, ``p.data = new`` / ``.to()`` the address."""
+        return stamp(self.parameters())
 
     def _blocks_eval(self, x, prefix, record):
         """The eval forward on the rows of x.  record (a list): plain causal attention, every block's qkv is appended and the

@@ -33,7 +33,9 @@ import torch.nn as nn
 
 from . import optim, sharded
 from .binning import AdaptiveBinActionEmbedding
+from .capture import Snapshot, capture, copy_in, warm_up
 from .default_branch import DefaultActionNetwork
+from .derived import mark_written, stamp
 from .gpt import StalePromptCache
 from .tokenizer import LLFQVAE_V4, VQVAE
 
@@ -218,7 +220,7 @@ class GraphedTokenizerStep:
       * warm-up steps (real training steps, on a side stream) run before the capture, so that lazy one-time work -- the
         per-device LDS reservations (hipFuncSetAttribute), AdamW's state -- is not issued while capturing;
       * ``invalidate_caches()`` runs again after the capture and after every replay, and every replay bumps the version of
-        every parameter (``increment_version``), as the eager optimizer step does: a replayed step does not, and eager code must
+        every parameter (``derived.mark_written``), as the eager optimizer step does: a replayed step does not, and eager code must
         never trust what predates it -- neither the model's own caches nor what OTHERS keyed on a parameter's version
         (``ICLInputEmbedding.code_table`` of the codebook, the backward of an eager forward that ran before the replay).
     The input is copied into a static buffer; shapes are fixed at construction."""
@@ -246,38 +248,15 @@ class GraphedTokenizerStep:
                     if st and "step" in st:
                         st["step"] = torch.as_tensor(float(st["step"]), dtype=torch.float32, device=prm.device)
         self.warmup_steps = int(warmup)
-        # The warm-up steps are REAL training steps (they have to be: they make the one-time work happen); construction must not
-        # train the model, though (round 2's did: two extra updates on the example batch).  Parameters and optimizer state are
-        # snapshotted here and put back IN PLACE after the warm-up -- in place, because the capture below records the state
-        # tensors' addresses and must find them allocated: state created by the warm-up is zeroed (= a fresh AdamW), state that
-        # came with `optimizer_state` gets its values back.  Replay k then equals eager step k.
+        # Construction must not train the model (round 2's did: two extra updates on the example batch): all that a step writes is put
+        # back after the warm-up -- parameters, AdamW's state, buffers (code_usage: warm-up counts would skew perplexity() and every
+        # rank's histogram) IN PLACE (capture.Snapshot); last_indices and the screen monitor's reading by hand
         params = self._params = list(vq_vae_model.parameters())
-        saved_params = [p.detach().clone() for p in params]
-        saved_state = {id(p): {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in self.vq_optimizer.state.get(p, {}).items()}
-                       for p in params}
-        # ... and so is everything else a step writes on the module: its buffers (code_usage -- warm-up counts would skew
-        # perplexity() and, sharded, every rank's all-reduced histogram), last_indices, the screen monitor's reading
-        saved_buffers = [(b, b.detach().clone()) for b in vq_vae_model.buffers()]
+        saved = Snapshot(params + list(vq_vae_model.buffers()), self.vq_optimizer, params)
         saved_last = getattr(vq_vae_model, "last_indices", None)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(self.warmup_steps):
-                self._eager_step()
-        torch.cuda.current_stream().wait_stream(side)
+        warm_up(self._eager_step, self.warmup_steps)
         torch.cuda.synchronize()
-        with torch.no_grad():
-            for p, sp in zip(params, saved_params):
-                p.copy_(sp)
-                for k, v in self.vq_optimizer.state.get(p, {}).items():
-                    if torch.is_tensor(v):
-                        old = saved_state[id(p)].get(k)
-                        if old is not None:
-                            v.copy_(old)
-                        else:
-                            v.zero_()
-            for b, sb in saved_buffers:
-                b.copy_(sb)
+        saved.restore()
         if hasattr(vq_vae_model, "last_indices"):
             vq_vae_model.last_indices = saved_last
         mon = getattr(vq_vae_model, "_screen_monitor", None)
@@ -285,9 +264,7 @@ class GraphedTokenizerStep:
             mon.reset()
         torch.cuda.synchronize()
         self.model.invalidate_caches()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self._loss = self._eager_step()
+        self.graph, self._loss = capture(self._eager_step)
         self.model.invalidate_caches()
         # the capture ran the forward once more (recording only): its index tensor is the graph's static one -- what a replay
         # fills -- and becomes `last_indices` with the first step(); until then the module shows what it showed before
@@ -306,13 +283,9 @@ class GraphedTokenizerStep:
     def step(self, prompt_actions: torch.Tensor):
         """One training step on a batch of the captured shape: (context_actions, loss) -- static tensors, valid until the
         next step."""
-        if prompt_actions.shape != self.static_x.shape:
-            raise ValueError(f"graphed step was captured for {tuple(self.static_x.shape)}, got {tuple(prompt_actions.shape)}")
-        self.static_x.copy_(prompt_actions)
+        copy_in(self.static_x, prompt_actions)
         self.graph.replay()
-        # a replayed optimizer step does not bump Tensor._version: do it here, as the eager step does
-        for p in self._params:
-            torch.autograd.graph.increment_version(p)
+        mark_written(self._params)       # a replayed optimizer step does not bump the versions: do it here, as the eager step does
         self.model.invalidate_caches()
         if hasattr(self.model, "last_indices"):
             self.model.last_indices = self._static_last
@@ -357,36 +330,13 @@ class GraphedPolicyStep:
         self.static_inputs = tuple(x.detach().clone().contiguous() for x in example_inputs)
         self.warmup_steps = int(warmup)
         lrs = [g["lr"] for g in optimizer.param_groups if torch.is_tensor(g["lr"])]
-        owned = [p for g in optimizer.param_groups for p in g["params"]]
-        saved_params = [p.detach().clone() for p in self.params]
-        saved_lrs = [t.detach().clone() for t in lrs]
-        saved_state = {id(p): {k: v.detach().clone() for k, v in optimizer.state.get(p, {}).items() if torch.is_tensor(v)}
-                       for p in owned}
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(self.warmup_steps):
-                self._eager_step()
-        torch.cuda.current_stream().wait_stream(side)
+        saved = Snapshot(self.params + lrs, optimizer, [p for g in optimizer.param_groups for p in g["params"]])
+        warm_up(self._eager_step, self.warmup_steps)
         torch.cuda.synchronize()
-        with torch.no_grad():
-            for p, sp in zip(self.params, saved_params):
-                p.copy_(sp)
-            for t, s in zip(lrs, saved_lrs):
-                t.copy_(s)
-            for p in owned:
-                for k, v in optimizer.state.get(p, {}).items():
-                    if torch.is_tensor(v):
-                        old = saved_state[id(p)].get(k)
-                        if old is not None:
-                            v.copy_(old)
-                        else:
-                            v.zero_()
+        saved.restore()
         torch.cuda.synchronize()
         optimizer.zero_grad(set_to_none=True)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self._loss = self._eager_step()
+        self.graph, self._loss = capture(self._eager_step)
         self.grad_stats = optimizer.grad_stats
 
     def _eager_step(self):
@@ -399,17 +349,9 @@ class GraphedPolicyStep:
     def step(self, *inputs):
         """One training step on a batch of the captured shapes: (loss, grad_stats) -- static device tensors, valid until the next
         step; ``grad_stats`` is None when the optimizer has no ``max_grad_norm``."""
-        if len(inputs) != len(self.static_inputs):
-            raise ValueError(f"graphed step was captured for {len(self.static_inputs)} inputs, got {len(inputs)}")
-        for x, s in zip(inputs, self.static_inputs):
-            if x.shape != s.shape:
-                raise ValueError(f"graphed step was captured for {[tuple(t.shape) for t in self.static_inputs]}, got {tuple(x.shape)}")
-        for x, s in zip(inputs, self.static_inputs):
-            s.copy_(x)
+        copy_in(self.static_inputs, inputs)
         self.graph.replay()
-        # a replayed optimizer step does not bump Tensor._version: do it here, as the eager step does
-        for p in self.params:
-            torch.autograd.graph.increment_version(p)
+        mark_written(self.params)        # a replayed optimizer step does not bump the versions: do it here, as the eager step does
         return self._loss, self.grad_stats
 
 
@@ -432,11 +374,8 @@ class PromptedPolicy:
         self._codebook, self._embedded = None, None
 
     def _embedded_key(self):
-        """(data_ptr, _version) of everything set_prompt's embedding read: the embedding's parameters, the codebook if any."""
-        ts = list(self.embedding.parameters())
-        if self._codebook is not None:
-            ts.append(self._codebook)
-        return tuple((t.data_ptr(), t._version) for t in ts)
+        """``derived.stamp`` of everything set_prompt's embedding read: the embedding's parameters, the codebook if any."""
+        return stamp([*self.embedding.parameters(), *(() if self._codebook is None else (self._codebook,))])
 
     def set_prompt(self, context_obs, context_actions=None, *, action_indices=None, codebook=None):
         """Embed and prefill the context: context_obs [Bp, T, F] with dense context_actions [Bp, T, F] or action_indices [Bp, T] +

@@ -5,6 +5,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from .capture import capture, copy_in, warm_up
 from .ops import ACT_NONE
 
 __all__ = ["LinearFn", "AddLayerNormFn", "GraphedEval"]
@@ -81,19 +82,11 @@ class GraphedEval:
             raise RuntimeError(f"{type(self).__name__} captures the eval-mode forward: call net.eval() first")
         self.net = net
         self._x = example.detach().contiguous().float().clone()
-        side = torch.cuda.Stream(device=self._x.device)
-        side.wait_stream(torch.cuda.current_stream(self._x.device))
-        with torch.no_grad(), torch.cuda.stream(side):            # first-use work (LDS reservations, lazy module state) stays out of the capture
-            for _ in range(3):
-                net(self._x)
-        torch.cuda.current_stream(self._x.device).wait_stream(side)
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self._graph):
-            self._y = net(self._x)
+        with torch.no_grad():
+            warm_up(lambda: net(self._x), 3, self._x.device)      # first-use work (LDS reservations, lazy module state) stays out of the capture
+            self._graph, self._y = capture(lambda: net(self._x))
 
     def __call__(self, inputs: torch.Tensor, /) -> torch.Tensor:
-        if inputs.shape != self._x.shape:
-            raise ValueError(f"captured for {tuple(self._x.shape)}, got {tuple(inputs.shape)}")
-        self._x.copy_(inputs)
+        copy_in(self._x, inputs, "captured")
         self._graph.replay()
         return self._y

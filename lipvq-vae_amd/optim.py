@@ -29,6 +29,7 @@ import math
 import torch
 
 from ._capi import check, lib
+from .derived import mark_written
 from .ops import _on, _stream
 
 _MAX = 32
@@ -97,8 +98,7 @@ def clip_grad_norm_(parameters, max_norm):
             chunk = grads[s:s + _MAX]
             check(lib.lipvq_grad_scale_f32(_ptrs(chunk), _numels(chunk), len(chunk), stats.data_ptr(), _stream()),
                   "lipvq_grad_scale_f32")
-    for g in grads:
-        torch.autograd.graph.increment_version(g)
+    mark_written(grads)                  # lipvq_grad_scale_f32 scaled them through their raw pointers
     return stats
 
 
@@ -180,8 +180,7 @@ class _FusedStep:
                               "lipvq_adam_f32")
                 # the kernel wrote the parameters behind autograd's back: bump their version counters, as an in-place torch op
                 # would (the tokenizer's packed-weight / prepared-codebook caches and autograd's saved-tensor checks key on them)
-                for t in chunk:
-                    torch.autograd.graph.increment_version(t[0])
+                mark_written(t[0] for t in chunk)
         return loss
 
 

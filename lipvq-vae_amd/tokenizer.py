@@ -29,37 +29,10 @@ import torch.nn as nn
 
 from . import ops
 from .backward import llfq_backward, vq_backward
+from .derived import _PackCache, mark_written  # noqa: F401  (_PackCache: embedding.py, binning.py and tests import it from here)
 from .ops import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, DIST_NORM, DIST_SQSUM
 
 __all__ = ["LLFQVAE_V4", "VQVAE", "LipschitzMLP", "LFQQuantizer"]
-
-
-class _PackCache:
-    """Re-lays weights out for the MFMA kernels only when a parameter changed (an optimizer
-    step bumps ``Tensor._version``; ``.to()``/``load_state_dict`` change data_ptr/version).
-
-    What the key CANNOT see: writes that bypass autograd's version counter -- ``p.data.add_(..)`` (the reference's own
-    ``embedding.weight.data.uniform_()`` idiom), a captured optimizer step replayed from a HIP graph, a raw-pointer writer.
-    After such a write call ``module.invalidate_caches()``; ``load_state_dict``, ``_apply`` (``.to()``, ``.cuda()``,
-    ``.float()``) and ``train()`` / ``eval()`` do it by themselves."""
-
-    def __init__(self):
-        self._key = None
-        self._val = None
-
-    def get(self, tensors, build):
-        key = tuple((t.data_ptr(), t._version, t.device) for t in tensors)
-        if key != self._key:
-            self._val = build()
-            self._key = key
-        return self._val
-
-    def invalidate(self):
-        self._key = None
-        self._val = None
-
-    def __deepcopy__(self, memo):
-        return type(self)()          # a copied module builds its own: the key holds the ORIGINAL's addresses
 
 
 class LipschitzMLP(nn.Module):
@@ -196,7 +169,7 @@ class _TokenizerBase(nn.Module):
     # -- derived buffers (packed weights, prepared codebook, fused-launch workspace) -------------------
     def invalidate_caches(self):
         """Drop everything derived from the parameters; the next call rebuilds it.  Needed after a write the version
-        counter does not see (see _PackCache); cheap (a few small launches on the next forward)."""
+        counter does not see (see derived.stamp); cheap (a few small launches on the next forward)."""
         for c in (self._enc_cache, self._dec_cache, self._cb_cache, self._enc16_cache):
             c.invalidate()
         self._tok_ws, self._tok_ws_key = None, None
@@ -231,7 +204,7 @@ class _TokenizerBase(nn.Module):
         """After an in-place write through a raw pointer: bump the version (autograd's saved-tensor checks), drop the prepared
         codebook and the fused workspace, and forget what the screen monitor learnt about the OLD codebook (a collapsed one sets
         its all-pairs bypass)."""
-        torch.autograd.graph.increment_version(self._codebook())
+        mark_written((self._codebook(),))
         self.invalidate_caches()
         self._screen_monitor.reset()
 
