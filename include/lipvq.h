@@ -537,6 +537,34 @@ int lipvq_gemm_bf16_tile(int64_t M, int Nc, int64_t chunks);
 int lipvq_wgrad_bf16(const float* G, const float* H, float* gW, float* gb, void* workspace, int64_t N, int J, int K,
                      void* stream);
 
+/* ---- the bf16x3 mode (GPTBackbone.set_matmul_precision("bf16x3"), what torch calls "bfloat16_3x"): the same three products
+ *      with every fp32 operand element SPLIT into two bf16 numbers and three matrix-pipe products per fp32 product.  The same
+ *      kernels (lipvq-vae_amd/csrc/lipvq_gemm_bf16.hip, SPLIT = true), arguments, validation, error codes, tile rule
+ *      (lipvq_gemm_bf16_tile), chunk rule and workspace (lipvq_wgrad_bf16_workspace_bytes) as the _bf16 entry points above.
+ *      Split: for an operand element v,  hi = bf16_rne(v),  lo = bf16_rne(v - float(hi));  the subtraction is exact in fp32;
+ *      where hi is not finite, lo = 0.
+ *      Product: C = sum_k (a_lo b_hi + a_hi b_lo + a_hi b_hi).  Each k-step of 16 of v_mfma_f32_32x32x16_bf16 runs three
+ *      MFMAs into the same fp32 accumulator IN THIS ORDER -- a_lo b_hi, then a_hi b_lo, then a_hi b_hi -- at every tile
+ *      instance, k-steps ascending, so a row's bits depend neither on its position nor on the tile it lands in, as above.
+ *      Everything after the accumulator is fp32 and is the _bf16 code: bias, pre-activation, activation, the chunk-ordered
+ *      reduce of the weight gradient; gb is the fp32 column sums of the UNROUNDED g.  No float atomics: results repeat bit
+ *      for bit.
+ *      Bound, for operand elements that are 0 or of normal magnitude with no bf16 overflow:
+ *          |v - hi| <= 2^-8 |v|,   |v - hi - lo| <= 2^-16 |v|,   |lo| <= 2^-8 (1 + 2^-8) |v|,
+ *      so the dropped a_lo b_lo term and the two residuals give  |a b - (three terms)| <= 3 2^-16 (1 + 2^-7) |a| |b|  per
+ *      product, against 2^-8 (1 + 2^-9) |a| |b| in the bf16 mode; the fp32 accumulation of the 3 L terms of a reduction of
+ *      length L adds at most (3 L + 1) 2^-24 sum(|a_hi b_hi| + |a_hi b_lo| + |a_lo b_hi|) under any-order round to nearest.
+ *      Limits: an |element| >= (2 - 2^-8) 2^127 (bit pattern 0x7f7f8000 up, FLT_MAX among them) rounds to +-Inf as in the bf16
+ *      mode; such an element, or a non-finite one, makes the outputs of its own line (its row of A or its column of B)
+ *      non-finite -- NaN or +-Inf is not specified, because Inf x (lo = 0) is NaN -- and changes nothing outside that line.
+ *      fp32-denormal operand elements keep only the bf16 mode's guarantee (their lo may be lost).  Both Linear widths must be
+ *      multiples of 8. ---- */
+int lipvq_linear_act_bf16x3(const float* x, const float* W, const float* b, float* y, float* pre, int64_t N, int Kin, int E,
+                            int act, void* stream);
+int lipvq_linear_nn_bf16x3(const float* g, const float* W, float* gx, int64_t N, int J, int K, void* stream);
+int lipvq_wgrad_bf16x3(const float* G, const float* H, float* gW, float* gb, void* workspace, int64_t N, int J, int K,
+                       void* stream);
+
 /* ---- the policy's GMM output head (pn = robomimic/models/policy_nets.py; ob:747-771 ObservationDecoder's three Linears
  *      mean | scale | logits, pn:2545-2575 tanh / softplus + min_std / MixtureSameFamily, icl.py:947 log_prob, icl.py:966 the NLL,
  *      pn:2599 sample).  lipvq-vae_amd/csrc/lipvq_gmm.hip, lipvq-vae_amd/gmm.py.

@@ -98,6 +98,9 @@ SIGNATURES = {
     "lipvq_wgrad_bf16_workspace_bytes": (_sz, [_i64, _i, _i]),
     "lipvq_gemm_bf16_tile": (_i, [_i64, _i, _i64]),
     "lipvq_wgrad_bf16": (_i, [_vp] * 5 + [_i64, _i, _i, _vp]),
+    "lipvq_linear_act_bf16x3": (_i, [_vp] * 5 + [_i64, _i, _i, _i, _vp]),
+    "lipvq_linear_nn_bf16x3": (_i, [_vp] * 3 + [_i64, _i, _i, _vp]),
+    "lipvq_wgrad_bf16x3": (_i, [_vp] * 5 + [_i64, _i, _i, _vp]),
     "lipvq_bin_minmax_f32": (_i, [_vp] * 3 + [_i64, _i, _vp]),
     "lipvq_bin_discretize_f32": (_i, [_vp] * 4 + [_i64, _i, _i, _vp]),
     "lipvq_bin_boundaries_f32": (_i, [_vp] * 3 + [_i, _i, _vp]),

@@ -20,6 +20,12 @@
 //       holds, per column, the 8 reduction-consecutive values of one 16-byte LDS write: the transpose happens in registers.
 // Out-of-range rows, columns and reduction steps are loaded from a clamped (valid) address and replaced by zero, so no
 // load depends on a branch and nothing outside the tensors is read; stores are masked.
+//
+// The bf16x3 mode (set_matmul_precision("bf16x3"), the lipvq_*_bf16x3 entry points) is the same kernel with SPLIT = true:
+// every operand element v is staged as TWO bf16 numbers, hi = rne(v) and lo = rne(v - hi) (the subtraction is exact in fp32;
+// lo = 0 where hi is not finite), formed from the staged fp32 registers at store time into a hi image and a lo image of the
+// same layout (LDS doubles, loads and staging registers do not grow), and every MFMA of the plain mode becomes three into
+// the same accumulator, in the fixed order a_lo b_hi, a_hi b_lo, a_hi b_hi.  The epilogue is the plain mode's.
 #include "lipvq_common.h"
 
 namespace {
@@ -37,6 +43,29 @@ constexpr int GB_LDK = 40;                 // bf16 per LDS row: 32 + 8 of paddin
 __device__ __forceinline__ uint32_t gb_pk(float lo, float hi) {
     const lq_f32x2 f = {lo, hi};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, lq_bf16x2));
+}
+
+// The residuals of the pair that gb_pk(a, b) rounded to `hi`: bf16(v - float(hi)) -- exact subtraction, one more rounding --
+// and 0 where hi is not finite (Inf - Inf and NaN must not reach the lo image: the line is non-finite through hi alone).
+__device__ __forceinline__ uint32_t gb_pk_lo(float a, float b, uint32_t hi) {
+    const float ha = __builtin_bit_cast(float, hi << 16), hb = __builtin_bit_cast(float, hi & 0xffff0000u);
+    const float la = __builtin_fabsf(ha) < __builtin_inff() ? a - ha : 0.0f;
+    const float lb = __builtin_fabsf(hb) < __builtin_inff() ? b - hb : 0.0f;
+    return gb_pk(la, lb);
+}
+
+// One 16-byte LDS write of eight reduction-consecutive floats as bf16: the hi image at s and (SPLIT) the lo image at s + lo_off.
+template <bool SPLIT>
+__device__ __forceinline__ void gb_stage8(unsigned short* __restrict__ s, int lo_off, float a0, float a1, float a2, float a3,
+                                          float a4, float a5, float a6, float a7) {
+    lq_u32x4 w;
+    w.x = gb_pk(a0, a1); w.y = gb_pk(a2, a3); w.z = gb_pk(a4, a5); w.w = gb_pk(a6, a7);
+    *reinterpret_cast<lq_u32x4*>(s) = w;
+    if constexpr (SPLIT) {
+        lq_u32x4 l;
+        l.x = gb_pk_lo(a0, a1, w.x); l.y = gb_pk_lo(a2, a3, w.y); l.z = gb_pk_lo(a4, a5, w.z); l.w = gb_pk_lo(a6, a7, w.w);
+        *reinterpret_cast<lq_u32x4*>(s + lo_off) = l;
+    }
 }
 
 struct GemmArgs {
@@ -60,7 +89,8 @@ __device__ __forceinline__ lq_f32x4 gb_keep(lq_f32x4 r, uint32_t m) {
 }
 
 // Staging registers of an operand whose reduction index is contiguous in memory: P[row][k], leading dimension ld.
-template <int BR, int NT>
+// SPLIT: store() writes the lo image BR rows behind the hi image.
+template <int BR, int NT, bool SPLIT>
 struct ContigStage {
     static constexpr int CH = BR * 4, PER = CH / NT;                 // chunks of 8 floats in a [BR][32] tile, per thread
     static_assert(CH % NT == 0, "every thread stages the same number of chunks");
@@ -82,10 +112,8 @@ struct ContigStage {
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int c = tid + i * NT;
-            lq_u32x4 w;
-            w.x = gb_pk(v[i][0].x, v[i][0].y); w.y = gb_pk(v[i][0].z, v[i][0].w);
-            w.z = gb_pk(v[i][1].x, v[i][1].y); w.w = gb_pk(v[i][1].z, v[i][1].w);
-            *reinterpret_cast<lq_u32x4*>(s + (c >> 2) * GB_LDK + (c & 3) * 8) = w;
+            gb_stage8<SPLIT>(s + (c >> 2) * GB_LDK + (c & 3) * 8, BR * GB_LDK, v[i][0].x, v[i][0].y, v[i][0].z, v[i][0].w,
+                             v[i][1].x, v[i][1].y, v[i][1].z, v[i][1].w);
         }
     }
 };
@@ -93,7 +121,7 @@ struct ContigStage {
 // Staging registers of an operand whose reduction index is the ROW index in memory: P[k][col], leading dimension ld.  A unit
 // is 8 reduction rows x 4 columns; the threads OFF .. OFF + units - 1 own one each (OFF lets the two operands of the weight
 // gradient use different threads of the workgroup).  SUM: also keep the fp32 column sums of what was loaded (the bias gradient).
-template <int BR, int NT, int OFF, bool SUM>
+template <int BR, int NT, int OFF, bool SUM, bool SPLIT>
 struct StridedStage {
     static constexpr int CG = BR / 4, UN = 4 * CG;
     static_assert(OFF + UN <= NT, "one unit per thread");
@@ -121,21 +149,17 @@ struct StridedStage {
         if (u >= 0 && u < UN) {
             unsigned short* d = s + ((u % CG) * 4) * GB_LDK + (u / CG) * 8;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                lq_u32x4 w;
-                w.x = gb_pk(v[0][e], v[1][e]); w.y = gb_pk(v[2][e], v[3][e]);
-                w.z = gb_pk(v[4][e], v[5][e]); w.w = gb_pk(v[6][e], v[7][e]);
-                *reinterpret_cast<lq_u32x4*>(d + e * GB_LDK) = w;
-            }
+            for (int e = 0; e < 4; ++e)
+                gb_stage8<SPLIT>(d + e * GB_LDK, BR * GB_LDK, v[0][e], v[1][e], v[2][e], v[3][e], v[4][e], v[5][e], v[6][e], v[7][e]);
             if (SUM) sum += ((((((v[0] + v[1]) + v[2]) + v[3]) + v[4]) + v[5]) + v[6]) + v[7];   // rows in ascending order
         }
     }
 };
 
-template <bool STRIDED, int BR, int NT, int OFF, bool SUM>
-struct StageOf { typedef ContigStage<BR, NT> type; };
-template <int BR, int NT, int OFF, bool SUM>
-struct StageOf<true, BR, NT, OFF, SUM> { typedef StridedStage<BR, NT, OFF, SUM> type; };
+template <bool STRIDED, int BR, int NT, int OFF, bool SUM, bool SPLIT>
+struct StageOf { typedef ContigStage<BR, NT, SPLIT> type; };
+template <int BR, int NT, int OFF, bool SUM, bool SPLIT>
+struct StageOf<true, BR, NT, OFF, SUM, SPLIT> { typedef StridedStage<BR, NT, OFF, SUM, SPLIT> type; };
 
 // A wave's RM x RN accumulator tiles to memory.  C/D map of the 32x32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2)
 // + 4 (lane >> 5); row0 / col0 already hold the lane's part.  FWD: + bias, the pre-activation, the activation (ACT = -1: a.act).
@@ -166,15 +190,18 @@ __device__ __forceinline__ void gb_store_tile(const f32x16 (&acc)[RM][RN], const
 }
 
 // AS / BS: the operand's reduction index is strided in memory.  (false, false) forward, (false, true) input gradient,
-// (true, true) weight gradient.
-template <int WM, int WN, int RM, int RN, bool AS, bool BS>
+// (true, true) weight gradient.  SPLIT: the bf16x3 mode -- an operand buffer is a hi image followed by a lo image (IM = 2
+// images), 80 KiB of LDS at the 128 tile, and a k-step is three MFMAs per accumulator tile.
+template <int WM, int WN, int RM, int RN, bool AS, bool BS, bool SPLIT>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(const GemmArgs a) {
-    constexpr int NT = 64 * WM * WN, BM = 32 * WM * RM, BN = 32 * WN * RN;
+    constexpr int NT = 64 * WM * WN, BM = 32 * WM * RM, BN = 32 * WN * RN, IM = SPLIT ? 2 : 1;
     constexpr bool FWD = !AS && !BS, WGRAD = AS && BS;
     constexpr int BOFF = (WGRAD && BM + BN <= NT) ? BM : 0;                           // A units: threads [0, BM); B units: the next BN
-    __shared__ __attribute__((aligned(16))) unsigned short lds[2 * (BM + BN) * GB_LDK];
+    constexpr int ABUF = IM * BM * GB_LDK, BBUF = IM * BN * GB_LDK;                   // one buffer of an operand, in bf16
+    __shared__ __attribute__((aligned(16))) unsigned short lds[2 * (ABUF + BBUF)];
+    static_assert(!WGRAD || sizeof(lds) >= 4 * BM * sizeof(float), "the bias-gradient reduce reuses the LDS");
     unsigned short* const sA = lds;
-    unsigned short* const sB = lds + 2 * BM * GB_LDK;
+    unsigned short* const sB = lds + 2 * ABUF;
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wm = wid / WN, wn = wid % WN;
     const int64_t row0 = (int64_t)blockIdx.x * BM;
@@ -184,8 +211,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(const GemmArgs 
     const int T = (int)((kend - kbeg + GB_BK - 1) / GB_BK);
     const int64_t lda = AS ? a.M : a.R, ldb = BS ? (int64_t)a.Nc : a.R;
 
-    typename StageOf<AS, BM, NT, 0, WGRAD>::type stA;
-    typename StageOf<BS, BN, NT, BOFF, false>::type stB;
+    typename StageOf<AS, BM, NT, 0, WGRAD, SPLIT>::type stA;
+    typename StageOf<BS, BN, NT, BOFF, false, SPLIT>::type stB;
     if constexpr (AS) stA.init();
 
     f32x16 acc[RM][RN];
@@ -210,8 +237,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(const GemmArgs 
             stA.load(a.A, lda, a.M, row0, k0, kend, tid);
             stB.load(a.B, ldb, a.Nc, col0, k0, kend, tid);
         }
-        const unsigned short* cA = sA + cur * BM * GB_LDK + (wm * RM * 32 + fr) * GB_LDK + fh * 8;
-        const unsigned short* cB = sB + cur * BN * GB_LDK + (wn * RN * 32 + fr) * GB_LDK + fh * 8;
+        const unsigned short* cA = sA + cur * ABUF + (wm * RM * 32 + fr) * GB_LDK + fh * 8;
+        const unsigned short* cB = sB + cur * BBUF + (wn * RN * 32 + fr) * GB_LDK + fh * 8;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             lq_bf16x8 fa[RM], fb[RN];
@@ -221,6 +248,27 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(const GemmArgs 
 #pragma unroll
             for (int n = 0; n < RN; ++n)
                 fb[n] = __builtin_bit_cast(lq_bf16x8, *reinterpret_cast<const lq_u32x4*>(cB + n * 32 * GB_LDK + s * 16));
+            if constexpr (SPLIT) {
+                // the two cross terms first, then hi x hi: per accumulator tile the same three-step chain at every tile
+                // instance; the term is the outer loop, so consecutive MFMAs write different accumulators where RM RN > 1
+                lq_bf16x8 la[RM], lb[RN];
+#pragma unroll
+                for (int m = 0; m < RM; ++m)
+                    la[m] = __builtin_bit_cast(lq_bf16x8, *reinterpret_cast<const lq_u32x4*>(cA + (BM + m * 32) * GB_LDK + s * 16));
+#pragma unroll
+                for (int n = 0; n < RN; ++n)
+                    lb[n] = __builtin_bit_cast(lq_bf16x8, *reinterpret_cast<const lq_u32x4*>(cB + (BN + n * 32) * GB_LDK + s * 16));
+#pragma unroll
+                for (int m = 0; m < RM; ++m)
+#pragma unroll
+                    for (int n = 0; n < RN; ++n)
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(la[m], fb[n], acc[m][n], 0, 0, 0);
+#pragma unroll
+                for (int m = 0; m < RM; ++m)
+#pragma unroll
+                    for (int n = 0; n < RN; ++n)
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[m], lb[n], acc[m][n], 0, 0, 0);
+            }
 #pragma unroll
             for (int m = 0; m < RM; ++m)
 #pragma unroll
@@ -228,8 +276,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(const GemmArgs 
                     acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[m], fb[n], acc[m][n], 0, 0, 0);
         }
         if (t + 1 < T) {
-            stA.store(sA + (cur ^ 1) * BM * GB_LDK, tid);
-            stB.store(sB + (cur ^ 1) * BN * GB_LDK, tid);
+            stA.store(sA + (cur ^ 1) * ABUF, tid);
+            stB.store(sB + (cur ^ 1) * BBUF, tid);
         }
         __syncthreads();
     }
@@ -274,15 +322,15 @@ __global__ __launch_bounds__(256) void wgrad_bf16_reduce_kernel(const float* __r
 // Tile choice from the shape alone (lipvq_gemm_bf16_tile below, the rule of include/lipvq.h): 128 x 128 (2 x 2 waves of
 // 64 x 64) once that gives the chip a workgroup per CU, else 64 x 64 (2 x 2 waves of 32 x 32), else one wave per 32 x 32 tile
 // (the 240-row step shape: 8 x 16 .. 8 x 64 workgroups).
-template <bool AS, bool BS>
+template <bool AS, bool BS, bool SPLIT>
 static int launch_gemm(const char* what, const GemmArgs& a, int64_t nchunks, hipStream_t st) {
     const int t = lipvq_gemm_bf16_tile(a.M, a.Nc, nchunks);
     const int64_t gx = (a.M + t - 1) / t, gy = (a.Nc + t - 1) / t;
     if (gx > 0x7fffffffLL || gy > 65535 || nchunks > 65535) return fail(LIPVQ_EUNSUPPORTED, "%s: too large", what);
     const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)nchunks);
-    if (t == 128) hipLaunchKernelGGL((gemm_bf16_kernel<2, 2, 2, 2, AS, BS>), grid, dim3(256), 0, st, a);
-    else if (t == 64) hipLaunchKernelGGL((gemm_bf16_kernel<2, 2, 1, 1, AS, BS>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gemm_bf16_kernel<1, 1, 1, 1, AS, BS>), grid, dim3(64), 0, st, a);
+    if (t == 128) hipLaunchKernelGGL((gemm_bf16_kernel<2, 2, 2, 2, AS, BS, SPLIT>), grid, dim3(256), 0, st, a);
+    else if (t == 64) hipLaunchKernelGGL((gemm_bf16_kernel<2, 2, 1, 1, AS, BS, SPLIT>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((gemm_bf16_kernel<1, 1, 1, 1, AS, BS, SPLIT>), grid, dim3(64), 0, st, a);
     return check_launch(what);
 }
 
@@ -304,31 +352,54 @@ static int64_t wgrad_chunk(int64_t N, int J, int K) {
     return chunk < 64 ? 64 : chunk;
 }
 
+template <bool SPLIT>
+static int linear_act(const char* what, const float* x, const float* W, const float* b, float* y, float* pre, int64_t N, int Kin, int E,
+                      int act, void* stream) {
+    const int rc = gemm_dims(what, N, E, Kin);
+    if (rc) return rc;
+    if (act < LIPVQ_ACT_NONE || act > LIPVQ_ACT_RELU) return fail(LIPVQ_EINVAL, "%s: bad activation %d", what, act);
+    if (N == 0) return LIPVQ_OK;
+    if (!x || !W || !y) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
+    if (misaligned(x) || misaligned(W)) return fail(LIPVQ_EINVAL, "%s: x and W must be 16-byte aligned", what);
+    GemmArgs a = {x, W, b, y, pre, nullptr, N, E, Kin, Kin, act};
+    return launch_gemm<false, false, SPLIT>(what, a, 1, (hipStream_t)stream);
+}
+
+template <bool SPLIT>
+static int linear_nn(const char* what, const float* g, const float* W, float* gx, int64_t N, int J, int K, void* stream) {
+    const int rc = gemm_dims(what, N, J, K);
+    if (rc) return rc;
+    if (N == 0) return LIPVQ_OK;
+    if (!g || !W || !gx) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
+    if (misaligned(g) || misaligned(W)) return fail(LIPVQ_EINVAL, "%s: g and W must be 16-byte aligned", what);
+    GemmArgs a = {g, W, nullptr, gx, nullptr, nullptr, N, K, J, J, LIPVQ_ACT_NONE};
+    return launch_gemm<false, true, SPLIT>(what, a, 1, (hipStream_t)stream);
+}
+
+template <bool SPLIT>
+static int wgrad(const char* what, const float* G, const float* H, float* gW, float* gb, void* workspace, int64_t N, int J, int K,
+                 void* stream) {
+    const int rc = gemm_dims(what, N, J, K);
+    if (rc) return rc;
+    if (N == 0) return LIPVQ_OK;
+    if (!G || !H || !gW || !workspace) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
+    if (misaligned(G) || misaligned(H) || misaligned(workspace))
+        return fail(LIPVQ_EINVAL, "%s: G, H and the workspace must be 16-byte aligned", what);
+    const int64_t chunk = wgrad_chunk(N, J, K), nch = (N + chunk - 1) / chunk;
+    const int64_t JK = (int64_t)J * K;
+    float* ws = static_cast<float*>(workspace);
+    GemmArgs a = {G, H, nullptr, ws, nullptr, ws + (size_t)nch * JK, J, K, N, chunk, LIPVQ_ACT_NONE};
+    const int lrc = launch_gemm<true, true, SPLIT>(what, a, nch, (hipStream_t)stream);
+    if (lrc) return lrc;
+    const int64_t total = JK + (gb ? J : 0);
+    hipLaunchKernelGGL(wgrad_bf16_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws,
+                       gW, gb, JK, J, (int)nch);
+    return check_launch("wgrad_bf16_reduce_kernel");
+}
+
 }  // namespace
 
 extern "C" {
-
-int lipvq_linear_act_bf16(const float* x, const float* W, const float* b, float* y, float* pre, int64_t N, int Kin, int E,
-                          int act, void* stream) {
-    const int rc = gemm_dims("lipvq_linear_act_bf16", N, E, Kin);
-    if (rc) return rc;
-    if (act < LIPVQ_ACT_NONE || act > LIPVQ_ACT_RELU) return fail(LIPVQ_EINVAL, "lipvq_linear_act_bf16: bad activation %d", act);
-    if (N == 0) return LIPVQ_OK;
-    if (!x || !W || !y) return fail(LIPVQ_EINVAL, "lipvq_linear_act_bf16: null pointer");
-    if (misaligned(x) || misaligned(W)) return fail(LIPVQ_EINVAL, "lipvq_linear_act_bf16: x and W must be 16-byte aligned");
-    GemmArgs a = {x, W, b, y, pre, nullptr, N, E, Kin, Kin, act};
-    return launch_gemm<false, false>("lipvq_linear_act_bf16", a, 1, (hipStream_t)stream);
-}
-
-int lipvq_linear_nn_bf16(const float* g, const float* W, float* gx, int64_t N, int J, int K, void* stream) {
-    const int rc = gemm_dims("lipvq_linear_nn_bf16", N, J, K);
-    if (rc) return rc;
-    if (N == 0) return LIPVQ_OK;
-    if (!g || !W || !gx) return fail(LIPVQ_EINVAL, "lipvq_linear_nn_bf16: null pointer");
-    if (misaligned(g) || misaligned(W)) return fail(LIPVQ_EINVAL, "lipvq_linear_nn_bf16: g and W must be 16-byte aligned");
-    GemmArgs a = {g, W, nullptr, gx, nullptr, nullptr, N, K, J, J, LIPVQ_ACT_NONE};
-    return launch_gemm<false, true>("lipvq_linear_nn_bf16", a, 1, (hipStream_t)stream);
-}
 
 int lipvq_gemm_bf16_tile(int64_t M, int Nc, int64_t chunks) {
     if (M <= 0 || Nc <= 0 || chunks <= 0) return 0;
@@ -342,24 +413,32 @@ size_t lipvq_wgrad_bf16_workspace_bytes(int64_t N, int J, int K) {
     return (size_t)((N + chunk - 1) / chunk) * ((size_t)J * K + J) * sizeof(float);
 }
 
+int lipvq_linear_act_bf16(const float* x, const float* W, const float* b, float* y, float* pre, int64_t N, int Kin, int E,
+                          int act, void* stream) {
+    return linear_act<false>("lipvq_linear_act_bf16", x, W, b, y, pre, N, Kin, E, act, stream);
+}
+
+int lipvq_linear_act_bf16x3(const float* x, const float* W, const float* b, float* y, float* pre, int64_t N, int Kin, int E,
+                            int act, void* stream) {
+    return linear_act<true>("lipvq_linear_act_bf16x3", x, W, b, y, pre, N, Kin, E, act, stream);
+}
+
+int lipvq_linear_nn_bf16(const float* g, const float* W, float* gx, int64_t N, int J, int K, void* stream) {
+    return linear_nn<false>("lipvq_linear_nn_bf16", g, W, gx, N, J, K, stream);
+}
+
+int lipvq_linear_nn_bf16x3(const float* g, const float* W, float* gx, int64_t N, int J, int K, void* stream) {
+    return linear_nn<true>("lipvq_linear_nn_bf16x3", g, W, gx, N, J, K, stream);
+}
+
 int lipvq_wgrad_bf16(const float* G, const float* H, float* gW, float* gb, void* workspace, int64_t N, int J, int K,
                      void* stream) {
-    const int rc = gemm_dims("lipvq_wgrad_bf16", N, J, K);
-    if (rc) return rc;
-    if (N == 0) return LIPVQ_OK;
-    if (!G || !H || !gW || !workspace) return fail(LIPVQ_EINVAL, "lipvq_wgrad_bf16: null pointer");
-    if (misaligned(G) || misaligned(H) || misaligned(workspace))
-        return fail(LIPVQ_EINVAL, "lipvq_wgrad_bf16: G, H and the workspace must be 16-byte aligned");
-    const int64_t chunk = wgrad_chunk(N, J, K), nch = (N + chunk - 1) / chunk;
-    const int64_t JK = (int64_t)J * K;
-    float* ws = static_cast<float*>(workspace);
-    GemmArgs a = {G, H, nullptr, ws, nullptr, ws + (size_t)nch * JK, J, K, N, chunk, LIPVQ_ACT_NONE};
-    const int lrc = launch_gemm<true, true>("lipvq_wgrad_bf16", a, nch, (hipStream_t)stream);
-    if (lrc) return lrc;
-    const int64_t total = JK + (gb ? J : 0);
-    hipLaunchKernelGGL(wgrad_bf16_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws,
-                       gW, gb, JK, J, (int)nch);
-    return check_launch("wgrad_bf16_reduce_kernel");
+    return wgrad<false>("lipvq_wgrad_bf16", G, H, gW, gb, workspace, N, J, K, stream);
+}
+
+int lipvq_wgrad_bf16x3(const float* G, const float* H, float* gW, float* gb, void* workspace, int64_t N, int J, int K,
+                       void* stream) {
+    return wgrad<true>("lipvq_wgrad_bf16x3", G, H, gW, gb, workspace, N, J, K, stream);
 }
 
 }  // extern "C"

@@ -20,7 +20,9 @@ model.  Every op is a ``torch.autograd.Function`` over the backward kernels (lip
 lipvq_gpt_layernorm_bwd_f32 -- which folds the residual stream's incoming gradient in --, lipvq_act_bwd_f32, lipvq_wgrad_f32);
 none of them uses float atomics, so gradients repeat bit for bit.  ``set_matmul_precision("bf16")`` moves the four Linears of
 every block -- forward, input gradient, weight gradient -- to lipvq_linear_act_bf16 / lipvq_linear_nn_bf16 / lipvq_wgrad_bf16
-(operands rounded to bf16 as they are read, fp32 accumulation, fp32 tensors, still no atomics); the default is fp32.
+(operands rounded to bf16 as they are read, fp32 accumulation, fp32 tensors, still no atomics), ``"bf16x3"`` to their
+_bf16x3 siblings (every operand split into two bf16 numbers, three products per product: near fp32 accuracy on the same pipe);
+the default is fp32.
 
 Rollouts (``ICLTransformer.get_action``, icl.py:827-853) pass the same context for a whole evaluation, so the first 2T of the
 3T positions (obs_nets.py:2584-2596) and, the backbone being causal and adding no positional term of its own, every block's
@@ -134,7 +136,7 @@ class GPTBackbone(nn.Module):
 
     @property
     def matmul_precision(self) -> str:
-        """"fp32" (default) or "bf16": how the four Linears of every block multiply (set_matmul_precision)."""
+        """"fp32" (default), "bf16" or "bf16x3": how the four Linears of every block multiply (set_matmul_precision)."""
         return self._matmul_precision
 
     def set_matmul_precision(self, precision: str) -> "GPTBackbone":
@@ -142,9 +144,13 @@ class GPTBackbone(nn.Module):
         pipe: both operands of each product are rounded to bf16 (nearest even) as the kernel reads them, products are
         accumulated in fp32, and every tensor (activations, saved tensors, gradients, parameters) stays fp32.  Attention,
         LayerNorm, GELU and its derivative stay fp32.  "fp32" restores the default bit for bit.  Needs embed_dim % 8 == 0
-        (every supported head width gives that).  Not part of state_dict(); returns self."""
-        if precision not in ("fp32", "bf16"):
-            raise ValueError(f"GPTBackbone: matmul precision must be 'fp32' or 'bf16', got {precision!r}")
+        (every supported head width gives that).  Not part of state_dict(); returns self.
+
+        "bf16x3" (torch's "bfloat16_3x"): the same Linears on the same pipe, with every fp32 operand element split into
+        hi = bf16(v) and lo = bf16(v - hi) and a_lo b_hi + a_hi b_lo + a_hi b_hi accumulated in fp32: about 2^-16 relative
+        per product instead of 2^-8, for three times the matrix-pipe work (include/lipvq.h states the bound and its limits)."""
+        if precision not in ("fp32", "bf16", "bf16x3"):
+            raise ValueError(f"GPTBackbone: matmul precision must be 'fp32', 'bf16' or 'bf16x3', got {precision!r}")
         self._matmul_precision = precision
         return self
 

@@ -14,14 +14,16 @@ __all__ = ["LinearFn", "AddLayerNormFn", "GraphedEval"]
 class LinearFn(torch.autograd.Function):
     """act(x W^T + b) over the last dimension, b optional; backward = act' (elementwise), one more Linear (gx), the wgrad kernel.
     precision="bf16": the three matrix products run on the bf16 matrix pipe (ops.linear_bf16 / linear_nn_bf16 / wgrad_bf16:
-    operands rounded to bf16 as they are read, fp32 accumulation, fp32 tensors); act' stays the fp32 kernel."""
+    operands rounded to bf16 as they are read, fp32 accumulation, fp32 tensors); precision="bf16x3": the same pipe with every
+    operand split into two bf16 numbers and three products per product (ops.linear_bf16x3 / linear_nn_bf16x3 / wgrad_bf16x3);
+    act' stays the fp32 kernel."""
 
     @staticmethod
     def forward(ctx, x, W, b, act, precision="fp32"):
-        if precision not in ("fp32", "bf16"):
-            raise ValueError(f"LinearFn: precision must be 'fp32' or 'bf16', got {precision!r}")
-        ctx.act, ctx.has_bias, ctx.shape, ctx.bf16 = act, b is not None, x.shape, precision == "bf16"
-        linear = ops.linear_bf16 if ctx.bf16 else ops.linear
+        if precision not in ("fp32", "bf16", "bf16x3"):
+            raise ValueError(f"LinearFn: precision must be 'fp32', 'bf16' or 'bf16x3', got {precision!r}")
+        ctx.act, ctx.has_bias, ctx.shape, ctx.pipe = act, b is not None, x.shape, ("" if precision == "fp32" else "_" + precision)
+        linear = getattr(ops, "linear" + ctx.pipe)
         x2 = x if x.dim() == 2 else x.reshape(-1, x.shape[-1])      # (2-D callers: no view objects on their host-bound paths)
         if act != ACT_NONE:
             y, pre = linear(x2, W, b, act=act, save_pre=True)
@@ -41,9 +43,9 @@ class LinearFn(torch.autograd.Function):
             x2, W = ctx.saved_tensors
         gx = gW = gb = None
         if ctx.needs_input_grad[0]:
-            gx = (ops.linear_nn_bf16(gy, W) if ctx.bf16 else ops.linear(gy, W.t().contiguous())).view(ctx.shape)
+            gx = (getattr(ops, "linear_nn" + ctx.pipe)(gy, W) if ctx.pipe else ops.linear(gy, W.t().contiguous())).view(ctx.shape)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            gW, gb = (ops.wgrad_bf16 if ctx.bf16 else ops.wgrad)(gy, x2, want_bias=ctx.has_bias)
+            gW, gb = getattr(ops, "wgrad" + ctx.pipe)(gy, x2, want_bias=ctx.has_bias)
         return gx, gW, gb, None, None
 
 

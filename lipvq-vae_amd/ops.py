@@ -704,50 +704,44 @@ def _bf16_widths(what, Kin, E):
         raise ValueError(f"{what}: the bf16 mode needs both Linear widths to be multiples of 8 (got {Kin} -> {E})")
 
 
-def linear_bf16(x, W, b=None, act=ACT_NONE, save_pre=False):
-    """``linear`` in the bf16 matrix-pipe mode: x and W are rounded to bf16 (nearest even) as the kernel reads them, products
-    are accumulated in fp32, bias and activation are the fp32 epilogue of ``linear``; every tensor stays fp32."""
+def _linear_pipe(name, entry, x, W, b, act, save_pre):
     x, W = _chk(x, "x"), _chk(W, "W")
     if x.dim() != 2 or W.dim() != 2 or W.shape[1] != x.shape[1]:
-        raise ValueError(f"linear_bf16: x {tuple(x.shape)} and W {tuple(W.shape)} do not match")
+        raise ValueError(f"{name}: x {tuple(x.shape)} and W {tuple(W.shape)} do not match")
     if b is not None:
         b = _chk(b, "b")
         if b.shape != (W.shape[0],):
-            raise ValueError("linear_bf16: bias shape")
+            raise ValueError(f"{name}: bias shape")
     N, Kin = x.shape
     E = W.shape[0]
-    _bf16_widths("linear_bf16", Kin, E)
+    _bf16_widths(name, Kin, E)
     y = torch.empty((N, E), device=x.device, dtype=torch.float32)
     pre = torch.empty_like(y) if save_pre else None
     with _on(x.device):
-        check(lib.lipvq_linear_act_bf16(_ptr(x), _ptr(W), _ptr(b), _ptr(y), _ptr(pre), N, Kin, E, int(act), _stream()),
-              "lipvq_linear_act_bf16")
+        check(getattr(lib, entry)(_ptr(x), _ptr(W), _ptr(b), _ptr(y), _ptr(pre), N, Kin, E, int(act), _stream()), entry)
     return (y, pre) if save_pre else y
 
 
-def linear_nn_bf16(g, W):
-    """gx = g . W in the bf16 mode (the input gradient of ``linear_bf16``): W [J, K] is read as stored, no transposed copy."""
+def _linear_nn_pipe(name, entry, g, W):
     g, W = _chk(g, "g"), _chk(W, "W")
     if g.dim() != 2 or W.dim() != 2 or W.shape[0] != g.shape[1]:
-        raise ValueError(f"linear_nn_bf16: g {tuple(g.shape)} and W {tuple(W.shape)} do not match")
+        raise ValueError(f"{name}: g {tuple(g.shape)} and W {tuple(W.shape)} do not match")
     N, J = g.shape
     K = W.shape[1]
-    _bf16_widths("linear_nn_bf16", K, J)
+    _bf16_widths(name, K, J)
     gx = torch.empty((N, K), device=g.device, dtype=torch.float32)
     with _on(g.device):
-        check(lib.lipvq_linear_nn_bf16(_ptr(g), _ptr(W), _ptr(gx), N, J, K, _stream()), "lipvq_linear_nn_bf16")
+        check(getattr(lib, entry)(_ptr(g), _ptr(W), _ptr(gx), N, J, K, _stream()), entry)
     return gx
 
 
-def wgrad_bf16(G, H, want_bias=True):
-    """(gW[J,K], gb[J]) of one Linear in the bf16 mode: gW = G^T . H on bf16-rounded operands with fp32 accumulation, gb = the
-    fp32 column sums of the unrounded G.  Row chunks are added in a fixed order: repeated calls give the same bits."""
+def _wgrad_pipe(name, entry, G, H, want_bias):
     G, H = _chk(G, "G"), _chk(H, "H")
     if G.dim() != 2 or H.dim() != 2 or H.shape[0] != G.shape[0]:
-        raise ValueError("wgrad_bf16: G and H must be 2-D with the same number of rows")
+        raise ValueError(f"{name}: G and H must be 2-D with the same number of rows")
     N, J = G.shape
     K = H.shape[1]
-    _bf16_widths("wgrad_bf16", K, J)
+    _bf16_widths(name, K, J)
     dev = G.device
     if N == 0:
         return torch.zeros((J, K), device=dev), (torch.zeros(J, device=dev) if want_bias else None)
@@ -755,8 +749,44 @@ def wgrad_bf16(G, H, want_bias=True):
     gb = torch.empty(J, device=dev, dtype=torch.float32) if want_bias else None
     ws = torch.empty(lib.lipvq_wgrad_bf16_workspace_bytes(N, J, K), device=dev, dtype=torch.uint8)
     with _on(dev):
-        check(lib.lipvq_wgrad_bf16(_ptr(G), _ptr(H), _ptr(gW), _ptr(gb), _ptr(ws), N, J, K, _stream()), "lipvq_wgrad_bf16")
+        check(getattr(lib, entry)(_ptr(G), _ptr(H), _ptr(gW), _ptr(gb), _ptr(ws), N, J, K, _stream()), entry)
     return gW, gb
+
+
+def linear_bf16(x, W, b=None, act=ACT_NONE, save_pre=False):
+    """``linear`` in the bf16 matrix-pipe mode: x and W are rounded to bf16 (nearest even) as the kernel reads them, products
+    are accumulated in fp32, bias and activation are the fp32 epilogue of ``linear``; every tensor stays fp32."""
+    return _linear_pipe("linear_bf16", "lipvq_linear_act_bf16", x, W, b, act, save_pre)
+
+
+def linear_nn_bf16(g, W):
+    """gx = g . W in the bf16 mode (the input gradient of ``linear_bf16``): W [J, K] is read as stored, no transposed copy."""
+    return _linear_nn_pipe("linear_nn_bf16", "lipvq_linear_nn_bf16", g, W)
+
+
+def wgrad_bf16(G, H, want_bias=True):
+    """(gW[J,K], gb[J]) of one Linear in the bf16 mode: gW = G^T . H on bf16-rounded operands with fp32 accumulation, gb = the
+    fp32 column sums of the unrounded G.  Row chunks are added in a fixed order: repeated calls give the same bits."""
+    return _wgrad_pipe("wgrad_bf16", "lipvq_wgrad_bf16", G, H, want_bias)
+
+
+def linear_bf16x3(x, W, b=None, act=ACT_NONE, save_pre=False):
+    """``linear`` in the bf16x3 mode: every element of x and W is split into hi = bf16(v) and lo = bf16(v - hi) as the kernel
+    reads it, and a_lo b_hi + a_hi b_lo + a_hi b_hi is accumulated in fp32 on the bf16 matrix pipe (about 2^-16 relative per
+    product instead of 2^-8; include/lipvq.h has the bound).  The epilogue and the tensors are those of ``linear_bf16``."""
+    return _linear_pipe("linear_bf16x3", "lipvq_linear_act_bf16x3", x, W, b, act, save_pre)
+
+
+def linear_nn_bf16x3(g, W):
+    """gx = g . W in the bf16x3 mode (the input gradient of ``linear_bf16x3``): W [J, K] is read as stored."""
+    return _linear_nn_pipe("linear_nn_bf16x3", "lipvq_linear_nn_bf16x3", g, W)
+
+
+def wgrad_bf16x3(G, H, want_bias=True):
+    """(gW[J,K], gb[J]) of one Linear in the bf16x3 mode: gW = G^T . H with both operands split into two bf16 numbers and
+    three products per element pair, gb = the fp32 column sums of the unrounded G.  The chunks, their order and the
+    workspace are those of ``wgrad_bf16``: repeated calls give the same bits."""
+    return _wgrad_pipe("wgrad_bf16x3", "lipvq_wgrad_bf16x3", G, H, want_bias)
 
 
 def _embed_args(src, idx, pos, N, T, E):

@@ -1,11 +1,13 @@
 """Dev measurement (GPU): GPTBackbone (lipvq-vae_amd/gpt.py) against the plain-torch restatement of the same op sequence
 (tests/gpt_ref.py: what the reference's eager GPT_Backbone issues), same parameters, same GPU, same process.
 
-    python scripts/bench_gpt.py [--precision bf16] [B ...]   (default: 8 and 4096 -- the ICRT step shape and a large batch; L = 30,
-                                                              E = 512, 6 layers)
+    python scripts/bench_gpt.py [--precision bf16|bf16x3] [B ...]   (default: 8 and 4096 -- the ICRT step shape and a large
+                                                                     batch; L = 30, E = 512, 6 layers)
 
 --precision bf16 measures four sides instead of two: ours with set_matmul_precision("bf16"), ours in fp32 (the same build, the
 fp32 kernels), plain torch in fp32 and plain torch under torch.autocast(dtype=torch.bfloat16).
+--precision bf16x3 measures ours with set_matmul_precision("bf16x3"), ours in fp32, ours in "bf16" and plain torch in fp32, in
+seven alternating rounds instead of five.
 
 Per shape: the eval forward and a training forward + backward (dropout 0.1: the attention mask drawn by torch.rand and the two
 block-output dropouts by F.dropout, on both sides), each eager
@@ -71,14 +73,17 @@ def window(fn, n):
     return a.elapsed_time(b) / n
 
 
-def alternate(fns, n, rounds=5):
+ROUNDS = 5
+
+
+def alternate(fns, n, rounds=None):
     """Median per side of `rounds` rounds in which the sides take turns; also the clock and every side's min-max."""
     for _ in range(3):
         for f in fns:
             f()
     torch.cuda.synchronize()
     t = [[] for _ in fns]
-    for _ in range(rounds):
+    for _ in range(rounds or ROUNDS):
         for i, f in enumerate(fns):
             t[i].append(window(f, n))
     spread = " / ".join(f"[{min(v):.3f}-{max(v):.3f}]" for v in t)
@@ -103,15 +108,20 @@ def graphed_step(module, x):
 
 def main():
     args = sys.argv[1:]
-    bf16 = False
+    global ROUNDS
+    bf16 = x3 = False
     if "--precision" in args:
         i = args.index("--precision")
-        if args[i + 1:i + 2] not in (["bf16"], ["fp32"]):
-            sys.exit("--precision takes fp32 or bf16")
-        bf16 = args[i + 1] == "bf16"
+        if args[i + 1:i + 2] not in (["bf16"], ["bf16x3"], ["fp32"]):
+            sys.exit("--precision takes fp32, bf16 or bf16x3")
+        bf16, x3 = args[i + 1] == "bf16", args[i + 1] == "bf16x3"
         del args[i:i + 2]
     batches = [int(a) for a in args] or [8, 4096]
-    names = ["ours-bf16", "ours-fp32", "torch-fp32", "torch-autocast-bf16"] if bf16 else ["ours", "plain torch"]
+    names = ["ours", "plain torch"]
+    if bf16:
+        names = ["ours-bf16", "ours-fp32", "torch-fp32", "torch-autocast-bf16"]
+    if x3:
+        names, ROUNDS = ["ours-bf16x3", "ours-fp32", "ours-bf16", "torch-fp32"], 7
     print(f"device {torch.cuda.get_device_name(0)}; L={L} E={E} heads={H} layers={LAYERS}; times in ms ({' / '.join(names)}), "
           "median of alternating rounds")
 
@@ -123,9 +133,17 @@ def main():
         ours = GPTBackbone(E, L).cuda()
         ref = TorchBackbone(ours)
         mods = [ours, ref]                                              # the callables below, in the order of `names`
+        extra = ()                                                      # further modules of ours, with their own mode
+        if x3:
+            ours3 = GPTBackbone(E, L).cuda().set_matmul_precision("bf16x3")
+            ours16 = GPTBackbone(E, L).cuda().set_matmul_precision("bf16")
+            ours3.load_state_dict(ours.state_dict())
+            ours16.load_state_dict(ours.state_dict())
+            mods, extra = [ours3, ours, ours16, ref], (ours3, ours16)
         if bf16:
             ours16 = GPTBackbone(E, L).cuda().set_matmul_precision("bf16")
             ours16.load_state_dict(ours.state_dict())
+            extra = (ours16,)
 
             def ref16(x):
                 with torch.autocast("cuda", dtype=torch.bfloat16):
@@ -134,7 +152,7 @@ def main():
             mods = [ours16, ours, ref, ref16]
         x = torch.randn(B, L, E, device="cuda")
         n = 300 if B <= 64 else 4
-        for m in (ours, ref) + ((ours16,) if bf16 else ()):
+        for m in (ours, ref) + extra:
             m.eval()
         with torch.no_grad():
             base = ref(x)
@@ -156,7 +174,7 @@ def main():
                     graphs.append((g.replay, None))
             t, c = alternate([g for g, _ in graphs], n)
             line(B, "eval forward, graph replay", t, c, f"   (replay == eager: {[s for _, s in graphs if s is not None]})")
-        for m in (ours, ref) + ((ours16,) if bf16 else ()):
+        for m in (ours, ref) + extra:
             m.train()
 
         def step(m):
@@ -167,9 +185,11 @@ def main():
         replays = [graphed_step(m, x) for m in mods]
         t, c = alternate(replays, max(2, n // 2))
         line(B, "forward + backward, graph", t, c)
-        del ours, ref, mods, x, replays, graphs, base
+        del ours, ref, mods, x, replays, graphs, base, extra
         if bf16:
             del ours16, ref16
+        if x3:
+            del ours3, ours16
         torch.cuda.empty_cache()
 
 
