@@ -180,6 +180,47 @@ __device__ __forceinline__ void tok_gelu_fixup(f32x16& out, const f32x16& pre) {
             if (!(pre[r] * pre[r] < 18.0f)) out[r] = lq_gelu_tail(pre[r]);
     }
 }
+// The forms of the instances that run a tile's activation as one straight-line block behind its MFMA chain (tokenize_body, LOCKSTEP):
+// hipcc emitted that block as one Horner chain after the other, a wait state between every two packed ops.  Here the 8 packed pairs
+// of the tile go through the polynomial TOK_CHAINS at a time in lockstep (lq_gelu_poly2xN / lq_sigmoid2_finite_xN: no packed op
+// reads the result of the instruction in front of it); same operations per element, same bits (profiles/r09_phase_a_chains_ab.txt).
+constexpr int TOK_CHAINS = 4;                 // pairs in flight
+__device__ __forceinline__ void tok_gelu_poly_tile(f32x16& out, const f32x16& pre) {
+#pragma unroll
+    for (int r0 = 0; r0 < 16; r0 += 2 * TOK_CHAINS) {
+        lq_v2f g[TOK_CHAINS];
+#pragma unroll
+        for (int i = 0; i < TOK_CHAINS; ++i) g[i] = (lq_v2f){pre[r0 + 2 * i], pre[r0 + 2 * i + 1]};
+        lq_gelu_poly2xN(g);
+#pragma unroll
+        for (int i = 0; i < TOK_CHAINS; ++i) { out[r0 + 2 * i] = g[i].x; out[r0 + 2 * i + 1] = g[i].y; }
+    }
+}
+// the finite sigmoid of the first `nreg` registers of a tile (16, or 8 where only the tile's first 16 features exist), in place
+__device__ __forceinline__ void tok_sigmoid_finite_tile(f32x16& acc, const int nreg) {
+#pragma unroll
+    for (int r0 = 0; r0 < 16; r0 += 2 * TOK_CHAINS) {
+        if (r0 >= nreg) continue;
+        lq_v2f z[TOK_CHAINS];
+#pragma unroll
+        for (int i = 0; i < TOK_CHAINS; ++i) z[i] = (lq_v2f){acc[r0 + 2 * i], acc[r0 + 2 * i + 1]};
+        lq_sigmoid2_finite_xN(z);
+#pragma unroll
+        for (int i = 0; i < TOK_CHAINS; ++i) { acc[r0 + 2 * i] = z[i].x; acc[r0 + 2 * i + 1] = z[i].y; }
+    }
+}
+// tok_gelu_fixup with the maximum in plain C: hipcc selects v_max3_f32 with |...| modifiers itself and pads nothing behind it (an
+// asm statement's result costs a wait state in front of its reader).  fmaxf skips a NaN as v_max3 does: the same decisions.
+__device__ __forceinline__ void tok_gelu_fixup_lumped(f32x16& out, const f32x16& pre) {
+    float mx = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) mx = __builtin_fmaxf(__builtin_fmaxf(mx, __builtin_fabsf(pre[r])), __builtin_fabsf(pre[r + 1]));
+    if (__builtin_amdgcn_ballot_w64(!(mx * mx < 18.0f)) != 0ull) {          // wave-uniform, practically never taken
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (!(pre[r] * pre[r] < 18.0f)) out[r] = lq_gelu_tail(pre[r]);
+    }
+}
 // the lane's 16 bias values of tile t (see the bias re-layout in tokenize_body's prologue): four 16-byte LDS reads
 __device__ __forceinline__ f32x16 tok_bias16(const float* wb, int t, int h) {
     f32x16 b;
@@ -589,6 +630,11 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
             const int64_t rowc = row < a.N ? row : a.N - 1;
             float n2 = 0.0f, a2lo = 0.0f, amax = 0.0f;
             float zt[VQ ? T2 : 1][16];                           // VQ: the centred latent in fp32 until the row's scale is known
+            constexpr bool LUMPED = !FAST && !VQ && !STREAM2;    // a tile's activation is one block behind its MFMA chain (see layer 1)
+            // ... and there its packed pairs go through the polynomials four at a time in lockstep (tok_gelu_poly_tile).  Not in the training
+            // instances, which also hold the tile's pre-activations for their store: with four in flight tokenize_kernel<4, .., TRAIN>
+            // spilled two registers it did not spill before, and with two hipcc moved the unfenced ops back in front of their readers
+            constexpr bool LOCKSTEP = LUMPED && !TRAIN;
             // sigmoid, centring, row statistics and the optional z_e store of one finished 32-feature tile
             auto finish_tile = [&](const int t, f32x16& acc) {
                 if constexpr (TRAIN) lq_tile_store16(a.pre2, a.D, row, row < a.N, t, h, acc, a.D, true);
@@ -607,12 +653,23 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                     if constexpr (!FAST) {
                         // the canonical sigmoid, two elements per instruction; a tile that holds a NaN or an infinity (wave-uniform test,
                         // practically never true) takes the one-element form, whose clamps propagate NaN
-                        lq_v2f chk = lq_bc2(0.0f);
+                        lq_v2f chk = lq_bc2(0.0f), chk1 = lq_bc2(0.0f);
+                        if constexpr (LOCKSTEP) {
+                            // two running checks, both tested: no op reads the result of the one in front of it
 #pragma unroll
-                        for (int r = 0; r < 16; r += 2) chk = lq_nonfinite_acc2((lq_v2f){acc[r], acc[r + 1]}, chk);
-                        if (__builtin_amdgcn_ballot_w64(!(chk.x == 0.0f && chk.y == 0.0f)) != 0ull) {
+                            for (int r = 0; r < 16; r += 4) {
+                                chk = lq_nonfinite_acc2((lq_v2f){acc[r], acc[r + 1]}, chk);
+                                chk1 = lq_nonfinite_acc2((lq_v2f){acc[r + 2], acc[r + 3]}, chk1);
+                            }
+                        } else {
+#pragma unroll
+                            for (int r = 0; r < 16; r += 2) chk = lq_nonfinite_acc2((lq_v2f){acc[r], acc[r + 1]}, chk);
+                        }
+                        if (__builtin_amdgcn_ballot_w64(!(chk.x == 0.0f && chk.y == 0.0f && chk1.x == 0.0f && chk1.y == 0.0f)) != 0ull) {
 #pragma unroll
                             for (int r = 0; r < 16; ++r) acc[r] = lq_sigmoid(acc[r]);
+                        } else if constexpr (LOCKSTEP) {
+                            tok_sigmoid_finite_tile(acc, 2 * t + 1 < S ? 16 : 2 * t < S ? 8 : 0);
                         } else {
 #pragma unroll
                             for (int r = 0; r < 16; r += 2) {
@@ -722,6 +779,9 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                         if constexpr (VQ) {
 #pragma unroll
                             for (int r = 0; r < 16; ++r) h0[t][r] = pre[r] > 0.0f ? pre[r] : 0.0f;
+                        } else if constexpr (LOCKSTEP) {
+                            tok_gelu_poly_tile(h0[t], pre);
+                            tok_gelu_fixup_lumped(h0[t], pre);
                         } else {
 #pragma unroll
                             for (int r = 0; r < 16; r += 2) {
@@ -757,7 +817,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                 // the interleaved stream loses another 9 % to issue arbitration between the two waves (5 843).  Same values either way:
                 // cfg2 0.4095 -> 0.3997 ms per launch, same box (profiles/r04_b_lumped_gelu_ab.txt).  Not where every output tile of
                 // layer 2 waits at a workgroup barrier for its streamed weights (S = 13: 0.934 -> 1.00 ms lumped) -- there the staging stays.
-                constexpr bool LUMPED = !VQ && !STREAM2;
+                // (LUMPED itself: defined with LOCKSTEP above finish_tile.)
                 constexpr int G1 = S1 / 4, G2 = S2 / 4;             // groups per tile
                 auto wread = [&](int gidx) {                        // group gidx of the stream (compile-time after unrolling)
                     if (STREAM2 && gidx >= T1 * G1) gidx = T1 * G1 - 1;             // streamed layer 2: its groups are read from the slab ring
@@ -799,7 +859,10 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                         __builtin_amdgcn_sched_barrier(0x6);
                     }
                     if constexpr (!VQ) { if (t > 0 && !LUMPED) tok_gelu_fixup(h1[t - 1], pend); }
-                    if constexpr (LUMPED) {
+                    if constexpr (LOCKSTEP) {
+                        tok_gelu_poly_tile(h1[t], acc);
+                        tok_gelu_fixup_lumped(h1[t], acc);
+                    } else if constexpr (LUMPED) {
 #pragma unroll
                         for (int r = 0; r < 16; r += 2) {
                             const lq_v2f g2 = lq_gelu_poly2((lq_v2f){acc[r], acc[r + 1]});

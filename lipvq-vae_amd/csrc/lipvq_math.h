@@ -202,6 +202,54 @@ __device__ __forceinline__ lq_v2f lq_gelu_poly2(lq_v2f x) {
     return lq_fma2(t * lq_bc2(0.35355339059327376220f), s, lq_bc2(0.5f) * x);
 }
 
+/* ---- several pairs in lockstep ---------------------------------------------------------------------------------
+ * A packed fp32 op that reads the result of the instruction directly in front of it costs a wait state (hipcc puts an
+ * `s_nop 0` between the two), and hipcc schedules the pairs of a tile as one Horner chain after the other: twelve wait
+ * states per pair.  The forms below take NP pairs and are written op by op ACROSS the pairs.  LQ_LOCKSTEP(i, stmt) is
+ * one step of every pair: stmt for the first half of the pairs, a fence, stmt for the second half, a fence.  The
+ * fence is sched_barrier(0): it emits no instruction, and no instruction is scheduled across it.  A step's ops of one
+ * half are independent of each other and read what the step before wrote for THAT half, i.e. two fences back --
+ * whatever order hipcc gives the ops between two fences, at least NP / 2 instructions stand between a result and its
+ * reader.  The arithmetic stays plain C (the hazard recognizer sees all of it; an empty asm statement as the fence
+ * costs a wait state on either side of it).  Per element: the operations of the one-pair forms in the same order. */
+#define LQ_LOCKSTEP(i, ...)                                                        \
+    do {                                                                           \
+        _Pragma("unroll") for (int i = 0; i < NP / 2; ++i) { __VA_ARGS__; }        \
+        __builtin_amdgcn_sched_barrier(0);                                         \
+        _Pragma("unroll") for (int i = NP / 2; i < NP; ++i) { __VA_ARGS__; }       \
+        __builtin_amdgcn_sched_barrier(0);                                         \
+    } while (0)
+/* one Horner step of every pair: s = s u + c */
+template <int NP>
+__device__ __forceinline__ void lq_horner2(lq_v2f (&s)[NP], const lq_v2f (&u)[NP], float c) {
+    LQ_LOCKSTEP(i, s[i] = lq_fma2(s[i], u[i], lq_bc2(c)));
+}
+
+/* lq_gelu_poly2 on NP pairs in lockstep, in place */
+template <int NP>
+__device__ __forceinline__ void lq_gelu_poly2xN(lq_v2f (&x)[NP]) {
+    lq_v2f t[NP], u[NP], s[NP], hx[NP];
+    LQ_LOCKSTEP(i, t[i] = x[i] * x[i]);
+    /* (0.5 x here, not in front of the last step: the squares read no fenced value, hipcc gathers them in front of the first
+     * fence in an order of its own, and the step behind them must not be the one that reads them) */
+    LQ_LOCKSTEP(i, hx[i] = lq_bc2(0.5f) * x[i]);
+    LQ_LOCKSTEP(i, u[i] = lq_fma2(t[i], lq_bc2(0.11111111111111111111f), lq_bc2(-1.0f)));
+    LQ_LOCKSTEP(i, s[i] = lq_fma2(lq_bc2(0.00012666420661844313f), u[i], lq_bc2(-0.00043783686123788357f)));
+    lq_horner2(s, u, 0.0008924771682359278f);
+    lq_horner2(s, u, -0.002175821689888835f);
+    lq_horner2(s, u, 0.005515238270163536f);
+    lq_horner2(s, u, -0.01217574905604124f);
+    lq_horner2(s, u, 0.02415713667869568f);
+    lq_horner2(s, u, -0.043842192739248276f);
+    lq_horner2(s, u, 0.07253222167491913f);
+    lq_horner2(s, u, -0.11009667813777924f);
+    lq_horner2(s, u, 0.15749694406986237f);
+    lq_horner2(s, u, -0.2287982553243637f);
+    lq_horner2(s, u, 0.4701318144798279f);
+    LQ_LOCKSTEP(i, t[i] = t[i] * lq_bc2(0.35355339059327376220f));
+    LQ_LOCKSTEP(i, x[i] = lq_fma2(t[i], s[i], hx[i]));
+}
+
 /* 1 / d for d in [1, 2^126): hipcc's IEEE division sequence (v_div_scale, v_rcp, four refinement fmas, v_div_fmas,
  * v_div_fixup) with the range handling removed -- for such d and numerator 1 the scaling is the identity and the fix-up
  * passes the value through, so what remains is v_rcp + six fmas, the same bits as 1.0f / d (probe_pk.hip: all 2^23
@@ -238,6 +286,40 @@ __device__ __forceinline__ lq_v2f lq_sigmoid2_finite(lq_v2f x) {
     const lq_v2f e = p * sc;
     return lq_rcp2_ge1(lq_bc2(1.0f) + e);
 }
+/* lq_sigmoid2_finite (with its lq_rcp2_ge1) on NP pairs in lockstep, in place */
+template <int NP>
+__device__ __forceinline__ void lq_sigmoid2_finite_xN(lq_v2f (&x)[NP]) {
+    const lq_v2f magic = lq_bc2(12582912.0f), one = lq_bc2(1.0f);
+    lq_v2f t[NP], nf[NP], sc[NP], n[NP], r[NP], q[NP], p[NP];
+    LQ_LOCKSTEP(i, t[i] = (lq_v2f){__builtin_amdgcn_fmed3f(-x[i].x, -87.0f, 87.0f), __builtin_amdgcn_fmed3f(-x[i].y, -87.0f, 87.0f)});
+    LQ_LOCKSTEP(i, nf[i] = lq_fma2(t[i], lq_bc2(1.44269504088896341f), magic));
+    LQ_LOCKSTEP(i, n[i] = nf[i] - magic);
+    LQ_LOCKSTEP(i, r[i] = lq_fma2(n[i], lq_bc2(-0.693145751953125f), t[i]));
+    LQ_LOCKSTEP(i, r[i] = lq_fma2(n[i], lq_bc2(-1.42860682030941723e-6f), r[i]));
+    LQ_LOCKSTEP(i, q[i] = lq_fma2(lq_bc2(0.00019907570094801486f), r[i], lq_bc2(0.0013933652080595493f)));
+    lq_horner2(q, r, 0.00833328627049923f);
+    lq_horner2(q, r, 0.04166646674275398f);
+    lq_horner2(q, r, 0.1666666716337204f);
+    lq_horner2(q, r, 0.5f);
+    LQ_LOCKSTEP(i, p[i] = r[i] * r[i]);
+    LQ_LOCKSTEP(i, p[i] = lq_fma2(p[i], q[i], r[i]));
+    LQ_LOCKSTEP(i, p[i] = p[i] + one);
+    /* (bits(nf) - 0x4B400000 + 127) << 23 = (bits(nf) << 23) + 0x3F800000, as in lq_sigmoid2_finite */
+    LQ_LOCKSTEP(i, sc[i] = (lq_v2f){lq_u2f((lq_f2u(nf[i].x) << 23) + 0x3F800000u), lq_u2f((lq_f2u(nf[i].y) << 23) + 0x3F800000u)});
+    LQ_LOCKSTEP(i, p[i] = p[i] * sc[i]);                       /* e */
+    LQ_LOCKSTEP(i, p[i] = one + p[i]);                         /* d = 1 + e, in [1, 2^126) */
+    /* lq_rcp2_ge1(d) */
+    LQ_LOCKSTEP(i, r[i] = (lq_v2f){__builtin_amdgcn_rcpf(p[i].x), __builtin_amdgcn_rcpf(p[i].y)});
+    _Pragma("unroll") for (int i = 0; i < NP; ++i) n[i] = -p[i];          /* nd: a source modifier of the fmas, no instruction */
+    LQ_LOCKSTEP(i, t[i] = lq_fma2(n[i], r[i], one));           /* e */
+    LQ_LOCKSTEP(i, r[i] = lq_fma2(t[i], r[i], r[i]));
+    LQ_LOCKSTEP(i, t[i] = lq_fma2(n[i], r[i], one));           /* err */
+    LQ_LOCKSTEP(i, q[i] = lq_fma2(t[i], r[i], r[i]));
+    LQ_LOCKSTEP(i, t[i] = lq_fma2(n[i], q[i], one));           /* err */
+    LQ_LOCKSTEP(i, x[i] = lq_fma2(t[i], r[i], q[i]));
+}
+#undef LQ_LOCKSTEP
+
 /* d/dx gelu(x) = Phi(x) + x phi(x), straight-line on x*x < 18 (device code: the backward chains evaluate it for every saved
  * pre-activation, 192 per row and stack): Phi through the SAME erf polynomial as lq_gelu_poly -- erf(x/sqrt 2) = (x/sqrt 2) s(x^2/9 - 1)
  * -- and exp(-x^2/2) through lq_expf's polynomial with ONE exact scaling (the argument stays in (-9, 0]: no clamps, no
