@@ -44,7 +44,7 @@ __device__ __forceinline__ float ah_smoothl1(float d) {
     return z < 1.0f ? (0.5f * d) * d : z - 0.5f;
 }
 __device__ __forceinline__ float ah_smoothl1_grad(float d) {
-    return fabsf(d) < 1.0f ? d : (d > 0.0f ? 1.0f : -1.0f);
+    return d <= -1.0f ? -1.0f : (d >= 1.0f ? 1.0f : d);             // (a NaN fails both tests and stays a NaN, as in torch)
 }
 
 // nn.CosineSimilarity over 3 components (fewer: padded with zeros, which add nothing), each norm clamped on its own:
@@ -56,7 +56,7 @@ __device__ __forceinline__ float ah_cos_sim(const float (&p)[3], const float (&t
 #pragma unroll
     for (int c = 0; c < 3; ++c) { pp += p[c] * p[c]; tt += t[c] * t[c]; }
     const float np = sqrtf(pp), nt = sqrtf(tt);
-    clamped = !(np > AH_COS_EPS);
+    clamped = np <= AH_COS_EPS;                                      // (false for a NaN norm: its sim, a NaN, reaches every d sim / d p_c)
     np_out = fmaxf(np, AH_COS_EPS);
     const float ntc = fmaxf(nt, AH_COS_EPS);
     float sim = 0.0f;

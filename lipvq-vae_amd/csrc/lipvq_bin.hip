@@ -177,7 +177,7 @@ __global__ __launch_bounds__(1024) void bin_hidden_kernel(const BinHiddenArgs a)
 __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ g, const float* __restrict__ pre,
                                                       float* __restrict__ out, int64_t n, int act) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        out[i] = g[i] * lq_act_grad(pre[i], act);
+        out[i] = lq_act_bwd(g[i], pre[i], act);
 }
 
 static int stream_grid(int64_t work_items, int per_block, int cap) {

@@ -224,7 +224,7 @@ __device__ __forceinline__ f32x4 wg5_act(f32x4 v, int act) {
         }
         return o;
     }
-    if (act == LIPVQ_ACT_RELU) return (f32x4){v.x > 0.f ? v.x : 0.f, v.y > 0.f ? v.y : 0.f, v.z > 0.f ? v.z : 0.f, v.w > 0.f ? v.w : 0.f};
+    if (act == LIPVQ_ACT_RELU) return (f32x4){v.x <= 0.f ? 0.f : v.x, v.y <= 0.f ? 0.f : v.y, v.z <= 0.f ? 0.f : v.z, v.w <= 0.f ? 0.f : v.w};
     if (act == LIPVQ_ACT_SIGMOID) return (f32x4){lq_sigmoid(v.x), lq_sigmoid(v.y), lq_sigmoid(v.z), lq_sigmoid(v.w)};
     return v;
 }

@@ -99,7 +99,7 @@ __host__ __device__ static inline float lq_act_apply(float v, int act) {
     switch (act) {
         case LIPVQ_ACT_GELU: return lq_gelu(v);
         case LIPVQ_ACT_SIGMOID: return lq_sigmoid(v);
-        case LIPVQ_ACT_RELU: return v > 0.0f ? v : 0.0f;
+        case LIPVQ_ACT_RELU: return v <= 0.0f ? 0.0f : v;            // torch.relu: a NaN stays a NaN
         default: return v;
     }
 }
@@ -113,8 +113,15 @@ __host__ __device__ static inline float lq_act_grad(float v, int act) {
         case LIPVQ_ACT_GELU: return lq_gelu_grad(v);
 #endif
         case LIPVQ_ACT_SIGMOID: { const float s = lq_sigmoid(v); return s * (1.0f - s); }
-        case LIPVQ_ACT_RELU: return v > 0.0f ? 1.0f : 0.0f;
+        case LIPVQ_ACT_RELU: return v <= 0.0f ? 0.0f : 1.0f;          // torch's threshold_backward: the gradient passes at a NaN
         default: return 1.0f;
     }
+}
+
+// g * d act(pre) / d pre, as torch's backward functions form it: ReLU SELECTS (threshold_backward: 0 where pre <= 0 whatever g is,
+// g itself -- a NaN or an infinity included -- elsewhere, also at a NaN pre); the others multiply, so a non-finite g stays non-finite
+__host__ __device__ static inline float lq_act_bwd(float g, float pre, int act) {
+    if (act == LIPVQ_ACT_RELU) return pre <= 0.0f ? 0.0f : g;
+    return g * lq_act_grad(pre, act);
 }
 #endif

@@ -63,7 +63,7 @@ struct ActStage<true> {
     __device__ __forceinline__ void stage0(float a, float b) { a_ = a; b_ = b; }
     __device__ __forceinline__ void stage1() {}
     __device__ __forceinline__ void stage2() {}
-    __device__ __forceinline__ void stage3(float& o0, float& o1) { o0 = a_ > 0.0f ? a_ : 0.0f; o1 = b_ > 0.0f ? b_ : 0.0f; }
+    __device__ __forceinline__ void stage3(float& o0, float& o1) { o0 = a_ <= 0.0f ? 0.0f : a_; o1 = b_ <= 0.0f ? 0.0f : b_; }
 };
 
 // the launch's LDS (FusedLds, lipvq_fused_lds.h), as the host asks for it
@@ -642,7 +642,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         if (2 * t + (r >> 3) >= S) { zt[t][r] = 0.0f; continue; }
-                        const float zv = acc[r] > 0.0f ? acc[r] : 0.0f;      // the canonical ReLU (lq_act_apply)
+                        const float zv = acc[r] <= 0.0f ? 0.0f : acc[r];     // the canonical ReLU (lq_act_apply): a NaN stays
                         acc[r] = zv;
                         const float v = zv - w_mu[32 * t + 2 * r + h_w];
                         zt[t][r] = v;
@@ -778,7 +778,7 @@ __device__ __forceinline__ void tokenize_body(const TokArgs& a) {
                         if constexpr (TRAIN) lq_tile_store16(a.pre0, 32 * T0, row, row < a.N, t, h, pre, 32 * T0, true);
                         if constexpr (VQ) {
 #pragma unroll
-                            for (int r = 0; r < 16; ++r) h0[t][r] = pre[r] > 0.0f ? pre[r] : 0.0f;
+                            for (int r = 0; r < 16; ++r) h0[t][r] = pre[r] <= 0.0f ? 0.0f : pre[r];
                         } else if constexpr (LOCKSTEP) {
                             tok_gelu_poly_tile(h0[t], pre);
                             tok_gelu_fixup_lumped(h0[t], pre);

@@ -42,15 +42,19 @@ struct GmmArgs {
     float min_std;
 };
 
+// torch.exp of the EXP mode's pre-activation: lq_expf clamps its result to 3.4e38 by design (lipvq_math.h); a pre-activation that
+// IS +inf -- a diverged run -- gives +inf here, as torch does, so that it shows in the scale, the log-probability and the gradient
+__device__ __forceinline__ float gmm_exp(float p) { return p == INFINITY ? INFINITY : lq_expf(p); }
+
 __device__ __forceinline__ float gmm_sigma(float p, int mode, float min_std) {
     if (mode == LIPVQ_GMM_LOW_NOISE) return GMM_LOW_NOISE_STD;
-    return (mode == LIPVQ_GMM_EXP ? lq_expf(p) : lq_softplus(p)) + min_std;
+    return (mode == LIPVQ_GMM_EXP ? gmm_exp(p) : lq_softplus(p)) + min_std;
 }
 
 // d sigma / d p at the pre-activation p
 __device__ __forceinline__ float gmm_dsigma(float p, int mode) {
     if (mode == LIPVQ_GMM_LOW_NOISE) return 0.0f;
-    if (mode == LIPVQ_GMM_EXP) return lq_expf(p);
+    if (mode == LIPVQ_GMM_EXP) return gmm_exp(p);
     return p > 20.0f ? 1.0f : lq_sigmoid(p);
 }
 
@@ -172,8 +176,10 @@ __global__ __launch_bounds__(256) void gmm_head_kernel(const GmmArgs a, int side
             }
             const float* ep = a.eps + (size_t)(row0 + row) * A;
             float* dst = a.sample + (size_t)(row0 + row) * A;
+            // a row whose mixture weights are not numbers (a NaN or +inf logit: se is a NaN) has no draw: every comparison above was
+            // false and `pick` is the last mode -- the sample is a NaN, not that mode's finite draw
             for (int aa = part; aa < A; aa += 8)
-                dst[aa] = tanhf(pr[pick * A + aa]) + gmm_sigma(pr[MA + pick * A + aa], a.scale_mode, a.min_std) * ep[aa];
+                dst[aa] = se == se ? tanhf(pr[pick * A + aa]) + gmm_sigma(pr[MA + pick * A + aa], a.scale_mode, a.min_std) * ep[aa] : se;
         }
     }
 }

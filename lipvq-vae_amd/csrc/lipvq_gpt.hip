@@ -137,7 +137,9 @@ __global__ __launch_bounds__(64) void gpt_attention_kernel(const float* __restri
     }
     if (i < L) {
         gpt_store_t<DH, DT>(out + (b * L + i) * (size_t)E + (size_t)h * DH, o, hf, 1.0f);
-        if (hf == 0) lse[bh * L + i] = m + lq_logf_ge1(l);         // (l >= 1: the row maximum contributes exp(0))
+        // (l >= 1: the row maximum contributes exp(0); a NaN l -- a score that is a NaN or +inf -- stays a NaN: lq_logf_ge1 works on
+        // the bits and would return a number)
+        if (hf == 0) lse[bh * L + i] = m + (l == l ? lq_logf_ge1(l) : l);
     }
 }
 
@@ -286,7 +288,7 @@ __global__ __launch_bounds__(64) void gpt_attention_bwd_q_kernel(const float* __
             const float p = ok ? lq_expf(sa[g] * scale - ls) : 0.0f;
             float dp = pa[g];
             if (keep) dp = keep[(bh * L + ic) * L + jc] ? dp * inv_keep : 0.0f;
-            sa[g] = p * (dp - dl);
+            sa[g] = ok ? p * (dp - dl) : 0.0f;                      // (a select: 0 * (a NaN dp or delta) would be a NaN)
         }
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
@@ -345,7 +347,9 @@ __global__ __launch_bounds__(64) void gpt_attention_bwd_kv_kernel(const float* _
             const float p = ok ? lq_expf(sa[g] * scale - lse[bh * L + ic]) : 0.0f;
             float kp = 1.0f;
             if (keep) kp = keep[(bh * L + ic) * L + jc] ? inv_keep : 0.0f;
-            sa[g] = p * (pa[g] * kp - delta[bh * L + ic]);
+            // a closed position is closed by a select: 0 * (the NaN delta of a query row that is not finite) would put that row into
+            // the gradient of every key behind it
+            sa[g] = ok ? p * (pa[g] * kp - delta[bh * L + ic]) : 0.0f;
             pa[g] = p * kp;
         }
 #pragma unroll

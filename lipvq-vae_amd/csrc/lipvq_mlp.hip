@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void mlp3_kernel(Mlp3Args a) {
             const int k = 2 * s + h;
             float bv = (k < a.K0) ? xr[k] : 0.0f;
             if (BWD) {
-                if (a.in_pre && k < a.K0) bv = bv * lq_act_grad(a.in_pre[(size_t)rowc * a.K0 + k], a.act_in);
+                if (a.in_pre && k < a.K0) bv = lq_act_bwd(bv, a.in_pre[(size_t)rowc * a.K0 + k], a.act_in);
                 if (a.out2 && valid && k < a.K0) a.out2[(size_t)row * a.K0 + k] = bv;
             }
 #pragma unroll
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256) void mlp3_kernel(Mlp3Args a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const size_t o = (size_t)rowc * a.J0 + 32 * t + 2 * r + h;
-                    acc0[t][r] = acc0[t][r] * lq_act_grad(a.mul0[o], a.act0);
+                    acc0[t][r] = lq_act_bwd(acc0[t][r], a.mul0[o], a.act0);
                     if (valid) a.out0[o] = acc0[t][r];
                 }
         }
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256) void mlp3_kernel(Mlp3Args a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const size_t o = (size_t)rowc * a.J1 + 32 * t + 2 * r + h;
-                    acc1[t][r] = acc1[t][r] * lq_act_grad(a.mul1[o], a.act1);
+                    acc1[t][r] = lq_act_bwd(acc1[t][r], a.mul1[o], a.act1);
                     if (valid) a.out1[o] = acc1[t][r];
                 }
             if (!a.y) continue;      // wave-uniform: the caller does not need d/d(input)
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(64 * MLPS_WAVES) void mlp3_wg_kernel(Mlp3Args a) {
             const float* src = a.gather_idx ? a.x + (size_t)a.gather_idx[rc] * a.K0 : a.x + (size_t)rc * a.K0;
             v = src[k];
             if (BWD) {
-                if (a.in_pre) v = v * lq_act_grad(a.in_pre[(size_t)rc * a.K0 + k], a.act_in);
+                if (a.in_pre) v = lq_act_bwd(v, a.in_pre[(size_t)rc * a.K0 + k], a.act_in);
                 if (a.out2 && ok) a.out2[(size_t)rw * a.K0 + k] = v;
             }
         }
@@ -393,7 +393,7 @@ __global__ __launch_bounds__(64 * MLPS_WAVES) void mlp3_wg_kernel(Mlp3Args a) {
         } else {
             const f32x16 m = lq_tile_load16(a.mul0, a.J0, rowc, t, h, a.J0, vec0m);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = acc[r] * lq_act_grad(m[r], a.act0);
+            for (int r = 0; r < 16; ++r) acc[r] = lq_act_bwd(acc[r], m[r], a.act0);
             lq_tile_store16(a.out0, a.J0, row, valid, t, h, acc, a.J0, vec0);
         }
 #pragma unroll
@@ -420,7 +420,7 @@ __global__ __launch_bounds__(64 * MLPS_WAVES) void mlp3_wg_kernel(Mlp3Args a) {
         } else {
             const f32x16 m = lq_tile_load16(a.mul1, a.J1, rowc, t, h, a.J1, vec1m);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = acc[r] * lq_act_grad(m[r], a.act1);
+            for (int r = 0; r < 16; ++r) acc[r] = lq_act_bwd(acc[r], m[r], a.act1);
             lq_tile_store16(a.out1, a.J1, row, valid, t, h, acc, a.J1, vec1);
         }
 #pragma unroll
@@ -518,7 +518,7 @@ __device__ __forceinline__ void mlpl_actgrad16(f32x16& g, f32x16 m, int act) {
         for (int r = 0; r < 16; ++r) { const float sg = lq_sigmoid(m[r]); g[r] = g[r] * (sg * (1.0f - sg)); }
     } else if (act == LIPVQ_ACT_RELU) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) g[r] = g[r] * (m[r] > 0.0f ? 1.0f : 0.0f);
+        for (int r = 0; r < 16; ++r) g[r] = m[r] <= 0.0f ? 0.0f : g[r];   // (lq_act_bwd)
     }
 }
 

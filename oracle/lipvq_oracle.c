@@ -49,7 +49,7 @@ static inline float act_apply(float v, int act) {
     switch (act) {
         case LQ_ACT_GELU: return lq_gelu(v);
         case LQ_ACT_SIGMOID: return lq_sigmoid(v);
-        case LQ_ACT_RELU: return v > 0.0f ? v : 0.0f;   /* torch relu: max(x,0); NaN not on this path */
+        case LQ_ACT_RELU: return v <= 0.0f ? 0.0f : v;   /* torch relu: a NaN stays a NaN */
         default: return v;
     }
 }
@@ -168,9 +168,16 @@ static inline double act_grad(float pre, int act) {
     switch (act) {
         case LQ_ACT_GELU: return (double)lq_gelu_grad(pre);
         case LQ_ACT_SIGMOID: { double s = (double)lq_sigmoid(pre); return s * (1.0 - s); }
-        case LQ_ACT_RELU: return pre > 0.0f ? 1.0 : 0.0;
+        case LQ_ACT_RELU: return pre <= 0.0f ? 0.0 : 1.0;
         default: return 1.0;
     }
+}
+
+/* g * act'(pre) as torch's backward forms it: ReLU selects (threshold_backward: 0 where pre <= 0 whatever g is, g elsewhere,
+ * also at a NaN pre), the others multiply */
+static inline double act_bwd(double g, float pre, int act) {
+    if (act == LQ_ACT_RELU) return pre <= 0.0f ? 0.0 : g;
+    return g * act_grad(pre, act);
 }
 
 /* Backward of lq_ref_mlp3.  gy = dL/dy [N][J2].  Outputs (all nullable): gW0..2, gb0..2 (same shapes
@@ -195,7 +202,7 @@ LQ_EXPORT void lq_ref_mlp3_bwd(const float* x, const float* W0, const float* W1,
         for (int j = 0; j < J0; ++j) h0[j] = (double)act_apply(pre0[(size_t)n * J0 + j], act0);
         for (int j = 0; j < J1; ++j) h1[j] = (double)act_apply(pre1[(size_t)n * J1 + j], act1);
         for (int j = 0; j < J2; ++j)
-            g2[j] = (double)gy[(size_t)n * J2 + j] * act_grad(pre2[(size_t)n * J2 + j], act2);
+            g2[j] = act_bwd((double)gy[(size_t)n * J2 + j], pre2[(size_t)n * J2 + j], act2);
         for (int k = 0; k < J1; ++k) g1[k] = 0.0;
         for (int j = 0; j < J2; ++j) {
             ab2[j] += g2[j];
@@ -204,7 +211,7 @@ LQ_EXPORT void lq_ref_mlp3_bwd(const float* x, const float* W0, const float* W1,
                 g1[k] += g2[j] * (double)W2[(size_t)j * J1 + k];
             }
         }
-        for (int k = 0; k < J1; ++k) g1[k] *= act_grad(pre1[(size_t)n * J1 + k], act1);
+        for (int k = 0; k < J1; ++k) g1[k] = act_bwd(g1[k], pre1[(size_t)n * J1 + k], act1);
         for (int k = 0; k < J0; ++k) g0[k] = 0.0;
         for (int j = 0; j < J1; ++j) {
             ab1[j] += g1[j];
@@ -213,7 +220,7 @@ LQ_EXPORT void lq_ref_mlp3_bwd(const float* x, const float* W0, const float* W1,
                 g0[k] += g1[j] * (double)W1[(size_t)j * J0 + k];
             }
         }
-        for (int k = 0; k < J0; ++k) g0[k] *= act_grad(pre0[(size_t)n * J0 + k], act0);
+        for (int k = 0; k < J0; ++k) g0[k] = act_bwd(g0[k], pre0[(size_t)n * J0 + k], act0);
         for (int j = 0; j < J0; ++j) {
             ab0[j] += g0[j];
             for (int k = 0; k < K0; ++k) aW0[(size_t)j * K0 + k] += g0[j] * (double)x[(size_t)n * K0 + k];

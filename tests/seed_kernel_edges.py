@@ -114,14 +114,14 @@ def act_sweep(dense=4001):
 
 
 def act_reference(oracle, x, act):
-    """act(x) as the canonical oracle evaluates it (math_probe for gelu / sigmoid; ReLU is `v > 0 ? v : 0`)."""
+    """act(x) as the canonical oracle evaluates it (math_probe for gelu / sigmoid; ReLU is `v <= 0 ? 0 : v`)."""
     x = np.ascontiguousarray(x, F32)
     if act == ACT_GELU:
         return oracle.math_probe(x, 2)
     if act == ACT_SIGMOID:
         return oracle.math_probe(x, 3)
     if act == ACT_RELU:
-        return np.where(x > 0, x, F32(0.0)).astype(F32)
+        return np.where(x <= 0, F32(0.0), x).astype(F32)
     return x.copy()
 
 

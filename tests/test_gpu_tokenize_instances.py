@@ -442,8 +442,10 @@ def test_rows_equal_to_the_centring_vector(lipvq_option, no_screen_monitor, vari
 @pytest.mark.parametrize("variant", ["vq", "llfq"])
 def test_nonfinite_rows(lipvq_option, no_screen_monitor, variant, K, screen):
     """NaN, +-inf, +-1e30 and +-1e37 rows and single elements beside ordinary rows of the same wave, and a wave of nothing else.
-    At most the planted rows leave the oracle comparison: those whose z_e, by the oracle, is not finite (the ReLU stack turns a NaN
-    into 0 and keeps 1e37 finite: its rows stay in; their distances overflow and no code wins: index 0 by `v < best`)."""
+    At most the planted rows leave the oracle comparison: those whose z_e, by the oracle, is not finite (the ReLU stack keeps a
+    NaN, as torch.relu does, and keeps 1e37 finite: the 1e37 rows stay in; their distances overflow and no code wins: index 0 by
+    `v < best`).  A VQ row with a NaN input has a NaN z_e in the torch restatement, in the oracle and (compared with == and NaN
+    == NaN in every launch below) in the fused instances, and gets the code of the "no finite distance" rule: 0."""
     D = 128
     lipvq_option("screen_mode", screen)
     p = C.params(variant, A, D, K)
@@ -457,7 +459,11 @@ def test_nonfinite_rows(lipvq_option, no_screen_monitor, variant, K, screen):
     model = _model(("plain", variant, A, D, K), variant, p, A, D, K)
     print(f"{variant} K={K} {screen}: {int((~fin).sum())} of {planted.size} planted rows have a non-finite z_e")
     if variant == "vq":
+        restated = C.O.torch_vq_forward({k: torch.from_numpy(np.array(v)) for k, v in p.items()}, torch.from_numpy(x))[2]["z_e"]
+        assert bool(restated[nan_rows].isnan().any(1).all()) and bool(np.isnan(ref["ze"][nan_rows]).any(axis=1).all())
         _vq_launches(model, p, x, ("nonfinite", variant, D, K), D, K, screen, fin=fin)
+        r = _fused(model, torch.from_numpy(x).cuda(), want_ze=True)
+        assert bool(r["ze"][nan_rows].isnan().any(1).all()) and bool((r["idx"][nan_rows] == 0).all())
     else:
         for shape in SHAPES:
             lipvq_option("tok_shape", shape)
