@@ -114,11 +114,7 @@ __global__ __launch_bounds__(64) void gpt_attention_kernel(const float* __restri
     }
     l += __shfl_xor(l, 32, 64);
     const float inv = 1.0f / l;
-    f32x16 o[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int g = 0; g < 16; ++g) o[dt][g] = 0.0f;
+    f32x16 o[DT] = {};
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
         if (kt < kt_end) {
@@ -205,11 +201,7 @@ __global__ __launch_bounds__(64) void gpt_attention_prefix_kernel(const float* _
     }
     l += __shfl_xor(l, 32, 64);
     const float inv = 1.0f / l;
-    f32x16 o[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int g = 0; g < 16; ++g) o[dt][g] = 0.0f;
+    f32x16 o[DT] = {};
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
         if (kt < kt_end) {
@@ -233,6 +225,8 @@ __global__ __launch_bounds__(64) void gpt_attention_prefix_kernel(const float* _
 // dS_ij = P_ij (dP_ij - delta_i);  dQ_i = scale sum_j dS_ij K_j;  dK_j = scale sum_i dS_ij Q_i;  dV_j = sum_i (keep_ij / keep_prob) P_ij dO_i.
 // gpt_attention_bwd_q: wave = (b, h, 32 queries), loops over key tiles -> dQ, delta.  gpt_attention_bwd_kv: wave = (b, h, 32 keys),
 // loops over query tiles -> dK, dV.  The same transposed-score layout as the forward: the lane owns the row the wave reduces INTO.
+// The two close a dropped position differently -- bwd_q by a select on keep, bwd_kv by the factor kp = 0 -- and so differ where
+// dO . V is not finite at a dropped position (LABNOTES, "GPT attention: dispatch and zeroing shared"): do not merge the two treatments.
 template <int DH>
 __global__ __launch_bounds__(64) void gpt_attention_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
                                                                  const float* __restrict__ go, const float* __restrict__ lse,
@@ -262,11 +256,7 @@ __global__ __launch_bounds__(64) void gpt_attention_bwd_q_kernel(const float* __
     dl += __shfl_xor(dl, 32, 64);
     const float ls = lse[bh * L + ic];
     if (hf == 0 && i < L) delta[bh * L + i] = dl;
-    f32x16 dq[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int g = 0; g < 16; ++g) dq[dt][g] = 0.0f;
+    f32x16 dq[DT] = {};
 #pragma unroll 1
     for (int kt = 0; kt < kt_end; ++kt) {
         const int jr = kt * 32 + gpt_perm(c), jrc = jr < L ? jr : L - 1;
@@ -323,9 +313,7 @@ __global__ __launch_bounds__(64) void gpt_attention_bwd_kv_kernel(const float* _
     gpt_load_half<DH>(base + (size_t)jc * 3 * E + 2 * E, hf, v);
     f32x16 dk[DT], dv[DT];
 #pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int g = 0; g < 16; ++g) { dk[dt][g] = 0.0f; dv[dt][g] = 0.0f; }
+    for (int dt = 0; dt < DT; ++dt) { dk[dt] = f32x16{}; dv[dt] = f32x16{}; }
 #pragma unroll 1
     for (int qt = causal ? kt : 0; qt < NT; ++qt) {
         const int ir = qt * 32 + gpt_perm(c), irc = ir < L ? ir : L - 1;
@@ -383,6 +371,14 @@ static int gpt_attention_args(const char* what, int64_t B, int L, int E, int H, 
     return 0;
 }
 
+// the instances: f(DH) for the head width, f(DH, NKT) for a forward over nkt = 1 .. 4 key tiles (what gpt_attention_args let through)
+template <typename F>
+static void gpt_for_width(int dh, F&& f) { lq_dispatch<16, 32, 64>(dh, f); }
+template <typename F>
+static void gpt_for_forward(int dh, int nkt, F&& f) {
+    gpt_for_width(dh, [&](auto d) { lq_dispatch<1, 2, 3, 4>(nkt, [&](auto n) { f(d, n); }); });
+}
+
 extern "C" int lipvq_gpt_attention_f32(const float* qkv, float* out, float* lse, const unsigned char* keep, float keep_prob,
                                        int64_t B, int L, int E, int H, int causal, void* stream) {
     bool empty = false;
@@ -390,15 +386,11 @@ extern "C" int lipvq_gpt_attention_f32(const float* qkv, float* out, float* lse,
     if (empty) return 0;
     if (!qkv || !out || !lse) return fail(LIPVQ_EINVAL, "gpt_attention: null pointer");
     if ((((uintptr_t)qkv | (uintptr_t)out) & 15) != 0) return fail(LIPVQ_EINVAL, "gpt_attention: qkv / out must be 16-byte aligned");
-    typedef void (*fn_t)(const float*, float*, float*, const unsigned char*, float, int, int, int, int);
-    const int dh = E / H, NT = (L + 31) / 32;
-    fn_t kfn = nullptr;
-#define LQ_GA(DH_) if (dh == DH_) kfn = NT == 1 ? (fn_t)gpt_attention_kernel<DH_, 1> : NT == 2 ? (fn_t)gpt_attention_kernel<DH_, 2> \
-                                      : NT == 3 ? (fn_t)gpt_attention_kernel<DH_, 3> : (fn_t)gpt_attention_kernel<DH_, 4>;
-    LQ_GA(16) LQ_GA(32) LQ_GA(64)
-#undef LQ_GA
-    hipLaunchKernelGGL(kfn, dim3((unsigned)(B * H * NT)), dim3(64), 0, (hipStream_t)stream, qkv, out, lse, keep,
-                       keep ? 1.0f / keep_prob : 1.0f, L, E, H, causal);
+    const int NT = (L + 31) / 32;
+    gpt_for_forward(E / H, NT, [&](auto d, auto n) {
+        hipLaunchKernelGGL((gpt_attention_kernel<d(), n()>), dim3((unsigned)(B * H * NT)), dim3(64), 0, (hipStream_t)stream, qkv, out, lse,
+                           keep, keep ? 1.0f / keep_prob : 1.0f, L, E, H, causal);
+    });
     return check_launch("gpt_attention");
 }
 
@@ -415,15 +407,12 @@ extern "C" int lipvq_gpt_attention_prefix_f32(const float* prefix_qkv, const flo
     if (!qkv || !out || (P > 0 && !prefix_qkv)) return fail(LIPVQ_EINVAL, "gpt_attention_prefix: null pointer");
     if ((((uintptr_t)prefix_qkv | (uintptr_t)qkv | (uintptr_t)out) & 15) != 0)
         return fail(LIPVQ_EINVAL, "gpt_attention_prefix: prefix_qkv / qkv / out must be 16-byte aligned");
-    typedef void (*fn_t)(const float*, const float*, float*, size_t, int, int, int, int, int);
-    const int dh = E / H, NQT = (Lq + 31) / 32, NKT = (P + Lq + 31) / 32;
-    fn_t kfn = nullptr;
-#define LQ_GA(DH_) if (dh == DH_) kfn = NKT == 1 ? (fn_t)gpt_attention_prefix_kernel<DH_, 1> : NKT == 2 ? (fn_t)gpt_attention_prefix_kernel<DH_, 2> \
-                                      : NKT == 3 ? (fn_t)gpt_attention_prefix_kernel<DH_, 3> : (fn_t)gpt_attention_prefix_kernel<DH_, 4>;
-    LQ_GA(16) LQ_GA(32) LQ_GA(64)
-#undef LQ_GA
+    const int NQT = (Lq + 31) / 32;
     const size_t pstride = Bp == 1 ? 0 : (size_t)P * 3 * E;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)(B * H * NQT)), dim3(64), 0, (hipStream_t)stream, prefix_qkv, qkv, out, pstride, P, Lq, E, H, NQT);
+    gpt_for_forward(E / H, (P + Lq + 31) / 32, [&](auto d, auto n) {
+        hipLaunchKernelGGL((gpt_attention_prefix_kernel<d(), n()>), dim3((unsigned)(B * H * NQT)), dim3(64), 0, (hipStream_t)stream,
+                           prefix_qkv, qkv, out, pstride, P, Lq, E, H, NQT);
+    });
     return check_launch("gpt_attention_prefix");
 }
 
@@ -436,13 +425,13 @@ extern "C" int lipvq_gpt_attention_bwd_f32(const float* qkv, const float* out, c
     if (!qkv || !out || !gout || !lse || !gqkv || !delta) return fail(LIPVQ_EINVAL, "gpt_attention_bwd: null pointer");
     if ((((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)gout | (uintptr_t)gqkv) & 15) != 0)
         return fail(LIPVQ_EINVAL, "gpt_attention_bwd: qkv / out / gout / gqkv must be 16-byte aligned");
-    const int dh = E / H, NT = (L + 31) / 32;
+    const int NT = (L + 31) / 32;
     const dim3 grid((unsigned)(B * H * NT));
     const float ik = keep ? 1.0f / keep_prob : 1.0f;
-    auto kq = dh == 16 ? gpt_attention_bwd_q_kernel<16> : (dh == 32 ? gpt_attention_bwd_q_kernel<32> : gpt_attention_bwd_q_kernel<64>);
-    auto kkv = dh == 16 ? gpt_attention_bwd_kv_kernel<16> : (dh == 32 ? gpt_attention_bwd_kv_kernel<32> : gpt_attention_bwd_kv_kernel<64>);
-    hipLaunchKernelGGL(kq, grid, dim3(64), 0, (hipStream_t)stream, qkv, out, gout, lse, gqkv, delta, keep, ik, L, E, H, causal, NT);
-    hipLaunchKernelGGL(kkv, grid, dim3(64), 0, (hipStream_t)stream, qkv, gout, lse, delta, gqkv, keep, ik, L, E, H, causal, NT);
+    gpt_for_width(E / H, [&](auto d) {
+        hipLaunchKernelGGL(gpt_attention_bwd_q_kernel<d()>, grid, dim3(64), 0, (hipStream_t)stream, qkv, out, gout, lse, gqkv, delta, keep, ik, L, E, H, causal, NT);
+        hipLaunchKernelGGL(gpt_attention_bwd_kv_kernel<d()>, grid, dim3(64), 0, (hipStream_t)stream, qkv, gout, lse, delta, gqkv, keep, ik, L, E, H, causal, NT);
+    });
     return check_launch("gpt_attention_bwd");
 }
 

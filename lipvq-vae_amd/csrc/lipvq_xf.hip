@@ -134,6 +134,10 @@ static int attention_args(const char* what, const unsigned char* keep, float kee
     return 0;
 }
 
+// the head width padded to 8, 16 or 32 columns (compile-time loops: the reference's 8 heads give 8 at D = 64, 26 at D = 208)
+template <typename F>
+static void xf_for_width(int dh, F&& f) { lq_dispatch<8, 16, 32>(dh <= 8 ? 8 : dh <= 16 ? 16 : 32, f); }
+
 template <int DH>
 __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse,
                                                         const unsigned char* __restrict__ keep, float inv_keep, int S, int D, int H) {
@@ -206,11 +210,10 @@ extern "C" int lipvq_attention_f32(const float* qkv, float* out, float* lse, con
                                    int64_t S, int D, int H, void* stream) {
     if (!qkv || !out || !lse) return fail(LIPVQ_EINVAL, "attention: null pointer");
     if (int rc = attention_args("attention", keep, keep_prob, S, D, H)) return rc;
-    // head width padded to 8, 16 or 32 columns (compile-time loops: the reference's 8 heads give 8 at D = 64, 26 at D = 208)
-    const int dh = D / H;
-    auto kfn = dh <= 8 ? attention_kernel<8> : (dh <= 16 ? attention_kernel<16> : attention_kernel<32>);
-    hipLaunchKernelGGL(kfn, dim3((unsigned)((S + XF_QB - 1) / XF_QB), H), dim3(256), 0, (hipStream_t)stream, qkv, out, lse,
-                       keep, keep ? 1.0f / keep_prob : 1.0f, (int)S, D, H);
+    xf_for_width(D / H, [&](auto w) {
+        hipLaunchKernelGGL(attention_kernel<w()>, dim3((unsigned)((S + XF_QB - 1) / XF_QB), H), dim3(256), 0, (hipStream_t)stream, qkv, out,
+                           lse, keep, keep ? 1.0f / keep_prob : 1.0f, (int)S, D, H);
+    });
     return check_launch("attention");
 }
 
@@ -350,10 +353,9 @@ extern "C" int lipvq_attention_bwd_f32(const float* qkv, const float* out, const
     if (int rc = attention_args("attention_bwd", keep, keep_prob, S, D, H)) return rc;
     const dim3 grid((unsigned)((S + XF_QB - 1) / XF_QB), H);
     const float ik = keep ? 1.0f / keep_prob : 1.0f;
-    const int dh = D / H;
-    auto kq = dh <= 8 ? attention_bwd_q_kernel<8> : (dh <= 16 ? attention_bwd_q_kernel<16> : attention_bwd_q_kernel<32>);
-    auto kkv = dh <= 8 ? attention_bwd_kv_kernel<8> : (dh <= 16 ? attention_bwd_kv_kernel<16> : attention_bwd_kv_kernel<32>);
-    hipLaunchKernelGGL(kq, grid, dim3(256), 0, (hipStream_t)stream, qkv, out, gout, lse, gqkv, delta, keep, ik, (int)S, D, H);
-    hipLaunchKernelGGL(kkv, grid, dim3(256), 0, (hipStream_t)stream, qkv, gout, lse, delta, gqkv, keep, ik, (int)S, D, H);
+    xf_for_width(D / H, [&](auto w) {
+        hipLaunchKernelGGL(attention_bwd_q_kernel<w()>, grid, dim3(256), 0, (hipStream_t)stream, qkv, out, gout, lse, gqkv, delta, keep, ik, (int)S, D, H);
+        hipLaunchKernelGGL(attention_bwd_kv_kernel<w()>, grid, dim3(256), 0, (hipStream_t)stream, qkv, gout, lse, delta, gqkv, keep, ik, (int)S, D, H);
+    });
     return check_launch("attention_bwd");
 }
