@@ -37,24 +37,26 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .nnfn import KernelFunction, first_order_only, wants_backward
 
 __all__ = ["ActionHead"]
 
 LOSS_KEYS = ("l2_loss", "l1_loss", "cos_loss", "action_loss")       # ICL._compute_losses' keys, in its order
 
 
-class _ActionsFn(torch.autograd.Function):
+class _ActionsFn(KernelFunction):
     """actions [B, T, A] over lipvq_action_head_f32 / lipvq_action_head_bwd_f32 (the gy mode)."""
 
     @staticmethod
     def forward(ctx, feats, W, b):
-        keep = any(ctx.needs_input_grad)
+        keep = wants_backward(ctx)
         out = ops.action_head(feats, W, b, want_pre=keep)
         if keep:
             ctx.save_for_backward(feats, out["pre"], W)
         return out["actions"].view(tuple(feats.shape[:-1]) + (W.shape[0],))
 
     @staticmethod
+    @first_order_only
     def backward(ctx, gy):
         feats, pre, W = ctx.saved_tensors
         gpre = ops.action_head_bwd(pre, gy=gy.reshape(pre.shape))
@@ -62,13 +64,13 @@ class _ActionsFn(torch.autograd.Function):
         return ops.head_linear_grads(need[0], need[1] or need[2], feats, gpre, (W,))
 
 
-class _LossesFn(torch.autograd.Function):
+class _LossesFn(KernelFunction):
     """losses [4] = (l2, l1, cos, action) over lipvq_action_head_f32 / lipvq_action_head_bwd_f32; the backward's upstream
     gradient [4] stays on the device."""
 
     @staticmethod
     def forward(ctx, feats, target, W, b, weights):
-        keep = any(ctx.needs_input_grad)
+        keep = wants_backward(ctx)
         out = ops.action_head(feats, W, b, target, weights, want_actions=False, want_pre=keep)
         if keep:
             ctx.weights = weights
@@ -76,6 +78,7 @@ class _LossesFn(torch.autograd.Function):
         return out["losses"]
 
     @staticmethod
+    @first_order_only
     def backward(ctx, g):
         feats, target, pre, W = ctx.saved_tensors
         gpre = ops.action_head_bwd(pre, target, g=g, weights=ctx.weights)

@@ -19,6 +19,7 @@ import torch
 
 from . import ops
 from .derived import stamp
+from .nnfn import first_order_only
 from .tokenizer import LLFQVAE_V4, VQVAE
 
 # (the triples are defined on the tokenizer classes; these names are kept for tests and measurement scripts)
@@ -35,7 +36,11 @@ def _check_versions(ctx, params):
 
 
 class _TokenizerFn(torch.autograd.Function):
-    """(z_latent, loss) = f(x, the module's parameters in module._params() order).  z_latent is non-differentiable (v5:74)."""
+    """(z_latent, loss) = f(x, the module's parameters in module._params() order).  z_latent is non-differentiable (v5:74).
+    x gets NO gradient: backward returns None for it even where x.requires_grad (the reference's autograd would return one, the
+    loss depends on x through the encoder and the reconstruction error; no caller here differentiates the tokenizer's input).
+    The parameter gradients are all formed together, whichever subset of the parameters requires one; need_grad -- any parameter
+    does -- picks the plan and what is saved.  First order only (nnfn.first_order_only)."""
 
     @staticmethod
     def forward(ctx, module, x, *params):
@@ -81,6 +86,7 @@ class _TokenizerFn(torch.autograd.Function):
         return latent, l3[2]
 
     @staticmethod
+    @first_order_only
     def backward(ctx, _g_latent, g_loss):
         m = ctx.module
         _check_versions(ctx, m._params())
@@ -110,6 +116,10 @@ class _Ctx:
 
 
 def tokenizer_forward(module, x):
+    """(z_latent, loss) of module(x).  Autograd is involved only where grad mode is on AND a parameter requires a gradient;
+    otherwise the no-autograd path runs (nothing saved).  x.requires_grad plays no part: with every parameter frozen the returned
+    loss does not require a gradient even if x does, and with a trainable parameter x still gets none (_TokenizerFn).  The three
+    paths and forward_backward return the same z_latent and loss bits."""
     params = module._params()
     if torch.is_grad_enabled() and any(p.requires_grad for p in params):
         return _TokenizerFn.apply(module, x, *params)

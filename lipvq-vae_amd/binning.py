@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .nnfn import KernelFunction, first_order_only, wants_backward
 from .ops import ACT_GELU
 from .tokenizer import _PackCache
 
@@ -30,13 +31,13 @@ def _code_table(embs, W1, ed):
     return torch.stack([ops.linear(e, W1[:, ed * i:ed * (i + 1)].contiguous()) for i, e in enumerate(embs)])
 
 
-class _BinFn(torch.autograd.Function):
+class _BinFn(KernelFunction):
     """out = gelu(L2(gelu(b1 + sum_i P[i][bins[i]]))) with gradients to the embeddings and both Linears."""
 
     @staticmethod
     def forward(ctx, bins, ed, W1, b1, W2, b2, *embs):
         P = _code_table(embs, W1, ed)
-        need = any(ctx.needs_input_grad)
+        need = wants_backward(ctx)
         if need:
             h, pre1 = ops.bin_hidden(bins, P, b1, save_pre=True)
             out, pre2 = ops.linear(h, W2, b2, act=ACT_GELU, save_pre=True)
@@ -47,6 +48,7 @@ class _BinFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @first_order_only
     def backward(ctx, gy):
         bins, W1, W2, pre1, pre2, *embs = ctx.saved_tensors
         ed = ctx.ed

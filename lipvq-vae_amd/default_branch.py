@@ -26,7 +26,7 @@ import torch.nn.functional as F
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .nnfn import AddLayerNormFn, GraphedEval, LinearFn
+from .nnfn import AddLayerNormFn, GraphedEval, LinearFn, first_order_only
 from .ops import ACT_GELU, ACT_NONE
 
 
@@ -40,6 +40,7 @@ class _SpectralFn(torch.autograd.Function):
         return Wsn
 
     @staticmethod
+    @first_order_only
     def backward(ctx, gWsn):
         Wsn, u, v, sigma = ctx.saved_tensors
         return ops.spectral_norm_bwd(gWsn.contiguous(), Wsn, u, v, sigma), None, None, None, None
@@ -54,6 +55,7 @@ class _AttentionFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @first_order_only
     def backward(ctx, gout):
         qkv, out, lse = ctx.saved_tensors
         return ops.attention_bwd(qkv, out, gout.contiguous(), lse, ctx.nhead, ctx.keep, ctx.keep_prob), None, None, None

@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .nnfn import LinearFn
+from .nnfn import KernelFunction, LinearFn, first_order_only, wants_backward
 from .ops import ACT_NONE
 from .tokenizer import _PackCache
 
@@ -42,7 +42,7 @@ def sinusoidal_table(T: int, E: int, device) -> torch.Tensor:
     return pe
 
 
-class _EmbedStreamsFn(torch.autograd.Function):
+class _EmbedStreamsFn(KernelFunction):
     """LayerNorm(src_s[idx_s | n] + pos[t]) for every stream s, each written into its slots of ONE output tensor.
 
     slots: tuple of (t_stride, offset) in floats per stream; the batch stride is the whole [S, E] block."""
@@ -51,7 +51,7 @@ class _EmbedStreamsFn(torch.autograd.Function):
     def forward(ctx, pos, ln_w, ln_b, eps, B, T, S, slots, idxs, *srcs):
         E = ln_w.numel()
         out = torch.empty((B, S, E), device=ln_w.device, dtype=torch.float32)
-        need = any(ctx.needs_input_grad)
+        need = wants_backward(ctx)
         stats = []
         for (tstride, offset), idx, src in zip(slots, idxs, srcs):
             stats.append(ops.embed_rows(src, idx, pos, ln_w, ln_b, eps, out, B * T, T, S * E, tstride, offset,
@@ -61,6 +61,7 @@ class _EmbedStreamsFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @first_order_only
     def backward(ctx, gout):
         B, T, S, slots, idxs = ctx.meta
         n = len(slots)

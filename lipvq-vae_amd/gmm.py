@@ -32,6 +32,7 @@ import torch.distributions as D
 import torch.nn as nn
 
 from . import ops
+from .nnfn import KernelFunction, first_order_only, wants_backward
 from .ops import GMM_EXP, GMM_LOW_NOISE, GMM_SOFTPLUS
 
 __all__ = ["GMMActionHead"]
@@ -45,13 +46,13 @@ def _linear_grads(need_x, need_params, feats, gpre, Wm, Ws, Wl, MA):
     return gx, gW[:MA], gb[:MA], gW[MA:2 * MA], gb[MA:2 * MA], gW[2 * MA:], gb[2 * MA:]
 
 
-class _LogProbFn(torch.autograd.Function):
+class _LogProbFn(KernelFunction):
     """(log_prob [B, T], sum of log_prob or None) over lipvq_gmm_head_f32 / lipvq_gmm_head_bwd_f32."""
 
     @staticmethod
     def forward(ctx, feats, actions, Wm, bm, Ws, bs, Wl, bl, M, A, mode, min_std, want_sum):
         ctx.set_materialize_grads(False)
-        keep = any(ctx.needs_input_grad)
+        keep = wants_backward(ctx)
         out = ops.gmm_head(feats, (Wm, bm, Ws, bs, Wl, bl), M, A, actions, mode, min_std, want_pre=keep, want_sum=want_sum)
         if keep:
             ctx.cfg = (M, A, mode, min_std)
@@ -60,6 +61,7 @@ class _LogProbFn(torch.autograd.Function):
         return lp, out.get("sum")
 
     @staticmethod
+    @first_order_only
     def backward(ctx, glp, gsum):
         feats, actions, pre, Wm, Ws, Wl = ctx.saved_tensors
         M, A, mode, min_std = ctx.cfg
@@ -71,13 +73,13 @@ class _LogProbFn(torch.autograd.Function):
         return (g[0], None) + g[1:] + (None,) * 5
 
 
-class _ParamsFn(torch.autograd.Function):
+class _ParamsFn(KernelFunction):
     """(mean [B, T, M, A], scale [B, T, M, A], logits [B, T, M]) over lipvq_gmm_head_f32 / lipvq_gmm_params_bwd_f32."""
 
     @staticmethod
     def forward(ctx, feats, Wm, bm, Ws, bs, Wl, bl, M, A, mode, min_std):
         ctx.set_materialize_grads(False)
-        keep = any(ctx.needs_input_grad)
+        keep = wants_backward(ctx)
         out = ops.gmm_head(feats, (Wm, bm, Ws, bs, Wl, bl), M, A, None, mode, min_std, want_pre=keep, want_params=True)
         if keep:
             ctx.cfg = (M, A, mode)
@@ -86,6 +88,7 @@ class _ParamsFn(torch.autograd.Function):
         return out["mean"].view(lead + (M, A)), out["scale"].view(lead + (M, A)), out["logits"].view(lead + (M,))
 
     @staticmethod
+    @first_order_only
     def backward(ctx, gmean, gscale, glogits):
         feats, pre, Wm, Ws, Wl = ctx.saved_tensors
         M, A, mode = ctx.cfg

@@ -47,7 +47,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .derived import stamp
-from .nnfn import AddLayerNormFn, GraphedEval, LinearFn
+from .nnfn import AddLayerNormFn, GraphedEval, LinearFn, first_order_only
 from .ops import ACT_GELU, ACT_NONE
 
 __all__ = ["GPTBackbone", "GraphedGPTBackbone", "PromptCache", "PromptedGPTBackbone", "StalePromptCache"]
@@ -66,6 +66,7 @@ class _AttentionFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @first_order_only
     def backward(ctx, gout):
         qkv, out, lse = ctx.saved_tensors
         return (ops.gpt_attention_bwd(qkv, out, gout.contiguous(), lse, ctx.nhead, ctx.causal, ctx.keep, ctx.keep_prob),

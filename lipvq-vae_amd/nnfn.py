@@ -2,16 +2,72 @@
 ``torch.autograd.Function``s over the library's kernels, and the eval-forward HIP-graph wrapper."""
 from __future__ import annotations
 
+import functools
+import threading
+
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import ops
 from .capture import capture, copy_in, warm_up
 from .ops import ACT_NONE
 
-__all__ = ["LinearFn", "AddLayerNormFn", "GraphedEval"]
+__all__ = ["LinearFn", "AddLayerNormFn", "GraphedEval", "KernelFunction", "first_order_only", "wants_backward"]
+
+_applying = threading.local()
 
 
-class LinearFn(torch.autograd.Function):
+class KernelFunction(torch.autograd.Function):
+    """Base of the library's Functions.  ``forward`` always runs with grad mode off and ``ctx.needs_input_grad`` repeats the inputs'
+    ``requires_grad`` whatever the caller's grad mode was, so a forward cannot tell a ``torch.no_grad()`` call of a trainable
+    module from a training call: ``apply`` notes the caller's grad mode for ``wants_backward``."""
+
+    @classmethod
+    def apply(cls, *args):
+        prev = getattr(_applying, "grad_mode", True)
+        _applying.grad_mode = torch.is_grad_enabled()
+        try:
+            return super().apply(*args)
+        finally:
+            _applying.grad_mode = prev
+
+
+def wants_backward(ctx) -> bool:
+    """In ``forward``: will a backward of this call ever run?  No under ``torch.no_grad()`` and no when no input requires a
+    gradient: then nothing is written or kept for it (no pre-activations, LayerNorm statistics, saved tensors)."""
+    return getattr(_applying, "grad_mode", True) and any(ctx.needs_input_grad)
+
+
+def first_order_only(backward):
+    """The decorator of every ``backward`` of the library: ``torch.autograd.function.once_differentiable``, closed where that one
+    is open.  The backward kernels return tensors without a graph, so a gradient of a gradient does not exist.  torch's decorator
+    makes a second differentiation raise only when an upstream gradient itself requires a gradient; under ``create_graph=True``
+    with a constant upstream gradient (``out.sum()``, any scalar loss) it hands the graph-less tensors on, and a loss that adds a
+    function of such a gradient to an ordinary term would train on the ordinary term alone, silently.  Here every gradient that
+    leaves a backward run under ``create_graph=True`` hangs on an error node: differentiating through it raises ``RuntimeError``.
+    A first-order backward (grad mode off inside the engine) returns what the wrapped function returned, untouched."""
+    inner = once_differentiable(backward)
+
+    @functools.wraps(backward)
+    def wrapper(ctx, *grads):
+        outputs = inner(ctx, *grads)
+        if not torch.is_grad_enabled():
+            return outputs
+        outs = outputs if isinstance(outputs, tuple) else (outputs,)
+        tensors = [o for o in outs if isinstance(o, torch.Tensor)]
+        if not tensors or any(o.requires_grad for o in tensors):      # nothing to guard, or once_differentiable's error node is there already
+            return outputs
+        err = torch._C._functions.DelayedError(
+            b"lipvq: this function's backward runs graph-less HIP kernels and is differentiable once only "
+            b"(first_order_only): a gradient computed under create_graph=True cannot be differentiated again", len(outs))
+        guarded = err(*[None if o is None else o.detach().requires_grad_(True) for o in outs])
+        return guarded if isinstance(outputs, tuple) else guarded[0]
+
+    wrapper.first_order_only = True
+    return wrapper
+
+
+class LinearFn(KernelFunction):
     """act(x W^T + b) over the last dimension, b optional; backward = act' (elementwise), one more Linear (gx), the wgrad kernel.
     precision="bf16": the three matrix products run on the bf16 matrix pipe (ops.linear_bf16 / linear_nn_bf16 / wgrad_bf16:
     operands rounded to bf16 as they are read, fp32 accumulation, fp32 tensors); precision="bf16x3": the same pipe with every
@@ -25,7 +81,9 @@ class LinearFn(torch.autograd.Function):
         ctx.act, ctx.has_bias, ctx.shape, ctx.pipe = act, b is not None, x.shape, ("" if precision == "fp32" else "_" + precision)
         linear = getattr(ops, "linear" + ctx.pipe)
         x2 = x if x.dim() == 2 else x.reshape(-1, x.shape[-1])      # (2-D callers: no view objects on their host-bound paths)
-        if act != ACT_NONE:
+        if not wants_backward(ctx):                            # eval / no_grad: no pre-activation is written, nothing is kept
+            y = linear(x2, W, b, act=act)
+        elif act != ACT_NONE:
             y, pre = linear(x2, W, b, act=act, save_pre=True)
             ctx.save_for_backward(x2, W, pre)
         else:
@@ -34,6 +92,7 @@ class LinearFn(torch.autograd.Function):
         return y if x.dim() == 2 else y.view(*x.shape[:-1], W.shape[0])
 
     @staticmethod
+    @first_order_only
     def backward(ctx, gy):
         gy = gy.reshape(-1, gy.shape[-1]).contiguous()
         if ctx.act != ACT_NONE:
@@ -49,7 +108,7 @@ class LinearFn(torch.autograd.Function):
         return gx, gW, gb, None, None
 
 
-class AddLayerNormFn(torch.autograd.Function):
+class AddLayerNormFn(KernelFunction):
     """(s, y) = (a + b, LayerNorm(a + b) w + bias), b optional; s is None unless want_s (a post-norm residual and the closing
     LayerNorm of a pre-norm stack discard it, and without b the caller keeps using a).  Backward: the gradient of a and of b is
     LayerNorm's plus the gradient that arrives for s (the residual stream), added inside the kernel."""
@@ -58,13 +117,14 @@ class AddLayerNormFn(torch.autograd.Function):
     def forward(ctx, a, b, w, bias, eps, want_s):
         ctx.set_materialize_grads(False)
         ctx.has_b = b is not None
-        if not any(ctx.needs_input_grad):                      # eval / no_grad: nothing is kept for a backward
+        if not wants_backward(ctx):                            # eval / no_grad: nothing is kept for a backward
             return ops.gpt_layernorm(a, b, w, bias, eps, want_s=want_s)
         s, y, xhat, rstd = ops.gpt_layernorm(a, b, w, bias, eps, want_s=want_s, save=True)
         ctx.save_for_backward(xhat, rstd, w)
         return s, y
 
     @staticmethod
+    @first_order_only
     def backward(ctx, gs, gy):
         if gy is None:
             return gs, (gs if ctx.has_b else None), None, None, None, None
