@@ -494,6 +494,51 @@ size_t lipvq_gpt_layernorm_bwd_workspace_bytes(int64_t N, int E);
 int lipvq_gpt_layernorm_bwd_f32(const float* gy, const float* xhat, const float* rstd, const float* w, const float* gres,
                                 float* gs, float* gw, float* gb, void* workspace, int64_t N, int E, void* stream);
 
+/* ---- in-kernel dropout for the backbone (GPTBackbone.set_dropout_source("kernel")): the three dropout sites of a block
+ *      (tf:195 attn_dropout, tf:205 and tf:289 the two block-output dropouts) decided INSIDE the kernels that touch those elements.
+ *      No mask tensor exists: every decision is a pure function of (seed, step, site, row, col), and the backward regenerates it.
+ *      lipvq-vae_amd/csrc/lipvq_rng.h (generator and mapping, one header for device and host), lipvq-vae_amd/csrc/lipvq_gpt.hip.
+ *
+ *      The mapping (the contract).  A site is a 2-D field of decisions.  With Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57,
+ *      Weyl constants 0x9E3779B9 / 0xBB67AE85, 10 rounds; the Random123 known answers hold), the decision for element (row, col) is
+ *          word  col & 3  of  philox(counter = (col >> 2, row, site, step & 0xffffffff), key = (seed & 0xffffffff, seed >> 32)).
+ *      The element is KEPT iff word >= thr, thr = (uint32) floor(p * 2^32) formed in double, for 0 < p < 1; a kept element is
+ *      multiplied by inv_keep = 1.0f / (float)(1.0 - p) -- the factor the keep-byte entry points form from keep_prob = 1 - p, so
+ *      the two paths agree in bits for the same decisions.  rows >= 2^32: LIPVQ_EUNSUPPORTED.  p outside (0, 1): LIPVQ_EINVAL
+ *      (no dropout is the caller's choice of the plain entry point).  Only the low 32 bits of `step` enter the counter: a
+ *      (seed, site) pair's fields repeat after 2^32 steps.
+ *      Fields.  Attention probabilities: row = (b H + h) L + i, col = j (the layout of the keep bytes [B][H][L][L]).  A branch of
+ *      the residual stream: row = the row of [N][E], col = e.  GPTBackbone uses site 4 layer + 0 for a block's attention
+ *      probabilities, 4 layer + 1 for its attention-output branch and 4 layer + 2 for its MLP branch.
+ *
+ *      State.  `state` is a device int64[2] = (seed, step).  lipvq_dropout_begin (one thread) copies it to `snap` (another device
+ *      int64[2]) and stores step + 1 back.  Every dropout kernel of one forward call and of its backward reads that snap: a
+ *      captured graph advances on every replay without the host, and a backward sees its own forward's step however many forwards
+ *      ran in between. ---- */
+int lipvq_dropout_begin(int64_t* state, int64_t* snap, void* stream);
+/* The decisions of one site as bytes, out [rows][cols] = 1 kept / 0 dropped: what the kernels below decide, for tests and for
+ * users who want to see a mask.  _u8 runs on the device from a snap; _host is the same header code on the host from (seed, step)
+ * and makes no GPU call.  rows == 0 or cols == 0: no-op.  cols <= 2^32. */
+int lipvq_dropout_keep_u8(const int64_t* snap, uint32_t site, int64_t rows, int64_t cols, double p, unsigned char* out, void* stream);
+int lipvq_dropout_keep_host(uint64_t seed, uint64_t step, uint32_t site, int64_t rows, int64_t cols, double p, unsigned char* out);
+/* lipvq_gpt_attention_f32 / _bwd_f32 with the attention-probability decisions of `site` drawn in the kernel (B H L < 2^32 rows):
+ * the bits of the keep-byte form given the bytes of lipvq_dropout_keep_u8(snap, site, B H L, L, p) and keep_prob = (float)(1 - p).
+ * A query row all of whose keys are dropped has a zero output row and its lse unchanged. */
+int lipvq_gpt_attention_drop_f32(const float* qkv, float* out, float* lse, const int64_t* snap, uint32_t site, double p, int64_t B,
+                                 int L, int E, int H, int causal, void* stream);
+int lipvq_gpt_attention_bwd_drop_f32(const float* qkv, const float* out, const float* gout, const float* lse, float* gqkv,
+                                     float* delta, const int64_t* snap, uint32_t site, double p, int64_t B, int L, int E, int H,
+                                     int causal, void* stream);
+/* lipvq_gpt_layernorm_f32 with the branch's dropout inside: s = a + b * m, m = inv_keep where (row, e) of `site` is kept and 0
+ * where it is dropped (the product torch's dropout forms), y = LayerNorm(s) * w + bias.  b is required. */
+int lipvq_gpt_layernorm_drop_f32(const float* a, const float* b, const float* w, const float* bias, float eps, const int64_t* snap,
+                                 uint32_t site, double p, float* s, float* y, float* xhat, float* rstd, int64_t N, int E, void* stream);
+/* Its backward.  With dropout on b the gradients of a and b differ: gs [N][E] is lipvq_gpt_layernorm_bwd_f32's (the gradient of
+ * a), gbranch [N][E] = gs * m (the gradient of b) is written by the same launch from the regenerated decisions. */
+int lipvq_gpt_layernorm_bwd_drop_f32(const float* gy, const float* xhat, const float* rstd, const float* w, const float* gres,
+                                     const int64_t* snap, uint32_t site, double p, float* gs, float* gbranch, float* gw, float* gb,
+                                     void* workspace, int64_t N, int E, void* stream);
+
 /* ---- the backbone's opt-in bf16 matrix-pipe mode (GPTBackbone.set_matmul_precision("bf16")): the three products of one
  *      nn.Linear on the bf16 MFMAs.  lipvq-vae_amd/csrc/lipvq_gemm_bf16.hip.
  *      Rounding rule: every tensor is fp32 in memory, as for the _f32 entry points; each element of the two MATRIX operands of

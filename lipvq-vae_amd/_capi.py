@@ -116,6 +116,13 @@ SIGNATURES = {
     "lipvq_gpt_layernorm_f32": (_i, [_vp] * 4 + [C.c_float] + [_vp] * 4 + [_i64, _i, _vp]),
     "lipvq_gpt_layernorm_bwd_workspace_bytes": (_sz, [_i64, _i]),
     "lipvq_gpt_layernorm_bwd_f32": (_i, [_vp] * 9 + [_i64, _i, _vp]),
+    "lipvq_dropout_begin": (_i, [_vp, _vp, _vp]),
+    "lipvq_dropout_keep_u8": (_i, [_vp, C.c_uint32, _i64, _i64, C.c_double, _vp, _vp]),
+    "lipvq_dropout_keep_host": (_i, [C.c_uint64, C.c_uint64, C.c_uint32, _i64, _i64, C.c_double, _vp]),
+    "lipvq_gpt_attention_drop_f32": (_i, [_vp] * 4 + [C.c_uint32, C.c_double, _i64, _i, _i, _i, _i, _vp]),
+    "lipvq_gpt_attention_bwd_drop_f32": (_i, [_vp] * 7 + [C.c_uint32, C.c_double, _i64, _i, _i, _i, _i, _vp]),
+    "lipvq_gpt_layernorm_drop_f32": (_i, [_vp] * 4 + [C.c_float, _vp, C.c_uint32, C.c_double] + [_vp] * 4 + [_i64, _i, _vp]),
+    "lipvq_gpt_layernorm_bwd_drop_f32": (_i, [_vp] * 6 + [C.c_uint32, C.c_double] + [_vp] * 5 + [_i64, _i, _vp]),
     "lipvq_gmm_workspace_bytes": (_sz, [_i64]),
     "lipvq_gmm_head_f32": (_i, [_vp, _i64] + [_vp] * 14 + [_i64] + [_i] * 5 + [C.c_float, _vp]),
     "lipvq_gmm_head_bwd_f32": (_i, [_vp] * 5 + [_i64, _i, _i, _i, C.c_float, _vp]),

@@ -1,0 +1,81 @@
+/* lipvq_rng.h -- the counter-based generator behind the backbone's in-kernel dropout.
+ *
+ * ONE definition of Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11; the
+ * Random123 known answers hold: tests/test_dropout_host.py) and of the mapping from a dropout SITE to its draws, shared
+ * verbatim by the gfx950 device code (hipcc) and by the host (plain g++ / gcc), the way lipvq_math.h is.  Integer arithmetic
+ * only: both sides agree in every bit.
+ *
+ * The contract (include/lipvq.h, "in-kernel dropout", repeats it).  A site is a 2-D field of decisions; the decision for
+ * element (row, col) is word  col & 3  of
+ *     philox4x32_10(counter = (col >> 2, row, site, step & 0xffffffff), key = (seed & 0xffffffff, seed >> 32))
+ * and the element is KEPT iff  word >= thr,  thr = (uint32) floor(p * 2^32) formed in double (0 < p < 1).  One draw decides
+ * four neighbouring columns.  rows < 2^32.  Only the low 32 bits of the step enter: the field repeats after 2^32 steps.
+ */
+#ifndef LIPVQ_RNG_H_
+#define LIPVQ_RNG_H_
+
+#include "lipvq_math.h"
+
+#define LQ_PHILOX_M0 0xD2511F53u
+#define LQ_PHILOX_M1 0xCD9E8D57u
+#define LQ_PHILOX_W0 0x9E3779B9u
+#define LQ_PHILOX_W1 0xBB67AE85u
+
+typedef struct { uint32_t w[4]; } lq_philox4;
+
+LQ_HD uint32_t lq_mulhi32(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * (uint64_t)b) >> 32); }
+
+LQ_HD lq_philox4 lq_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = lq_mulhi32(LQ_PHILOX_M0, c0), lo0 = LQ_PHILOX_M0 * c0;
+        const uint32_t hi1 = lq_mulhi32(LQ_PHILOX_M1, c2), lo1 = LQ_PHILOX_M1 * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += LQ_PHILOX_W0;                 /* (the bump after the last round is unused) */
+        k1 += LQ_PHILOX_W1;
+    }
+    lq_philox4 out;
+    out.w[0] = c0; out.w[1] = c1; out.w[2] = c2; out.w[3] = c3;
+    return out;
+}
+
+/* what every dropout kernel of one forward call and of its backward is handed: the (seed, step) pair lipvq_dropout_begin
+ * wrote, the site, the threshold and the factor of a kept element */
+typedef struct {
+    uint32_t k0, k1, step, site, thr;
+    float inv_keep;
+} lq_dropout;
+
+/* thr and inv_keep of a drop probability 0 < p < 1: inv_keep is what the keep-byte path forms from keep_prob = (float)(1 - p) */
+LQ_HD uint32_t lq_dropout_thr(double p) { return (uint32_t)(p * 4294967296.0); }
+LQ_HD float lq_dropout_inv_keep(double p) { return 1.0f / (float)(1.0 - p); }
+
+LQ_HD lq_dropout lq_dropout_make(uint64_t seed, uint64_t step, uint32_t site, double p) {
+    lq_dropout d;
+    d.k0 = (uint32_t)(seed & 0xffffffffu);
+    d.k1 = (uint32_t)(seed >> 32);
+    d.step = (uint32_t)(step & 0xffffffffu);
+    d.site = site;
+    d.thr = lq_dropout_thr(p);
+    d.inv_keep = lq_dropout_inv_keep(p);
+    return d;
+}
+
+/* the draw that decides columns 4 col4 .. 4 col4 + 3 of `row` */
+LQ_HD lq_philox4 lq_dropout_draw(lq_dropout d, uint32_t row, uint32_t col4) {
+    return lq_philox4x32_10(col4, row, d.site, d.step, d.k0, d.k1);
+}
+
+/* bit w = the decision of column 4 col4 + w (1: kept) */
+LQ_HD uint32_t lq_dropout_keep4(lq_dropout d, uint32_t row, uint32_t col4) {
+    const lq_philox4 r = lq_dropout_draw(d, row, col4);
+    return (uint32_t)(r.w[0] >= d.thr) | ((uint32_t)(r.w[1] >= d.thr) << 1) | ((uint32_t)(r.w[2] >= d.thr) << 2) |
+           ((uint32_t)(r.w[3] >= d.thr) << 3);
+}
+
+#endif

@@ -36,6 +36,15 @@ applied inside the attention kernel; the two block-output dropouts (transformers
 (``F.dropout`` on the branch before the fused residual launch) -- they are elementwise over ``[B L, E]`` and vanish in eval.
 Training-mode outputs match the reference in distribution, not in bits (torch draws the attention mask inside its own
 dropout kernel).  ``activation="geglu"`` is not implemented (the ICRT configuration uses ``gelu``).
+
+Dropout, the opt-in in-kernel source (``set_dropout_source("kernel")``): the same three sites are decided INSIDE the kernels
+that touch those elements -- the attention probabilities in lipvq_gpt_attention_drop_f32 / _bwd_drop_f32, a branch in the
+residual launch that adds it, lipvq_gpt_layernorm_drop_f32 / _bwd_drop_f32 (the attention-output branch on ln2, the MLP branch
+on the next block's ln1 or the closing output_ln).  Every decision is a pure function of (seed, step, site = 4 layer + 0 / 1 / 2,
+row, col) through Philox4x32-10 (csrc/lipvq_rng.h; the contract is in include/lipvq.h): no mask tensor exists, nothing of it is
+saved, the backward regenerates it, and torch's generators are not touched.  One one-thread launch per training forward
+(lipvq_dropout_begin) hands the call its (seed, step) and advances the step on the device, so a captured graph advances on every
+replay.  The launch count of a training forward is the eval forward's plus that one.  Eval mode ignores the source.
 """
 from __future__ import annotations
 
@@ -47,7 +56,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .derived import stamp
-from .nnfn import AddLayerNormFn, GraphedEval, LinearFn, first_order_only
+from .nnfn import AddDropLayerNormFn, AddLayerNormFn, GraphedEval, KernelFunction, LinearFn, first_order_only, wants_backward
 from .ops import ACT_GELU, ACT_NONE
 
 __all__ = ["GPTBackbone", "GraphedGPTBackbone", "PromptCache", "PromptedGPTBackbone", "StalePromptCache"]
@@ -71,6 +80,26 @@ class _AttentionFn(torch.autograd.Function):
         qkv, out, lse = ctx.saved_tensors
         return (ops.gpt_attention_bwd(qkv, out, gout.contiguous(), lse, ctx.nhead, ctx.causal, ctx.keep, ctx.keep_prob),
                 None, None, None, None)
+
+
+class _AttentionDropFn(KernelFunction):
+    """_AttentionFn with the attention-probability dropout drawn inside the kernels (in-kernel source: snap, site, p).  No mask
+    is saved: the two backward launches regenerate the decisions from snap."""
+
+    @staticmethod
+    def forward(ctx, qkv, nhead, causal, snap, site, p):
+        out, lse = ops.gpt_attention(qkv, nhead, causal, dropout=(snap, site, p))
+        if wants_backward(ctx):
+            ctx.nhead, ctx.causal, ctx.dropout = nhead, causal, (snap, site, p)
+            ctx.save_for_backward(qkv, out, lse)
+        return out
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, gout):
+        qkv, out, lse = ctx.saved_tensors
+        return (ops.gpt_attention_bwd(qkv, out, gout.contiguous(), lse, ctx.nhead, ctx.causal, dropout=ctx.dropout),
+                None, None, None, None, None)
 
 
 class _SelfAttention(nn.Module):
@@ -134,6 +163,7 @@ class GPTBackbone(nn.Module):
         self.nets["output_ln"] = nn.LayerNorm(embed_dim)
         self.apply(self._init_weights)
         self._matmul_precision = "fp32"
+        self._dropout_source = "torch"
 
     @property
     def matmul_precision(self) -> str:
@@ -153,6 +183,51 @@ class GPTBackbone(nn.Module):
         if precision not in ("fp32", "bf16", "bf16x3"):
             raise ValueError(f"GPTBackbone: matmul precision must be 'fp32', 'bf16' or 'bf16x3', got {precision!r}")
         self._matmul_precision = precision
+        return self
+
+    @property
+    def dropout_source(self) -> str:
+        """"torch" (default) or "kernel": where training-mode dropout decisions come from (set_dropout_source)."""
+        return self._dropout_source
+
+    def set_dropout_source(self, source: str, seed: int | None = None) -> "GPTBackbone":
+        """"kernel": the three dropouts of every block (attention probabilities, attention-output branch, MLP branch) are decided
+        inside the HIP kernels that touch those elements, each decision a pure function of (seed, step, site, row, col)
+        (include/lipvq.h, "in-kernel dropout"; site = 4 layer + 0 / 1 / 2).  No mask tensor is drawn, stored or saved for the
+        backward, and torch's generators are not touched.  A training-mode forward makes one ``ops.dropout_begin`` launch, which
+        hands the call its (seed, step) and advances the step on the device -- also under ``torch.no_grad()`` and inside a
+        captured graph, where every replay advances it.  "torch" restores the default (masks from torch's generator) bit for bit.
+        Eval mode ignores the source.
+
+        The state, ``dropout_state`` -- a device int64[2] tensor (seed, step) --, is created by the first call with "kernel" (never
+        at construction: a seeded construction consumes torch's RNG exactly as before), seeded with ``seed`` or, for None,
+        ``torch.initial_seed()``; a later call with a seed reseeds it (step 0), one without leaves it.  It is a non-persistent
+        buffer: ``.to()`` moves it, ``state_dict()`` does not hold it.  Returns self."""
+        if source not in ("torch", "kernel"):
+            raise ValueError(f"GPTBackbone: dropout source must be 'torch' or 'kernel', got {source!r}")
+        if source == "kernel":
+            if getattr(self, "_dropout_state", None) is None:
+                dev = next(self.parameters()).device
+                self.register_buffer("_dropout_state", torch.zeros(2, dtype=torch.int64, device=dev), persistent=False)
+                self.reseed_dropout(torch.initial_seed() if seed is None else seed)
+            elif seed is not None:
+                self.reseed_dropout(seed)
+        self._dropout_source = source
+        return self
+
+    @property
+    def dropout_state(self):
+        """The device int64[2] tensor (seed, step) of the in-kernel source, None before the first set_dropout_source("kernel").
+        Pass it to ``icl.GraphedPolicyStep(..., extra_state=[net.dropout_state])`` so that the warm-up steps do not advance it."""
+        return getattr(self, "_dropout_state", None)
+
+    def reseed_dropout(self, seed: int, step: int = 0) -> "GPTBackbone":
+        """Set the in-kernel source's (seed, step) in place: seed any integer (taken modulo 2^64), step the next forward's."""
+        if getattr(self, "_dropout_state", None) is None:
+            raise RuntimeError("GPTBackbone.reseed_dropout: call set_dropout_source('kernel') first (it creates the state)")
+        words = [int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)]
+        words = [v - 2 ** 64 if v >= 2 ** 63 else v for v in words]          # (the bit pattern, as int64)
+        self._dropout_state.copy_(torch.tensor(words, dtype=torch.int64))
         return self
 
     @staticmethod
@@ -175,6 +250,8 @@ class GPTBackbone(nn.Module):
         x = inputs.contiguous().float()
         B, L, H = x.shape[0], self.context_length, self.num_heads
         prec = self._matmul_precision
+        if self.training and self._dropout_source == "kernel":
+            return self._forward_kernel_dropout(x)
         a, b = x, None
         for blk in self.nets["transformer"]:
             att, mlp, ln1, ln2 = blk.nets["attention"], blk.nets["mlp"], blk.nets["ln1"], blk.nets["ln2"]
@@ -204,6 +281,47 @@ class GPTBackbone(nn.Module):
         out = AddLayerNormFn.apply(a, b, ln.weight, ln.bias, ln.eps, False)[1]
         return out
 
+    def _forward_kernel_dropout(self, x):
+        """The training forward under the in-kernel source: one dropout_begin launch, then the same launches per block as eval,
+        the _drop forms where a p is positive.  A branch's dropout rides on the residual launch that adds the branch: the
+        attention-output branch's on ln2, the MLP branch's on the NEXT block's ln1 (the closing output_ln for the last)."""
+        H, prec = self.num_heads, self._matmul_precision
+        if self._dropout_state.device != x.device:
+            raise RuntimeError("GPTBackbone: the dropout state is not on the input's device (move the module with .to())")
+        snap = ops.dropout_begin(self._dropout_state)
+
+        def p_of(module, what):
+            p = float(module.p)
+            if p >= 1.0:
+                raise ValueError(f"GPTBackbone: {what} p={p} under the kernel dropout source (0 <= p < 1)")
+            return p
+
+        def add_ln(a, b, drop, ln, want_s):
+            if drop is not None and drop[1] > 0.0:
+                return AddDropLayerNormFn.apply(a, b, ln.weight, ln.bias, ln.eps, want_s, snap, drop[0], drop[1])
+            return AddLayerNormFn.apply(a, b, ln.weight, ln.bias, ln.eps, want_s)
+
+        a, b, b_drop = x, None, None
+        for i, blk in enumerate(self.nets["transformer"]):
+            att, mlp, ln1, ln2 = blk.nets["attention"], blk.nets["mlp"], blk.nets["ln1"], blk.nets["ln2"]
+            p_att, p_out, p_mlp = (p_of(att.nets["attn_dropout"], "attn_dropout"), p_of(att.nets["output_dropout"], "output_dropout"),
+                                   p_of(mlp[3], "mlp dropout"))
+            if b is None:
+                s, y = a, AddLayerNormFn.apply(a, None, ln1.weight, ln1.bias, ln1.eps, False)[1]
+            else:
+                s, y = add_ln(a, b, b_drop, ln1, True)
+            qkv = LinearFn.apply(y, att.nets["qkv"].weight, None, ACT_NONE, prec)
+            if p_att > 0.0:
+                o = _AttentionDropFn.apply(qkv, H, bool(self.causal), snap, 4 * i, p_att)
+            else:
+                o = _AttentionFn.apply(qkv, H, bool(self.causal), None, 1.0)
+            o = LinearFn.apply(o, att.nets["output"].weight, att.nets["output"].bias, ACT_NONE, prec)
+            s, y = add_ln(s, o, (4 * i + 1, p_out), ln2, True)
+            f = LinearFn.apply(y, mlp[0].weight, mlp[0].bias, ACT_GELU, prec)
+            f = LinearFn.apply(f, mlp[2].weight, mlp[2].bias, ACT_NONE, prec)
+            a, b, b_drop = s, f, (4 * i + 2, p_mlp)
+        ln = self.nets["output_ln"]
+        return add_ln(a, b, b_drop, ln, False)[1]
 
     # -- the prompt cache: a rollout's constant prefix is run once, every step runs its new tokens alone ---------------------
     def _cacheable(self, what):

@@ -313,9 +313,15 @@ class GraphedPolicyStep:
 
     ``loss_fn(*inputs)`` must return a scalar loss, be free of host synchronisation, and do the same work for every batch of the
     captured shapes (e.g. ``lambda x, a: head.nll(net(x)[:, -T:], a)`` with a ``GMMActionHead``, or
-    ``lambda x, a: head.losses(net(x)[:, -T:], a)["action_loss"]`` with an ``ActionHead``); ``example_inputs`` is a tensor or a sequence of tensors."""
+    ``lambda x, a: head.losses(net(x)[:, -T:], a)["action_loss"]`` with an ``ActionHead``); ``example_inputs`` is a tensor or a sequence of tensors.
 
-    def __init__(self, loss_fn, params, optimizer, example_inputs, warmup: int = 3):
+    ``extra_state``: further tensors that a step writes and that are neither parameters nor optimizer state; they are snapshotted
+    and restored in place with the parameters.  A ``GPTBackbone`` under ``set_dropout_source("kernel")`` has one: its
+    ``dropout_state`` (seed, step), which every training forward advances on the device -- the warm-up steps included.  Pass
+    ``extra_state=[net.dropout_state]`` and replay ``k`` draws the masks of eager step ``k`` again (the captured ``dropout_begin``
+    launch advances the step on every replay); without it the replays run ``warmup`` steps ahead of an eager run from the same seed."""
+
+    def __init__(self, loss_fn, params, optimizer, example_inputs, warmup: int = 3, extra_state=()):
         if not isinstance(optimizer, (optim.Adam, optim.AdamW)):
             raise TypeError("GraphedPolicyStep captures lipvq_vae_amd.optim.Adam / AdamW only (their step makes no host "
                             f"synchronisation and keeps its counters on the device), got {type(optimizer).__name__}")
@@ -330,7 +336,10 @@ class GraphedPolicyStep:
         self.static_inputs = tuple(x.detach().clone().contiguous() for x in example_inputs)
         self.warmup_steps = int(warmup)
         lrs = [g["lr"] for g in optimizer.param_groups if torch.is_tensor(g["lr"])]
-        saved = Snapshot(self.params + lrs, optimizer, [p for g in optimizer.param_groups for p in g["params"]])
+        self.extra_state = list(extra_state)
+        if not all(torch.is_tensor(t) for t in self.extra_state):
+            raise TypeError("GraphedPolicyStep: extra_state must be tensors (e.g. [net.dropout_state])")
+        saved = Snapshot(self.params + lrs + self.extra_state, optimizer, [p for g in optimizer.param_groups for p in g["params"]])
         warm_up(self._eager_step, self.warmup_steps)
         torch.cuda.synchronize()
         saved.restore()

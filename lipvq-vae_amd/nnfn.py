@@ -12,7 +12,7 @@ from . import ops
 from .capture import capture, copy_in, warm_up
 from .ops import ACT_NONE
 
-__all__ = ["LinearFn", "AddLayerNormFn", "GraphedEval", "KernelFunction", "first_order_only", "wants_backward"]
+__all__ = ["LinearFn", "AddLayerNormFn", "AddDropLayerNormFn", "GraphedEval", "KernelFunction", "first_order_only", "wants_backward"]
 
 _applying = threading.local()
 
@@ -131,6 +131,35 @@ class AddLayerNormFn(KernelFunction):
         xhat, rstd, w = ctx.saved_tensors
         g, gw, gb = ops.gpt_layernorm_bwd(gy.contiguous(), xhat, rstd, w, None if gs is None else gs.contiguous())
         return g, (g if ctx.has_b else None), gw, gb, None, None
+
+
+class AddDropLayerNormFn(KernelFunction):
+    """(s, y) = (a + drop(b), LayerNorm(a + drop(b)) w + bias) with the branch's dropout decided inside the launch (in-kernel
+    source: dropout = (snap, site, p), include/lipvq.h).  No mask is saved: the backward launch regenerates the decisions from
+    snap and writes the gradient of a (LayerNorm's plus the stream's) and that of b (the same times the mask factor) itself."""
+
+    @staticmethod
+    def forward(ctx, a, b, w, bias, eps, want_s, snap, site, p):
+        ctx.set_materialize_grads(False)
+        ctx.dropout = (snap, site, p)
+        if not wants_backward(ctx):
+            return ops.gpt_layernorm_drop(a, b, w, bias, eps, ctx.dropout, want_s=want_s)
+        s, y, xhat, rstd = ops.gpt_layernorm_drop(a, b, w, bias, eps, ctx.dropout, want_s=want_s, save=True)
+        ctx.save_for_backward(xhat, rstd, w)
+        return s, y
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, gs, gy):
+        xhat, rstd, w = ctx.saved_tensors
+        if gy is None and gs is None:
+            return (None,) * 9
+        if gy is None:                                         # only s was used: LayerNorm's part is that of a zero gradient
+            gy = torch.zeros_like(xhat)
+        g, gbr, gw, gb = ops.gpt_layernorm_drop_bwd(gy.contiguous(), xhat, rstd, w, ctx.dropout, None if gs is None else gs.contiguous())
+        need = ctx.needs_input_grad
+        return (g if need[0] else None, gbr if need[1] else None, gw if need[2] else None, gb if need[3] else None,
+                None, None, None, None, None)
 
 
 class GraphedEval:

@@ -1087,18 +1087,38 @@ def _gpt_keep(keep, B, H, L, dev):
     return keep
 
 
-def gpt_attention(qkv, nhead: int, causal: bool = True, keep=None, keep_prob: float = 1.0):
-    """(out [B, L, E], lse [B, H, L]) of batched multi-head self-attention over qkv [B, L, 3E] (q | k | v), causal or not."""
+def _dropout_args(what, dropout, dev, keep=None):
+    """dropout = (snap, site, p) of the in-kernel source (include/lipvq.h, "in-kernel dropout") -> (snap, site, p) checked."""
+    if keep is not None:
+        raise ValueError(f"{what}: keep (mask bytes) and dropout (the in-kernel source) are mutually exclusive")
+    snap, site, p = dropout
+    if not isinstance(snap, torch.Tensor) or snap.dtype != torch.int64 or snap.numel() != 2 or not snap.is_contiguous() or snap.device != dev:
+        raise ValueError(f"{what}: snap must be the contiguous int64[2] tensor of dropout_begin on the input's device")
+    p = float(p)
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"{what}: dropout p={p} (0 < p < 1; p == 0 is the plain form)")
+    return snap, int(site), p
+
+
+def gpt_attention(qkv, nhead: int, causal: bool = True, keep=None, keep_prob: float = 1.0, *, dropout=None):
+    """(out [B, L, E], lse [B, H, L]) of batched multi-head self-attention over qkv [B, L, 3E] (q | k | v), causal or not.
+    Attention-probability dropout: keep [B, H, L, L] bytes with keep_prob, or dropout=(snap, site, p), drawn in the kernel."""
     qkv = _chk(qkv, "qkv")
     if qkv.dim() != 3 or qkv.shape[2] % 3 != 0:
         raise ValueError(f"gpt_attention: qkv {tuple(qkv.shape)}")
     B, L, E = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
+    if dropout is not None:
+        snap, site, p = _dropout_args("gpt_attention", dropout, qkv.device, keep)
     keep = _gpt_keep(keep, B, nhead, L, qkv.device)
     out = torch.empty((B, L, E), device=qkv.device, dtype=torch.float32)
     lse = torch.empty((B, nhead, L), device=qkv.device, dtype=torch.float32)
     with _on(qkv.device):
-        check(lib.lipvq_gpt_attention_f32(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(keep), float(keep_prob), B, L, E, int(nhead),
-                                          int(bool(causal)), _stream()), "lipvq_gpt_attention_f32")
+        if dropout is not None:
+            check(lib.lipvq_gpt_attention_drop_f32(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(snap), site, p, B, L, E, int(nhead),
+                                                   int(bool(causal)), _stream()), "lipvq_gpt_attention_drop_f32")
+        else:
+            check(lib.lipvq_gpt_attention_f32(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(keep), float(keep_prob), B, L, E, int(nhead),
+                                              int(bool(causal)), _stream()), "lipvq_gpt_attention_f32")
     return out, lse
 
 
@@ -1119,18 +1139,25 @@ def gpt_attention_prefix(prefix_qkv, qkv, nhead: int):
     return out
 
 
-def gpt_attention_bwd(qkv, out, gout, lse, nhead: int, causal: bool = True, keep=None, keep_prob: float = 1.0):
+def gpt_attention_bwd(qkv, out, gout, lse, nhead: int, causal: bool = True, keep=None, keep_prob: float = 1.0, *, dropout=None):
     qkv, out, gout, lse = _chk(qkv, "qkv"), _chk(out, "out"), _chk(gout, "gout"), _chk(lse, "lse")
     B, L, E = out.shape
     if qkv.shape != (B, L, 3 * E) or gout.shape != out.shape or lse.shape != (B, nhead, L):
         raise ValueError("gpt_attention_bwd: shapes do not match")
+    if dropout is not None:
+        snap, site, p = _dropout_args("gpt_attention_bwd", dropout, qkv.device, keep)
     keep = _gpt_keep(keep, B, nhead, L, qkv.device)
     gqkv = torch.empty_like(qkv)
     delta = torch.empty_like(lse)
     with _on(qkv.device):
-        check(lib.lipvq_gpt_attention_bwd_f32(_ptr(qkv), _ptr(out), _ptr(gout), _ptr(lse), _ptr(gqkv), _ptr(delta), _ptr(keep),
-                                              float(keep_prob), B, L, E, int(nhead), int(bool(causal)), _stream()),
-              "lipvq_gpt_attention_bwd_f32")
+        if dropout is not None:
+            check(lib.lipvq_gpt_attention_bwd_drop_f32(_ptr(qkv), _ptr(out), _ptr(gout), _ptr(lse), _ptr(gqkv), _ptr(delta), _ptr(snap),
+                                                       site, p, B, L, E, int(nhead), int(bool(causal)), _stream()),
+                  "lipvq_gpt_attention_bwd_drop_f32")
+        else:
+            check(lib.lipvq_gpt_attention_bwd_f32(_ptr(qkv), _ptr(out), _ptr(gout), _ptr(lse), _ptr(gqkv), _ptr(delta), _ptr(keep),
+                                                  float(keep_prob), B, L, E, int(nhead), int(bool(causal)), _stream()),
+                  "lipvq_gpt_attention_bwd_f32")
     return gqkv
 
 
@@ -1171,6 +1198,79 @@ def gpt_layernorm_bwd(gy, xhat, rstd, w, gres=None):
         check(lib.lipvq_gpt_layernorm_bwd_f32(_ptr(gy), _ptr(xhat), _ptr(_chk(rstd, "rstd")), _ptr(_chk(w, "w")), _ptr(gres), _ptr(gs),
                                               _ptr(gw), _ptr(gb), _ptr(ws), N, E, _stream()), "lipvq_gpt_layernorm_bwd_f32")
     return gs, gw, gb
+
+
+def gpt_layernorm_drop(a, b, w, bias, eps: float, dropout, want_s: bool = True, save: bool = False):
+    """gpt_layernorm with the branch's dropout inside the launch: s = a + b * m, m = 1 / (1 - p) where dropout = (snap, site, p)
+    keeps (row, e) and 0 where it drops it; y = LayerNorm(s) * w + bias.  Returns as gpt_layernorm does."""
+    a, b = _chk(a, "a"), _chk(b, "b")
+    if b.shape != a.shape:
+        raise ValueError("gpt_layernorm_drop: shapes differ")
+    snap, site, p = _dropout_args("gpt_layernorm_drop", dropout, a.device)
+    E = a.shape[-1]
+    N = a.numel() // E if E else 0
+    s = torch.empty_like(a) if want_s else None
+    y = torch.empty_like(a)
+    xhat = torch.empty_like(a) if save else None
+    rstd = torch.empty(N, device=a.device, dtype=torch.float32) if save else None
+    with _on(a.device):
+        check(lib.lipvq_gpt_layernorm_drop_f32(_ptr(a), _ptr(b), _ptr(_chk(w, "w")), _ptr(_chk(bias, "bias")), float(eps), _ptr(snap), site,
+                                               p, _ptr(s), _ptr(y), _ptr(xhat), _ptr(rstd), N, E, _stream()),
+              "lipvq_gpt_layernorm_drop_f32")
+    return (s, y, xhat, rstd) if save else (s, y)
+
+
+def gpt_layernorm_drop_bwd(gy, xhat, rstd, w, dropout, gres=None):
+    """(gs, gbranch, gw, gb): gpt_layernorm_bwd's three and gbranch = gs * m, the gradient of the dropped branch b, from the
+    decisions the forward's (snap, site, p) regenerates."""
+    gy, xhat = _chk(gy, "gy"), _chk(xhat, "xhat")
+    if gres is not None:
+        gres = _chk(gres, "gres")
+        if gres.shape != gy.shape:
+            raise ValueError("gpt_layernorm_drop_bwd: gres shape")
+    snap, site, p = _dropout_args("gpt_layernorm_drop_bwd", dropout, gy.device)
+    E = gy.shape[-1]
+    N = gy.numel() // E if E else 0
+    gs, gbr = torch.empty_like(gy), torch.empty_like(gy)
+    gw = torch.empty(E, device=gy.device, dtype=torch.float32)
+    gb = torch.empty(E, device=gy.device, dtype=torch.float32)
+    ws = torch.empty(max(1, lib.lipvq_gpt_layernorm_bwd_workspace_bytes(N, E)), device=gy.device, dtype=torch.uint8)
+    with _on(gy.device):
+        check(lib.lipvq_gpt_layernorm_bwd_drop_f32(_ptr(gy), _ptr(xhat), _ptr(_chk(rstd, "rstd")), _ptr(_chk(w, "w")), _ptr(gres),
+                                                   _ptr(snap), site, p, _ptr(gs), _ptr(gbr), _ptr(gw), _ptr(gb), _ptr(ws), N, E,
+                                                   _stream()), "lipvq_gpt_layernorm_bwd_drop_f32")
+    return gs, gbr, gw, gb
+
+
+def dropout_begin(state):
+    """snap, a fresh int64[2] device tensor = the (seed, step) of ``state`` (int64[2], device) as it was; ``state``'s step is
+    advanced by one, on the device: one one-thread launch, no host synchronisation."""
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int64 or state.shape != (2,) or not state.is_cuda or not state.is_contiguous():
+        raise ValueError("dropout_begin: state must be a contiguous int64[2] device tensor (seed, step)")
+    snap = torch.empty(2, device=state.device, dtype=torch.int64)
+    with _on(state.device):
+        check(lib.lipvq_dropout_begin(_ptr(state), _ptr(snap), _stream()), "lipvq_dropout_begin")
+    return snap
+
+
+def dropout_keep(snap, site: int, rows: int, cols: int, p: float):
+    """The decisions of one site as a uint8 [rows, cols] device tensor (1 kept, 0 dropped), from a snap of dropout_begin."""
+    if not isinstance(snap, torch.Tensor) or snap.dtype != torch.int64 or snap.numel() != 2 or not snap.is_cuda or not snap.is_contiguous():
+        raise ValueError("dropout_keep: snap must be a contiguous int64[2] device tensor")
+    ok = 0 <= int(rows) < 2 ** 32 and 0 <= int(cols) <= 2 ** 32            # (anything else the library refuses before it writes)
+    out = torch.empty((int(rows), int(cols)) if ok else (0, 0), device=snap.device, dtype=torch.uint8)
+    with _on(snap.device):
+        check(lib.lipvq_dropout_keep_u8(_ptr(snap), int(site), int(rows), int(cols), float(p), _ptr(out), _stream()), "lipvq_dropout_keep_u8")
+    return out
+
+
+def dropout_keep_host(seed: int, step: int, site: int, rows: int, cols: int, p: float):
+    """The same field as a uint8 [rows, cols] CPU tensor from (seed, step), computed on the host: no GPU call."""
+    ok = 0 <= int(rows) < 2 ** 32 and 0 <= int(cols) <= 2 ** 32
+    out = torch.empty((int(rows), int(cols)) if ok else (0, 0), dtype=torch.uint8)
+    check(lib.lipvq_dropout_keep_host(int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), int(site), int(rows), int(cols), float(p),
+                                      out.data_ptr()), "lipvq_dropout_keep_host")
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------
