@@ -385,6 +385,21 @@ int lipvq_embed_rows_bwd_ws_f32(const float* gout, const float* src, const int64
                                 int64_t N, int T, int E, int64_t src_rows, int64_t out_batch_stride, int64_t out_t_stride,
                                 int64_t out_offset, void* stream);
 
+/* The same backward with the sums in a fixed order, for any N >= 1 (T <= 1024): no floating-point atomics, so repeated runs
+ * give bit-identical g_pos, g_lnw, g_lnb and (but for the one case named below) g_src.  A wave owns one time step as in _ws; each workgroup leaves
+ * its partial (g_pos, g_lnw, g_lnb) sums in the workspace and a second launch adds them in workgroup order (one writer per
+ * address); indexed rows are summed per table row by lipvq_scatter_add_sorted_f32 where it is supported, else by
+ * lipvq_scatter_add_det_f32 while src_rows * N * ceil(E / 256) <= 2^24 (its cost in index reads), else by lipvq_scatter_add_f32:
+ * the one case in which g_src, and only g_src, is added with atomics, as lipvq_embed_rows_bwd_f32 adds it.  The outputs are accumulated into as above and g_pos / g_lnw / g_lnb must be 16-byte aligned.
+ * snap != NULL: gout is read as gout * m of the in-kernel dropout source (site, p; see "in-kernel dropout for the embedding
+ * stage"), snap == NULL: plain.  workspace: lipvq_embed_rows_bwd_det_workspace_bytes(N, T, E, src_rows, idx != NULL) bytes.
+ * This is the route the Python module takes. */
+size_t lipvq_embed_rows_bwd_det_workspace_bytes(int64_t N, int T, int E, int64_t src_rows, int indexed);
+int lipvq_embed_rows_bwd_det_f32(const float* gout, const float* src, const int64_t* idx, const float* pos, const float* stats,
+                                 const float* ln_w, float* g_src, float* g_pos, float* g_lnw, float* g_lnb, void* workspace,
+                                 const int64_t* snap, uint32_t site, double p, int64_t N, int T, int E, int64_t src_rows,
+                                 int64_t out_batch_stride, int64_t out_t_stride, int64_t out_offset, void* stream);
+
 /* lipvq_linear_f32 with an activation epilogue: y = act(x . W^T + b); pre (may be NULL) receives the pre-activation
  * for the backward.  bin:29-30 (second Linear + GELU of AdaptiveBinActionEmbedding.output_layer). */
 int lipvq_linear_act_f32(const float* x, const float* W, const float* b, float* y, float* pre, int64_t N, int Kin,
@@ -538,6 +553,53 @@ int lipvq_gpt_layernorm_drop_f32(const float* a, const float* b, const float* w,
 int lipvq_gpt_layernorm_bwd_drop_f32(const float* gy, const float* xhat, const float* rstd, const float* w, const float* gres,
                                      const int64_t* snap, uint32_t site, double p, float* gs, float* gbranch, float* gw, float* gb,
                                      void* workspace, int64_t N, int E, void* stream);
+
+/* ---- in-kernel dropout for the embedding stage and the default action branch (ICLInputEmbedding / DefaultActionNetwork
+ *      .set_dropout_source("kernel")).  Generator, threshold, inv_keep, snap and the refusals (p outside (0, 1): LIPVQ_EINVAL;
+ *      rows >= 2^32: LIPVQ_EUNSUPPORTED) are those of the section above; only the SITES are new.  The site is one 32-bit counter
+ *      word, and the two modules take theirs from ranges the backbone's 4 layer + {0, 1, 2} cannot reach:
+ *          LIPVQ_DROPOUT_SITE_EMBED              the dropout after the embedding LayerNorm.  Field: row = the OUTPUT row b S + s
+ *                                                of the call's [B][S][E] result (S = 3T for forward, 2T for prompt_embedding, T
+ *                                                for input_embedding*), col = e.
+ *          LIPVQ_DROPOUT_SITE_DEFAULT + 4 layer + k   encoder layer `layer` of the default action branch:
+ *              k = 0  attention probabilities, row = h S + q, col = key (the layout of the keep bytes [H][S][S])
+ *              k = 1  dropout1, the attention-output branch: row of [S][D], col = d
+ *              k = 2  dropout2, the FFN-output branch: the same field
+ *              k = 3  dropout between linear1's GELU and linear2: row of [S][FF], col = f
+ *      The site word enters every draw, so two modules whose states hold equal (seed, step) still draw unrelated fields. ---- */
+#define LIPVQ_DROPOUT_SITE_EMBED 0x40000000u
+#define LIPVQ_DROPOUT_SITE_DEFAULT 0x80000000u
+/* lipvq_attention_f32 / _bwd_f32 with the attention-probability decisions of `site` drawn in the kernels (H S < 2^32 rows): the
+ * bits of the keep-byte form given the bytes of lipvq_dropout_keep_u8(snap, site, H S, S, p) and keep_prob = (float)(1 - p),
+ * for every head-width instance.  A query row all of whose keys are dropped has a zero output row and its lse unchanged. */
+int lipvq_attention_drop_f32(const float* qkv, float* out, float* lse, const int64_t* snap, uint32_t site, double p, int64_t S,
+                             int D, int H, void* stream);
+int lipvq_attention_bwd_drop_f32(const float* qkv, const float* out, const float* gout, const float* lse, float* gqkv,
+                                 float* delta, const int64_t* snap, uint32_t site, double p, int64_t S, int D, int H, void* stream);
+/* lipvq_linear_act_f32 whose stored y is act(pre) * m, m = inv_keep where (row, col) of `site` is kept and 0 where it is dropped
+ * (a product: a NaN at a dropped position stays a NaN).  pre is the plain pre-activation.  Same kernel choice, same chains. */
+int lipvq_linear_act_drop_f32(const float* x, const float* W, const float* b, float* y, float* pre, const int64_t* snap,
+                              uint32_t site, double p, int64_t N, int Kin, int E, int act, void* stream);
+/* The first step of its backward in one launch: out [rows][cols] = lipvq_act_bwd_f32 of (g * m) at pre, m regenerated from
+ * (snap, site, p).  act == LIPVQ_ACT_NONE gives g * m. */
+int lipvq_act_bwd_drop_f32(const float* g, const float* pre, float* out, const int64_t* snap, uint32_t site, double p,
+                           int64_t rows, int64_t cols, int act, void* stream);
+/* lipvq_embed_rows_f32 that stores LayerNorm(...) * m.  The field row is the OUTPUT row of the slot,
+ * (b out_batch_stride + t out_t_stride + out_offset) / E -- not the stream's own row number --, so the streams of one result
+ * share one field; the strides and the offset must be multiples of E (LIPVQ_EINVAL).  stats stay the pre-dropout statistics. */
+int lipvq_embed_rows_drop_f32(const float* src, const int64_t* idx, const float* pos, const float* ln_w, const float* ln_b,
+                              float eps, float* out, float* stats, const int64_t* snap, uint32_t site, double p, int64_t N, int T,
+                              int E, int64_t src_rows, int64_t out_batch_stride, int64_t out_t_stride, int64_t out_offset,
+                              void* stream);
+/* lipvq_embed_rows_bwd_f32 / _bwd_ws_f32 reading gout * m from the regenerated decisions (the same field, the same limits). */
+int lipvq_embed_rows_bwd_drop_f32(const float* gout, const float* src, const int64_t* idx, const float* pos, const float* stats,
+                                  const float* ln_w, float* g_src, float* g_pos, float* g_lnw, float* g_lnb, const int64_t* snap,
+                                  uint32_t site, double p, int64_t N, int T, int E, int64_t src_rows, int64_t out_batch_stride,
+                                  int64_t out_t_stride, int64_t out_offset, void* stream);
+int lipvq_embed_rows_bwd_ws_drop_f32(const float* gout, const float* src, const int64_t* idx, const float* pos, const float* stats,
+                                     const float* ln_w, float* g_src, float* g_pos, float* g_lnw, float* g_lnb, void* workspace,
+                                     const int64_t* snap, uint32_t site, double p, int64_t N, int T, int E, int64_t src_rows,
+                                     int64_t out_batch_stride, int64_t out_t_stride, int64_t out_offset, void* stream);
 
 /* ---- the backbone's opt-in bf16 matrix-pipe mode (GPTBackbone.set_matmul_precision("bf16")): the three products of one
  *      nn.Linear on the bf16 MFMAs.  lipvq-vae_amd/csrc/lipvq_gemm_bf16.hip.

@@ -92,6 +92,8 @@ SIGNATURES = {
     "lipvq_embed_rows_bwd_ws_supported": (_i, [_i64, _i, _i, _i64]),
     "lipvq_embed_rows_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _i64]),
     "lipvq_embed_rows_bwd_ws_f32": (_i, [_vp] * 11 + [_i64, _i, _i] + [_i64] * 4 + [_vp]),
+    "lipvq_embed_rows_bwd_det_workspace_bytes": (_sz, [_i64, _i, _i, _i64, _i]),
+    "lipvq_embed_rows_bwd_det_f32": (_i, [_vp] * 12 + [C.c_uint32, C.c_double, _i64, _i, _i] + [_i64] * 4 + [_vp]),
     "lipvq_linear_act_f32": (_i, [_vp] * 5 + [_i64, _i, _i, _i, _vp]),
     "lipvq_linear_act_bf16": (_i, [_vp] * 5 + [_i64, _i, _i, _i, _vp]),
     "lipvq_linear_nn_bf16": (_i, [_vp] * 3 + [_i64, _i, _i, _vp]),
@@ -123,6 +125,13 @@ SIGNATURES = {
     "lipvq_gpt_attention_bwd_drop_f32": (_i, [_vp] * 7 + [C.c_uint32, C.c_double, _i64, _i, _i, _i, _i, _vp]),
     "lipvq_gpt_layernorm_drop_f32": (_i, [_vp] * 4 + [C.c_float, _vp, C.c_uint32, C.c_double] + [_vp] * 4 + [_i64, _i, _vp]),
     "lipvq_gpt_layernorm_bwd_drop_f32": (_i, [_vp] * 6 + [C.c_uint32, C.c_double] + [_vp] * 5 + [_i64, _i, _vp]),
+    "lipvq_attention_drop_f32": (_i, [_vp] * 4 + [C.c_uint32, C.c_double, _i64, _i, _i, _vp]),
+    "lipvq_attention_bwd_drop_f32": (_i, [_vp] * 7 + [C.c_uint32, C.c_double, _i64, _i, _i, _vp]),
+    "lipvq_linear_act_drop_f32": (_i, [_vp] * 6 + [C.c_uint32, C.c_double, _i64, _i, _i, _i, _vp]),
+    "lipvq_act_bwd_drop_f32": (_i, [_vp] * 4 + [C.c_uint32, C.c_double, _i64, _i64, _i, _vp]),
+    "lipvq_embed_rows_drop_f32": (_i, [_vp] * 5 + [C.c_float, _vp, _vp, _vp, C.c_uint32, C.c_double, _i64, _i, _i] + [_i64] * 4 + [_vp]),
+    "lipvq_embed_rows_bwd_drop_f32": (_i, [_vp] * 11 + [C.c_uint32, C.c_double, _i64, _i, _i] + [_i64] * 4 + [_vp]),
+    "lipvq_embed_rows_bwd_ws_drop_f32": (_i, [_vp] * 12 + [C.c_uint32, C.c_double, _i64, _i, _i] + [_i64] * 4 + [_vp]),
     "lipvq_gmm_workspace_bytes": (_sz, [_i64]),
     "lipvq_gmm_head_f32": (_i, [_vp, _i64] + [_vp] * 14 + [_i64] + [_i] * 5 + [C.c_float, _vp]),
     "lipvq_gmm_head_bwd_f32": (_i, [_vp] * 5 + [_i64, _i, _i, _i, C.c_float, _vp]),

@@ -14,6 +14,7 @@
 // lower-bound search are restated in lipvq_math.h).  Canonical layer 1: acc = b1[j]; acc = acc + P[i][bin_i][j], i ascending.
 // ABI: include/lipvq.h.
 #include "lipvq_common.h"
+#include "lipvq_rng.h"
 
 // ---------------------------------------------------------------------------------------------------
 // bin:37-40  running_min = minimum(running_min, actions.min(0)), running_max likewise (in place, atomics on the
@@ -180,6 +181,32 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
         out[i] = lq_act_bwd(g[i], pre[i], act);
 }
 
+// out = (g * m) * act'(pre), m = inv_keep or 0 by the decision at (row, col) of a [rows][cols] field: the first backward step of
+// lipvq_linear_act_drop_f32 (y = act(pre) * m), the mask regenerated, not read.  One thread per draw = four neighbouring columns
+// of one row (a float4 when cols % 4 == 0); pre == NULL with act = NONE.
+__global__ __launch_bounds__(256) void act_bwd_drop_kernel(const float* __restrict__ g, const float* __restrict__ pre,
+                                                           float* __restrict__ out, lq_dropout_src src, int64_t rows, int64_t cols,
+                                                           int act) {
+    const lq_dropout dr = lq_dropout_load(src);
+    const int64_t c4n = (cols + 3) >> 2, items = rows * c4n;
+    const bool vec = (cols & 3) == 0;                                  // (uniform)
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < items; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / c4n, c4 = i - row * c4n;
+        const uint32_t kb = lq_dropout_keep4(dr, (uint32_t)row, (uint32_t)c4);
+        const size_t at = (size_t)row * cols + 4 * c4;
+        if (vec) {
+            const float4 gv = *reinterpret_cast<const float4*>(g + at);
+            const float4 pv = pre ? *reinterpret_cast<const float4*>(pre + at) : make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4*>(out + at) =
+                make_float4(lq_act_bwd(gv.x * ((kb & 1u) ? dr.inv_keep : 0.0f), pv.x, act), lq_act_bwd(gv.y * ((kb & 2u) ? dr.inv_keep : 0.0f), pv.y, act),
+                            lq_act_bwd(gv.z * ((kb & 4u) ? dr.inv_keep : 0.0f), pv.z, act), lq_act_bwd(gv.w * ((kb & 8u) ? dr.inv_keep : 0.0f), pv.w, act));
+        } else {
+            for (int w = 0; w < 4 && 4 * c4 + w < cols; ++w)
+                out[at + w] = lq_act_bwd(g[at + w] * (((kb >> w) & 1u) ? dr.inv_keep : 0.0f), pre ? pre[at + w] : 0.0f, act);
+        }
+    }
+}
+
 static int stream_grid(int64_t work_items, int per_block, int cap) {
     int64_t g = (work_items + per_block - 1) / per_block;
     if (g > cap) g = cap;
@@ -257,6 +284,19 @@ int lipvq_act_bwd_f32(const float* g, const float* pre, float* out, int64_t n, i
     if (n == 0) return LIPVQ_OK;
     hipLaunchKernelGGL(act_bwd_kernel, dim3(stream_grid(n, 256 * 4, 4096)), dim3(256), 0, (hipStream_t)stream, g, pre, out, n, act);
     return check_launch("act_bwd_kernel");
+}
+
+int lipvq_act_bwd_drop_f32(const float* g, const float* pre, float* out, const int64_t* snap, uint32_t site, double p,
+                           int64_t rows, int64_t cols, int act, void* stream) {
+    if (rows < 0 || cols < 0 || act < LIPVQ_ACT_NONE || act > LIPVQ_ACT_RELU) return fail(LIPVQ_EINVAL, "lipvq_act_bwd_drop_f32: bad arguments");
+    if (int rc = lq_dropout_check("lipvq_act_bwd_drop_f32", snap, p, rows)) return rc;
+    if (!g || !out || (!pre && act != LIPVQ_ACT_NONE)) return fail(LIPVQ_EINVAL, "lipvq_act_bwd_drop_f32: null pointer");
+    if (rows == 0 || cols == 0) return LIPVQ_OK;
+    if ((cols & 3) == 0 && (((uintptr_t)g | (uintptr_t)pre | (uintptr_t)out) & 15) != 0)
+        return fail(LIPVQ_EINVAL, "lipvq_act_bwd_drop_f32: g / pre / out must be 16-byte aligned");
+    hipLaunchKernelGGL(act_bwd_drop_kernel, dim3(stream_grid(rows * ((cols + 3) / 4), 256 * 2, 4096)), dim3(256), 0, (hipStream_t)stream, g, pre,
+                       out, lq_dropout_src_make(snap, site, p), rows, cols, act);
+    return check_launch("act_bwd_drop_kernel");
 }
 
 }  // extern "C"

@@ -95,6 +95,15 @@ int lipvq_mse_finish(const double* partial, int64_t nx, int64_t nz, float* out, 
 #define fail lipvq_fail
 #define check_launch lipvq_check_launch
 
+// what every entry point of the in-kernel dropout source refuses (include/lipvq.h, "in-kernel dropout"): 0 < p < 1, a snap to
+// read, and a field whose rows fit the 32-bit counter word
+static inline int lq_dropout_check(const char* what, const void* snap, double p, int64_t rows) {
+    if (!(p > 0.0 && p < 1.0)) return fail(LIPVQ_EINVAL, "%s: dropout p=%g (0 < p < 1)", what, p);
+    if (rows >= (1LL << 32)) return fail(LIPVQ_EUNSUPPORTED, "%s: %lld rows of decisions (< 2^32)", what, (long long)rows);
+    if (!snap) return fail(LIPVQ_EINVAL, "%s: null snap", what);
+    return 0;
+}
+
 __host__ __device__ static inline float lq_act_apply(float v, int act) {
     switch (act) {
         case LIPVQ_ACT_GELU: return lq_gelu(v);

@@ -1,7 +1,8 @@
 // lipvq_embed.hip -- the step right after the tokenizer: the reference's
 // ICLTransformer.input_embedding() + the interleave of (context_obs, context_actions, obs)
 // (reference robomimic/models/obs_nets.py:2525-2543 and :2580-2596):
-//     e = LayerNorm(Linear(z_latent) + time_embedding[t])          dropout is the caller's (identity in eval)
+//     e = LayerNorm(Linear(z_latent) + time_embedding[t])          dropout is the caller's (identity in eval), or decided here:
+//                                                                  the DROP instances, lipvq_rng.h, field row = the output row
 //     transformer_embeddings[b, 2t] = e(context_obs), [b, 2t+1] = e(context_actions), [b, 2T+t] = e(obs)
 //
 // MI355X design.  For the LipVQ tokenizer z_latent[n] IS codebook[idx[n]] (v5:47,84), so
@@ -23,10 +24,14 @@
 // inexact unless E is a power of two, so the mean of a constant row comes out an ulp off and rstd = 1/sqrt(eps) = 316
 // multiplies the residue (1e-4 of max|y| on rows of 3.0 at E = 252; tests/test_gpu_embed_edges.py).  stats keeps the
 // corrected mean, from which the backward kernels rebuild xhat = (v - mean) * rstd in one step.
+// In-kernel dropout (include/lipvq.h, "in-kernel dropout for the embedding stage and the default action branch"): linear_kernel
+// and linear_big_kernel take DROP as a template parameter (y = act(pre) * m in the epilogue), embed_rows_kernel and its two
+// backward kernels likewise (out * m, gout * m); the plain instances are the kernels they were.
 // ABI: include/lipvq.h.
 #include <stdlib.h>
 
 #include "lipvq_common.h"
+#include "lipvq_rng.h"
 
 // ---------------------------------------------------------------------------------------------------
 // y[N][E] = x[N][Kin] . W[E][Kin]^T + b      (nn.Linear; obs_nets.py:2536 `embed_encoder`)
@@ -38,9 +43,32 @@
 #define LIN_ROWS 32
 #define LIN_KC 64
 
+// DROP epilogue (lipvq_linear_act_drop_f32): the decisions of one 32 x 32 result tile for the lane's column `ecol`, bit r = the
+// row of accumulator register r (row_of(r) = tile row0 + (r & 3) + 8 (r >> 2) + 4 kh).  The four lanes of a quad share
+// ecol >> 2 and kh, hence all sixteen draws (one per r); lane q = lane & 3 runs those of r = q, q + 4, q + 8, q + 12 and the quad
+// exchanges the nibbles: four draws per lane and tile.  Every lane of the wave must call it.
+__device__ __forceinline__ uint32_t lin_keep_tile(lq_dropout d, int64_t row0, int kh, int ecol, int lane) {
+    const int q = lane & 3;
+    uint32_t mine = 0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int r = q + 4 * t;
+        mine |= lq_dropout_keep4(d, (uint32_t)(row0 + (r & 3) + 8 * (r >> 2) + 4 * kh), (uint32_t)(ecol >> 2)) << (4 * t);
+    }
+    uint32_t bits = 0;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const uint32_t m = (uint32_t)__shfl((int)mine, (lane & ~3) | s, 64);          // lane s of the quad: r = s + 4 t at bits 4 t .. 4 t + 3
+#pragma unroll
+        for (int t = 0; t < 4; ++t) bits |= ((m >> (4 * t + q)) & 1u) << (s + 4 * t);
+    }
+    return bits;
+}
+
+template <bool DROP>
 __global__ __launch_bounds__(256) void linear_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                      const float* __restrict__ bias, float* __restrict__ y,
-                                                     float* __restrict__ pre, int act, int64_t N, int Kin, int E) {
+                                                     float* __restrict__ pre, int act, lq_dropout_src src, int64_t N, int Kin, int E) {
     __shared__ float xs[LIN_ROWS][LIN_KC + 1];
     __shared__ float ws[128][LIN_KC + 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -90,13 +118,16 @@ __global__ __launch_bounds__(256) void linear_kernel(const float* __restrict__ x
         }
         __syncthreads();
     }
+    uint32_t kb = 0;
+    if constexpr (DROP) kb = lin_keep_tile(lq_dropout_load(src), row0, kh, ecol, lane);      // (before any lane leaves)
     if (ecol >= E) return;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int64_t row = row0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
         if (row < N) {
             if (pre) pre[(size_t)row * E + ecol] = acc[r];
-            y[(size_t)row * E + ecol] = lq_act_apply(acc[r], act);
+            if constexpr (DROP) y[(size_t)row * E + ecol] = lq_act_apply(acc[r], act) * (((kb >> r) & 1u) ? src.inv_keep : 0.0f);
+            else y[(size_t)row * E + ecol] = lq_act_apply(acc[r], act);
         }
     }
 }
@@ -107,10 +138,10 @@ __global__ __launch_bounds__(256) void linear_kernel(const float* __restrict__ x
 #define LINB_KC 32
 
 // WR x WC waves, each owning a 64 x 64 block: (2, 2) = 128 x 128 tile; (4, 1) = 256 x 64 tile for narrow outputs (E <= 64)
-template <int WR, int WC>
+template <int WR, int WC, bool DROP>
 __global__ __launch_bounds__(256) void linear_big_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                          const float* __restrict__ bias, float* __restrict__ y,
-                                                         float* __restrict__ pre, int act, int64_t N, int Kin, int E) {
+                                                         float* __restrict__ pre, int act, lq_dropout_src src, int64_t N, int Kin, int E) {
     constexpr int TR = 64 * WR, TC = 64 * WC;
     __shared__ float xs[TR][LINB_KC + 1];
     __shared__ float ws[TC][LINB_KC + 1];
@@ -171,18 +202,23 @@ __global__ __launch_bounds__(256) void linear_big_kernel(const float* __restrict
         }
         __syncthreads();
     }
+    lq_dropout dr = {};
+    if constexpr (DROP) dr = lq_dropout_load(src);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int ecol = e0 + (2 * wc + j) * 32 + li;
+            uint32_t kb = 0;
+            if constexpr (DROP) kb = lin_keep_tile(dr, row0 + (2 * wr + i) * 32, kh, ecol, lane);      // (all lanes: before the column test)
             if (ecol >= E) continue;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int64_t row = row0 + (2 * wr + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
                 if (row < N) {
                     if (pre) pre[(size_t)row * E + ecol] = acc[i][j][r];
-                    y[(size_t)row * E + ecol] = lq_act_apply(acc[i][j][r], act);
+                    if constexpr (DROP) y[(size_t)row * E + ecol] = lq_act_apply(acc[i][j][r], act) * (((kb >> r) & 1u) ? src.inv_keep : 0.0f);
+                    else y[(size_t)row * E + ecol] = lq_act_apply(acc[i][j][r], act);
                 }
             }
         }
@@ -229,12 +265,13 @@ struct EmbedRowsArgs {
     int64_t N, src_rows, out_bstride, out_tstride, out_offset;
     int T, E, chunk;
     float eps;
+    lq_dropout_src drop;       // DROP instances: out = LayerNorm(...) * m, field row = the OUTPUT row of the slot, col = e
 };
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define EMB_CHUNK 16        // most steps per workgroup item (4 indices per step and wave: 64 lanes fetch 16 steps)
 
-template <int NJ>
+template <int NJ, bool DROP>
 __global__ __launch_bounds__(256) void embed_rows_kernel(const EmbedRowsArgs a) {
     extern __shared__ float4 emb_lds[];                      // [ln_w: E4][ln_b: E4]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -251,6 +288,8 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(const EmbedRowsArgs a) 
     const float qnan = __builtin_nanf("");
     const int q16 = 16 / a.T, r16 = 16 - q16 * a.T;
     const int64_t per_item = 16 * (int64_t)a.chunk;
+    lq_dropout dr = {};
+    if constexpr (DROP) dr = lq_dropout_load(a.drop);
     for (int64_t n0 = (int64_t)blockIdx.x * per_item; n0 < a.N; n0 += (int64_t)gridDim.x * per_item) {
         // this wave's indices for all steps of the item in one vector load: lane (r = lane >> 2, g = lane & 3)
         int64_t kv = n0 + (lane >> 2) * 16 + wave * 4 + (lane & 3);
@@ -306,7 +345,10 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(const EmbedRowsArgs a) 
                 }
             const float var = lq_row_allsum(ss) * invE;
             const float rstd = 1.0f / lq_sqrt(var + a.eps);
-            float4* orow = reinterpret_cast<float4*>(a.out + (size_t)(b * a.out_bstride + t * a.out_tstride + a.out_offset));
+            const size_t slot = (size_t)(b * a.out_bstride + t * a.out_tstride + a.out_offset);
+            float4* orow = reinterpret_cast<float4*>(a.out + slot);
+            uint32_t orow_n = 0;                                 // the output row b S + s of the slot (host: strides and offset are multiples of E)
+            if constexpr (DROP) orow_n = (uint32_t)(slot / (size_t)a.E);
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 const int q = l + 16 * j;
@@ -317,6 +359,11 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(const EmbedRowsArgs a) 
                     o.y = lq_fma(v[j].y * rstd, w.y, bb.y);
                     o.z = lq_fma(v[j].z * rstd, w.z, bb.z);
                     o.w = lq_fma(v[j].w * rstd, w.w, bb.w);
+                    if constexpr (DROP) {                        // lane's float4 = columns 4 q .. 4 q + 3: one draw
+                        const uint32_t kb = lq_dropout_keep4(dr, orow_n, (uint32_t)q);
+                        o.x *= (kb & 1u) ? dr.inv_keep : 0.0f; o.y *= (kb & 2u) ? dr.inv_keep : 0.0f;
+                        o.z *= (kb & 4u) ? dr.inv_keep : 0.0f; o.w *= (kb & 8u) ? dr.inv_keep : 0.0f;
+                    }
                     if (!ok) o = f32x4{qnan, qnan, qnan, qnan};
                     __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(orow + q));   // written once, read by a later launch
                 }
@@ -355,18 +402,31 @@ struct EmbedBwdArgs {
     int T, E;
     float* gv;                 // large batches: the rows' gradients are written here (and scattered by a second pass), not added atomically
     int64_t* idx_clean;        // ... with the indices made safe for that pass (a row with a bad index: code 0, zero gradient)
+    lq_dropout_src drop;       // DROP instances: gout is read as gout * m, m regenerated from the forward's field
+    float* part;               // gv kernel, fixed-order route: workgroup w leaves its (g_pos, g_lnw, g_lnb) sums at part[w][3][E] and
+                               // embed_param_reduce_kernel adds them in workgroup order -- no atomics, the same bits every run
 };
+
+// gout * m for the float4 at columns 4 q .. 4 q + 3 of the output row that holds float offset `slot`
+__device__ __forceinline__ float4 emb_drop4(float4 g, lq_dropout dr, size_t slot, int E, int q) {
+    const uint32_t kb = lq_dropout_keep4(dr, (uint32_t)(slot / (size_t)E), (uint32_t)q);
+    g.x *= (kb & 1u) ? dr.inv_keep : 0.0f; g.y *= (kb & 2u) ? dr.inv_keep : 0.0f;
+    g.z *= (kb & 4u) ? dr.inv_keep : 0.0f; g.w *= (kb & 8u) ? dr.inv_keep : 0.0f;
+    return g;
+}
 
 // Large batches (lipvq_embed_rows_bwd_ws_f32).  The kernel above adds every row's E-float gradient to its table row AND to its
 // time-embedding row with fp32 atomics: 2 N E atomics, the time-embedding ones onto T E addresses -- 8.7 ms at the metric's
 // batch (N = 524 280, E = 512, T = 10), 55 ms when the codes collapse onto one table row.  Here a wave owns ONE time step t and
 // walks batches b, b + W, ...: the time-embedding gradient stays in registers and costs one flush per wave; the row gradient is
 // written once (gv [N][E]) and summed per code by the counting-sort scatter (lipvq_scatter.hip): no atomics on the table either.
-template <int NJ>
+template <int NJ, bool DROP>
 __global__ __launch_bounds__(256) void embed_rows_bwd_gv_kernel(const EmbedBwdArgs a) {
     const int lane = threadIdx.x & 63;
     const int E4 = a.E >> 2;
     const float fE = (float)a.E;
+    lq_dropout dr = {};
+    if constexpr (DROP) dr = lq_dropout_load(a.drop);
     float4 w[NJ], aw[NJ], ab[NJ], ap[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -401,8 +461,8 @@ __global__ __launch_bounds__(256) void embed_rows_bwd_gv_kernel(const EmbedBwdAr
         }
         const float mean = a.stats[2 * n], rstd = a.stats[2 * n + 1];
         const float4* srow = reinterpret_cast<const float4*>(a.src + (size_t)k * a.E);
-        const float4* grow =
-            reinterpret_cast<const float4*>(a.gout + (size_t)(b * a.out_bstride + t * a.out_tstride + a.out_offset));
+        const size_t slot = (size_t)(b * a.out_bstride + t * a.out_tstride + a.out_offset);
+        const float4* grow = reinterpret_cast<const float4*>(a.gout + slot);
         float4 xh[NJ], gh[NJ];
         float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
@@ -416,7 +476,8 @@ __global__ __launch_bounds__(256) void embed_rows_bwd_gv_kernel(const EmbedBwdAr
                 }
                 c.x = (c.x - mean) * rstd; c.y = (c.y - mean) * rstd;
                 c.z = (c.z - mean) * rstd; c.w = (c.w - mean) * rstd;
-                const float4 g = grow[q];
+                float4 g = grow[q];
+                if constexpr (DROP) g = emb_drop4(g, dr, slot, a.E, q);
                 aw[j].x += g.x * c.x; aw[j].y += g.y * c.y; aw[j].z += g.z * c.z; aw[j].w += g.w * c.w;
                 ab[j].x += g.x; ab[j].y += g.y; ab[j].z += g.z; ab[j].w += g.w;
                 float4 h;
@@ -464,6 +525,11 @@ __global__ __launch_bounds__(256) void embed_rows_bwd_gv_kernel(const EmbedBwdAr
                 sw.x += ww.x; sw.y += ww.y; sw.z += ww.z; sw.w += ww.w;
                 sb.x += bb.x; sb.y += bb.y; sb.z += bb.z; sb.w += bb.w;
             }
+            if (a.part) {                                      // (uniform) fixed-order route: one partial row triple per workgroup
+                float4* d = reinterpret_cast<float4*>(a.part + (size_t)blockIdx.x * 3 * a.E);
+                d[q] = sp; d[E4 + q] = sw; d[2 * E4 + q] = sb;
+                continue;
+            }
             if (a.g_pos) {
                 float* d = a.g_pos + (size_t)t * a.E + 4 * q;
                 atomicAdd(d + 0, sp.x); atomicAdd(d + 1, sp.y); atomicAdd(d + 2, sp.z); atomicAdd(d + 3, sp.w);
@@ -480,11 +546,46 @@ __global__ __launch_bounds__(256) void embed_rows_bwd_gv_kernel(const EmbedBwdAr
     }
 }
 
-template <int NJ>
+// The second pass of the fixed-order route.  part [nwg][3][E]: workgroup w = i T + t of embed_rows_bwd_gv_kernel (time step t, i-th
+// of the gpt workgroups of that step).  Item (which, q), owned by 16 lanes: which < T adds the gpt partial sums of time step `which`
+// to g_pos, which == T / T + 1 all nwg partial sums to g_lnw / g_lnb.  Lane k of the 16 adds partials k, k + 16, ... in ascending
+// order, the 16 lane sums are combined by a fixed xor butterfly, lane 0 writes: one order, one writer per address.
+__global__ __launch_bounds__(256) void embed_param_reduce_kernel(const float* __restrict__ part, int nwg, int T, int E,
+                                                                 float* __restrict__ g_pos, float* __restrict__ g_lnw,
+                                                                 float* __restrict__ g_lnb) {
+    const int E4 = E >> 2;
+    const int gid = blockIdx.x * 256 + threadIdx.x, item = gid >> 4, k = gid & 15;
+    if (item >= (T + 2) * E4) return;                              // (whole 16-lane groups)
+    const int which = item / E4, q = item - which * E4;
+    float* dst = which < T ? g_pos : (which == T ? g_lnw : g_lnb);
+    if (!dst) return;
+    const int kind = which < T ? 0 : which - T + 1;
+    const int count = which < T ? nwg / T : nwg, stride = which < T ? T : 1, base = which < T ? which : 0;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4
+    for (int j = k; j < count; j += 16) {
+        const float4 v = reinterpret_cast<const float4*>(part + ((size_t)(base + j * stride) * 3 + kind) * E)[q];
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+        s.x += __shfl_xor(s.x, off, 64); s.y += __shfl_xor(s.y, off, 64);
+        s.z += __shfl_xor(s.z, off, 64); s.w += __shfl_xor(s.w, off, 64);
+    }
+    if (k != 0) return;
+    float4* d = reinterpret_cast<float4*>(dst + (which < T ? (size_t)which * E : 0)) + q;
+    float4 o = *d;
+    o.x += s.x; o.y += s.y; o.z += s.z; o.w += s.w;
+    *d = o;
+}
+
+template <int NJ, bool DROP>
 __global__ __launch_bounds__(256) void embed_rows_bwd_kernel(const EmbedBwdArgs a) {
     const int lane = threadIdx.x & 63;
     const int E4 = a.E >> 2;
     const float fE = (float)a.E;
+    lq_dropout dr = {};
+    if constexpr (DROP) dr = lq_dropout_load(a.drop);
     float4 w[NJ], aw[NJ], ab[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -503,8 +604,8 @@ __global__ __launch_bounds__(256) void embed_rows_bwd_kernel(const EmbedBwdArgs 
         const float mean = a.stats[2 * n], rstd = a.stats[2 * n + 1];
         const float4* srow = reinterpret_cast<const float4*>(a.src + (size_t)k * a.E);
         const float4* prow = a.pos ? reinterpret_cast<const float4*>(a.pos + (size_t)t * a.E) : nullptr;
-        const float4* grow =
-            reinterpret_cast<const float4*>(a.gout + (size_t)(b * a.out_bstride + t * a.out_tstride + a.out_offset));
+        const size_t slot = (size_t)(b * a.out_bstride + t * a.out_tstride + a.out_offset);
+        const float4* grow = reinterpret_cast<const float4*>(a.gout + slot);
         float4 xh[NJ], gh[NJ];
         float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
@@ -518,7 +619,8 @@ __global__ __launch_bounds__(256) void embed_rows_bwd_kernel(const EmbedBwdArgs 
                 }
                 c.x = (c.x - mean) * rstd; c.y = (c.y - mean) * rstd;
                 c.z = (c.z - mean) * rstd; c.w = (c.w - mean) * rstd;
-                const float4 g = grow[q];
+                float4 g = grow[q];
+                if constexpr (DROP) g = emb_drop4(g, dr, slot, a.E, q);
                 aw[j].x += g.x * c.x; aw[j].y += g.y * c.y; aw[j].z += g.z * c.z; aw[j].w += g.w * c.w;
                 ab[j].x += g.x; ab[j].y += g.y; ab[j].z += g.z; ab[j].w += g.w;
                 float4 h;
@@ -597,31 +699,241 @@ static int embed_check(const char* what, int64_t N, int T, int E, int64_t src_ro
     return LIPVQ_OK;
 }
 
-extern "C" {
-
-int lipvq_linear_act_f32(const float* x, const float* W, const float* b, float* y, float* pre, int64_t N, int Kin,
-                         int E, int act, void* stream) {
-    if (!x || !W || !y) return fail(LIPVQ_EINVAL, "lipvq_linear_act_f32: null pointer");
-    if (N < 0 || Kin <= 0 || E <= 0) return fail(LIPVQ_EINVAL, "lipvq_linear_act_f32: bad sizes");
-    if (act < LIPVQ_ACT_NONE || act > LIPVQ_ACT_RELU) return fail(LIPVQ_EINVAL, "lipvq_linear_act_f32: bad activation %d", act);
+// one launch for lipvq_linear_act_f32 (snap == NULL) and lipvq_linear_act_drop_f32: the same kernel choice for both
+static int linear_act_launch(const char* what, const float* x, const float* W, const float* b, float* y, float* pre,
+                             const int64_t* snap, uint32_t site, double p, int64_t N, int Kin, int E, int act, void* stream) {
+    if (!x || !W || !y) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
+    if (N < 0 || Kin <= 0 || E <= 0) return fail(LIPVQ_EINVAL, "%s: bad sizes", what);
+    if (act < LIPVQ_ACT_NONE || act > LIPVQ_ACT_RELU) return fail(LIPVQ_EINVAL, "%s: bad activation %d", what, act);
     if (N == 0) return LIPVQ_OK;
     const int64_t gx = (N + LIN_ROWS - 1) / LIN_ROWS;
-    if (gx > 0x7fffffffLL) return fail(LIPVQ_EUNSUPPORTED, "lipvq_linear_act_f32: N too large");
+    if (gx > 0x7fffffffLL) return fail(LIPVQ_EUNSUPPORTED, "%s: N too large", what);
+    const lq_dropout_src src = snap ? lq_dropout_src_make(snap, site, p) : lq_dropout_src{};
 #define LQ_LIN_BIG_MIN 512          // workgroups of the 128 x 128 tiling needed before it pays (2 per CU)
     const bool narrow = E <= 64;                                  // 256 x 64 tiles instead of 128 x 128
     const int TR = narrow ? 256 : 128, TC = narrow ? 64 : 128;
     const int64_t big_wgs = ((N + TR - 1) / TR) * ((E + TC - 1) / TC);
     if (big_wgs >= LQ_LIN_BIG_MIN && (Kin & 3) == 0) {
         dim3 grid((unsigned)((N + TR - 1) / TR), (unsigned)((E + TC - 1) / TC));
-        if (narrow)
-            hipLaunchKernelGGL((linear_big_kernel<4, 1>), grid, dim3(256), 0, (hipStream_t)stream, x, W, b, y, pre, act, N, Kin, E);
-        else
-            hipLaunchKernelGGL((linear_big_kernel<2, 2>), grid, dim3(256), 0, (hipStream_t)stream, x, W, b, y, pre, act, N, Kin, E);
+        lq_dispatch<0, 1>(snap ? 1 : 0, [&](auto drop) {
+            constexpr bool DROP = decltype(drop)::value != 0;
+            if (narrow)
+                hipLaunchKernelGGL((linear_big_kernel<4, 1, DROP>), grid, dim3(256), 0, (hipStream_t)stream, x, W, b, y, pre, act, src, N, Kin, E);
+            else
+                hipLaunchKernelGGL((linear_big_kernel<2, 2, DROP>), grid, dim3(256), 0, (hipStream_t)stream, x, W, b, y, pre, act, src, N, Kin, E);
+        });
         return check_launch("linear_big_kernel");
     }
     dim3 grid((unsigned)gx, (unsigned)((E + 127) / 128));
-    hipLaunchKernelGGL(linear_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, W, b, y, pre, act, N, Kin, E);
+    if (snap)
+        hipLaunchKernelGGL(linear_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, W, b, y, pre, act, src, N, Kin, E);
+    else
+        hipLaunchKernelGGL(linear_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, W, b, y, pre, act, src, N, Kin, E);
     return check_launch("linear_kernel");
+}
+
+// the in-kernel source of an embed_rows call: the field row is the output row of a slot, so the slots must be whole rows of E
+// floats, and the last output row must fit the 32-bit counter word
+static int embed_drop_check(const char* what, const int64_t* snap, double p, int64_t N, int T, int E, int64_t bstride, int64_t tstride,
+                            int64_t offset) {
+    if (E <= 0 || T <= 0 || N < 0) return fail(LIPVQ_EINVAL, "%s: bad sizes", what);
+    if (bstride % E || tstride % E || offset % E || bstride < 0 || tstride < 0 || offset < 0)
+        return fail(LIPVQ_EINVAL, "%s: output strides/offset must be multiples of E under the in-kernel dropout source", what);
+    const int64_t B = (N + T - 1) / T;
+    const int64_t rows = N == 0 ? 0 : ((B - 1) * bstride + (int64_t)(T - 1) * tstride + offset) / E + 1;
+    return lq_dropout_check(what, snap, p, rows);
+}
+
+// one forward launch for lipvq_embed_rows_f32 (drop == NULL) and lipvq_embed_rows_drop_f32
+static int embed_rows_launch(const char* what, const float* src, const int64_t* idx, const float* pos, const float* ln_w,
+                             const float* ln_b, float eps, float* out, float* stats, const lq_dropout_src* drop, int64_t N, int T,
+                             int E, int64_t src_rows, int64_t out_batch_stride, int64_t out_t_stride, int64_t out_offset,
+                             void* stream) {
+    if (!src || !ln_w || !ln_b || !out) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
+    const int rc = embed_check(what, N, T, E, src_rows, out_batch_stride, out_t_stride, out_offset);
+    if (rc) return rc;
+    if (!idx && src_rows < N) return fail(LIPVQ_EINVAL, "%s: src has fewer rows than N", what);
+    if (N == 0) return LIPVQ_OK;
+    const int chunk = embed_chunk(N);
+    EmbedRowsArgs a{src, idx, pos, ln_w, ln_b, out, stats, N, src_rows, out_batch_stride, out_t_stride, out_offset, T, E,
+                    chunk, eps, drop ? *drop : lq_dropout_src{}};
+    const dim3 grid(embed_grid(16 * chunk, N)), block(256);
+    const size_t lds = (size_t)2 * E * sizeof(float);       // ln_w, ln_b
+    hipStream_t st = (hipStream_t)stream;
+    const int nj = (E / 4 + 15) / 16;
+    lq_dispatch<0, 1>(drop ? 1 : 0, [&](auto dsel) {
+        constexpr bool DROP = decltype(dsel)::value != 0;
+        if (nj <= 2) hipLaunchKernelGGL((embed_rows_kernel<2, DROP>), grid, block, lds, st, a);
+        else if (nj <= 4) hipLaunchKernelGGL((embed_rows_kernel<4, DROP>), grid, block, lds, st, a);
+        else if (nj <= 8) hipLaunchKernelGGL((embed_rows_kernel<8, DROP>), grid, block, lds, st, a);
+        else hipLaunchKernelGGL((embed_rows_kernel<16, DROP>), grid, block, lds, st, a);
+    });
+    return check_launch("embed_rows_kernel");
+}
+
+// the two backward launches, shared by the plain and the _drop entry points (drop == NULL: plain)
+static int embed_rows_bwd_launch(const char* what, const float* gout, const float* src, const int64_t* idx, const float* pos,
+                                 const float* stats, const float* ln_w, float* g_src, float* g_pos, float* g_lnw, float* g_lnb,
+                                 const lq_dropout_src* drop, int64_t N, int T, int E, int64_t src_rows, int64_t out_batch_stride,
+                                 int64_t out_t_stride, int64_t out_offset, void* stream) {
+    if (!gout || !src || !stats || !ln_w) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
+    const int rc = embed_check(what, N, T, E, src_rows, out_batch_stride, out_t_stride, out_offset);
+    if (rc) return rc;
+    if (!idx && src_rows < N) return fail(LIPVQ_EINVAL, "%s: src has fewer rows than N", what);
+    if (N == 0) return LIPVQ_OK;
+    EmbedBwdArgs a{gout, src, idx, pos, stats, ln_w, g_src, g_pos, g_lnw, g_lnb, N, src_rows,
+                   out_batch_stride, out_t_stride, out_offset, T, E, nullptr, nullptr, drop ? *drop : lq_dropout_src{}, nullptr};
+    int g = embed_grid(4, N);
+    if (g > 512) g = 512;                 // fewer waves = fewer final flushes of the LayerNorm gradients
+    const dim3 grid(g), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    lq_dispatch<0, 1>(drop ? 1 : 0, [&](auto dsel) {
+        constexpr bool DROP = decltype(dsel)::value != 0;
+        switch ((E + 255) / 256) {
+            case 1: hipLaunchKernelGGL((embed_rows_bwd_kernel<1, DROP>), grid, block, 0, st, a); break;
+            case 2: hipLaunchKernelGGL((embed_rows_bwd_kernel<2, DROP>), grid, block, 0, st, a); break;
+            case 3: hipLaunchKernelGGL((embed_rows_bwd_kernel<3, DROP>), grid, block, 0, st, a); break;
+            default: hipLaunchKernelGGL((embed_rows_bwd_kernel<4, DROP>), grid, block, 0, st, a); break;
+        }
+    });
+    return check_launch("embed_rows_bwd_kernel");
+}
+
+static int embed_rows_bwd_ws_launch(const char* what, const float* gout, const float* src, const int64_t* idx, const float* pos,
+                                    const float* stats, const float* ln_w, float* g_src, float* g_pos, float* g_lnw, float* g_lnb,
+                                    void* workspace, const lq_dropout_src* drop, int64_t N, int T, int E, int64_t src_rows,
+                                    int64_t out_batch_stride, int64_t out_t_stride, int64_t out_offset, void* stream) {
+    if (!gout || !src || !stats || !ln_w || (idx && !workspace)) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
+    const int rc = embed_check(what, N, T, E, src_rows, out_batch_stride, out_t_stride, out_offset);
+    if (rc) return rc;
+    if (!idx && src_rows < N) return fail(LIPVQ_EINVAL, "%s: src has fewer rows than N", what);
+    const bool okay = idx ? lipvq_embed_rows_bwd_ws_supported(N, T, E, src_rows) != 0 : (N >= 32768 && T <= 1024);
+    if (!okay)
+        return fail(LIPVQ_EUNSUPPORTED, "%s: N=%lld T=%d E=%d src_rows=%lld outside the supported range", what,
+                    (long long)N, T, E, (long long)src_rows);
+    const size_t gvb = ((size_t)N * E * sizeof(float) + 255) & ~(size_t)255, icb = ((size_t)N * sizeof(int64_t) + 255) & ~(size_t)255;
+    // dense rows (idx == NULL): row n of g_src has one writer -- the row gradients ARE g_src, nothing to scatter
+    float* gv = !g_src ? nullptr : (idx ? (float*)workspace : g_src);
+    int64_t* idx_clean = (g_src && idx) ? (int64_t*)((char*)workspace + gvb) : nullptr;
+    EmbedBwdArgs a{gout, src, idx, pos, stats, ln_w, g_src, g_pos, g_lnw, g_lnb, N, src_rows,
+                   out_batch_stride, out_t_stride, out_offset, T, E, gv, idx_clean, drop ? *drop : lq_dropout_src{}, nullptr};
+    const dim3 grid(1024 < T ? T : 1024), block(256);          // >= one workgroup per time step (T <= 1024)
+    hipStream_t st = (hipStream_t)stream;
+    lq_dispatch<0, 1>(drop ? 1 : 0, [&](auto dsel) {
+        constexpr bool DROP = decltype(dsel)::value != 0;
+        switch ((E + 255) / 256) {
+            case 1: hipLaunchKernelGGL((embed_rows_bwd_gv_kernel<1, DROP>), grid, block, 0, st, a); break;
+            case 2: hipLaunchKernelGGL((embed_rows_bwd_gv_kernel<2, DROP>), grid, block, 0, st, a); break;
+            case 3: hipLaunchKernelGGL((embed_rows_bwd_gv_kernel<3, DROP>), grid, block, 0, st, a); break;
+            default: hipLaunchKernelGGL((embed_rows_bwd_gv_kernel<4, DROP>), grid, block, 0, st, a); break;
+        }
+    });
+    if (int e = check_launch("embed_rows_bwd_gv_kernel")) return e;
+    if (!g_src || !idx) return LIPVQ_OK;
+    return lipvq_scatter_add_sorted_f32(gv, idx_clean, g_src, (char*)workspace + gvb + icb, N, (int)src_rows, E, 0, stream);
+}
+
+// The fixed-order backward (lipvq_embed_rows_bwd_det_f32): the gv kernel at any N with its flush sent to partial sums, the
+// second pass, and for indexed rows a table scatter without atomics.  workspace: [part][gv][idx_clean][sorted-scatter workspace].
+static int embed_det_groups(int64_t N, int T) {                    // workgroups per time step
+    const int64_t B = (N + T - 1) / T;
+    int64_t g = (B + 3) / 4, cap = 1024 / T;
+    if (g > cap) g = cap;
+    return (int)(g < 1 ? 1 : g);
+}
+// Indexed rows the counting-sort scatter does not take (N < 32768, or more than 16384 table rows).  The row-order scatter has
+// one workgroup per table row scan all N indices once per 256 columns: src_rows * N * ceil(E / 256) index reads, microseconds at
+// a training step and out of proportion for a large table or a mid-size batch.  Up to LQ_EMB_DET_SCAN_MAX reads it is taken
+// (the table gradient then repeats bit for bit too); beyond, the table rows are added with the fp32 atomics of
+// lipvq_scatter_add_f32, as lipvq_embed_rows_bwd_f32 adds them -- g_pos, g_lnw and g_lnb keep their fixed order either way.
+#define LQ_EMB_DET_SCAN_MAX (1LL << 24)
+static bool embed_det_row_order_scatter(int64_t N, int64_t src_rows, int E) {
+    return src_rows * N * ((E + 255) / 256) <= LQ_EMB_DET_SCAN_MAX;
+}
+
+static size_t embed_det_part_bytes(int64_t N, int T, int E) {
+    return (((size_t)embed_det_groups(N, T) * T * 3 * E * sizeof(float)) + 255) & ~(size_t)255;
+}
+
+static int embed_rows_bwd_det_launch(const char* what, const float* gout, const float* src, const int64_t* idx, const float* pos,
+                                     const float* stats, const float* ln_w, float* g_src, float* g_pos, float* g_lnw, float* g_lnb,
+                                     void* workspace, const lq_dropout_src* drop, int64_t N, int T, int E, int64_t src_rows,
+                                     int64_t out_batch_stride, int64_t out_t_stride, int64_t out_offset, void* stream) {
+    if (!gout || !src || !stats || !ln_w || !workspace) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
+    const int rc = embed_check(what, N, T, E, src_rows, out_batch_stride, out_t_stride, out_offset);
+    if (rc) return rc;
+    if (!idx && src_rows < N) return fail(LIPVQ_EINVAL, "%s: src has fewer rows than N", what);
+    if (T > 1024 || (idx && src_rows > 0x7fffffffLL)) return fail(LIPVQ_EUNSUPPORTED, "%s: T=%d src_rows=%lld", what, T, (long long)src_rows);
+    if ((((uintptr_t)g_pos | (uintptr_t)g_lnw | (uintptr_t)g_lnb | (uintptr_t)workspace) & 15) != 0)
+        return fail(LIPVQ_EINVAL, "%s: g_pos / g_lnw / g_lnb / workspace must be 16-byte aligned", what);
+    if (N == 0) return LIPVQ_OK;
+    const size_t pb = embed_det_part_bytes(N, T, E);
+    const size_t gvb = ((size_t)N * E * sizeof(float) + 255) & ~(size_t)255, icb = ((size_t)N * sizeof(int64_t) + 255) & ~(size_t)255;
+    float* part = (float*)workspace;
+    float* gv = !g_src ? nullptr : (idx ? (float*)((char*)workspace + pb) : g_src);
+    int64_t* idx_clean = (g_src && idx) ? (int64_t*)((char*)workspace + pb + gvb) : nullptr;
+    EmbedBwdArgs a{gout, src, idx, pos, stats, ln_w, g_src, g_pos, g_lnw, g_lnb, N, src_rows,
+                   out_batch_stride, out_t_stride, out_offset, T, E, gv, idx_clean, drop ? *drop : lq_dropout_src{}, part};
+    const int nwg = embed_det_groups(N, T) * T;
+    const dim3 grid(nwg), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    lq_dispatch<0, 1>(drop ? 1 : 0, [&](auto dsel) {
+        constexpr bool DROP = decltype(dsel)::value != 0;
+        switch ((E + 255) / 256) {
+            case 1: hipLaunchKernelGGL((embed_rows_bwd_gv_kernel<1, DROP>), grid, block, 0, st, a); break;
+            case 2: hipLaunchKernelGGL((embed_rows_bwd_gv_kernel<2, DROP>), grid, block, 0, st, a); break;
+            case 3: hipLaunchKernelGGL((embed_rows_bwd_gv_kernel<3, DROP>), grid, block, 0, st, a); break;
+            default: hipLaunchKernelGGL((embed_rows_bwd_gv_kernel<4, DROP>), grid, block, 0, st, a); break;
+        }
+    });
+    if (int e = check_launch("embed_rows_bwd_gv_kernel")) return e;
+    if (g_pos || g_lnw || g_lnb) {
+        const int items = (T + 2) * (E >> 2);
+        hipLaunchKernelGGL(embed_param_reduce_kernel, dim3((items + 15) / 16), block, 0, st, part, nwg, T, E, g_pos, g_lnw, g_lnb);
+        if (int e = check_launch("embed_param_reduce_kernel")) return e;
+    }
+    if (!g_src || !idx) return LIPVQ_OK;
+    if (lipvq_scatter_add_sorted_supported(N, (int)src_rows, E))
+        return lipvq_scatter_add_sorted_f32(gv, idx_clean, g_src, (char*)workspace + pb + gvb + icb, N, (int)src_rows, E, 0, stream);
+    if (embed_det_row_order_scatter(N, src_rows, E)) return lipvq_scatter_add_det_f32(gv, idx_clean, g_src, N, (int)src_rows, E, stream);
+    return lipvq_scatter_add_f32(gv, idx_clean, g_src, N, (int)src_rows, E, stream);
+}
+
+extern "C" {
+
+size_t lipvq_embed_rows_bwd_det_workspace_bytes(int64_t N, int T, int E, int64_t src_rows, int indexed) {
+    if (N <= 0 || T <= 0 || T > 1024 || E <= 0 || src_rows <= 0) return 0;
+    size_t b = embed_det_part_bytes(N, T, E);
+    if (indexed) {
+        b += (((size_t)N * E * sizeof(float) + 255) & ~(size_t)255) + (((size_t)N * sizeof(int64_t) + 255) & ~(size_t)255);
+        if (src_rows <= 0x7fffffffLL && lipvq_scatter_add_sorted_supported(N, (int)src_rows, E))
+            b += lipvq_scatter_add_sorted_workspace_bytes(N, (int)src_rows, E);
+    }
+    return b;
+}
+
+int lipvq_embed_rows_bwd_det_f32(const float* gout, const float* src, const int64_t* idx, const float* pos, const float* stats,
+                                 const float* ln_w, float* g_src, float* g_pos, float* g_lnw, float* g_lnb, void* workspace,
+                                 const int64_t* snap, uint32_t site, double p, int64_t N, int T, int E, int64_t src_rows,
+                                 int64_t out_batch_stride, int64_t out_t_stride, int64_t out_offset, void* stream) {
+    if (!snap)
+        return embed_rows_bwd_det_launch("lipvq_embed_rows_bwd_det_f32", gout, src, idx, pos, stats, ln_w, g_src, g_pos, g_lnw, g_lnb,
+                                         workspace, nullptr, N, T, E, src_rows, out_batch_stride, out_t_stride, out_offset, stream);
+    if (int rc = embed_drop_check("lipvq_embed_rows_bwd_det_f32", snap, p, N, T, E, out_batch_stride, out_t_stride, out_offset)) return rc;
+    const lq_dropout_src drop = lq_dropout_src_make(snap, site, p);
+    return embed_rows_bwd_det_launch("lipvq_embed_rows_bwd_det_f32", gout, src, idx, pos, stats, ln_w, g_src, g_pos, g_lnw, g_lnb,
+                                     workspace, &drop, N, T, E, src_rows, out_batch_stride, out_t_stride, out_offset, stream);
+}
+
+int lipvq_linear_act_f32(const float* x, const float* W, const float* b, float* y, float* pre, int64_t N, int Kin,
+                         int E, int act, void* stream) {
+    return linear_act_launch("lipvq_linear_act_f32", x, W, b, y, pre, nullptr, 0, 0.0, N, Kin, E, act, stream);
+}
+
+int lipvq_linear_act_drop_f32(const float* x, const float* W, const float* b, float* y, float* pre, const int64_t* snap,
+                              uint32_t site, double p, int64_t N, int Kin, int E, int act, void* stream) {
+    if (int rc = lq_dropout_check("lipvq_linear_act_drop_f32", snap, p, N)) return rc;
+    return linear_act_launch("lipvq_linear_act_drop_f32", x, W, b, y, pre, snap, site, p, N, Kin, E, act, stream);
 }
 
 int lipvq_linear_f32(const float* x, const float* W, const float* b, float* y, int64_t N, int Kin, int E,
@@ -632,47 +944,36 @@ int lipvq_linear_f32(const float* x, const float* W, const float* b, float* y, i
 int lipvq_embed_rows_f32(const float* src, const int64_t* idx, const float* pos, const float* ln_w, const float* ln_b,
                          float eps, float* out, float* stats, int64_t N, int T, int E, int64_t src_rows,
                          int64_t out_batch_stride, int64_t out_t_stride, int64_t out_offset, void* stream) {
-    if (!src || !ln_w || !ln_b || !out) return fail(LIPVQ_EINVAL, "lipvq_embed_rows_f32: null pointer");
-    const int rc = embed_check("lipvq_embed_rows_f32", N, T, E, src_rows, out_batch_stride, out_t_stride, out_offset);
-    if (rc) return rc;
-    if (!idx && src_rows < N) return fail(LIPVQ_EINVAL, "lipvq_embed_rows_f32: src has fewer rows than N");
-    if (N == 0) return LIPVQ_OK;
-    const int chunk = embed_chunk(N);
-    EmbedRowsArgs a{src, idx, pos, ln_w, ln_b, out, stats, N, src_rows, out_batch_stride, out_t_stride, out_offset, T, E,
-                    chunk, eps};
-    const dim3 grid(embed_grid(16 * chunk, N)), block(256);
-    const size_t lds = (size_t)2 * E * sizeof(float);       // ln_w, ln_b
-    hipStream_t st = (hipStream_t)stream;
-    const int nj = (E / 4 + 15) / 16;
-    if (nj <= 2) hipLaunchKernelGGL(embed_rows_kernel<2>, grid, block, lds, st, a);
-    else if (nj <= 4) hipLaunchKernelGGL(embed_rows_kernel<4>, grid, block, lds, st, a);
-    else if (nj <= 8) hipLaunchKernelGGL(embed_rows_kernel<8>, grid, block, lds, st, a);
-    else hipLaunchKernelGGL(embed_rows_kernel<16>, grid, block, lds, st, a);
-    return check_launch("embed_rows_kernel");
+    return embed_rows_launch("lipvq_embed_rows_f32", src, idx, pos, ln_w, ln_b, eps, out, stats, nullptr, N, T, E, src_rows,
+                             out_batch_stride, out_t_stride, out_offset, stream);
+}
+
+int lipvq_embed_rows_drop_f32(const float* src, const int64_t* idx, const float* pos, const float* ln_w, const float* ln_b,
+                              float eps, float* out, float* stats, const int64_t* snap, uint32_t site, double p, int64_t N, int T,
+                              int E, int64_t src_rows, int64_t out_batch_stride, int64_t out_t_stride, int64_t out_offset,
+                              void* stream) {
+    if (int rc = embed_drop_check("lipvq_embed_rows_drop_f32", snap, p, N, T, E, out_batch_stride, out_t_stride, out_offset)) return rc;
+    const lq_dropout_src drop = lq_dropout_src_make(snap, site, p);
+    return embed_rows_launch("lipvq_embed_rows_drop_f32", src, idx, pos, ln_w, ln_b, eps, out, stats, &drop, N, T, E, src_rows,
+                             out_batch_stride, out_t_stride, out_offset, stream);
 }
 
 int lipvq_embed_rows_bwd_f32(const float* gout, const float* src, const int64_t* idx, const float* pos,
                              const float* stats, const float* ln_w, float* g_src, float* g_pos, float* g_lnw,
                              float* g_lnb, int64_t N, int T, int E, int64_t src_rows, int64_t out_batch_stride,
                              int64_t out_t_stride, int64_t out_offset, void* stream) {
-    if (!gout || !src || !stats || !ln_w) return fail(LIPVQ_EINVAL, "lipvq_embed_rows_bwd_f32: null pointer");
-    const int rc = embed_check("lipvq_embed_rows_bwd_f32", N, T, E, src_rows, out_batch_stride, out_t_stride, out_offset);
-    if (rc) return rc;
-    if (!idx && src_rows < N) return fail(LIPVQ_EINVAL, "lipvq_embed_rows_bwd_f32: src has fewer rows than N");
-    if (N == 0) return LIPVQ_OK;
-    EmbedBwdArgs a{gout, src, idx, pos, stats, ln_w, g_src, g_pos, g_lnw, g_lnb, N, src_rows,
-                   out_batch_stride, out_t_stride, out_offset, T, E, nullptr, nullptr};
-    int g = embed_grid(4, N);
-    if (g > 512) g = 512;                 // fewer waves = fewer final flushes of the LayerNorm gradients
-    const dim3 grid(g), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    switch ((E + 255) / 256) {
-        case 1: hipLaunchKernelGGL(embed_rows_bwd_kernel<1>, grid, block, 0, st, a); break;
-        case 2: hipLaunchKernelGGL(embed_rows_bwd_kernel<2>, grid, block, 0, st, a); break;
-        case 3: hipLaunchKernelGGL(embed_rows_bwd_kernel<3>, grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL(embed_rows_bwd_kernel<4>, grid, block, 0, st, a); break;
-    }
-    return check_launch("embed_rows_bwd_kernel");
+    return embed_rows_bwd_launch("lipvq_embed_rows_bwd_f32", gout, src, idx, pos, stats, ln_w, g_src, g_pos, g_lnw, g_lnb, nullptr, N, T,
+                                 E, src_rows, out_batch_stride, out_t_stride, out_offset, stream);
+}
+
+int lipvq_embed_rows_bwd_drop_f32(const float* gout, const float* src, const int64_t* idx, const float* pos, const float* stats,
+                                  const float* ln_w, float* g_src, float* g_pos, float* g_lnw, float* g_lnb, const int64_t* snap,
+                                  uint32_t site, double p, int64_t N, int T, int E, int64_t src_rows, int64_t out_batch_stride,
+                                  int64_t out_t_stride, int64_t out_offset, void* stream) {
+    if (int rc = embed_drop_check("lipvq_embed_rows_bwd_drop_f32", snap, p, N, T, E, out_batch_stride, out_t_stride, out_offset)) return rc;
+    const lq_dropout_src drop = lq_dropout_src_make(snap, site, p);
+    return embed_rows_bwd_launch("lipvq_embed_rows_bwd_drop_f32", gout, src, idx, pos, stats, ln_w, g_src, g_pos, g_lnw, g_lnb, &drop, N,
+                                 T, E, src_rows, out_batch_stride, out_t_stride, out_offset, stream);
 }
 
 // Large batches of indexed rows: no atomics on the table or the time embedding (embed_rows_bwd_gv_kernel + the counting-sort
@@ -692,31 +993,18 @@ int lipvq_embed_rows_bwd_ws_f32(const float* gout, const float* src, const int64
                                 const float* ln_w, float* g_src, float* g_pos, float* g_lnw, float* g_lnb, void* workspace,
                                 int64_t N, int T, int E, int64_t src_rows, int64_t out_batch_stride, int64_t out_t_stride,
                                 int64_t out_offset, void* stream) {
-    if (!gout || !src || !stats || !ln_w || (idx && !workspace)) return fail(LIPVQ_EINVAL, "lipvq_embed_rows_bwd_ws_f32: null pointer");
-    const int rc = embed_check("lipvq_embed_rows_bwd_ws_f32", N, T, E, src_rows, out_batch_stride, out_t_stride, out_offset);
-    if (rc) return rc;
-    if (!idx && src_rows < N) return fail(LIPVQ_EINVAL, "lipvq_embed_rows_bwd_ws_f32: src has fewer rows than N");
-    const bool okay = idx ? lipvq_embed_rows_bwd_ws_supported(N, T, E, src_rows) != 0 : (N >= 32768 && T <= 1024);
-    if (!okay)
-        return fail(LIPVQ_EUNSUPPORTED, "lipvq_embed_rows_bwd_ws_f32: N=%lld T=%d E=%d src_rows=%lld outside the supported range",
-                    (long long)N, T, E, (long long)src_rows);
-    const size_t gvb = ((size_t)N * E * sizeof(float) + 255) & ~(size_t)255, icb = ((size_t)N * sizeof(int64_t) + 255) & ~(size_t)255;
-    // dense rows (idx == NULL): row n of g_src has one writer -- the row gradients ARE g_src, nothing to scatter
-    float* gv = !g_src ? nullptr : (idx ? (float*)workspace : g_src);
-    int64_t* idx_clean = (g_src && idx) ? (int64_t*)((char*)workspace + gvb) : nullptr;
-    EmbedBwdArgs a{gout, src, idx, pos, stats, ln_w, g_src, g_pos, g_lnw, g_lnb, N, src_rows,
-                   out_batch_stride, out_t_stride, out_offset, T, E, gv, idx_clean};
-    const dim3 grid(1024 < T ? T : 1024), block(256);          // >= one workgroup per time step (T <= 1024)
-    hipStream_t st = (hipStream_t)stream;
-    switch ((E + 255) / 256) {
-        case 1: hipLaunchKernelGGL(embed_rows_bwd_gv_kernel<1>, grid, block, 0, st, a); break;
-        case 2: hipLaunchKernelGGL(embed_rows_bwd_gv_kernel<2>, grid, block, 0, st, a); break;
-        case 3: hipLaunchKernelGGL(embed_rows_bwd_gv_kernel<3>, grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL(embed_rows_bwd_gv_kernel<4>, grid, block, 0, st, a); break;
-    }
-    if (int e = check_launch("embed_rows_bwd_gv_kernel")) return e;
-    if (!g_src || !idx) return LIPVQ_OK;
-    return lipvq_scatter_add_sorted_f32(gv, idx_clean, g_src, (char*)workspace + gvb + icb, N, (int)src_rows, E, 0, stream);
+    return embed_rows_bwd_ws_launch("lipvq_embed_rows_bwd_ws_f32", gout, src, idx, pos, stats, ln_w, g_src, g_pos, g_lnw, g_lnb,
+                                    workspace, nullptr, N, T, E, src_rows, out_batch_stride, out_t_stride, out_offset, stream);
+}
+
+int lipvq_embed_rows_bwd_ws_drop_f32(const float* gout, const float* src, const int64_t* idx, const float* pos, const float* stats,
+                                     const float* ln_w, float* g_src, float* g_pos, float* g_lnw, float* g_lnb, void* workspace,
+                                     const int64_t* snap, uint32_t site, double p, int64_t N, int T, int E, int64_t src_rows,
+                                     int64_t out_batch_stride, int64_t out_t_stride, int64_t out_offset, void* stream) {
+    if (int rc = embed_drop_check("lipvq_embed_rows_bwd_ws_drop_f32", snap, p, N, T, E, out_batch_stride, out_t_stride, out_offset)) return rc;
+    const lq_dropout_src drop = lq_dropout_src_make(snap, site, p);
+    return embed_rows_bwd_ws_launch("lipvq_embed_rows_bwd_ws_drop_f32", gout, src, idx, pos, stats, ln_w, g_src, g_pos, g_lnw, g_lnb,
+                                    workspace, &drop, N, T, E, src_rows, out_batch_stride, out_t_stride, out_offset, stream);
 }
 
 }  // extern "C"

@@ -10,6 +10,10 @@
  *     philox4x32_10(counter = (col >> 2, row, site, step & 0xffffffff), key = (seed & 0xffffffff, seed >> 32))
  * and the element is KEPT iff  word >= thr,  thr = (uint32) floor(p * 2^32) formed in double (0 < p < 1).  One draw decides
  * four neighbouring columns.  rows < 2^32.  Only the low 32 bits of the step enter: the field repeats after 2^32 steps.
+ *
+ * Sites.  The backbone uses 4 layer + {0, 1, 2}; the embedding stage LIPVQ_DROPOUT_SITE_EMBED (0x40000000) and the default action
+ * branch LIPVQ_DROPOUT_SITE_DEFAULT (0x80000000) + 4 layer + {0, 1, 2, 3} (include/lipvq.h lists the fields).  The site is a
+ * counter word of every draw: modules whose states hold equal (seed, step) draw unrelated fields.
  */
 #ifndef LIPVQ_RNG_H_
 #define LIPVQ_RNG_H_
@@ -69,6 +73,28 @@ LQ_HD lq_dropout lq_dropout_make(uint64_t seed, uint64_t step, uint32_t site, do
 /* the draw that decides columns 4 col4 .. 4 col4 + 3 of `row` */
 LQ_HD lq_philox4 lq_dropout_draw(lq_dropout d, uint32_t row, uint32_t col4) {
     return lq_philox4x32_10(col4, row, d.site, d.step, d.k0, d.k1);
+}
+
+/* what a host entry point hands a dropout kernel: the snap lipvq_dropout_begin wrote (read on the device), the site, and the
+ * threshold and factor of p */
+typedef struct {
+    const int64_t* snap;
+    uint32_t site, thr;
+    float inv_keep;
+} lq_dropout_src;
+
+LQ_HD lq_dropout_src lq_dropout_src_make(const int64_t* snap, uint32_t site, double p) {
+    lq_dropout_src s;
+    s.snap = snap; s.site = site; s.thr = lq_dropout_thr(p); s.inv_keep = lq_dropout_inv_keep(p);
+    return s;
+}
+
+LQ_HD lq_dropout lq_dropout_load(lq_dropout_src s) {
+    const uint64_t seed = (uint64_t)s.snap[0], step = (uint64_t)s.snap[1];
+    lq_dropout d;
+    d.k0 = (uint32_t)(seed & 0xffffffffu); d.k1 = (uint32_t)(seed >> 32); d.step = (uint32_t)(step & 0xffffffffu);
+    d.site = s.site; d.thr = s.thr; d.inv_keep = s.inv_keep;
+    return d;
 }
 
 /* bit w = the decision of column 4 col4 + w (1: kept) */

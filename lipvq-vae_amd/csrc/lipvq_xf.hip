@@ -10,8 +10,11 @@
 // and its backward on lipvq_gpt_layernorm_f32 / lipvq_gpt_layernorm_bwd_f32 (lipvq_gpt.hip) with s = NULL, gres = NULL.
 // All sizes here are small (S = B*T rows of a training step, D <= 256): the kernels are written for launch latency and
 // occupancy of a few workgroups, not for a roofline.
-// ABI: include/lipvq.h ("default action branch").  Tolerance against torch: 1e-5 of each tensor's scale (tests/test_gpu_default.py).
+//   in-kernel dropout      the three attention kernels' <DH, true> instances draw the attention-probability decisions themselves
+//                          (lipvq_rng.h) where the <DH, false> ones read keep bytes: same lanes, same order, same bits
+// ABI: include/lipvq.h ("default action branch", "in-kernel dropout for the embedding stage and the default action branch").  Tolerance against torch: 1e-5 of each tensor's scale (tests/test_gpu_default.py).
 #include "lipvq_common.h"
+#include "lipvq_rng.h"
 
 // ---------------------------------------------------------------------------------------------------
 // spectral norm (torch/nn/utils/spectral_norm.py compute_weight): W [J][K] = weight_orig, u [J], v [K]
@@ -138,9 +141,24 @@ static int attention_args(const char* what, const unsigned char* keep, float kee
 template <typename F>
 static void xf_for_width(int dh, F&& f) { lq_dispatch<8, 16, 32>(dh <= 8 ? 8 : dh <= 16 ? 16 : 32, f); }
 
-template <int DH>
+// PHILOX instances (forward, bwd_q): the decisions of one query `row` for the 64 keys of the tile at k0, bit n = key k0 + n.
+// The tile's 16 draws (4 columns each) are shared by the query's 16 key lanes: lane p runs draw k0 / 4 + p and the lanes OR
+// their nibbles together.  Every lane of the wave must call it (k0 is uniform); lane p then tests bits p, p + 16, p + 32, p + 48.
+__device__ __forceinline__ uint64_t xf_keep_tile_q(lq_dropout d, uint32_t row, int k0, int p) {
+    const uint32_t nib = lq_dropout_keep4(d, row, (uint32_t)(k0 >> 2) + (uint32_t)p) << (4 * (p & 7));
+    uint32_t lo = p < 8 ? nib : 0u, hi = p < 8 ? 0u : nib;
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+        lo |= (uint32_t)__shfl_xor((int)lo, off, 64);
+        hi |= (uint32_t)__shfl_xor((int)hi, off, 64);
+    }
+    return ((uint64_t)hi << 32) | lo;
+}
+
+template <int DH, bool PHILOX>
 __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse,
-                                                        const unsigned char* __restrict__ keep, float inv_keep, int S, int D, int H) {
+                                                        const unsigned char* __restrict__ keep, float inv_keep, lq_dropout_src src,
+                                                        int S, int D, int H) {
     __shared__ float sk[XF_KT][DH + 1], svv[XF_KT][DH + 1];
     const int dh = D / H, h = blockIdx.y;
     const int tid = threadIdx.x, qi = tid >> 4, p = tid & 15;
@@ -156,7 +174,11 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
     }
     double m = -INFINITY;
     float l = 0.0f;
+    lq_dropout dr = {};
+    if constexpr (PHILOX) dr = lq_dropout_load(src);
     for (int k0 = 0; k0 < S; k0 += XF_KT) {
+        uint64_t kb = 0;
+        if constexpr (PHILOX) kb = xf_keep_tile_q(dr, (uint32_t)((size_t)h * S + qc), k0, p);
         __syncthreads();
         for (int i = tid; i < XF_KT * DH; i += 256) {
             const int j = i / DH, d = i - j * DH;
@@ -176,7 +198,9 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
                 const double mn = fmax(m, s);
                 const float c = xf_exp((float)(m - mn)), e = xf_exp((float)(s - mn));
                 l = lq_fma(l, c, e);
-                const float w = keep ? (keep[((size_t)h * S + qc) * S + k0 + j] ? e * inv_keep : 0.0f) : e;
+                float w;
+                if constexpr (PHILOX) w = ((kb >> j) & 1u) ? e * inv_keep : 0.0f;
+                else w = keep ? (keep[((size_t)h * S + qc) * S + k0 + j] ? e * inv_keep : 0.0f) : e;
 #pragma unroll
                 for (int d = 0; d < DH; ++d)
                     acc[d] = lq_fma(acc[d], c, w * svv[j][d]);
@@ -211,20 +235,34 @@ extern "C" int lipvq_attention_f32(const float* qkv, float* out, float* lse, con
     if (!qkv || !out || !lse) return fail(LIPVQ_EINVAL, "attention: null pointer");
     if (int rc = attention_args("attention", keep, keep_prob, S, D, H)) return rc;
     xf_for_width(D / H, [&](auto w) {
-        hipLaunchKernelGGL(attention_kernel<w()>, dim3((unsigned)((S + XF_QB - 1) / XF_QB), H), dim3(256), 0, (hipStream_t)stream, qkv, out,
-                           lse, keep, keep ? 1.0f / keep_prob : 1.0f, (int)S, D, H);
+        hipLaunchKernelGGL((attention_kernel<w(), false>), dim3((unsigned)((S + XF_QB - 1) / XF_QB), H), dim3(256), 0, (hipStream_t)stream,
+                           qkv, out, lse, keep, keep ? 1.0f / keep_prob : 1.0f, lq_dropout_src{}, (int)S, D, H);
     });
     return check_launch("attention");
+}
+
+extern "C" int lipvq_attention_drop_f32(const float* qkv, float* out, float* lse, const int64_t* snap, uint32_t site, double p,
+                                        int64_t S, int D, int H, void* stream) {
+    if (int rc = attention_args("attention_drop", nullptr, 1.0f, S, D, H)) return rc;
+    if (int rc = lq_dropout_check("attention_drop", snap, p, (int64_t)H * S)) return rc;
+    if (!qkv || !out || !lse) return fail(LIPVQ_EINVAL, "attention_drop: null pointer");
+    const lq_dropout_src src = lq_dropout_src_make(snap, site, p);
+    xf_for_width(D / H, [&](auto w) {
+        hipLaunchKernelGGL((attention_kernel<w(), true>), dim3((unsigned)((S + XF_QB - 1) / XF_QB), H), dim3(256), 0, (hipStream_t)stream,
+                           qkv, out, lse, nullptr, src.inv_keep, src, (int)S, D, H);
+    });
+    return check_launch("attention_drop");
 }
 
 // Backward.  delta[h][i] = sum_d dO[i][hd] O[i][hd];  P_ij = exp(s_ij - lse_i);  dP_ij = (keep_ij / keep_prob) dO_i . V_j;
 // dS_ij = P_ij (dP_ij - delta_i);  dQ_i = scale sum_j dS_ij K_j;  dK_j = scale sum_i dS_ij Q_i;  dV_j = sum_i (keep_ij/keep_prob) P_ij dO_i.
 // attention_bwd_q: workgroup = 16 queries x 16 key lanes (as the forward) -> dQ;  attention_bwd_kv: 16 keys x 16 query lanes -> dK, dV.
-template <int DH>
+template <int DH, bool PHILOX>
 __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
                                                               const float* __restrict__ go, const float* __restrict__ lse,
                                                               float* __restrict__ gqkv, float* __restrict__ delta,
-                                                              const unsigned char* __restrict__ keep, float inv_keep, int S, int D, int H) {
+                                                              const unsigned char* __restrict__ keep, float inv_keep,
+                                                              lq_dropout_src src, int S, int D, int H) {
     __shared__ float sk[XF_KT][DH + 1], svv[XF_KT][DH + 1];
     const int dh = D / H, h = blockIdx.y;
     const int tid = threadIdx.x, qi = tid >> 4, p = tid & 15;
@@ -242,7 +280,11 @@ __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const float* __res
     }
     const float ls = lse[(size_t)h * S + qc];
     if (p == 0 && q < S) delta[(size_t)h * S + q] = dl;
+    lq_dropout dr = {};
+    if constexpr (PHILOX) dr = lq_dropout_load(src);
     for (int k0 = 0; k0 < S; k0 += XF_KT) {
+        uint64_t kb = 0;
+        if constexpr (PHILOX) kb = xf_keep_tile_q(dr, (uint32_t)((size_t)h * S + qc), k0, p);
         __syncthreads();
         for (int i = tid; i < XF_KT * DH; i += 256) {
             const int j = i / DH, d = i - j * DH;
@@ -261,7 +303,8 @@ __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const float* __res
                 for (int d = 0; d < DH; ++d)
                     { s = fma((double)qr[d], (double)sk[j][d], s); dp = lq_fma(gor[d], svv[j][d], dp); }
                 const float pr = xf_exp((float)(s - (double)ls));
-                if (keep) dp = keep[((size_t)h * S + qc) * S + k0 + j] ? dp * inv_keep : 0.0f;
+                if constexpr (PHILOX) dp = ((kb >> j) & 1u) ? dp * inv_keep : 0.0f;
+                else if (keep) dp = keep[((size_t)h * S + qc) * S + k0 + j] ? dp * inv_keep : 0.0f;
                 const float ds = pr * (dp - dl) * scale;
 #pragma unroll
                 for (int d = 0; d < DH; ++d)
@@ -280,13 +323,16 @@ __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const float* __res
         for (int d = p; d < dh; d += 16) gqkv[(size_t)q * 3 * D + h * dh + d] = acc[d];
 }
 
-template <int DH>
+// PHILOX: the roles are swapped -- the workgroup's 16 keys are 4 draws wide and a tile has 64 queries: 256 draws, one per thread
+// (query tid >> 2 of the tile, columns 4 (tid & 3) .. + 3 of the 16 keys), left in LDS as nibbles with the tile's other operands.
+template <int DH, bool PHILOX>
 __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ go,
                                                                const float* __restrict__ lse, const float* __restrict__ delta,
                                                                float* __restrict__ gqkv, const unsigned char* __restrict__ keep,
-                                                               float inv_keep, int S, int D, int H) {
+                                                               float inv_keep, lq_dropout_src src, int S, int D, int H) {
     __shared__ float sq[XF_KT][DH + 1], sg[XF_KT][DH + 1];
     __shared__ float sl[XF_KT], sd[XF_KT];
+    __shared__ unsigned char sb[PHILOX ? XF_KT : 1][4];
     const int dh = D / H, h = blockIdx.y;
     const int tid = threadIdx.x, ki = tid >> 4, p = tid & 15;
     const int k = blockIdx.x * XF_QB + ki;
@@ -299,6 +345,8 @@ __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const float* __re
         vr[d] = d < dh ? qkv[(size_t)kc * 3 * D + 2 * D + h * dh + d] : 0.0f;
         ak[d] = 0.0f; av[d] = 0.0f;
     }
+    lq_dropout dr = {};
+    if constexpr (PHILOX) dr = lq_dropout_load(src);
     for (int q0 = 0; q0 < S; q0 += XF_KT) {
         __syncthreads();
         for (int i = tid; i < XF_KT * DH; i += 256) {
@@ -312,6 +360,10 @@ __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const float* __re
             sl[tid] = lse[(size_t)h * S + qj];
             sd[tid] = delta[(size_t)h * S + qj];
         }
+        if constexpr (PHILOX) {
+            const int j = tid >> 2, qj = q0 + j < S ? q0 + j : S - 1;
+            sb[j][tid & 3] = (unsigned char)lq_dropout_keep4(dr, (uint32_t)((size_t)h * S + qj), (uint32_t)(4 * blockIdx.x + (tid & 3)));
+        }
         __syncthreads();
 #pragma unroll
         for (int jj = 0; jj < XF_KT / 16; ++jj) {
@@ -324,7 +376,8 @@ __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const float* __re
                     { s = fma((double)sq[j][d], (double)kr[d], s); dp = lq_fma(sg[j][d], vr[d], dp); }
                 const float pr = xf_exp((float)(s - (double)sl[j]));
                 float kp = 1.0f;
-                if (keep) kp = keep[((size_t)h * S + q0 + j) * S + kc] ? inv_keep : 0.0f;
+                if constexpr (PHILOX) kp = ((sb[j][ki >> 2] >> (ki & 3)) & 1u) ? inv_keep : 0.0f;
+                else if (keep) kp = keep[((size_t)h * S + q0 + j) * S + kc] ? inv_keep : 0.0f;
                 const float ds = pr * (dp * kp - sd[j]);          // (the forward's q was pre-scaled: dK_j = sum_i dS_ij (scale Q_i))
                 const float pv = pr * kp;
 #pragma unroll
@@ -354,8 +407,27 @@ extern "C" int lipvq_attention_bwd_f32(const float* qkv, const float* out, const
     const dim3 grid((unsigned)((S + XF_QB - 1) / XF_QB), H);
     const float ik = keep ? 1.0f / keep_prob : 1.0f;
     xf_for_width(D / H, [&](auto w) {
-        hipLaunchKernelGGL(attention_bwd_q_kernel<w()>, grid, dim3(256), 0, (hipStream_t)stream, qkv, out, gout, lse, gqkv, delta, keep, ik, (int)S, D, H);
-        hipLaunchKernelGGL(attention_bwd_kv_kernel<w()>, grid, dim3(256), 0, (hipStream_t)stream, qkv, gout, lse, delta, gqkv, keep, ik, (int)S, D, H);
+        hipLaunchKernelGGL((attention_bwd_q_kernel<w(), false>), grid, dim3(256), 0, (hipStream_t)stream, qkv, out, gout, lse, gqkv, delta,
+                           keep, ik, lq_dropout_src{}, (int)S, D, H);
+        hipLaunchKernelGGL((attention_bwd_kv_kernel<w(), false>), grid, dim3(256), 0, (hipStream_t)stream, qkv, gout, lse, delta, gqkv,
+                           keep, ik, lq_dropout_src{}, (int)S, D, H);
     });
     return check_launch("attention_bwd");
+}
+
+extern "C" int lipvq_attention_bwd_drop_f32(const float* qkv, const float* out, const float* gout, const float* lse, float* gqkv,
+                                            float* delta, const int64_t* snap, uint32_t site, double p, int64_t S, int D, int H,
+                                            void* stream) {
+    if (int rc = attention_args("attention_bwd_drop", nullptr, 1.0f, S, D, H)) return rc;
+    if (int rc = lq_dropout_check("attention_bwd_drop", snap, p, (int64_t)H * S)) return rc;
+    if (!qkv || !out || !gout || !lse || !gqkv || !delta) return fail(LIPVQ_EINVAL, "attention_bwd_drop: null pointer");
+    const dim3 grid((unsigned)((S + XF_QB - 1) / XF_QB), H);
+    const lq_dropout_src src = lq_dropout_src_make(snap, site, p);
+    xf_for_width(D / H, [&](auto w) {
+        hipLaunchKernelGGL((attention_bwd_q_kernel<w(), true>), grid, dim3(256), 0, (hipStream_t)stream, qkv, out, gout, lse, gqkv, delta,
+                           nullptr, src.inv_keep, src, (int)S, D, H);
+        hipLaunchKernelGGL((attention_bwd_kv_kernel<w(), true>), grid, dim3(256), 0, (hipStream_t)stream, qkv, gout, lse, delta, gqkv,
+                           nullptr, src.inv_keep, src, (int)S, D, H);
+    });
+    return check_launch("attention_bwd_drop");
 }

@@ -17,6 +17,12 @@ treats as ONE unbatched sequence: every action of the batch attends to every oth
 kept).  Dropout (p = 0.1, four places per layer) follows torch's semantics with torch's own RNG -- elementwise ones through
 ``F.dropout``, the attention-probability one as a keep-mask handed to the kernel -- so training-mode outputs match the
 reference in distribution, eval-mode outputs to 1e-5 (tests/test_gpu_default.py).
+
+``set_dropout_source("kernel")`` (opt-in) decides the four dropouts of every encoder layer inside the kernels instead, at sites
+``ops.DROPOUT_SITE_DEFAULT + 4 layer + k`` (include/lipvq.h): k = 0 the attention probabilities in lipvq_attention_drop_f32 /
+_bwd_drop_f32, k = 1 dropout1 and k = 2 dropout2 in the residual launch that adds the branch (lipvq_gpt_layernorm_drop_f32 /
+_bwd_drop_f32), k = 3 the FFN's inner dropout in linear1's epilogue (lipvq_linear_act_drop_f32 / lipvq_act_bwd_drop_f32).  One
+``ops.dropout_begin`` launch per training forward; no ``rand``, no mask tensor, nothing of it saved, torch's generators untouched.
 """
 from __future__ import annotations
 
@@ -26,7 +32,8 @@ import torch.nn.functional as F
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .nnfn import AddLayerNormFn, GraphedEval, LinearFn, first_order_only
+from .nnfn import (AddDropLayerNormFn, AddLayerNormFn, AttentionDropFn, GraphedEval, KernelDropoutSource, LinearDropFn, LinearFn,
+                   first_order_only)
 from .ops import ACT_GELU, ACT_NONE
 
 
@@ -61,10 +68,11 @@ class _AttentionFn(torch.autograd.Function):
         return ops.attention_bwd(qkv, out, gout.contiguous(), lse, ctx.nhead, ctx.keep, ctx.keep_prob), None, None, None
 
 
-class DefaultActionNetwork(nn.Sequential):
+class DefaultActionNetwork(KernelDropoutSource, nn.Sequential):
     """Drop-in for the reference's default ``action_network`` (obs_nets.py:1244-1260)."""
 
     NHEAD, FF = 8, 256
+    DROPOUT_OWNER = "DefaultActionNetwork"
 
     def __init__(self, action_input_shape: int, action_output_shape: int, num_layers: int = 4):
         D = int(action_output_shape)
@@ -97,6 +105,9 @@ class DefaultActionNetwork(nn.Sequential):
         h = LinearFn.apply(h, self._sn_weight(self[2]), self[2].bias, ACT_GELU)
         h = LinearFn.apply(h, self._sn_weight(self[4]), self[4].bias, ACT_NONE)
         S = h.shape[0]
+        if self._kernel_dropout():
+            h = self._encoder_kernel_dropout(h)
+            return LinearFn.apply(h, self[6].weight, self[6].bias, ACT_NONE)
         for layer in self[5].layers:
             attn = layer.self_attn
             p = float(attn.dropout) if self.training else 0.0
@@ -115,6 +126,35 @@ class DefaultActionNetwork(nn.Sequential):
             f = F.dropout(f, layer.dropout2.p, self.training)
             h = AddLayerNormFn.apply(h, f, layer.norm2.weight, layer.norm2.bias, layer.norm2.eps, False)[1]
         return LinearFn.apply(h, self[6].weight, self[6].bias, ACT_NONE)
+
+    def _encoder_kernel_dropout(self, h):
+        """The encoder layers of a training forward under the in-kernel source: one dropout_begin launch, then per layer the
+        launches of the eval forward, the _drop form wherever a p is positive (a site with p == 0 takes the plain entry point)."""
+        snap = self._dropout_begin(h.device)
+
+        def add_ln(a, b, site, p, norm):
+            if p > 0.0:
+                return AddDropLayerNormFn.apply(a, b, norm.weight, norm.bias, norm.eps, False, snap, site, p)[1]
+            return AddLayerNormFn.apply(a, b, norm.weight, norm.bias, norm.eps, False)[1]
+
+        for i, layer in enumerate(self[5].layers):
+            attn, site = layer.self_attn, ops.DROPOUT_SITE_DEFAULT + 4 * i
+            p_att, p1 = self._dropout_p(attn.dropout, "attention dropout"), self._dropout_p(layer.dropout1.p, "dropout1")
+            p2, p_ff = self._dropout_p(layer.dropout2.p, "dropout2"), self._dropout_p(layer.dropout.p, "dropout")
+            qkv = LinearFn.apply(h, attn.in_proj_weight, attn.in_proj_bias, ACT_NONE)
+            if p_att > 0.0:
+                a = AttentionDropFn.apply(qkv, self.NHEAD, snap, site, p_att)
+            else:
+                a = _AttentionFn.apply(qkv, self.NHEAD, None, 1.0)
+            a = LinearFn.apply(a, attn.out_proj.weight, attn.out_proj.bias, ACT_NONE)
+            h = add_ln(h, a, site + 1, p1, layer.norm1)
+            if p_ff > 0.0:
+                f = LinearDropFn.apply(h, layer.linear1.weight, layer.linear1.bias, ACT_GELU, snap, site + 3, p_ff)
+            else:
+                f = LinearFn.apply(h, layer.linear1.weight, layer.linear1.bias, ACT_GELU)
+            f = LinearFn.apply(f, layer.linear2.weight, layer.linear2.bias, ACT_NONE)
+            h = add_ln(h, f, site + 2, p2, layer.norm2)
+        return h
 
 
 class GraphedDefaultBranch(GraphedEval):

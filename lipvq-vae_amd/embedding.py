@@ -15,7 +15,10 @@ stack/view/cat copies), and for the LipVQ tokenizer -- whose output rows ARE cod
 collapses into a [K, E] table rebuilt only when a parameter changes; the per-action work is a gather + LayerNorm driven
 by the tokenizer's int64 indices, so z_latent never round-trips HBM.  Gradients (embed_encoder, time embedding,
 LayerNorm, and the dense inputs; NOT the codebook: z_latent is detached in the reference, v5:74) come from the
-library's backward kernels wrapped in torch.autograd.Functions.  Dropout stays torch's (identity in eval).
+library's backward kernels wrapped in torch.autograd.Functions.  Dropout (identity in eval) is torch's ``nn.Dropout`` on the
+finished tensor by default; ``set_dropout_source("kernel")`` decides it inside the stream launches instead (site
+``ops.DROPOUT_SITE_EMBED``, field row = the output row b S + s, col = e; include/lipvq.h): no mask tensor, no extra launch over
+the [B, S, E] tensor, torch's generators untouched, and the backward launches regenerate the decisions.
 """
 from __future__ import annotations
 
@@ -25,7 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .nnfn import KernelFunction, LinearFn, first_order_only, wants_backward
+from .nnfn import KernelDropoutSource, KernelFunction, LinearFn, first_order_only, wants_backward
 from .ops import ACT_NONE
 from .tokenizer import _PackCache
 
@@ -45,25 +48,28 @@ def sinusoidal_table(T: int, E: int, device) -> torch.Tensor:
 class _EmbedStreamsFn(KernelFunction):
     """LayerNorm(src_s[idx_s | n] + pos[t]) for every stream s, each written into its slots of ONE output tensor.
 
-    slots: tuple of (t_stride, offset) in floats per stream; the batch stride is the whole [S, E] block."""
+    slots: tuple of (t_stride, offset) in floats per stream; the batch stride is the whole [S, E] block.
+    dropout: None, or (snap, site, p) of the in-kernel source -- every stream's launch then stores its rows times the mask factor
+    of one shared [B S, E] field (the row is the output slot's), and the backward launches read gout times the same factor,
+    regenerated: no mask is saved."""
 
     @staticmethod
-    def forward(ctx, pos, ln_w, ln_b, eps, B, T, S, slots, idxs, *srcs):
+    def forward(ctx, pos, ln_w, ln_b, eps, B, T, S, slots, idxs, dropout, *srcs):
         E = ln_w.numel()
         out = torch.empty((B, S, E), device=ln_w.device, dtype=torch.float32)
         need = wants_backward(ctx)
         stats = []
         for (tstride, offset), idx, src in zip(slots, idxs, srcs):
             stats.append(ops.embed_rows(src, idx, pos, ln_w, ln_b, eps, out, B * T, T, S * E, tstride, offset,
-                                        want_stats=need))
-        ctx.meta = (B, T, S, slots, idxs)
+                                        want_stats=need, dropout=dropout))
+        ctx.meta = (B, T, S, slots, idxs, dropout)
         ctx.save_for_backward(pos, ln_w, *[s for s in stats if s is not None], *srcs)
         return out
 
     @staticmethod
     @first_order_only
     def backward(ctx, gout):
-        B, T, S, slots, idxs = ctx.meta
+        B, T, S, slots, idxs, dropout = ctx.meta
         n = len(slots)
         pos, ln_w, *rest = ctx.saved_tensors
         stats, srcs = rest[:n], rest[n:]
@@ -74,15 +80,18 @@ class _EmbedStreamsFn(KernelFunction):
         g_lnb = torch.zeros(E, device=gout.device, dtype=torch.float32) if ctx.needs_input_grad[2] else None
         g_srcs = []
         for i, ((tstride, offset), idx, src, st) in enumerate(zip(slots, idxs, srcs, stats)):
-            want = ctx.needs_input_grad[9 + i]
+            want = ctx.needs_input_grad[10 + i]
             g_src = (torch.zeros_like(src) if idx is not None else torch.empty_like(src)) if want else None
-            ops.embed_rows_bwd(gout, src, idx, pos, st, ln_w, g_src, g_pos, g_lnw, g_lnb, B * T, T, S * E, tstride, offset)
+            ops.embed_rows_bwd(gout, src, idx, pos, st, ln_w, g_src, g_pos, g_lnw, g_lnb, B * T, T, S * E, tstride, offset,
+                               dropout=dropout)
             g_srcs.append(g_src)
-        return (g_pos, g_lnw, g_lnb, None, None, None, None, None, None, *g_srcs)
+        return (g_pos, g_lnw, g_lnb, None, None, None, None, None, None, None, *g_srcs)
 
 
-class ICLInputEmbedding(nn.Module):
+class ICLInputEmbedding(KernelDropoutSource, nn.Module):
     """Embedding stage of the reference's ICLTransformer (ob:2425-2450, 2485-2543, 2580-2596) on the HIP path."""
+
+    DROPOUT_OWNER = "ICLInputEmbedding"
 
     def __init__(self, input_dim, embed_dim=512, context_length=10, emb_dropout=0.1, sinusoidal_embedding=False,
                  nn_parameter_for_timesteps=True):
@@ -146,9 +155,16 @@ class ICLInputEmbedding(nn.Module):
 
     def _embed(self, B, T, S, slots, idxs, srcs):
         ln = self.nets["embed_ln"]
-        out = _EmbedStreamsFn.apply(self.time_table(T), ln.weight, ln.bias, ln.eps, B, T, S, tuple(slots), tuple(idxs),
+        drop = self.nets["embed_drop"]
+        if self._kernel_dropout():                          # the in-kernel source: embed_drop rides on the stream launches
+            p = self._dropout_p(drop.p, "embed_drop")
+            if p > 0.0:
+                snap = self._dropout_begin(ln.weight.device)
+                return _EmbedStreamsFn.apply(self.time_table(T), ln.weight, ln.bias, ln.eps, B, T, S, tuple(slots), tuple(idxs),
+                                             (snap, ops.DROPOUT_SITE_EMBED, p), *srcs)
+        out = _EmbedStreamsFn.apply(self.time_table(T), ln.weight, ln.bias, ln.eps, B, T, S, tuple(slots), tuple(idxs), None,
                                     *srcs)
-        return self.nets["embed_drop"](out)                                                # ob:2541
+        return drop(out)                                                                   # ob:2541
 
     # -- the reference's entry points -----------------------------------------------------------------
     def input_embedding(self, inputs: torch.Tensor) -> torch.Tensor:

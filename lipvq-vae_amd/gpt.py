@@ -56,7 +56,8 @@ import torch.nn.functional as F
 
 from . import ops
 from .derived import stamp
-from .nnfn import AddDropLayerNormFn, AddLayerNormFn, GraphedEval, KernelFunction, LinearFn, first_order_only, wants_backward
+from .nnfn import (AddDropLayerNormFn, AddLayerNormFn, GraphedEval, KernelDropoutSource, KernelFunction, LinearFn, first_order_only,
+                   wants_backward)
 from .ops import ACT_GELU, ACT_NONE
 
 __all__ = ["GPTBackbone", "GraphedGPTBackbone", "PromptCache", "PromptedGPTBackbone", "StalePromptCache"]
@@ -131,10 +132,11 @@ class _SelfAttentionBlock(nn.Module):
         self.nets["ln2"] = nn.LayerNorm(embed_dim)
 
 
-class GPTBackbone(nn.Module):
+class GPTBackbone(KernelDropoutSource, nn.Module):
     """Drop-in for the reference's ``GPT_Backbone`` (transformers.py:321-440) on the HIP library."""
 
     MAX_CONTEXT, MAX_EMBED, HEAD_WIDTHS = 128, 1024, (16, 32, 64)
+    DROPOUT_OWNER = "GPTBackbone"
 
     def __init__(self, embed_dim, context_length, causal=True, attn_dropout=0.1, block_output_dropout=0.1, num_layers=6,
                  num_heads=8, activation="gelu"):
@@ -163,7 +165,7 @@ class GPTBackbone(nn.Module):
         self.nets["output_ln"] = nn.LayerNorm(embed_dim)
         self.apply(self._init_weights)
         self._matmul_precision = "fp32"
-        self._dropout_source = "torch"
+        self._dropout_source = "torch"            # (set_dropout_source, reseed_dropout, dropout_state: nnfn.KernelDropoutSource)
 
     @property
     def matmul_precision(self) -> str:
@@ -183,51 +185,6 @@ class GPTBackbone(nn.Module):
         if precision not in ("fp32", "bf16", "bf16x3"):
             raise ValueError(f"GPTBackbone: matmul precision must be 'fp32', 'bf16' or 'bf16x3', got {precision!r}")
         self._matmul_precision = precision
-        return self
-
-    @property
-    def dropout_source(self) -> str:
-        """"torch" (default) or "kernel": where training-mode dropout decisions come from (set_dropout_source)."""
-        return self._dropout_source
-
-    def set_dropout_source(self, source: str, seed: int | None = None) -> "GPTBackbone":
-        """"kernel": the three dropouts of every block (attention probabilities, attention-output branch, MLP branch) are decided
-        inside the HIP kernels that touch those elements, each decision a pure function of (seed, step, site, row, col)
-        (include/lipvq.h, "in-kernel dropout"; site = 4 layer + 0 / 1 / 2).  No mask tensor is drawn, stored or saved for the
-        backward, and torch's generators are not touched.  A training-mode forward makes one ``ops.dropout_begin`` launch, which
-        hands the call its (seed, step) and advances the step on the device -- also under ``torch.no_grad()`` and inside a
-        captured graph, where every replay advances it.  "torch" restores the default (masks from torch's generator) bit for bit.
-        Eval mode ignores the source.
-
-        The state, ``dropout_state`` -- a device int64[2] tensor (seed, step) --, is created by the first call with "kernel" (never
-        at construction: a seeded construction consumes torch's RNG exactly as before), seeded with ``seed`` or, for None,
-        ``torch.initial_seed()``; a later call with a seed reseeds it (step 0), one without leaves it.  It is a non-persistent
-        buffer: ``.to()`` moves it, ``state_dict()`` does not hold it.  Returns self."""
-        if source not in ("torch", "kernel"):
-            raise ValueError(f"GPTBackbone: dropout source must be 'torch' or 'kernel', got {source!r}")
-        if source == "kernel":
-            if getattr(self, "_dropout_state", None) is None:
-                dev = next(self.parameters()).device
-                self.register_buffer("_dropout_state", torch.zeros(2, dtype=torch.int64, device=dev), persistent=False)
-                self.reseed_dropout(torch.initial_seed() if seed is None else seed)
-            elif seed is not None:
-                self.reseed_dropout(seed)
-        self._dropout_source = source
-        return self
-
-    @property
-    def dropout_state(self):
-        """The device int64[2] tensor (seed, step) of the in-kernel source, None before the first set_dropout_source("kernel").
-        Pass it to ``icl.GraphedPolicyStep(..., extra_state=[net.dropout_state])`` so that the warm-up steps do not advance it."""
-        return getattr(self, "_dropout_state", None)
-
-    def reseed_dropout(self, seed: int, step: int = 0) -> "GPTBackbone":
-        """Set the in-kernel source's (seed, step) in place: seed any integer (taken modulo 2^64), step the next forward's."""
-        if getattr(self, "_dropout_state", None) is None:
-            raise RuntimeError("GPTBackbone.reseed_dropout: call set_dropout_source('kernel') first (it creates the state)")
-        words = [int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)]
-        words = [v - 2 ** 64 if v >= 2 ** 63 else v for v in words]          # (the bit pattern, as int64)
-        self._dropout_state.copy_(torch.tensor(words, dtype=torch.int64))
         return self
 
     @staticmethod
@@ -250,7 +207,7 @@ class GPTBackbone(nn.Module):
         x = inputs.contiguous().float()
         B, L, H = x.shape[0], self.context_length, self.num_heads
         prec = self._matmul_precision
-        if self.training and self._dropout_source == "kernel":
+        if self._kernel_dropout():
             return self._forward_kernel_dropout(x)
         a, b = x, None
         for blk in self.nets["transformer"]:
@@ -286,15 +243,10 @@ class GPTBackbone(nn.Module):
         the _drop forms where a p is positive.  A branch's dropout rides on the residual launch that adds the branch: the
         attention-output branch's on ln2, the MLP branch's on the NEXT block's ln1 (the closing output_ln for the last)."""
         H, prec = self.num_heads, self._matmul_precision
-        if self._dropout_state.device != x.device:
-            raise RuntimeError("GPTBackbone: the dropout state is not on the input's device (move the module with .to())")
-        snap = ops.dropout_begin(self._dropout_state)
+        snap = self._dropout_begin(x.device)
 
         def p_of(module, what):
-            p = float(module.p)
-            if p >= 1.0:
-                raise ValueError(f"GPTBackbone: {what} p={p} under the kernel dropout source (0 <= p < 1)")
-            return p
+            return self._dropout_p(module.p, what)
 
         def add_ln(a, b, drop, ln, want_s):
             if drop is not None and drop[1] > 0.0:

@@ -12,7 +12,8 @@ from . import ops
 from .capture import capture, copy_in, warm_up
 from .ops import ACT_NONE
 
-__all__ = ["LinearFn", "AddLayerNormFn", "AddDropLayerNormFn", "GraphedEval", "KernelFunction", "first_order_only", "wants_backward"]
+__all__ = ["LinearFn", "LinearDropFn", "AddLayerNormFn", "AddDropLayerNormFn", "AttentionDropFn", "GraphedEval", "KernelDropoutSource",
+           "KernelFunction", "first_order_only", "wants_backward"]
 
 _applying = threading.local()
 
@@ -108,6 +109,61 @@ class LinearFn(KernelFunction):
         return gx, gW, gb, None, None
 
 
+class LinearDropFn(KernelFunction):
+    """act(x W^T + b) * m with the dropout decided in the Linear's epilogue (in-kernel source: snap, site, p; field = the rows and
+    columns of the 2-D result).  fp32 only.  No mask is saved: the backward's first launch forms act'(pre) (gy m) from the
+    regenerated decisions (ops.act_bwd_drop), then the input-gradient Linear and the wgrad kernel of LinearFn follow."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, act, snap, site, p):
+        ctx.act, ctx.has_bias, ctx.shape, ctx.dropout = act, b is not None, x.shape, (snap, site, p)
+        x2 = x if x.dim() == 2 else x.reshape(-1, x.shape[-1])
+        if not wants_backward(ctx):
+            y = ops.linear_act_drop(x2, W, b, act, ctx.dropout)
+        elif act != ACT_NONE:
+            y, pre = ops.linear_act_drop(x2, W, b, act, ctx.dropout, save_pre=True)
+            ctx.save_for_backward(x2, W, pre)
+        else:
+            y = ops.linear_act_drop(x2, W, b, act, ctx.dropout)
+            ctx.save_for_backward(x2, W)
+        return y if x.dim() == 2 else y.view(*x.shape[:-1], W.shape[0])
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, gy):
+        gy = gy.reshape(-1, gy.shape[-1]).contiguous()
+        if ctx.act != ACT_NONE:
+            x2, W, pre = ctx.saved_tensors
+        else:
+            (x2, W), pre = ctx.saved_tensors, None
+        gy = ops.act_bwd_drop(gy, pre, ctx.act, ctx.dropout)
+        gx = gW = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = ops.linear(gy, W.t().contiguous()).view(ctx.shape)
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            gW, gb = ops.wgrad(gy, x2, want_bias=ctx.has_bias)
+        return gx, gW, gb, None, None, None, None
+
+
+class AttentionDropFn(KernelFunction):
+    """Unbatched multi-head self-attention over qkv [S, 3D] (ops.attention) with the attention-probability dropout drawn inside
+    the kernels (in-kernel source: snap, site, p).  No mask is saved: the two backward launches regenerate the decisions."""
+
+    @staticmethod
+    def forward(ctx, qkv, nhead, snap, site, p):
+        out, lse = ops.attention_drop(qkv, nhead, (snap, site, p))
+        if wants_backward(ctx):
+            ctx.nhead, ctx.dropout = nhead, (snap, site, p)
+            ctx.save_for_backward(qkv, out, lse)
+        return out
+
+    @staticmethod
+    @first_order_only
+    def backward(ctx, gout):
+        qkv, out, lse = ctx.saved_tensors
+        return ops.attention_bwd_drop(qkv, out, gout.contiguous(), lse, ctx.nhead, ctx.dropout), None, None, None, None
+
+
 class AddLayerNormFn(KernelFunction):
     """(s, y) = (a + b, LayerNorm(a + b) w + bias), b optional; s is None unless want_s (a post-norm residual and the closing
     LayerNorm of a pre-norm stack discard it, and without b the caller keeps using a).  Backward: the gradient of a and of b is
@@ -160,6 +216,78 @@ class AddDropLayerNormFn(KernelFunction):
         need = ctx.needs_input_grad
         return (g if need[0] else None, gbr if need[1] else None, gw if need[2] else None, gb if need[3] else None,
                 None, None, None, None, None)
+
+
+class KernelDropoutSource:
+    """Mixin of the modules with training-mode dropout (GPTBackbone, ICLInputEmbedding, DefaultActionNetwork): where the decisions
+    come from, and the state of the in-kernel source.  The host class is an ``nn.Module``; nothing is created at construction
+    (the attributes are looked up with defaults), so a seeded construction consumes torch's RNG exactly as without the mixin."""
+
+    DROPOUT_OWNER = None        # the class name the messages carry; a subclass keeps its base's texts unless it sets its own
+
+    def _dropout_owner(self) -> str:
+        return self.DROPOUT_OWNER or type(self).__name__
+
+    @property
+    def dropout_source(self) -> str:
+        """"torch" (default) or "kernel": where training-mode dropout decisions come from (set_dropout_source)."""
+        return getattr(self, "_dropout_source", "torch")
+
+    def set_dropout_source(self, source: str, seed: int | None = None):
+        """"kernel": every training-mode dropout of the module is decided inside the HIP kernels that touch those elements, each
+        decision a pure function of (seed, step, site, row, col) (include/lipvq.h, "in-kernel dropout"; the module's docstring
+        lists its sites).  No mask tensor is drawn, stored or saved for the backward, and torch's generators are not touched.  A
+        training-mode forward makes one ``ops.dropout_begin`` launch, which hands the call its (seed, step) and advances the step
+        on the device -- also under ``torch.no_grad()`` and inside a captured graph, where every replay advances it.  "torch"
+        restores the default (masks from torch's generator) bit for bit.  Eval mode ignores the source.
+
+        The state, ``dropout_state`` -- a device int64[2] tensor (seed, step) --, is created by the first call with "kernel" (never
+        at construction: a seeded construction consumes torch's RNG exactly as before), seeded with ``seed`` or, for None,
+        ``torch.initial_seed()``; a later call with a seed reseeds it (step 0), one without leaves it.  It is a non-persistent
+        buffer: ``.to()`` moves it, ``state_dict()`` does not hold it.  Each module owns its state; the sites of different
+        modules differ, so equal (seed, step) pairs still give unrelated fields.  Returns self."""
+        if source not in ("torch", "kernel"):
+            raise ValueError(f"{self._dropout_owner()}: dropout source must be 'torch' or 'kernel', got {source!r}")
+        if source == "kernel":
+            if getattr(self, "_dropout_state", None) is None:
+                dev = next(self.parameters()).device
+                self.register_buffer("_dropout_state", torch.zeros(2, dtype=torch.int64, device=dev), persistent=False)
+                self.reseed_dropout(torch.initial_seed() if seed is None else seed)
+            elif seed is not None:
+                self.reseed_dropout(seed)
+        self._dropout_source = source
+        return self
+
+    @property
+    def dropout_state(self):
+        """The device int64[2] tensor (seed, step) of the in-kernel source, None before the first set_dropout_source("kernel").
+        Pass it to ``icl.GraphedPolicyStep(..., extra_state=[net.dropout_state])`` so that the warm-up steps do not advance it."""
+        return getattr(self, "_dropout_state", None)
+
+    def reseed_dropout(self, seed: int, step: int = 0):
+        """Set the in-kernel source's (seed, step) in place: seed any integer (taken modulo 2^64), step the next forward's."""
+        if getattr(self, "_dropout_state", None) is None:
+            raise RuntimeError(f"{self._dropout_owner()}.reseed_dropout: call set_dropout_source('kernel') first (it creates the state)")
+        words = [int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)]
+        words = [v - 2 ** 64 if v >= 2 ** 63 else v for v in words]          # (the bit pattern, as int64)
+        self._dropout_state.copy_(torch.tensor(words, dtype=torch.int64))
+        return self
+
+    def _kernel_dropout(self) -> bool:
+        """Is this call's dropout the in-kernel source's?  (Training mode only: eval ignores the source.)"""
+        return self.training and getattr(self, "_dropout_source", "torch") == "kernel"
+
+    def _dropout_begin(self, device):
+        """The snap of one training forward: one dropout_begin launch on the module's own state."""
+        if self._dropout_state.device != device:
+            raise RuntimeError(f"{self._dropout_owner()}: the dropout state is not on the input's device (move the module with .to())")
+        return ops.dropout_begin(self._dropout_state)
+
+    def _dropout_p(self, p, what) -> float:
+        p = float(p)
+        if p >= 1.0:
+            raise ValueError(f"{self._dropout_owner()}: {what} p={p} under the kernel dropout source (0 <= p < 1)")
+        return p
 
 
 class GraphedEval:

@@ -803,9 +803,11 @@ def _embed_args(src, idx, pos, N, T, E):
     return idx, pos
 
 
-def embed_rows(src, idx, pos, ln_w, ln_b, eps, out, N, T, bstride, tstride, offset, want_stats=False):
+def embed_rows(src, idx, pos, ln_w, ln_b, eps, out, N, T, bstride, tstride, offset, want_stats=False, dropout=None):
     """out[slot(n)] = LayerNorm(src[idx[n] | n] + pos[n % T]) * ln_w + ln_b, slot(b*T+t) = b*bstride + t*tstride + offset
-    floats into ``out`` (reference obs_nets.py:2537-2540 and the interleave of :2584-2596).  Returns stats [N,2] or None."""
+    floats into ``out`` (reference obs_nets.py:2537-2540 and the interleave of :2584-2596).  Returns stats [N,2] or None.
+    dropout=(snap, site, p): the stored rows are multiplied by the in-kernel source's mask factor, decided at (output row
+    slot // E, column e); stats stay the pre-dropout statistics."""
     src, ln_w, ln_b, out = _chk(src, "src"), _chk(ln_w, "ln_w"), _chk(ln_b, "ln_b"), _chk(out, "out")
     E = ln_w.numel()
     idx, pos = _embed_args(src, idx, pos, N, T, E)
@@ -816,14 +818,21 @@ def embed_rows(src, idx, pos, ln_w, ln_b, eps, out, N, T, bstride, tstride, offs
             raise ValueError("embed_rows: the output slots do not fit in `out`")
     stats = torch.empty((N, 2), device=src.device, dtype=torch.float32) if want_stats else None
     with _on(src.device):
+        if dropout is not None:
+            snap, site, p = _dropout_args("embed_rows", dropout, src.device)
+            check(lib.lipvq_embed_rows_drop_f32(_ptr(src), _ptr(idx), _ptr(pos), _ptr(ln_w), _ptr(ln_b), float(eps), _ptr(out),
+                                                _ptr(stats), _ptr(snap), site, p, N, T, E, src.shape[0], bstride, tstride, offset,
+                                                _stream()), "lipvq_embed_rows_drop_f32")
+            return stats
         check(lib.lipvq_embed_rows_f32(_ptr(src), _ptr(idx), _ptr(pos), _ptr(ln_w), _ptr(ln_b), float(eps), _ptr(out),
                                        _ptr(stats), N, T, E, src.shape[0], bstride, tstride, offset, _stream()),
               "lipvq_embed_rows_f32")
     return stats
 
 
-def embed_rows_bwd(gout, src, idx, pos, stats, ln_w, g_src, g_pos, g_lnw, g_lnb, N, T, bstride, tstride, offset):
-    """Backward of embed_rows; accumulates into g_src / g_pos / g_lnw / g_lnb (each may be None)."""
+def embed_rows_bwd(gout, src, idx, pos, stats, ln_w, g_src, g_pos, g_lnw, g_lnb, N, T, bstride, tstride, offset, dropout=None):
+    """Backward of embed_rows; accumulates into g_src / g_pos / g_lnw / g_lnb (each may be None), every sum in a fixed order
+    (lipvq_embed_rows_bwd_det_f32).  dropout=(snap, site, p) of the forward: gout is read as gout * m, the decisions regenerated."""
     gout, src, stats, ln_w = _chk(gout, "gout"), _chk(src, "src"), _chk(stats, "stats"), _chk(ln_w, "ln_w")
     E = ln_w.numel()
     idx, pos = _embed_args(src, idx, pos, N, T, E)
@@ -831,20 +840,26 @@ def embed_rows_bwd(gout, src, idx, pos, stats, ln_w, g_src, g_pos, g_lnw, g_lnb,
                            ("g_lnb", g_lnb, (E,))):
         if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32):
             raise ValueError(f"embed_rows_bwd: {name} must be a contiguous fp32 tensor of shape {shape}")
+    if dropout is None:
+        snap, site, p = None, 0, 0.0
+    else:
+        snap, site, p = _dropout_args("embed_rows_bwd", dropout, src.device)
     with _on(src.device):
-        big_dense = idx is None and N >= 32768 and T <= 1024
-        if big_dense or (idx is not None and lib.lipvq_embed_rows_bwd_ws_supported(N, T, E, src.shape[0])):
-            # large batches: no atomics on the table / time embedding (row gradients written once, counting-sort scatter; dense
-            # rows: the row gradients are g_src)
-            ws = None if big_dense else torch.empty(lib.lipvq_embed_rows_bwd_workspace_bytes(N, T, E, src.shape[0]),
-                                                    device=src.device, dtype=torch.uint8)
-            check(lib.lipvq_embed_rows_bwd_ws_f32(_ptr(gout), _ptr(src), _ptr(idx), _ptr(pos), _ptr(stats), _ptr(ln_w),
-                                                  _ptr(g_src), _ptr(g_pos), _ptr(g_lnw), _ptr(g_lnb), _ptr(ws), N, T, E,
-                                                  src.shape[0], bstride, tstride, offset, _stream()), "lipvq_embed_rows_bwd_ws_f32")
+        if T <= 1024:
+            # every sum in a fixed order (partial sums per workgroup and a second pass; the table through the counting-sort or the
+            # row-order scatter): no float atomics, the gradients repeat bit for bit
+            nbytes = lib.lipvq_embed_rows_bwd_det_workspace_bytes(N, T, E, src.shape[0], int(idx is not None))
+            ws = torch.empty(max(16, nbytes), device=src.device, dtype=torch.uint8)
+            check(lib.lipvq_embed_rows_bwd_det_f32(_ptr(gout), _ptr(src), _ptr(idx), _ptr(pos), _ptr(stats), _ptr(ln_w), _ptr(g_src),
+                                                   _ptr(g_pos), _ptr(g_lnw), _ptr(g_lnb), _ptr(ws), _ptr(snap), site, p, N, T, E,
+                                                   src.shape[0], bstride, tstride, offset, _stream()), "lipvq_embed_rows_bwd_det_f32")
             return
-        check(lib.lipvq_embed_rows_bwd_f32(_ptr(gout), _ptr(src), _ptr(idx), _ptr(pos), _ptr(stats), _ptr(ln_w),
-                                           _ptr(g_src), _ptr(g_pos), _ptr(g_lnw), _ptr(g_lnb), N, T, E, src.shape[0],
-                                           bstride, tstride, offset, _stream()), "lipvq_embed_rows_bwd_f32")
+        # more than 1024 time steps: the atomic kernel
+        drop, sfx = ((), "") if dropout is None else ((_ptr(snap), site, p), "drop_")
+        entry = f"lipvq_embed_rows_bwd_{sfx}f32"
+        check(getattr(lib, entry)(_ptr(gout), _ptr(src), _ptr(idx), _ptr(pos), _ptr(stats), _ptr(ln_w),
+                                  _ptr(g_src), _ptr(g_pos), _ptr(g_lnw), _ptr(g_lnb), *drop, N, T, E, src.shape[0],
+                                  bstride, tstride, offset, _stream()), entry)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -908,6 +923,48 @@ def act_bwd(g, pre, act):
     out = torch.empty_like(g)
     with _on(g.device):
         check(lib.lipvq_act_bwd_f32(_ptr(g), _ptr(pre), _ptr(out), g.numel(), int(act), _stream()), "lipvq_act_bwd_f32")
+    return out
+
+
+def linear_act_drop(x, W, b, act, dropout, save_pre=False):
+    """``linear`` whose stored y is act(x . W^T + b) * m: m = 1 / (1 - p) where dropout = (snap, site, p) keeps (row, col) of the
+    [N, E] result and 0 where it drops it, decided inside the Linear's epilogue (no mask tensor).  The pre-activation that
+    save_pre=True returns is the plain one."""
+    x, W = _chk(x, "x"), _chk(W, "W")
+    if x.dim() != 2 or W.dim() != 2 or W.shape[1] != x.shape[1]:
+        raise ValueError(f"linear_act_drop: x {tuple(x.shape)} and W {tuple(W.shape)} do not match")
+    if b is not None:
+        b = _chk(b, "b")
+        if b.shape != (W.shape[0],):
+            raise ValueError("linear_act_drop: bias shape")
+    snap, site, p = _dropout_args("linear_act_drop", dropout, x.device)
+    N, Kin = x.shape
+    E = W.shape[0]
+    y = torch.empty((N, E), device=x.device, dtype=torch.float32)
+    pre = torch.empty_like(y) if save_pre else None
+    with _on(x.device):
+        check(lib.lipvq_linear_act_drop_f32(_ptr(x), _ptr(W), _ptr(b), _ptr(y), _ptr(pre), _ptr(snap), site, p, N, Kin, E, int(act),
+                                            _stream()), "lipvq_linear_act_drop_f32")
+    return (y, pre) if save_pre else y
+
+
+def act_bwd_drop(g, pre, act, dropout):
+    """(g * m) * act'(pre) over a 2-D [rows, cols] gradient, m regenerated from dropout = (snap, site, p): the first backward
+    step of ``linear_act_drop``.  pre may be None for ACT_NONE (the result is g * m)."""
+    g = _chk(g, "g")
+    if g.dim() != 2:
+        raise ValueError("act_bwd_drop: g must be 2-D [rows, cols] (the dropout field)")
+    if pre is not None:
+        pre = _chk(pre, "pre")
+        if pre.shape != g.shape:
+            raise ValueError("act_bwd_drop: shapes differ")
+    elif act != ACT_NONE:
+        raise ValueError("act_bwd_drop: pre is required unless act is ACT_NONE")
+    snap, site, p = _dropout_args("act_bwd_drop", dropout, g.device)
+    out = torch.empty_like(g)
+    with _on(g.device):
+        check(lib.lipvq_act_bwd_drop_f32(_ptr(g), _ptr(pre), _ptr(out), _ptr(snap), site, p, g.shape[0], g.shape[1], int(act), _stream()),
+              "lipvq_act_bwd_drop_f32")
     return out
 
 
@@ -1079,6 +1136,38 @@ def attention_bwd(qkv, out, gout, lse, nhead: int, keep=None, keep_prob: float =
 # the transformer backbone (csrc/lipvq_gpt.hip; reference robomimic/models/transformers.py:80-439)
 # ---------------------------------------------------------------------------------------------------
 
+def attention_drop(qkv, nhead: int, dropout):
+    """``attention`` with the attention-probability dropout drawn inside the kernel: dropout = (snap, site, p) of the in-kernel
+    source, field row = h S + q, col = key.  The bits of ``attention`` given ``dropout_keep(snap, site, H S, S, p)`` reshaped
+    [H, S, S] and keep_prob = 1 - p."""
+    qkv = _chk(qkv, "qkv")
+    if qkv.dim() != 2 or qkv.shape[1] % 3 != 0:
+        raise ValueError(f"attention_drop: qkv {tuple(qkv.shape)}")
+    S, D = qkv.shape[0], qkv.shape[1] // 3
+    snap, site, p = _dropout_args("attention_drop", dropout, qkv.device)
+    out = torch.empty((S, D), device=qkv.device, dtype=torch.float32)
+    lse = torch.empty((nhead, S), device=qkv.device, dtype=torch.float32)
+    with _on(qkv.device):
+        check(lib.lipvq_attention_drop_f32(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(snap), site, p, S, D, int(nhead), _stream()),
+              "lipvq_attention_drop_f32")
+    return out, lse
+
+
+def attention_bwd_drop(qkv, out, gout, lse, nhead: int, dropout):
+    """``attention_bwd`` with the decisions of the forward's dropout = (snap, site, p) regenerated inside the two kernels."""
+    qkv, out, gout, lse = _chk(qkv, "qkv"), _chk(out, "out"), _chk(gout, "gout"), _chk(lse, "lse")
+    S, D = out.shape
+    if qkv.shape != (S, 3 * D) or gout.shape != out.shape or lse.shape != (nhead, S):
+        raise ValueError("attention_bwd_drop: shapes do not match")
+    snap, site, p = _dropout_args("attention_bwd_drop", dropout, qkv.device)
+    gqkv = torch.empty_like(qkv)
+    delta = torch.empty_like(lse)
+    with _on(qkv.device):
+        check(lib.lipvq_attention_bwd_drop_f32(_ptr(qkv), _ptr(out), _ptr(gout), _ptr(lse), _ptr(gqkv), _ptr(delta), _ptr(snap), site,
+                                               p, S, D, int(nhead), _stream()), "lipvq_attention_bwd_drop_f32")
+    return gqkv
+
+
 def _gpt_keep(keep, B, H, L, dev):
     if keep is None:
         return None
@@ -1240,6 +1329,11 @@ def gpt_layernorm_drop_bwd(gy, xhat, rstd, w, dropout, gres=None):
                                                    _ptr(snap), site, p, _ptr(gs), _ptr(gbr), _ptr(gw), _ptr(gb), _ptr(ws), N, E,
                                                    _stream()), "lipvq_gpt_layernorm_bwd_drop_f32")
     return gs, gbr, gw, gb
+
+
+# the site words of the modules outside the backbone (include/lipvq.h): the backbone's are 4 layer + {0, 1, 2}
+DROPOUT_SITE_EMBED = 0x40000000
+DROPOUT_SITE_DEFAULT = 0x80000000
 
 
 def dropout_begin(state):
