@@ -713,6 +713,64 @@ int lipvq_gmm_sample_f32(const float* x, int64_t bstride, const float* Wm, const
                          const float* Wl, const float* bl, const float* u, const float* eps, float* action, int64_t N, int T,
                          int E, int M, int A, int scale_mode, float min_std, void* stream);
 
+/* ---- in-kernel sampling (GMMActionHead.set_sample_source("kernel")): the sampling launch draws its uniform and its normals
+ *      itself; no noise tensor exists and torch's generators are not touched.  lipvq-vae_amd/csrc/lipvq_rng.h (one header for
+ *      device and host), lipvq-vae_amd/csrc/lipvq_gmm.hip.
+ *
+ *      The contract.  Generator, counter layout, key and state are those of "in-kernel dropout" above: the value for element
+ *      (row, col) of a field comes from
+ *          word  w = col & 3  of  philox(counter = (col >> 2, row, site, step & 0xffffffff), key = (seed & 0xffffffff, seed >> 32)),
+ *      so one Philox call serves four neighbouring columns, and only the low 32 bits of `step` enter (step 2^32 + 1 draws what
+ *      step 1 draws).
+ *      Sites.  LIPVQ_SAMPLE_SITE_GMM = 0xC0000000 is the UNIFORM field: one column per row (col = 0, so word 0 of counter
+ *      (0, row, site, step)).  LIPVQ_SAMPLE_SITE_GMM + 1 is the NORMAL field [rows][A]: col = the action component a.  Neither
+ *      word is a dropout site (backbone 4 layer + {0, 1, 2} < 0x40000000, embedding 0x40000000, default branch 0x80000000 +
+ *      4 layer + {0, 1, 2, 3} < 0xC0000000): a sampling state and a dropout state with equal (seed, step) draw unrelated fields.
+ *      Row word.  Input row n = (b, t) = (n / T, n % T) of a [B][T] call draws at
+ *          row = (uint32) (stream[b] T + t),
+ *      `streams` a device int64[B] of per-environment stream ids that the kernel reads itself; streams == NULL means
+ *      stream[b] = b.  The noise of an environment follows its id, not its batch position: a batch of ids (7, 3, 0) at one step
+ *      draws, row for row, what three B = 1 calls with ids 7, 3 and 0 draw at that step.  The product is formed in unsigned 64-bit
+ *      arithmetic and ONLY ITS LOW 32 BITS enter the counter: two (id, t) pairs with id T + t equal modulo 2^32 share their noise
+ *      (ids below 2^32 / T never collide; a negative id counts as its two's-complement bit pattern).
+ *      Uniform (the mode pick).   u = (float)(w >> 8) * 2^-24: in [0, 1), each value exact -- lipvq_gmm_sample_f32's `u`.
+ *      Normal.   v = (float)(2 (w >> 9) + 1) * 2^-24: 2^23 values strictly inside (0, 1), each exact in fp32, symmetric about 1/2.
+ *          eps = lq_normal_icdf(v) (lipvq_rng.h): Wichura's AS 241 PPND7 in fp32 with explicit fma, on min(v, 1 - v) and negated
+ *          for v < 1/2: icdf(1 - v) == -icdf(v) in every bit, the result is finite for every word and non-decreasing in v, and
+ *          device and host agree in every bit.  Within 2.4e-7 of the largest magnitude of the float64 inverse CDF over the whole
+ *          grid.  TRUNCATION: |eps| <= icdf(1 - 2^-24) ~= 5.2947; the tail mass 2 Phi(-5.2947) ~= 1.2e-7 is never drawn.
+ *          The evaluation, every operation one correctly rounded fp32 operation, fma(a, b, c) = a b + c rounded once, every
+ *          constant the fp32 value nearest the decimal:
+ *              w = v < 0.5 ? v : 1 - v;   q = 0.5 - w;
+ *              q <= 0.425:  r = fma(-q, q, 0.180625)
+ *                           n = fma(fma(fma(59.109374720, r, 159.29113202), r, 50.434271938), r, 3.3871327179)
+ *                           d = fma(fma(fma(67.187563600, r, 78.757757664), r, 17.895169469), r, 1)
+ *                           x = (q n) / d
+ *              otherwise:   r = sqrt(L(1 / w)) - 1.6
+ *                           n = fma(fma(fma(0.17023821103, r, 1.3067284816), r, 2.7568153900), r, 1.4234372777)
+ *                           d = fma(fma(0.12021132975, r, 0.73700164250), r, 1);   x = n / d
+ *              eps = v < 0.5 ? -x : x
+ *          L(t) = log t for t >= 1 is lipvq_math.h's lq_logf_ge1: t = m 2^e, m in [1, 2) from the bit pattern; if
+ *          m > 1.41421356237309504880 then m = 0.5 m, e = e + 1; s = (m - 1) / (m + 1); z = s s;
+ *          p = fma(fma(fma(fma(0.19365468621253967, z, 0.2219124436378479), z, 0.28571757674217224), z, 0.3999999761581421), z,
+ *          0.6666666865348816); lm = fma(s z, p, 2 s); L = fma(e, 0.693145751953125, fma(e, 1.42860682030941723e-6, lm)).
+ *      Step.  `snap` is what one lipvq_dropout_begin launch on the module's sampling state (device int64[2] = seed, step) wrote:
+ *      one such launch per sampling call hands it its (seed, step) and advances the step on the device, also in a captured graph. ---- */
+#define LIPVQ_SAMPLE_SITE_GMM 0xC0000000u
+/* lipvq_gmm_sample_f32 with u and eps drawn in the launch by the contract above (streams may be NULL): the bits of
+ * lipvq_gmm_sample_f32 given the u and eps of lipvq_gmm_noise_f32(snap, streams, ..., N / T, T, A); streams holds one id per batch
+ * entry, ceil(N / T) of them.  Same limits, same refusals, checked before any launch. */
+int lipvq_gmm_sample_draw_f32(const float* x, int64_t bstride, const float* Wm, const float* bm, const float* Ws, const float* bs,
+                              const float* Wl, const float* bl, const int64_t* snap, const int64_t* streams, float* action, int64_t N,
+                              int T, int E, int M, int A, int scale_mode, float min_std, void* stream);
+/* The two fields written out, u [B T] and eps [B T][A]: what the launch above draws, for tests and for users who want to see the
+ * noise.  _f32 runs on the device from a snap; _host is the same header code on the host from (seed, step) (streams then a host
+ * pointer) and makes no GPU call.  B == 0: no-op.  A outside 1..64: LIPVQ_EUNSUPPORTED. */
+int lipvq_gmm_noise_f32(const int64_t* snap, const int64_t* streams, float* u, float* eps, int64_t B, int T, int A, void* stream);
+int lipvq_gmm_noise_host(uint64_t seed, uint64_t step, const int64_t* streams, int64_t B, int T, int A, float* u, float* eps);
+/* out[i] = the normal that the raw 32-bit word words[i] maps to (v, then lq_normal_icdf), on the host. */
+int lipvq_normal_icdf_host(const uint32_t* words, float* out, int64_t n);
+
 /* ---- the deterministic policy's output head: what algo_factory (robomimic/algo/icl.py:41-75) builds when algo.gmm.enabled is
  *      False (config/icl_config.py:63, the default) -- ICLTransformer: the ObservationDecoder's one Linear `action`
  *      (obs_nets.py:747-771 with output_shapes = action (ac_dim,), pn:1683-1690), tanh (pn:1728-1731), and the losses of

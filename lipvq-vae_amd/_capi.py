@@ -137,6 +137,10 @@ SIGNATURES = {
     "lipvq_gmm_head_bwd_f32": (_i, [_vp] * 5 + [_i64, _i, _i, _i, C.c_float, _vp]),
     "lipvq_gmm_params_bwd_f32": (_i, [_vp] * 5 + [_i64, _i, _i, _i, _vp]),
     "lipvq_gmm_sample_f32": (_i, [_vp, _i64] + [_vp] * 9 + [_i64] + [_i] * 5 + [C.c_float, _vp]),
+    "lipvq_gmm_sample_draw_f32": (_i, [_vp, _i64] + [_vp] * 9 + [_i64] + [_i] * 5 + [C.c_float, _vp]),
+    "lipvq_gmm_noise_f32": (_i, [_vp] * 4 + [_i64, _i, _i, _vp]),
+    "lipvq_gmm_noise_host": (_i, [C.c_uint64, C.c_uint64, _vp, _i64, _i, _i, _vp, _vp]),
+    "lipvq_normal_icdf_host": (_i, [_vp, _vp, _i64]),
     "lipvq_action_head_workspace_bytes": (_sz, [_i64]),
     "lipvq_action_head_f32": (_i, [_vp, _i64] + [_vp] * 7 + [_i64, _i, _i, _i] + [C.c_float] * 3 + [_vp]),
     "lipvq_action_head_bwd_f32": (_i, [_vp] * 5 + [_i64, _i] + [C.c_float] * 3 + [_vp]),

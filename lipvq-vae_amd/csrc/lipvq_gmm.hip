@@ -20,6 +20,7 @@
 
 #include "lipvq_common.h"
 #include "lipvq_head_product.h"
+#include "lipvq_rng.h"
 
 #define GMM_ROWS HEAD_ROWS
 #define GMM_MAXM 16
@@ -35,7 +36,8 @@ struct GmmArgs {
     const float* Wm; const float* Ws; const float* Wl;
     const float* bm; const float* bs; const float* bl;
     const float* actions;
-    const float* u; const float* eps;
+    union { const float* u; const int64_t* snap; };                 // the sampling epilogue's noise: u / eps read, or (the DRAW
+    union { const float* eps; const int64_t* streams; };            // instances) snap / streams and the noise drawn in the kernel
     float* log_prob; float* pre; float* mean; float* scale; float* logits; float* partial; float* sample;
     int64_t N, bstride;
     int T, E, M, A, P, PS, scale_mode;
@@ -49,6 +51,11 @@ __device__ __forceinline__ float gmm_exp(float p) { return p == INFINITY ? INFIN
 __device__ __forceinline__ float gmm_sigma(float p, int mode, float min_std) {
     if (mode == LIPVQ_GMM_LOW_NOISE) return GMM_LOW_NOISE_STD;
     return (mode == LIPVQ_GMM_EXP ? gmm_exp(p) : lq_softplus(p)) + min_std;
+}
+
+// one component of a sample from the picked mode's pre-activations: the ONE expression behind both noise sources
+__device__ __forceinline__ float gmm_sample_value(float pmean, float pscale, float eps, int mode, float min_std) {
+    return tanhf(pmean) + gmm_sigma(pscale, mode, min_std) * eps;
 }
 
 // d sigma / d p at the pre-activation p
@@ -102,7 +109,7 @@ struct GmmCols {
 // lipvq_head_product.h, then the epilogues on its LDS tile.
 // dynamic LDS: max(staging [32 + 128 NT][KC + 1], tile [32][PS]) floats, then GMM_SIDE floats.
 // ---------------------------------------------------------------------------------------------------
-template <int NT, int KC>
+template <int NT, int KC, bool DRAW>
 __global__ __launch_bounds__(256) void gmm_head_kernel(const GmmArgs a, int side_off) {
     extern __shared__ float gmm_lds[];
     float* pt = gmm_lds;                                            // [32][PS], after the product
@@ -160,6 +167,17 @@ __global__ __launch_bounds__(256) void gmm_head_kernel(const GmmArgs a, int side
     }
     if (a.sample) {                                                // uniform
         const int row = tid & 31, part = tid >> 5;
+        lq_dropout dr;
+        uint32_t rw = 0;
+        if constexpr (DRAW) {
+            // the row's uniform is drawn once, by part 0, and handed to the row's other seven items through s_lp (free in this mode)
+            dr = lq_sample_make((uint64_t)a.snap[0], (uint64_t)a.snap[1]);
+            if (row < live) {
+                rw = lq_sample_row(a.streams, row0 + row, a.T);
+                if (part == 0) s_lp[row] = lq_sample_u(dr, rw);
+            }
+            __syncthreads();
+        }
         if (row < live) {
             const float* pr = pt + row * PS;
             const float* lg = pr + 2 * MA;
@@ -167,21 +185,55 @@ __global__ __launch_bounds__(256) void gmm_head_kernel(const GmmArgs a, int side
             for (int m = 1; m < M; ++m) mx = fmaxf(mx, lg[m]);
             float se = 0.0f;
             for (int m = 0; m < M; ++m) se += lq_expf(lg[m] - mx);
-            const float uu = a.u[row0 + row];
+            float uu;
+            if constexpr (DRAW) uu = s_lp[row];
+            else uu = a.u[row0 + row];
             float cdf = 0.0f;
             int pick = M - 1;                                      // the last mode if rounding leaves none
             for (int m = 0; m < M; ++m) {
                 cdf += lq_expf(lg[m] - mx) / se;
                 if (uu < cdf) { pick = m; break; }
             }
-            const float* ep = a.eps + (size_t)(row0 + row) * A;
             float* dst = a.sample + (size_t)(row0 + row) * A;
             // a row whose mixture weights are not numbers (a NaN or +inf logit: se is a NaN) has no draw: every comparison above was
             // false and `pick` is the last mode -- the sample is a NaN, not that mode's finite draw
-            for (int aa = part; aa < A; aa += 8)
-                dst[aa] = se == se ? tanhf(pr[pick * A + aa]) + gmm_sigma(pr[MA + pick * A + aa], a.scale_mode, a.min_std) * ep[aa] : se;
+            if constexpr (DRAW) {
+                // item (row, part) owns the draws part, part + 8, ...: each Philox call is made once and serves its four components
+                for (int g = part; 4 * g < A; g += 8) {
+                    const lq_philox4 r = lq_sample_eps_draw(dr, rw, (uint32_t)g);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int aa = 4 * g + k;
+                        if (aa < A)
+                            dst[aa] = se == se ? gmm_sample_value(pr[pick * A + aa], pr[MA + pick * A + aa], lq_normal_icdf(lq_sample_open(r.w[k])),
+                                                                  a.scale_mode, a.min_std) : se;
+                    }
+                }
+            } else {
+                const float* ep = a.eps + (size_t)(row0 + row) * A;
+                for (int aa = part; aa < A; aa += 8)
+                    dst[aa] = se == se ? gmm_sample_value(pr[pick * A + aa], pr[MA + pick * A + aa], ep[aa], a.scale_mode, a.min_std) : se;
+            }
         }
     }
+}
+
+// the noise the DRAW instances form, written out: u [rows] and eps [rows][A] (tests, users).  One thread per draw: item (row, g)
+// with g < G = ceil(A / 4) is the normals 4 g .. 4 g + 3 of the row, g == G its uniform.
+__global__ __launch_bounds__(256) void gmm_noise_kernel(const int64_t* __restrict__ snap, const int64_t* __restrict__ streams,
+                                                        float* __restrict__ u, float* __restrict__ eps, int64_t rows, int T, int A) {
+    const int G = (A + 3) / 4;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * (G + 1)) return;
+    const int64_t row = i / (G + 1);
+    const int g = (int)(i - row * (G + 1));
+    const lq_dropout dr = lq_sample_make((uint64_t)snap[0], (uint64_t)snap[1]);
+    const uint32_t rw = lq_sample_row(streams, row, T);
+    if (g == G) { u[row] = lq_sample_u(dr, rw); return; }
+    const lq_philox4 r = lq_sample_eps_draw(dr, rw, (uint32_t)g);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (4 * g + k < A) eps[row * A + 4 * g + k] = lq_normal_icdf(lq_sample_open(r.w[k]));
 }
 
 // sum of the per-workgroup partial sums in a fixed order (thread t: partials t, t + 256, ...; then a fixed tree)
@@ -304,7 +356,7 @@ static int gmm_check(const char* what, int64_t N, int T, int E, int M, int A, in
     return LIPVQ_OK;
 }
 
-static int gmm_launch(const char* what, GmmArgs& a, hipStream_t st) {
+static int gmm_launch(const char* what, GmmArgs& a, hipStream_t st, bool draw = false) {
     a.P = a.M * (2 * a.A + 1);
     a.PS = a.P | 1;                                                 // odd row stride: the items of a wave differ in the row
     const int tiles = (a.P + 31) / 32, nt = (tiles + 3) / 4;
@@ -313,10 +365,11 @@ static int gmm_launch(const char* what, GmmArgs& a, hipStream_t st) {
     const int side_off = stage > tile ? stage : tile;
     const size_t lds = (size_t)(side_off + GMM_SIDE) * sizeof(float);
     typedef void (*fn_t)(const GmmArgs, int);
-    const fn_t kfn = NT == 1 ? (fn_t)gmm_head_kernel<1, 32> : (NT == 2 ? (fn_t)gmm_head_kernel<2, 32> : (fn_t)gmm_head_kernel<4, 16>);
-    static LqLdsReserve reserved[3];
+    const fn_t kfn = draw ? (NT == 1 ? (fn_t)gmm_head_kernel<1, 32, true> : (NT == 2 ? (fn_t)gmm_head_kernel<2, 32, true> : (fn_t)gmm_head_kernel<4, 16, true>))
+                          : (NT == 1 ? (fn_t)gmm_head_kernel<1, 32, false> : (NT == 2 ? (fn_t)gmm_head_kernel<2, 32, false> : (fn_t)gmm_head_kernel<4, 16, false>));
+    static LqLdsReserve reserved[6];
     if (lds > 64 * 1024)
-        if (int rc = lipvq_reserve_lds(reserved[NT == 1 ? 0 : (NT == 2 ? 1 : 2)], (const void*)kfn, lds, what)) return rc;
+        if (int rc = lipvq_reserve_lds(reserved[(NT == 1 ? 0 : (NT == 2 ? 1 : 2)) + (draw ? 3 : 0)], (const void*)kfn, lds, what)) return rc;
     const dim3 grid((unsigned)((a.N + GMM_ROWS - 1) / GMM_ROWS)), block(256);
     hipLaunchKernelGGL(kfn, grid, block, lds, st, a, side_off);
     return check_launch(what);
@@ -344,7 +397,7 @@ int lipvq_gmm_head_f32(const float* x, int64_t bstride, const float* Wm, const f
     if (lp_sum && !workspace) return fail(LIPVQ_EINVAL, "lipvq_gmm_head_f32: the sum needs the workspace");
     if ((((uintptr_t)x | (uintptr_t)Wm | (uintptr_t)Ws | (uintptr_t)Wl) & 15) != 0)
         return fail(LIPVQ_EINVAL, "lipvq_gmm_head_f32: x and the weights must be 16-byte aligned");
-    GmmArgs a{x, Wm, Ws, Wl, bm, bs, bl, (log_prob || lp_sum) ? actions : nullptr, nullptr, nullptr, log_prob, pre, mean, scale, logits,
+    GmmArgs a{x, Wm, Ws, Wl, bm, bs, bl, (log_prob || lp_sum) ? actions : nullptr, {nullptr}, {nullptr}, log_prob, pre, mean, scale, logits,
               lp_sum ? (float*)workspace : nullptr, nullptr, N, bstride, T, E, M, A, 0, 0, scale_mode, min_std};
     if (int rc = gmm_launch("gmm_head_kernel", a, st)) return rc;
     if (!lp_sum) return LIPVQ_OK;
@@ -360,9 +413,66 @@ int lipvq_gmm_sample_f32(const float* x, int64_t bstride, const float* Wm, const
     if (!x || !Wm || !bm || !Ws || !bs || !Wl || !bl || !u || !eps || !action) return fail(LIPVQ_EINVAL, "lipvq_gmm_sample_f32: null pointer");
     if ((((uintptr_t)x | (uintptr_t)Wm | (uintptr_t)Ws | (uintptr_t)Wl) & 15) != 0)
         return fail(LIPVQ_EINVAL, "lipvq_gmm_sample_f32: x and the weights must be 16-byte aligned");
-    GmmArgs a{x, Wm, Ws, Wl, bm, bs, bl, nullptr, u, eps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, action,
+    GmmArgs a{x, Wm, Ws, Wl, bm, bs, bl, nullptr, {u}, {eps}, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, action,
               N, bstride, T, E, M, A, 0, 0, scale_mode, min_std};
     return gmm_launch("gmm_head_kernel (sample)", a, (hipStream_t)stream);
+}
+
+int lipvq_gmm_sample_draw_f32(const float* x, int64_t bstride, const float* Wm, const float* bm, const float* Ws, const float* bs,
+                              const float* Wl, const float* bl, const int64_t* snap, const int64_t* streams, float* action, int64_t N,
+                              int T, int E, int M, int A, int scale_mode, float min_std, void* stream) {
+    if (int rc = gmm_check("lipvq_gmm_sample_draw_f32", N, T, E, M, A, scale_mode, bstride)) return rc;
+    if (N == 0) return LIPVQ_OK;
+    if (!x || !Wm || !bm || !Ws || !bs || !Wl || !bl || !snap || !action) return fail(LIPVQ_EINVAL, "lipvq_gmm_sample_draw_f32: null pointer");
+    if ((((uintptr_t)x | (uintptr_t)Wm | (uintptr_t)Ws | (uintptr_t)Wl) & 15) != 0)
+        return fail(LIPVQ_EINVAL, "lipvq_gmm_sample_draw_f32: x and the weights must be 16-byte aligned");
+    GmmArgs a{x, Wm, Ws, Wl, bm, bs, bl, nullptr, {nullptr}, {nullptr}, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, action,
+              N, bstride, T, E, M, A, 0, 0, scale_mode, min_std};
+    a.snap = snap;
+    a.streams = streams;
+    return gmm_launch("gmm_head_kernel (sample, drawn)", a, (hipStream_t)stream, true);
+}
+
+static int gmm_noise_args(const char* what, int64_t B, int T, int A) {
+    if (B < 0 || T <= 0) return fail(LIPVQ_EINVAL, "%s: bad sizes B=%lld T=%d", what, (long long)B, T);
+    if (A < 1 || A > GMM_MAXA) return fail(LIPVQ_EUNSUPPORTED, "%s: ac_dim A=%d (1..%d)", what, A, GMM_MAXA);
+    if (B > 0x7fffffffLL * 8 / T) return fail(LIPVQ_EUNSUPPORTED, "%s: B=%lld T=%d is too large a field for one launch", what, (long long)B, T);
+    return LIPVQ_OK;
+}
+
+int lipvq_gmm_noise_f32(const int64_t* snap, const int64_t* streams, float* u, float* eps, int64_t B, int T, int A, void* stream) {
+    if (int rc = gmm_noise_args("lipvq_gmm_noise_f32", B, T, A)) return rc;
+    if (B == 0) return LIPVQ_OK;
+    if (!snap || !u || !eps) return fail(LIPVQ_EINVAL, "lipvq_gmm_noise_f32: null pointer");
+    const int64_t rows = B * T, items = rows * ((A + 3) / 4 + 1);
+    hipLaunchKernelGGL(gmm_noise_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, snap, streams, u, eps,
+                       rows, T, A);
+    return check_launch("gmm_noise_kernel");
+}
+
+// the same two fields from the header on the host: no GPU call
+int lipvq_gmm_noise_host(uint64_t seed, uint64_t step, const int64_t* streams, int64_t B, int T, int A, float* u, float* eps) {
+    if (int rc = gmm_noise_args("lipvq_gmm_noise_host", B, T, A)) return rc;
+    if (B == 0) return LIPVQ_OK;
+    if (!u || !eps) return fail(LIPVQ_EINVAL, "lipvq_gmm_noise_host: null pointer");
+    const lq_dropout dr = lq_sample_make(seed, step);
+    for (int64_t row = 0; row < B * T; ++row) {
+        const uint32_t rw = lq_sample_row(streams, row, T);
+        u[row] = lq_sample_u(dr, rw);
+        for (int g = 0; 4 * g < A; ++g) {
+            const lq_philox4 r = lq_sample_eps_draw(dr, rw, (uint32_t)g);
+            for (int k = 0; k < 4 && 4 * g + k < A; ++k) eps[row * A + 4 * g + k] = lq_normal_icdf(lq_sample_open(r.w[k]));
+        }
+    }
+    return LIPVQ_OK;
+}
+
+int lipvq_normal_icdf_host(const uint32_t* words, float* out, int64_t n) {
+    if (n < 0) return fail(LIPVQ_EINVAL, "lipvq_normal_icdf_host: n=%lld", (long long)n);
+    if (n == 0) return LIPVQ_OK;
+    if (!words || !out) return fail(LIPVQ_EINVAL, "lipvq_normal_icdf_host: null pointer");
+    for (int64_t i = 0; i < n; ++i) out[i] = lq_normal_icdf(lq_sample_open(words[i]));
+    return LIPVQ_OK;
 }
 
 int lipvq_gmm_head_bwd_f32(const float* pre, const float* actions, const float* g, const float* gsum, float* gpre, int64_t N,

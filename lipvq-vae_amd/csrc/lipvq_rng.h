@@ -1,4 +1,5 @@
-/* lipvq_rng.h -- the counter-based generator behind the backbone's in-kernel dropout.
+/* lipvq_rng.h -- the counter-based generator behind the in-kernel dropout and, at the end of the file, the GMM head's in-kernel
+ * sampling noise (uniform, and normal by an fp32 inverse CDF).
  *
  * ONE definition of Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11; the
  * Random123 known answers hold: tests/test_dropout_host.py) and of the mapping from a dropout SITE to its draws, shared
@@ -102,6 +103,76 @@ LQ_HD uint32_t lq_dropout_keep4(lq_dropout d, uint32_t row, uint32_t col4) {
     const lq_philox4 r = lq_dropout_draw(d, row, col4);
     return (uint32_t)(r.w[0] >= d.thr) | ((uint32_t)(r.w[1] >= d.thr) << 1) | ((uint32_t)(r.w[2] >= d.thr) << 2) |
            ((uint32_t)(r.w[3] >= d.thr) << 3);
+}
+
+/* ---- in-kernel sampling: the GMM head's noise (include/lipvq.h, "in-kernel sampling", repeats this contract).
+ *
+ * Two fields per sampling call, drawn with the dropout counter and key:
+ *     word  col & 3  of  philox4x32_10((col >> 2, row, site, step & 0xffffffff), (seed & 0xffffffff, seed >> 32)).
+ * Sites.  LIPVQ_SAMPLE_SITE_GMM (0xC0000000) is the UNIFORM field, one column (col = 0) per row: the mode pick.
+ * LIPVQ_SAMPLE_SITE_GMM + 1 is the NORMAL field [rows][A]: col = the action component.  Neither word is reachable by a dropout
+ * site (backbone 4 layer + k, embedding 0x40000000, default branch 0x80000000 + 4 layer + k).
+ * Row word.  Input row (b, t) of a [B][T] call draws at  row = (uint32)(stream[b] T + t),  stream an int64[B] of per-environment
+ * ids read on the device (NULL: stream[b] = b, the batch position).  The product is formed in 64 bits and only its low 32 bits
+ * enter the counter: ids whose stream T + t agree modulo 2^32 share their noise.
+ * Uniform.  u = (float)(w >> 8) 2^-24: 2^24 values in [0, 1), each exact.
+ * Normal.   v = (float)(2 (w >> 9) + 1) 2^-24: 2^23 values strictly inside (0, 1), each exact, symmetric about 1/2;
+ *           eps = lq_normal_icdf(v).  The grid truncates the normal: |eps| <= icdf(1 - 2^-24) ~= 5.2948, and the tail mass
+ *           2 Phi(-5.2948) ~= 1.2e-7 is never drawn.
+ * Step.  One lipvq_dropout_begin launch per sampling call hands it its (seed, step) snap and advances the step. */
+#define LQ_SAMPLE_SITE_GMM 0xC0000000u
+
+LQ_HD float lq_sample_uniform(uint32_t w) { return (float)(w >> 8) * 5.9604644775390625e-8f; }
+LQ_HD float lq_sample_open(uint32_t w) { return (float)(2u * (w >> 9) + 1u) * 5.9604644775390625e-8f; }
+
+/* Inverse of the standard normal CDF at v in (0, 1): Wichura's PPND7 (Algorithm AS 241, Appl. Statist. 37 (1988) 477-484),
+ * the central rational in r = 0.180625 - q^2 for |v - 1/2| <= 0.425 and the rational in sqrt(-log min(v, 1 - v)) - 1.6 outside.
+ * AS 241's third branch (sqrt(-log) > 5, v < 1.4e-11) is unreachable from the grid above (sqrt(-log 2^-24) = 4.08) and is left
+ * out: a v below 2^-24 is evaluated by the second rational, finite for every positive float.  Evaluated on w = min(v, 1 - v) and
+ * negated for v < 1/2, so icdf(1 - v) == -icdf(v) in every bit (1 - v is exact on the grid).  Only +, *, fma, / and lq_sqrt,
+ * and lq_logf_ge1(1 / w): hipcc and gcc agree in every bit. */
+LQ_HD float lq_normal_icdf(float v) {
+    const float w = v < 0.5f ? v : 1.0f - v;
+    const float q = 0.5f - w;                                   /* >= 0, exact on the grid */
+    float x;
+    if (q <= 0.425f) {
+        const float r = lq_fma(-q, q, 0.180625f);
+        float n = lq_fma(5.9109374720e+01f, r, 1.5929113202e+02f);
+        n = lq_fma(n, r, 5.0434271938e+01f);
+        n = lq_fma(n, r, 3.3871327179e+00f);
+        float d = lq_fma(6.7187563600e+01f, r, 7.8757757664e+01f);
+        d = lq_fma(d, r, 1.7895169469e+01f);
+        d = lq_fma(d, r, 1.0f);
+        x = q * n / d;
+    } else {
+        const float r = lq_sqrt(lq_logf_ge1(1.0f / w)) - 1.6f;
+        float n = lq_fma(1.7023821103e-01f, r, 1.3067284816e+00f);
+        n = lq_fma(n, r, 2.7568153900e+00f);
+        n = lq_fma(n, r, 1.4234372777e+00f);
+        float d = lq_fma(1.2021132975e-01f, r, 7.3700164250e-01f);
+        d = lq_fma(d, r, 1.0f);
+        x = n / d;
+    }
+    return v < 0.5f ? -x : x;
+}
+
+/* the (seed, step) of a sampling call: the key and step words of lq_dropout, its site the uniform field's */
+LQ_HD lq_dropout lq_sample_make(uint64_t seed, uint64_t step) { return lq_dropout_make(seed, step, LQ_SAMPLE_SITE_GMM, 0.5); }
+
+/* the row word of input row n = b T + t (see above) */
+LQ_HD uint32_t lq_sample_row(const int64_t* streams, int64_t n, int T) {
+    const int64_t b = n / T, t = n - b * T;
+    const uint64_t id = streams ? (uint64_t)streams[b] : (uint64_t)b;
+    return (uint32_t)(id * (uint64_t)T + (uint64_t)t);
+}
+
+LQ_HD float lq_sample_u(lq_dropout d, uint32_t row) {
+    return lq_sample_uniform(lq_philox4x32_10(0u, row, LQ_SAMPLE_SITE_GMM, d.step, d.k0, d.k1).w[0]);
+}
+
+/* the draw behind the normals of components 4 col4 .. 4 col4 + 3 of `row` */
+LQ_HD lq_philox4 lq_sample_eps_draw(lq_dropout d, uint32_t row, uint32_t col4) {
+    return lq_philox4x32_10(col4, row, LQ_SAMPLE_SITE_GMM + 1u, d.step, d.k0, d.k1);
 }
 
 #endif

@@ -14,6 +14,8 @@ parameter CONTAINERS only: no method calls them.  The compute is
     lipvq_gmm_head_bwd_f32    the gradient of the [rows, P] pre-activations from the responsibilities, one launch
     lipvq_wgrad_f32, lipvq_linear_act_f32      the six parameter gradients and the input gradient
     lipvq_gmm_sample_f32      inverse-CDF mode choice + mu + sigma eps, one launch
+    lipvq_gmm_sample_draw_f32 the same launch drawing u and eps itself (``set_sample_source("kernel")``), after one
+                              lipvq_dropout_begin launch on the module's (seed, step) state
 
 ``feats`` may be the non-contiguous view ``out[:, -T:]`` of a ``GPTBackbone`` output: its strides go to the kernel and the
 forward makes no copy (the backward's wgrad reads a dense copy of those rows, and the input gradient comes back dense, in the
@@ -22,7 +24,9 @@ repeat bit for bit.
 
 Sampling: ``forward`` draws ``u`` / ``eps`` with ``torch.rand`` / ``torch.randn`` and picks the mode by inverse CDF, where the
 reference's ``MixtureSameFamily.sample()`` draws a ``Categorical`` and a ``Normal`` sample for every mode and gathers: the actions
-agree with the reference in distribution, not in bits.  ``use_tanh=True`` (the TanhWrappedDistribution variant) is not implemented
+agree with the reference in distribution, not in bits.  Opt-in, ``set_sample_source("kernel")`` moves both draws into the sampling
+launch (Philox4x32-10 and an fp32 inverse normal CDF; include/lipvq.h, "in-kernel sampling"), addressed by a per-environment
+stream id instead of the batch position: no noise tensors, torch's generators untouched.  ``use_tanh=True`` (the TanhWrappedDistribution variant) is not implemented
 (the ICRT configuration does not use it).
 """
 from __future__ import annotations
@@ -32,7 +36,7 @@ import torch.distributions as D
 import torch.nn as nn
 
 from . import ops
-from .nnfn import KernelFunction, first_order_only, wants_backward
+from .nnfn import KernelFunction, KernelSampleSource, first_order_only, wants_backward
 from .ops import GMM_EXP, GMM_LOW_NOISE, GMM_SOFTPLUS
 
 __all__ = ["GMMActionHead"]
@@ -100,12 +104,13 @@ class _ParamsFn(KernelFunction):
         return (g[0],) + g[1:] + (None,) * 4
 
 
-class GMMActionHead(nn.Module):
+class GMMActionHead(KernelSampleSource, nn.Module):
     """The GMM head of the reference's ``ICL_MIMO_Transformer_GMM`` (policy_nets.py:2507-2599) on the HIP library.
 
     ``log_prob`` / ``nll`` are the training path (icl.py:916-966: ``forward_train(..., low_noise_eval=False).log_prob``, then
     ``-log_probs.mean()``), ``forward_train`` returns the reference's distribution object built from kernel-produced tensors, and
-    ``forward`` samples actions."""
+    ``forward`` samples actions.  ``set_sample_source("kernel")`` (nnfn.KernelSampleSource) makes the sampling launch draw its
+    own noise, addressed by per-environment stream ids (``forward``'s ``streams``)."""
 
     MAX_MODES, MAX_AC_DIM, MAX_COLUMNS, MAX_EMBED = 16, 64, 512, 1024
     _MODES = {"softplus": GMM_SOFTPLUS, "exp": GMM_EXP}
@@ -179,13 +184,29 @@ class GMMActionHead(nn.Module):
         component = D.Independent(D.Normal(loc=mean, scale=scale), 1)
         return D.MixtureSameFamily(mixture_distribution=D.Categorical(logits=logits), component_distribution=component)
 
-    def forward(self, feats, u=None, eps=None):
+    def forward(self, feats, u=None, eps=None, streams=None):
         """Sampled actions [B, T, A] (policy_nets.py:2593-2599).  u [B, T] uniform in [0, 1) picks each row's mode by inverse CDF
         over softmax(logits), eps [B, T, A] standard normal is the component's noise; both are drawn on feats' device when not
         given.  In eval mode with low_noise_eval the scale is 1e-4.  The actions agree with the reference's ``.sample()`` in
-        distribution, not in bits (see the module docstring).  No host synchronisation: capturable by nnfn.GraphedEval."""
+        distribution, not in bits (see the module docstring).  No host synchronisation: capturable by nnfn.GraphedEval.
+
+        Under ``set_sample_source("kernel")`` (eval and train mode alike) a call without u and eps makes one ``dropout_begin``
+        launch on ``sample_state`` and one sampling launch that draws the noise itself (include/lipvq.h, "in-kernel sampling"):
+        batch entry b draws from stream ``streams[b]`` (int64 [B] on feats' device; None: b itself), so an environment's noise
+        follows its id through any re-packing of the batch.  With u AND eps given they are used as they are, row by position, and
+        the state is not advanced; exactly one of them is a ValueError.  The "torch" source only validates streams' shape."""
         feats = self._check(feats)
         B, T = feats.shape[:2]
+        if streams is not None and (not isinstance(streams, torch.Tensor) or streams.dtype != torch.int64 or tuple(streams.shape) != (B,)):
+            raise ValueError(f"GMMActionHead: streams must be an int64 [{B}] tensor (one stream id per batch entry)")
+        if self.sample_source == "kernel" and (u is None or eps is None):
+            if u is not None or eps is not None:
+                raise ValueError("GMMActionHead: under the kernel sample source give both u and eps (explicit noise) or neither "
+                                 "(the launch draws both)")
+            with torch.no_grad():
+                act = ops.gmm_sample_draw(feats.detach(), tuple(p.detach() for p in self._params()), self.num_modes, self.ac_dim,
+                                          self._sample_begin(feats.device), streams, self._mode(None), float(self.min_std))
+            return act.view(B, T, self.ac_dim)
         if u is None:
             u = torch.rand((B, T), device=feats.device, dtype=torch.float32)
         if eps is None:

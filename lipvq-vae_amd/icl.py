@@ -414,5 +414,6 @@ class PromptedPolicy:
             except StalePromptCache as e:
                 raise RuntimeError(f"PromptedPolicy.features: call set_prompt() again ({e})") from e
 
-    def __call__(self, obs: torch.Tensor):
-        return self.head(self.features(obs))
+    def __call__(self, obs: torch.Tensor, **head_kwargs):
+        """head(features(obs), **head_kwargs): keyword arguments go to the head as they are (a GMMActionHead's ``streams=``)."""
+        return self.head(self.features(obs), **head_kwargs)

@@ -13,7 +13,7 @@ from .capture import capture, copy_in, warm_up
 from .ops import ACT_NONE
 
 __all__ = ["LinearFn", "LinearDropFn", "AddLayerNormFn", "AddDropLayerNormFn", "AttentionDropFn", "GraphedEval", "KernelDropoutSource",
-           "KernelFunction", "first_order_only", "wants_backward"]
+           "KernelSampleSource", "KernelFunction", "first_order_only", "wants_backward"]
 
 _applying = threading.local()
 
@@ -290,20 +290,85 @@ class KernelDropoutSource:
         return p
 
 
+class KernelSampleSource:
+    """Mixin of the modules that SAMPLE (GMMActionHead): where the sampling noise comes from, and the state of the in-kernel
+    source.  KernelDropoutSource's twin, with its rules and error types; unlike dropout, sampling is not a training-only act, so
+    the source applies in eval and in train mode.  Nothing is created at construction."""
+
+    @property
+    def sample_source(self) -> str:
+        """"torch" (default) or "kernel": where the sampling noise comes from (set_sample_source)."""
+        return getattr(self, "_sample_source", "torch")
+
+    def set_sample_source(self, source: str, seed: int | None = None):
+        """"kernel": the sampling launch draws its own uniform and normals, each a pure function of (seed, step, site, stream id,
+        t, component) (include/lipvq.h, "in-kernel sampling").  No noise tensor is drawn or stored and torch's generators are not
+        touched.  A sampling call makes one ``ops.dropout_begin`` launch, which hands the call its (seed, step) and advances the
+        step on the device -- also under ``torch.no_grad()`` and inside a captured graph, where every replay advances it.
+        "torch" restores the default (``torch.rand`` / ``torch.randn``) bit for bit.
+
+        The state, ``sample_state`` -- a device int64[2] tensor (seed, step) --, is created by the first call with "kernel" (never
+        at construction), seeded with ``seed`` or, for None, ``torch.initial_seed()``; a later call with a seed reseeds it
+        (step 0), one without leaves it.  It is a non-persistent buffer: ``.to()`` moves it, ``state_dict()`` does not hold it.
+        Returns self."""
+        if source not in ("torch", "kernel"):
+            raise ValueError(f"{type(self).__name__}: sample source must be 'torch' or 'kernel', got {source!r}")
+        if source == "kernel":
+            if getattr(self, "_sample_state", None) is None:
+                dev = next(self.parameters()).device
+                self.register_buffer("_sample_state", torch.zeros(2, dtype=torch.int64, device=dev), persistent=False)
+                self.reseed_sampling(torch.initial_seed() if seed is None else seed)
+            elif seed is not None:
+                self.reseed_sampling(seed)
+        self._sample_source = source
+        return self
+
+    @property
+    def sample_state(self):
+        """The device int64[2] tensor (seed, step) of the in-kernel source, None before the first set_sample_source("kernel")."""
+        return getattr(self, "_sample_state", None)
+
+    def reseed_sampling(self, seed: int, step: int = 0):
+        """Set the in-kernel source's (seed, step) in place: seed any integer (taken modulo 2^64), step the next sampling call's."""
+        if getattr(self, "_sample_state", None) is None:
+            raise RuntimeError(f"{type(self).__name__}.reseed_sampling: call set_sample_source('kernel') first (it creates the state)")
+        words = [int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)]
+        words = [v - 2 ** 64 if v >= 2 ** 63 else v for v in words]          # (the bit pattern, as int64)
+        self._sample_state.copy_(torch.tensor(words, dtype=torch.int64))
+        return self
+
+    def _sample_begin(self, device):
+        """The snap of one sampling call: one dropout_begin launch on the module's own state."""
+        if self._sample_state.device != device:
+            raise RuntimeError(f"{type(self).__name__}: the sampling state is not on the input's device (move the module with .to())")
+        return ops.dropout_begin(self._sample_state)
+
+
+def _sample_states(net):
+    """The in-kernel sampling states of net and its sub-modules (KernelSampleSource), those that exist."""
+    states = [getattr(m, "sample_state", None) for m in net.modules()]
+    return [s for s in states if isinstance(s, torch.Tensor)]
+
+
 class GraphedEval:
     """Eval-mode forward of ``net`` captured in ONE HIP graph for the shape of ``example``.  Parameters are read at replay time
     through their storage, so in-place updates (optimizer steps, load_state_dict) are seen; re-capture after anything that
     REPLACES a parameter tensor (.to(), .cuda()).  The returned tensor is the graph's own output buffer: copy it before the next
-    call if it must survive."""
+    call if it must survive.  A net that samples from the in-kernel source (KernelSampleSource) keeps its ``sample_state``: the
+    warm-up and the capture do not advance it, and every replay does, so replay k draws what eager call k would."""
 
     def __init__(self, net: torch.nn.Module, example: torch.Tensor, /):
         if net.training:
             raise RuntimeError(f"{type(self).__name__} captures the eval-mode forward: call net.eval() first")
         self.net = net
         self._x = example.detach().contiguous().float().clone()
+        states = _sample_states(net)
+        kept = [s.clone() for s in states]
         with torch.no_grad():
             warm_up(lambda: net(self._x), 3, self._x.device)      # first-use work (LDS reservations, lazy module state) stays out of the capture
             self._graph, self._y = capture(lambda: net(self._x))
+            for s, k in zip(states, kept):
+                s.copy_(k)
 
     def __call__(self, inputs: torch.Tensor, /) -> torch.Tensor:
         copy_in(self._x, inputs, "captured")

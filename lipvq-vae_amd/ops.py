@@ -1506,6 +1506,85 @@ def gmm_sample(feats, params, M: int, A: int, u, eps, scale_mode: int = GMM_SOFT
     return action
 
 
+# the site word of the GMM head's in-kernel sampling noise (include/lipvq.h, "in-kernel sampling"): the uniform field; the normal
+# field is SAMPLE_SITE_GMM + 1
+SAMPLE_SITE_GMM = 0xC0000000
+
+
+def _sample_snap(what, snap, dev=None):
+    if not isinstance(snap, torch.Tensor) or snap.dtype != torch.int64 or snap.numel() != 2 or not snap.is_cuda or not snap.is_contiguous() \
+            or (dev is not None and snap.device != dev):
+        raise ValueError(f"{what}: snap must be the contiguous int64[2] tensor of dropout_begin on the input's device")
+    return snap
+
+
+def _sample_streams(what, streams, B, dev):
+    """streams: None (stream b = batch position b) or one int64 id per batch entry, on `dev` (a torch.device, or None: the host)."""
+    if streams is None:
+        return None
+    if not isinstance(streams, torch.Tensor) or streams.dtype != torch.int64 or tuple(streams.shape) != (B,):
+        raise ValueError(f"{what}: streams must be an int64 [{B}] tensor (one stream id per batch entry)")
+    if (streams.device != dev) if dev is not None else streams.is_cuda:
+        raise ValueError(f"{what}: streams must be on " + ("the host" if dev is None else f"the device of the call ({dev})"))
+    return streams.contiguous()
+
+
+def gmm_sample_draw(feats, params, M: int, A: int, snap, streams=None, scale_mode: int = GMM_SOFTPLUS, min_std: float = 0.01):
+    """gmm_sample whose u and eps are drawn inside the launch (lipvq_gmm_sample_draw_f32) from snap, the (seed, step) a
+    dropout_begin on the sampling state wrote, and the rows' stream ids (streams int64 [B] on the device, None = batch position):
+    the bits of gmm_sample(feats, ..., *gmm_noise(snap, B, T, A, streams)).  One launch, no noise tensor."""
+    B = feats.shape[0] if isinstance(feats, torch.Tensor) and feats.dim() == 3 else 1
+    feats, N, T, E, bstride = _gmm_rows(feats)
+    Wm, bm, Ws, bs, Wl, bl = _gmm_params(params, M, A, E)
+    snap = _sample_snap("gmm_sample_draw", snap, feats.device)
+    streams = _sample_streams("gmm_sample_draw", streams, B, feats.device)
+    action = torch.empty((N, A), device=feats.device, dtype=torch.float32)
+    with _on(feats.device):
+        check(lib.lipvq_gmm_sample_draw_f32(_ptr(feats), bstride, _ptr(Wm), _ptr(bm), _ptr(Ws), _ptr(bs), _ptr(Wl), _ptr(bl), _ptr(snap),
+                                            _ptr(streams), _ptr(action), N, T, E, int(M), int(A), int(scale_mode), float(min_std),
+                                            _stream()), "lipvq_gmm_sample_draw_f32")
+    return action
+
+
+def gmm_noise(snap, B: int, T: int, A: int, streams=None):
+    """(u [B, T], eps [B, T, A]) device tensors: the noise gmm_sample_draw forms from snap (and streams) for a [B, T] call."""
+    snap = _sample_snap("gmm_noise", snap)
+    B, T, A = int(B), int(T), int(A)
+    if B < 0 or T <= 0:
+        raise ValueError(f"gmm_noise: B={B} T={T}")
+    streams = _sample_streams("gmm_noise", streams, B, snap.device)
+    ok = 1 <= A <= 64                                                              # (anything else the library refuses before it writes)
+    u = torch.empty((B, T) if ok else (0, T), device=snap.device, dtype=torch.float32)
+    eps = torch.empty((B, T, A) if ok else (0, T, 0), device=snap.device, dtype=torch.float32)
+    with _on(snap.device):
+        check(lib.lipvq_gmm_noise_f32(_ptr(snap), _ptr(streams), _ptr(u), _ptr(eps), B, T, A, _stream()), "lipvq_gmm_noise_f32")
+    return u, eps
+
+
+def gmm_noise_host(seed: int, step: int, B: int, T: int, A: int, streams=None):
+    """The same (u, eps) as CPU tensors from (seed, step), computed on the host (streams: a CPU int64 [B] tensor): no GPU call."""
+    B, T, A = int(B), int(T), int(A)
+    if B < 0 or T <= 0:
+        raise ValueError(f"gmm_noise_host: B={B} T={T}")
+    streams = _sample_streams("gmm_noise_host", streams, B, None)
+    ok = 1 <= A <= 64
+    u = torch.empty((B, T) if ok else (0, T), dtype=torch.float32)
+    eps = torch.empty((B, T, A) if ok else (0, T, 0), dtype=torch.float32)
+    check(lib.lipvq_gmm_noise_host(int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), None if streams is None else streams.data_ptr(),
+                                   B, T, A, u.data_ptr(), eps.data_ptr()), "lipvq_gmm_noise_host")
+    return u, eps
+
+
+def normal_icdf_host(words):
+    """eps [n] (CPU float32) for raw 32-bit draw words (a CPU tensor or array of integers below 2^32): v = (2 (w >> 9) + 1) 2^-24,
+    then the library's inverse normal CDF, on the host."""
+    import numpy as np
+    w = np.ascontiguousarray(np.asarray(words).astype(np.uint32, copy=False).reshape(-1))
+    out = torch.empty(w.size, dtype=torch.float32)
+    check(lib.lipvq_normal_icdf_host(w.ctypes.data, out.data_ptr(), int(w.size)), "lipvq_normal_icdf_host")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------
 # the deterministic policy's output head (csrc/lipvq_action_head.hip)
 # ---------------------------------------------------------------------------------------------------
