@@ -512,7 +512,8 @@ int lipvq_gpt_layernorm_bwd_f32(const float* gy, const float* xhat, const float*
 /* ---- in-kernel dropout for the backbone (GPTBackbone.set_dropout_source("kernel")): the three dropout sites of a block
  *      (tf:195 attn_dropout, tf:205 and tf:289 the two block-output dropouts) decided INSIDE the kernels that touch those elements.
  *      No mask tensor exists: every decision is a pure function of (seed, step, site, row, col), and the backward regenerates it.
- *      lipvq-vae_amd/csrc/lipvq_rng.h (generator and mapping, one header for device and host), lipvq-vae_amd/csrc/lipvq_gpt.hip.
+ *      lipvq-vae_amd/csrc/lipvq_rng.h (generator and mapping, one header for device and host), lipvq-vae_amd/csrc/lipvq_gpt.hip (the
+ *      backbone's kernels), lipvq-vae_amd/csrc/lipvq_rng.hip (lipvq_dropout_begin and the keep fields, shared by every module).
  *
  *      The mapping (the contract).  A site is a 2-D field of decisions.  With Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57,
  *      Weyl constants 0x9E3779B9 / 0xBB67AE85, 10 rounds; the Random123 known answers hold), the decision for element (row, col) is

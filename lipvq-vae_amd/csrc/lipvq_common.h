@@ -97,8 +97,12 @@ int lipvq_mse_finish(const double* partial, int64_t nx, int64_t nz, float* out, 
 
 // what every entry point of the in-kernel dropout source refuses (include/lipvq.h, "in-kernel dropout"): 0 < p < 1, a snap to
 // read, and a field whose rows fit the 32-bit counter word
-static inline int lq_dropout_check(const char* what, const void* snap, double p, int64_t rows) {
+static inline int lq_dropout_check_p(const char* what, double p) {
     if (!(p > 0.0 && p < 1.0)) return fail(LIPVQ_EINVAL, "%s: dropout p=%g (0 < p < 1)", what, p);
+    return 0;
+}
+static inline int lq_dropout_check(const char* what, const void* snap, double p, int64_t rows) {
+    if (int rc = lq_dropout_check_p(what, p)) return rc;
     if (rows >= (1LL << 32)) return fail(LIPVQ_EUNSUPPORTED, "%s: %lld rows of decisions (< 2^32)", what, (long long)rows);
     if (!snap) return fail(LIPVQ_EINVAL, "%s: null snap", what);
     return 0;

@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256) void gmm_head_kernel(const GmmArgs a, int side
         uint32_t rw = 0;
         if constexpr (DRAW) {
             // the row's uniform is drawn once, by part 0, and handed to the row's other seven items through s_lp (free in this mode)
-            dr = lq_sample_make((uint64_t)a.snap[0], (uint64_t)a.snap[1]);
+            dr = lq_sample_load(a.snap);
             if (row < live) {
                 rw = lq_sample_row(a.streams, row0 + row, a.T);
                 if (part == 0) s_lp[row] = lq_sample_u(dr, rw);
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256) void gmm_noise_kernel(const int64_t* __restric
     if (i >= rows * (G + 1)) return;
     const int64_t row = i / (G + 1);
     const int g = (int)(i - row * (G + 1));
-    const lq_dropout dr = lq_sample_make((uint64_t)snap[0], (uint64_t)snap[1]);
+    const lq_dropout dr = lq_sample_load(snap);
     const uint32_t rw = lq_sample_row(streams, row, T);
     if (g == G) { u[row] = lq_sample_u(dr, rw); return; }
     const lq_philox4 r = lq_sample_eps_draw(dr, rw, (uint32_t)g);

@@ -12,7 +12,7 @@
 //                               partial sums and a fixed-order second pass (bit-reproducible)
 //   in-kernel dropout           the attention kernels' mask source is a template parameter (none / keep bytes / Philox draws,
 //                               lipvq_rng.h); gpt_layernorm_kernel<true> and gpt_layernorm_bwd_kernel<true> drop the added branch;
-//                               gpt_dropout_begin_kernel hands a forward call its (seed, step) and advances the step
+//                               each is handed one lq_dropout_src (the state and the keep-field entry points: lipvq_rng.hip)
 // ABI: include/lipvq.h ("the transformer backbone", "in-kernel dropout").  Tolerances: tests/test_gpu_gpt.py; the dropout forms
 // are held to the keep-byte forms bit for bit: tests/test_gpu_gpt_dropout.py.
 //
@@ -75,15 +75,6 @@ __device__ __forceinline__ void gpt_store_t(float* __restrict__ dst, const f32x1
 //   GPT_MASK_PHILOX  drawn here (lipvq_rng.h): row = (b H + h) L + i, col = j -- the layout of the keep bytes -- of `site`
 enum { GPT_MASK_NONE = 0, GPT_MASK_BYTES = 1, GPT_MASK_PHILOX = 2 };
 
-// the (seed, step) pair lipvq_dropout_begin left in snap, with the site, threshold and factor the host passed
-__device__ __forceinline__ lq_dropout gpt_dropout_load(const int64_t* __restrict__ snap, uint32_t site, uint32_t thr, float inv_keep) {
-    const uint64_t seed = (uint64_t)snap[0], step = (uint64_t)snap[1];
-    lq_dropout d;
-    d.k0 = (uint32_t)(seed & 0xffffffffu); d.k1 = (uint32_t)(seed >> 32); d.step = (uint32_t)(step & 0xffffffffu);
-    d.site = site; d.thr = thr; d.inv_keep = inv_keep;
-    return d;
-}
-
 // Query on the lane (forward, bwd_q): bit n of the result = the decision for key 32 kt + n of the lane's query `row`; the lane's
 // register g holds key 2 g + hf.  The tile's eight draws (columns 32 kt + 4 q .. + 3, q = 0 .. 7) are the same for the two lanes
 // of a query, so lane half hf runs draws 4 hf .. 4 hf + 3 and the halves exchange their 16 decisions: four draws per lane and
@@ -117,6 +108,8 @@ __device__ __forceinline__ uint32_t gpt_keep_tile_kv(lq_dropout d, size_t bhL, i
     return bits;
 }
 
+// (the Philox source arrives as the three words of an lq_dropout_src, not as the struct the other kernels take: with the struct
+// the PHILOX instances load their arguments in another grouping and end two SGPRs off the figures on record, LABNOTES)
 template <int DH, int NKT, int MASK>
 __global__ __launch_bounds__(64) void gpt_attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse,
                                                            const unsigned char* __restrict__ keep, float inv_keep,
@@ -170,7 +163,7 @@ __global__ __launch_bounds__(64) void gpt_attention_kernel(const float* __restri
     const float inv = 1.0f / l;
     f32x16 o[DT] = {};
     lq_dropout dr = {};
-    if constexpr (MASK == GPT_MASK_PHILOX) dr = gpt_dropout_load(snap, site, thr, inv_keep);
+    if constexpr (MASK == GPT_MASK_PHILOX) dr = lq_dropout_load(lq_dropout_src{snap, site, thr, inv_keep});
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
         if (kt < kt_end) {
@@ -291,8 +284,7 @@ __global__ __launch_bounds__(64) void gpt_attention_bwd_q_kernel(const float* __
                                                                  const float* __restrict__ go, const float* __restrict__ lse,
                                                                  float* __restrict__ gqkv, float* __restrict__ delta,
                                                                  const unsigned char* __restrict__ keep, float inv_keep,
-                                                                 const int64_t* __restrict__ snap, uint32_t site, uint32_t thr, int L,
-                                                                 int E, int H, int causal, int NT) {
+                                                                 lq_dropout_src src, int L, int E, int H, int causal, int NT) {
     constexpr int DT = DH > 32 ? DH / 32 : 1;
     const int lane = threadIdx.x, c = lane & 31, hf = lane >> 5;
     const int qt = blockIdx.x % NT;
@@ -318,7 +310,7 @@ __global__ __launch_bounds__(64) void gpt_attention_bwd_q_kernel(const float* __
     if (hf == 0 && i < L) delta[bh * L + i] = dl;
     f32x16 dq[DT] = {};
     lq_dropout dr = {};
-    if constexpr (MASK == GPT_MASK_PHILOX) dr = gpt_dropout_load(snap, site, thr, inv_keep);
+    if constexpr (MASK == GPT_MASK_PHILOX) dr = lq_dropout_load(src);
 #pragma unroll 1
     for (int kt = 0; kt < kt_end; ++kt) {
         const int jr = kt * 32 + gpt_perm(c), jrc = jr < L ? jr : L - 1;
@@ -362,8 +354,8 @@ template <int DH, int MASK>
 __global__ __launch_bounds__(64) void gpt_attention_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ go,
                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
                                                                   float* __restrict__ gqkv, const unsigned char* __restrict__ keep,
-                                                                  float inv_keep, const int64_t* __restrict__ snap, uint32_t site,
-                                                                  uint32_t thr, int L, int E, int H, int causal, int NT) {
+                                                                  float inv_keep, lq_dropout_src src, int L, int E, int H, int causal,
+                                                                  int NT) {
     constexpr int DT = DH > 32 ? DH / 32 : 1;
     const int lane = threadIdx.x, c = lane & 31, hf = lane >> 5;
     const int kt = blockIdx.x % NT;
@@ -381,7 +373,7 @@ __global__ __launch_bounds__(64) void gpt_attention_bwd_kv_kernel(const float* _
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) { dk[dt] = f32x16{}; dv[dt] = f32x16{}; }
     lq_dropout dr = {};
-    if constexpr (MASK == GPT_MASK_PHILOX) dr = gpt_dropout_load(snap, site, thr, inv_keep);
+    if constexpr (MASK == GPT_MASK_PHILOX) dr = lq_dropout_load(src);
 #pragma unroll 1
     for (int qt = causal ? kt : 0; qt < NT; ++qt) {
         const int ir = qt * 32 + gpt_perm(c), irc = ir < L ? ir : L - 1;
@@ -450,25 +442,19 @@ static void gpt_for_forward(int dh, int nkt, F&& f) {
     gpt_for_width(dh, [&](auto d) { lq_dispatch<1, 2, 3, 4>(nkt, [&](auto n) { f(d, n); }); });
 }
 
-// the in-kernel source: 0 < p < 1, a snap to read, and a field whose rows fit the 32-bit counter word
-static int gpt_dropout_args(const char* what, const int64_t* snap, double p, int64_t rows) {
-    if (!(p > 0.0 && p < 1.0)) return fail(LIPVQ_EINVAL, "%s: dropout p=%g (0 < p < 1)", what, p);
-    if (rows >= (1LL << 32)) return fail(LIPVQ_EUNSUPPORTED, "%s: %lld rows of decisions (< 2^32)", what, (long long)rows);
-    if (!snap) return fail(LIPVQ_EINVAL, "%s: null snap", what);
-    return 0;
-}
+// the mask source of a launch: src.snap -> PHILOX (inv_keep is src's), keep -> BYTES (inv_keep = 1 / keep_prob), neither -> NONE
+static int gpt_mask_of(const unsigned char* keep, lq_dropout_src src) { return src.snap ? GPT_MASK_PHILOX : keep ? GPT_MASK_BYTES : GPT_MASK_NONE; }
 
-// one forward launch for the three mask sources (keep: BYTES; snap: PHILOX, inv_keep and thr those of its p; neither: NONE)
+// one forward launch for the three mask sources
 static int gpt_attention_launch(const char* what, const float* qkv, float* out, float* lse, const unsigned char* keep, float inv_keep,
-                                const int64_t* snap, uint32_t site, uint32_t thr, int64_t B, int L, int E, int H, int causal,
-                                void* stream) {
+                                lq_dropout_src src, int64_t B, int L, int E, int H, int causal, void* stream) {
     if (!qkv || !out || !lse) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
     if ((((uintptr_t)qkv | (uintptr_t)out) & 15) != 0) return fail(LIPVQ_EINVAL, "%s: qkv / out must be 16-byte aligned", what);
     const int NT = (L + 31) / 32;
-    lq_dispatch<GPT_MASK_NONE, GPT_MASK_BYTES, GPT_MASK_PHILOX>(snap ? GPT_MASK_PHILOX : keep ? GPT_MASK_BYTES : GPT_MASK_NONE, [&](auto m) {
+    lq_dispatch<GPT_MASK_NONE, GPT_MASK_BYTES, GPT_MASK_PHILOX>(gpt_mask_of(keep, src), [&](auto m) {
         gpt_for_forward(E / H, NT, [&](auto d, auto n) {
             hipLaunchKernelGGL((gpt_attention_kernel<d(), n(), decltype(m)::value>), dim3((unsigned)(B * H * NT)), dim3(64), 0, (hipStream_t)stream, qkv,
-                               out, lse, keep, inv_keep, snap, site, thr, L, E, H, causal);
+                               out, lse, keep, inv_keep, src.snap, src.site, src.thr, L, E, H, causal);
         });
     });
     return check_launch(what);
@@ -479,7 +465,7 @@ extern "C" int lipvq_gpt_attention_f32(const float* qkv, float* out, float* lse,
     bool empty = false;
     if (int rc = gpt_attention_args("gpt_attention", B, L, E, H, keep, keep_prob, &empty)) return rc;
     if (empty) return 0;
-    return gpt_attention_launch("gpt_attention", qkv, out, lse, keep, keep ? 1.0f / keep_prob : 1.0f, nullptr, 0, 0, B, L, E, H, causal,
+    return gpt_attention_launch("gpt_attention", qkv, out, lse, keep, keep ? 1.0f / keep_prob : 1.0f, lq_dropout_src{}, B, L, E, H, causal,
                                 stream);
 }
 
@@ -487,10 +473,10 @@ extern "C" int lipvq_gpt_attention_drop_f32(const float* qkv, float* out, float*
                                             int64_t B, int L, int E, int H, int causal, void* stream) {
     bool empty = false;
     if (int rc = gpt_attention_args("gpt_attention_drop", B, L, E, H, nullptr, 1.0f, &empty)) return rc;
-    if (int rc = gpt_dropout_args("gpt_attention_drop", snap, p, B * H * (int64_t)L)) return rc;
+    if (int rc = lq_dropout_check("gpt_attention_drop", snap, p, B * H * (int64_t)L)) return rc;
     if (empty) return 0;
-    return gpt_attention_launch("gpt_attention_drop", qkv, out, lse, nullptr, lq_dropout_inv_keep(p), snap, site, lq_dropout_thr(p), B, L,
-                                E, H, causal, stream);
+    const lq_dropout_src src = lq_dropout_src_make(snap, site, p);
+    return gpt_attention_launch("gpt_attention_drop", qkv, out, lse, nullptr, src.inv_keep, src, B, L, E, H, causal, stream);
 }
 
 extern "C" int lipvq_gpt_attention_prefix_f32(const float* prefix_qkv, const float* qkv, float* out, int64_t B, int64_t Bp, int P,
@@ -516,19 +502,19 @@ extern "C" int lipvq_gpt_attention_prefix_f32(const float* prefix_qkv, const flo
 }
 
 static int gpt_attention_bwd_launch(const char* what, const float* qkv, const float* out, const float* gout, const float* lse,
-                                    float* gqkv, float* delta, const unsigned char* keep, float ik, const int64_t* snap, uint32_t site,
-                                    uint32_t thr, int64_t B, int L, int E, int H, int causal, void* stream) {
+                                    float* gqkv, float* delta, const unsigned char* keep, float ik, lq_dropout_src src, int64_t B,
+                                    int L, int E, int H, int causal, void* stream) {
     if (!qkv || !out || !gout || !lse || !gqkv || !delta) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
     if ((((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)gout | (uintptr_t)gqkv) & 15) != 0)
         return fail(LIPVQ_EINVAL, "%s: qkv / out / gout / gqkv must be 16-byte aligned", what);
     const int NT = (L + 31) / 32;
     const dim3 grid((unsigned)(B * H * NT));
-    lq_dispatch<GPT_MASK_NONE, GPT_MASK_BYTES, GPT_MASK_PHILOX>(snap ? GPT_MASK_PHILOX : keep ? GPT_MASK_BYTES : GPT_MASK_NONE, [&](auto m) {
+    lq_dispatch<GPT_MASK_NONE, GPT_MASK_BYTES, GPT_MASK_PHILOX>(gpt_mask_of(keep, src), [&](auto m) {
         gpt_for_width(E / H, [&](auto d) {
             hipLaunchKernelGGL((gpt_attention_bwd_q_kernel<d(), decltype(m)::value>), grid, dim3(64), 0, (hipStream_t)stream, qkv, out, gout,
-                               lse, gqkv, delta, keep, ik, snap, site, thr, L, E, H, causal, NT);
+                               lse, gqkv, delta, keep, ik, src, L, E, H, causal, NT);
             hipLaunchKernelGGL((gpt_attention_bwd_kv_kernel<d(), decltype(m)::value>), grid, dim3(64), 0, (hipStream_t)stream, qkv, gout, lse,
-                               delta, gqkv, keep, ik, snap, site, thr, L, E, H, causal, NT);
+                               delta, gqkv, keep, ik, src, L, E, H, causal, NT);
         });
     });
     return check_launch(what);
@@ -540,8 +526,8 @@ extern "C" int lipvq_gpt_attention_bwd_f32(const float* qkv, const float* out, c
     bool empty = false;
     if (int rc = gpt_attention_args("gpt_attention_bwd", B, L, E, H, keep, keep_prob, &empty)) return rc;
     if (empty) return 0;
-    return gpt_attention_bwd_launch("gpt_attention_bwd", qkv, out, gout, lse, gqkv, delta, keep, keep ? 1.0f / keep_prob : 1.0f, nullptr,
-                                    0, 0, B, L, E, H, causal, stream);
+    return gpt_attention_bwd_launch("gpt_attention_bwd", qkv, out, gout, lse, gqkv, delta, keep, keep ? 1.0f / keep_prob : 1.0f,
+                                    lq_dropout_src{}, B, L, E, H, causal, stream);
 }
 
 extern "C" int lipvq_gpt_attention_bwd_drop_f32(const float* qkv, const float* out, const float* gout, const float* lse, float* gqkv,
@@ -549,10 +535,11 @@ extern "C" int lipvq_gpt_attention_bwd_drop_f32(const float* qkv, const float* o
                                                 int H, int causal, void* stream) {
     bool empty = false;
     if (int rc = gpt_attention_args("gpt_attention_bwd_drop", B, L, E, H, nullptr, 1.0f, &empty)) return rc;
-    if (int rc = gpt_dropout_args("gpt_attention_bwd_drop", snap, p, B * H * (int64_t)L)) return rc;
+    if (int rc = lq_dropout_check("gpt_attention_bwd_drop", snap, p, B * H * (int64_t)L)) return rc;
     if (empty) return 0;
-    return gpt_attention_bwd_launch("gpt_attention_bwd_drop", qkv, out, gout, lse, gqkv, delta, nullptr, lq_dropout_inv_keep(p), snap, site,
-                                    lq_dropout_thr(p), B, L, E, H, causal, stream);
+    const lq_dropout_src src = lq_dropout_src_make(snap, site, p);
+    return gpt_attention_bwd_launch("gpt_attention_bwd_drop", qkv, out, gout, lse, gqkv, delta, nullptr, src.inv_keep, src, B, L, E, H,
+                                    causal, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -566,14 +553,14 @@ template <bool DROP>
 __global__ __launch_bounds__(256) void gpt_layernorm_kernel(const float4* __restrict__ a, const float4* __restrict__ b,
                                                             const float4* __restrict__ w, const float4* __restrict__ bias, float eps,
                                                             float4* __restrict__ s_out, float4* __restrict__ y, float4* __restrict__ xhat,
-                                                            float* __restrict__ rstd, const int64_t* __restrict__ snap, uint32_t site,
-                                                            uint32_t thr, float inv_keep, int64_t N, int E) {
+                                                            float* __restrict__ rstd, lq_dropout_src src, int64_t N, int E) {
     const int lane = threadIdx.x & 63, E4 = E >> 2;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= N) return;
     const size_t r0 = (size_t)row * E4;
     lq_dropout dr = {};
-    if constexpr (DROP) dr = gpt_dropout_load(snap, site, thr, inv_keep);
+    if constexpr (DROP) dr = lq_dropout_load(src);
+    const float inv_keep = dr.inv_keep;
     float4 x[4];
     float s = 0.0f;
 #pragma unroll
@@ -634,36 +621,34 @@ __global__ __launch_bounds__(256) void gpt_layernorm_kernel(const float4* __rest
 }
 
 static int gpt_layernorm_launch(const char* what, const float* a, const float* b, const float* w, const float* bias, float eps, float* s,
-                                float* y, float* xhat, float* rstd, const int64_t* snap, uint32_t site, double p, int64_t N, int E,
-                                void* stream) {
+                                float* y, float* xhat, float* rstd, lq_dropout_src src, int64_t N, int E, void* stream) {
     if (N < 0 || E <= 0) return fail(LIPVQ_EINVAL, "%s: N=%lld E=%d", what, (long long)N, E);
     if (E > GPT_MAXE || (E & 3) != 0) return fail(LIPVQ_EUNSUPPORTED, "%s: E=%d (a multiple of 4, <= %d)", what, E, GPT_MAXE);
     if (N == 0) return 0;
-    if (!a || !w || !bias || !y || (snap && !b)) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
+    if (!a || !w || !bias || !y || (src.snap && !b)) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
     if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)s | (uintptr_t)y | (uintptr_t)xhat) & 15) != 0)
         return fail(LIPVQ_EINVAL, "%s: pointers must be 16-byte aligned", what);
     if ((N + 3) / 4 > 0x7fffffffLL) return fail(LIPVQ_EUNSUPPORTED, "%s: N=%lld", what, (long long)N);
     const dim3 grid((unsigned)((N + 3) / 4));
-    if (snap)
+    if (src.snap)
         hipLaunchKernelGGL(gpt_layernorm_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const float4*)a, (const float4*)b,
-                           (const float4*)w, (const float4*)bias, eps, (float4*)s, (float4*)y, (float4*)xhat, rstd, snap, site,
-                           lq_dropout_thr(p), lq_dropout_inv_keep(p), N, E);
+                           (const float4*)w, (const float4*)bias, eps, (float4*)s, (float4*)y, (float4*)xhat, rstd, src, N, E);
     else
         hipLaunchKernelGGL(gpt_layernorm_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const float4*)a, (const float4*)b,
-                           (const float4*)w, (const float4*)bias, eps, (float4*)s, (float4*)y, (float4*)xhat, rstd, snap, 0u, 0u, 1.0f, N, E);
+                           (const float4*)w, (const float4*)bias, eps, (float4*)s, (float4*)y, (float4*)xhat, rstd, src, N, E);
     return check_launch(what);
 }
 
 extern "C" int lipvq_gpt_layernorm_f32(const float* a, const float* b, const float* w, const float* bias, float eps, float* s,
                                        float* y, float* xhat, float* rstd, int64_t N, int E, void* stream) {
-    return gpt_layernorm_launch("gpt_layernorm", a, b, w, bias, eps, s, y, xhat, rstd, nullptr, 0, 0.0, N, E, stream);
+    return gpt_layernorm_launch("gpt_layernorm", a, b, w, bias, eps, s, y, xhat, rstd, lq_dropout_src{}, N, E, stream);
 }
 
 extern "C" int lipvq_gpt_layernorm_drop_f32(const float* a, const float* b, const float* w, const float* bias, float eps,
                                             const int64_t* snap, uint32_t site, double p, float* s, float* y, float* xhat, float* rstd,
                                             int64_t N, int E, void* stream) {
-    if (int rc = gpt_dropout_args("gpt_layernorm_drop", snap, p, N)) return rc;
-    return gpt_layernorm_launch("gpt_layernorm_drop", a, b, w, bias, eps, s, y, xhat, rstd, snap, site, p, N, E, stream);
+    if (int rc = lq_dropout_check("gpt_layernorm_drop", snap, p, N)) return rc;
+    return gpt_layernorm_launch("gpt_layernorm_drop", a, b, w, bias, eps, s, y, xhat, rstd, lq_dropout_src_make(snap, site, p), N, E, stream);
 }
 
 // gs = rstd (g w - mean(g w) - xhat mean(g w xhat)) + gres;  gw = sum_rows g xhat;  gb = sum_rows g.
@@ -683,13 +668,13 @@ template <bool DROP>
 __global__ __launch_bounds__(256) void gpt_layernorm_bwd_kernel(const float4* __restrict__ gy, const float4* __restrict__ xhat,
                                                                 const float* __restrict__ rstd, const float4* __restrict__ w,
                                                                 const float4* __restrict__ gres, float4* __restrict__ gs,
-                                                                float4* __restrict__ gbr, float* __restrict__ part,
-                                                                const int64_t* __restrict__ snap, uint32_t site, uint32_t thr,
-                                                                float inv_keep, int64_t N, int E, int rows_per_block) {
+                                                                float4* __restrict__ gbr, float* __restrict__ part, lq_dropout_src src,
+                                                                int64_t N, int E, int rows_per_block) {
     __shared__ float s_gw[4][GPT_MAXE], s_gb[4][GPT_MAXE];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, E4 = E >> 2;
     lq_dropout dr = {};
-    if constexpr (DROP) dr = gpt_dropout_load(snap, site, thr, inv_keep);
+    if constexpr (DROP) dr = lq_dropout_load(src);
+    const float inv_keep = dr.inv_keep;
     float4 pgw[4], pgb[4], ww[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -778,7 +763,7 @@ extern "C" size_t lipvq_gpt_layernorm_bwd_workspace_bytes(int64_t N, int E) {
 
 static int gpt_layernorm_bwd_launch(const char* what, const float* gy, const float* xhat, const float* rstd, const float* w,
                                     const float* gres, float* gs, float* gbr, float* gw, float* gb, void* workspace,
-                                    const int64_t* snap, uint32_t site, double p, int64_t N, int E, void* stream) {
+                                    lq_dropout_src src, int64_t N, int E, void* stream) {
     if (N < 0 || E <= 0) return fail(LIPVQ_EINVAL, "%s: N=%lld E=%d", what, (long long)N, E);
     if (E > GPT_MAXE || (E & 3) != 0) return fail(LIPVQ_EUNSUPPORTED, "%s: E=%d (a multiple of 4, <= %d)", what, E, GPT_MAXE);
     if (!gw || !gb) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
@@ -788,98 +773,30 @@ static int gpt_layernorm_bwd_launch(const char* what, const float* gy, const flo
             return fail(LIPVQ_EHIP, "%s: memset failed", what);
         return 0;
     }
-    if (!gy || !xhat || !rstd || !w || !gs || !workspace || (snap && !gbr)) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
+    if (!gy || !xhat || !rstd || !w || !gs || !workspace || (src.snap && !gbr)) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
     if ((((uintptr_t)gy | (uintptr_t)xhat | (uintptr_t)w | (uintptr_t)gres | (uintptr_t)gs | (uintptr_t)gbr) & 15) != 0)
         return fail(LIPVQ_EINVAL, "%s: pointers must be 16-byte aligned", what);
     const int rpb = gpt_ln_rows_per_block(N);
     const int nblk = (int)((N + rpb - 1) / rpb);
-    if (snap)
+    if (src.snap)
         hipLaunchKernelGGL(gpt_layernorm_bwd_kernel<true>, dim3(nblk), dim3(256), 0, st, (const float4*)gy, (const float4*)xhat, rstd,
-                           (const float4*)w, (const float4*)gres, (float4*)gs, (float4*)gbr, (float*)workspace, snap, site,
-                           lq_dropout_thr(p), lq_dropout_inv_keep(p), N, E, rpb);
+                           (const float4*)w, (const float4*)gres, (float4*)gs, (float4*)gbr, (float*)workspace, src, N, E, rpb);
     else
         hipLaunchKernelGGL(gpt_layernorm_bwd_kernel<false>, dim3(nblk), dim3(256), 0, st, (const float4*)gy, (const float4*)xhat, rstd,
-                           (const float4*)w, (const float4*)gres, (float4*)gs, (float4*)nullptr, (float*)workspace, snap, 0u, 0u, 1.0f, N,
-                           E, rpb);
+                           (const float4*)w, (const float4*)gres, (float4*)gs, (float4*)nullptr, (float*)workspace, src, N, E, rpb);
     hipLaunchKernelGGL(gpt_layernorm_bwd_reduce_kernel, dim3((E + 63) / 64, 2), dim3(256), 0, st, (const float*)workspace, gw, gb, nblk, E);
     return check_launch(what);
 }
 
 extern "C" int lipvq_gpt_layernorm_bwd_f32(const float* gy, const float* xhat, const float* rstd, const float* w, const float* gres,
                                            float* gs, float* gw, float* gb, void* workspace, int64_t N, int E, void* stream) {
-    return gpt_layernorm_bwd_launch("gpt_layernorm_bwd", gy, xhat, rstd, w, gres, gs, nullptr, gw, gb, workspace, nullptr, 0, 0.0, N, E,
-                                    stream);
+    return gpt_layernorm_bwd_launch("gpt_layernorm_bwd", gy, xhat, rstd, w, gres, gs, nullptr, gw, gb, workspace, lq_dropout_src{}, N, E, stream);
 }
 
 extern "C" int lipvq_gpt_layernorm_bwd_drop_f32(const float* gy, const float* xhat, const float* rstd, const float* w, const float* gres,
                                                 const int64_t* snap, uint32_t site, double p, float* gs, float* gbranch, float* gw,
                                                 float* gb, void* workspace, int64_t N, int E, void* stream) {
-    if (int rc = gpt_dropout_args("gpt_layernorm_bwd_drop", snap, p, N)) return rc;
-    return gpt_layernorm_bwd_launch("gpt_layernorm_bwd_drop", gy, xhat, rstd, w, gres, gs, gbranch, gw, gb, workspace, snap, site, p, N, E,
-                                    stream);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// in-kernel dropout: the state, and the decisions of a site as bytes (tests, users; the kernels above never read them)
-// ---------------------------------------------------------------------------------------------------
-__global__ void gpt_dropout_begin_kernel(int64_t* __restrict__ state, int64_t* __restrict__ snap) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const int64_t seed = state[0], step = state[1];
-    snap[0] = seed;
-    snap[1] = step;
-    state[1] = (int64_t)((uint64_t)step + 1u);
-}
-
-extern "C" int lipvq_dropout_begin(int64_t* state, int64_t* snap, void* stream) {
-    if (!state || !snap) return fail(LIPVQ_EINVAL, "dropout_begin: null pointer");
-    if (state == snap) return fail(LIPVQ_EINVAL, "dropout_begin: snap must not be the state itself");
-    hipLaunchKernelGGL(gpt_dropout_begin_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, snap);
-    return check_launch("dropout_begin");
-}
-
-static int gpt_keep_field_args(const char* what, int64_t rows, int64_t cols, double p) {
-    if (!(p > 0.0 && p < 1.0)) return fail(LIPVQ_EINVAL, "%s: dropout p=%g (0 < p < 1)", what, p);
-    if (rows < 0 || cols < 0) return fail(LIPVQ_EINVAL, "%s: rows=%lld cols=%lld", what, (long long)rows, (long long)cols);
-    if (rows >= (1LL << 32) || cols > (1LL << 32)) return fail(LIPVQ_EUNSUPPORTED, "%s: rows=%lld (< 2^32) cols=%lld (<= 2^32)", what, (long long)rows, (long long)cols);
-    return 0;
-}
-
-// one thread per draw: columns 4 c4 .. 4 c4 + 3 of one row
-__global__ __launch_bounds__(256) void gpt_dropout_keep_kernel(const int64_t* __restrict__ snap, uint32_t site, uint32_t thr,
-                                                               int64_t rows, int64_t cols, int64_t cols4, unsigned char* __restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= rows * cols4) return;
-    const int64_t row = t / cols4, c4 = t % cols4;
-    const lq_dropout dr = gpt_dropout_load(snap, site, thr, 1.0f);
-    const uint32_t kb = lq_dropout_keep4(dr, (uint32_t)row, (uint32_t)c4);
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (4 * c4 + k < cols) out[row * cols + 4 * c4 + k] = (unsigned char)((kb >> k) & 1u);
-}
-
-extern "C" int lipvq_dropout_keep_u8(const int64_t* snap, uint32_t site, int64_t rows, int64_t cols, double p, unsigned char* out,
-                                     void* stream) {
-    if (int rc = gpt_keep_field_args("dropout_keep", rows, cols, p)) return rc;
-    if (rows == 0 || cols == 0) return 0;
-    if (!snap || !out) return fail(LIPVQ_EINVAL, "dropout_keep: null pointer");
-    const int64_t cols4 = (cols + 3) / 4;
-    if (rows > (0x7fffffffLL * 256) / cols4) return fail(LIPVQ_EUNSUPPORTED, "dropout_keep: rows=%lld cols=%lld is too large a field for one launch", (long long)rows, (long long)cols);
-    hipLaunchKernelGGL(gpt_dropout_keep_kernel, dim3((unsigned)((rows * cols4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, snap, site,
-                       lq_dropout_thr(p), rows, cols, cols4, out);
-    return check_launch("dropout_keep");
-}
-
-// the same field from the header on the host: no GPU call
-extern "C" int lipvq_dropout_keep_host(uint64_t seed, uint64_t step, uint32_t site, int64_t rows, int64_t cols, double p,
-                                       unsigned char* out) {
-    if (int rc = gpt_keep_field_args("dropout_keep_host", rows, cols, p)) return rc;
-    if (rows == 0 || cols == 0) return 0;
-    if (!out) return fail(LIPVQ_EINVAL, "dropout_keep_host: null pointer");
-    const lq_dropout dr = lq_dropout_make(seed, step, site, p);
-    for (int64_t row = 0; row < rows; ++row)
-        for (int64_t c4 = 0; 4 * c4 < cols; ++c4) {
-            const uint32_t kb = lq_dropout_keep4(dr, (uint32_t)row, (uint32_t)c4);
-            for (int k = 0; k < 4 && 4 * c4 + k < cols; ++k) out[row * cols + 4 * c4 + k] = (unsigned char)((kb >> k) & 1u);
-        }
-    return 0;
+    if (int rc = lq_dropout_check("gpt_layernorm_bwd_drop", snap, p, N)) return rc;
+    return gpt_layernorm_bwd_launch("gpt_layernorm_bwd_drop", gy, xhat, rstd, w, gres, gs, gbranch, gw, gb, workspace,
+                                    lq_dropout_src_make(snap, site, p), N, E, stream);
 }

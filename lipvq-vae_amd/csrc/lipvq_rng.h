@@ -4,7 +4,8 @@
  * ONE definition of Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11; the
  * Random123 known answers hold: tests/test_dropout_host.py) and of the mapping from a dropout SITE to its draws, shared
  * verbatim by the gfx950 device code (hipcc) and by the host (plain g++ / gcc), the way lipvq_math.h is.  Integer arithmetic
- * only: both sides agree in every bit.
+ * only: both sides agree in every bit.  The entry points that belong to no module (lipvq_dropout_begin, the keep fields as bytes)
+ * are in lipvq_rng.hip.
  *
  * The contract (include/lipvq.h, "in-kernel dropout", repeats it).  A site is a 2-D field of decisions; the decision for
  * element (row, col) is word  col & 3  of
@@ -158,6 +159,9 @@ LQ_HD float lq_normal_icdf(float v) {
 
 /* the (seed, step) of a sampling call: the key and step words of lq_dropout, its site the uniform field's */
 LQ_HD lq_dropout lq_sample_make(uint64_t seed, uint64_t step) { return lq_dropout_make(seed, step, LQ_SAMPLE_SITE_GMM, 0.5); }
+
+/* the same from the snap lipvq_dropout_begin wrote, read where the noise is drawn */
+LQ_HD lq_dropout lq_sample_load(const int64_t* snap) { return lq_sample_make((uint64_t)snap[0], (uint64_t)snap[1]); }
 
 /* the row word of input row n = b T + t (see above) */
 LQ_HD uint32_t lq_sample_row(const int64_t* streams, int64_t n, int T) {

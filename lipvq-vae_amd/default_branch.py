@@ -23,6 +23,8 @@ reference in distribution, eval-mode outputs to 1e-5 (tests/test_gpu_default.py)
 _bwd_drop_f32, k = 1 dropout1 and k = 2 dropout2 in the residual launch that adds the branch (lipvq_gpt_layernorm_drop_f32 /
 _bwd_drop_f32), k = 3 the FFN's inner dropout in linear1's epilogue (lipvq_linear_act_drop_f32 / lipvq_act_bwd_drop_f32).  One
 ``ops.dropout_begin`` launch per training forward; no ``rand``, no mask tensor, nothing of it saved, torch's generators untouched.
+``forward`` is ONE encoder-layer loop for both sources: per site it hands the same Function either torch's mask / dropped tensor
+or ``dropout=(snap, site, p)``; under the kernel source a site with p == 0 takes the plain entry point.
 """
 from __future__ import annotations
 
@@ -32,8 +34,7 @@ import torch.nn.functional as F
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .nnfn import (AddDropLayerNormFn, AddLayerNormFn, AttentionDropFn, GraphedEval, KernelDropoutSource, LinearDropFn, LinearFn,
-                   first_order_only)
+from .nnfn import AddLayerNormFn, GraphedEval, KernelDropoutSource, KernelFunction, LinearFn, first_order_only, wants_backward
 from .ops import ACT_GELU, ACT_NONE
 
 
@@ -53,19 +54,25 @@ class _SpectralFn(torch.autograd.Function):
         return ops.spectral_norm_bwd(gWsn.contiguous(), Wsn, u, v, sigma), None, None, None, None
 
 
-class _AttentionFn(torch.autograd.Function):
+class _AttentionFn(KernelFunction):
+    """Unbatched multi-head self-attention over qkv [S, 3D] (ops.attention) with the attention-probability dropout of either
+    source: keep [H, S, S] bytes with keep_prob (torch's generator), or dropout=(snap, site, p) drawn inside the kernels -- then
+    no mask is saved, the two backward launches regenerate the decisions."""
+
     @staticmethod
-    def forward(ctx, qkv, nhead, keep, keep_prob):
-        out, lse = ops.attention(qkv, nhead, keep, keep_prob)
-        ctx.nhead, ctx.keep, ctx.keep_prob = nhead, keep, keep_prob
-        ctx.save_for_backward(qkv, out, lse)
+    def forward(ctx, qkv, nhead, keep=None, keep_prob=1.0, dropout=None):
+        out, lse = ops.attention(qkv, nhead, keep, keep_prob, dropout=dropout)
+        if wants_backward(ctx):
+            ctx.nhead, ctx.keep, ctx.keep_prob, ctx.dropout = nhead, keep, keep_prob, dropout
+            ctx.save_for_backward(qkv, out, lse)
         return out
 
     @staticmethod
     @first_order_only
     def backward(ctx, gout):
         qkv, out, lse = ctx.saved_tensors
-        return ops.attention_bwd(qkv, out, gout.contiguous(), lse, ctx.nhead, ctx.keep, ctx.keep_prob), None, None, None
+        return (ops.attention_bwd(qkv, out, gout.contiguous(), lse, ctx.nhead, ctx.keep, ctx.keep_prob, dropout=ctx.dropout),
+                None, None, None, None)
 
 
 class DefaultActionNetwork(KernelDropoutSource, nn.Sequential):
@@ -105,56 +112,34 @@ class DefaultActionNetwork(KernelDropoutSource, nn.Sequential):
         h = LinearFn.apply(h, self._sn_weight(self[2]), self[2].bias, ACT_GELU)
         h = LinearFn.apply(h, self._sn_weight(self[4]), self[4].bias, ACT_NONE)
         S = h.shape[0]
-        if self._kernel_dropout():
-            h = self._encoder_kernel_dropout(h)
-            return LinearFn.apply(h, self[6].weight, self[6].bias, ACT_NONE)
-        for layer in self[5].layers:
-            attn = layer.self_attn
-            p = float(attn.dropout) if self.training else 0.0
-            keep, keep_prob = None, 1.0
-            if p > 0.0:
-                keep = (torch.rand((self.NHEAD, S, S), device=h.device) >= p).to(torch.uint8)
-                keep_prob = 1.0 - p
-            qkv = LinearFn.apply(h, attn.in_proj_weight, attn.in_proj_bias, ACT_NONE)
-            a = _AttentionFn.apply(qkv, self.NHEAD, keep, keep_prob)
-            a = LinearFn.apply(a, attn.out_proj.weight, attn.out_proj.bias, ACT_NONE)
-            a = F.dropout(a, layer.dropout1.p, self.training)
-            h = AddLayerNormFn.apply(h, a, layer.norm1.weight, layer.norm1.bias, layer.norm1.eps, False)[1]
-            f = LinearFn.apply(h, layer.linear1.weight, layer.linear1.bias, ACT_GELU)
-            f = F.dropout(f, layer.dropout.p, self.training)
-            f = LinearFn.apply(f, layer.linear2.weight, layer.linear2.bias, ACT_NONE)
-            f = F.dropout(f, layer.dropout2.p, self.training)
-            h = AddLayerNormFn.apply(h, f, layer.norm2.weight, layer.norm2.bias, layer.norm2.eps, False)[1]
-        return LinearFn.apply(h, self[6].weight, self[6].bias, ACT_NONE)
-
-    def _encoder_kernel_dropout(self, h):
-        """The encoder layers of a training forward under the in-kernel source: one dropout_begin launch, then per layer the
-        launches of the eval forward, the _drop form wherever a p is positive (a site with p == 0 takes the plain entry point)."""
-        snap = self._dropout_begin(h.device)
-
-        def add_ln(a, b, site, p, norm):
-            if p > 0.0:
-                return AddDropLayerNormFn.apply(a, b, norm.weight, norm.bias, norm.eps, False, snap, site, p)[1]
-            return AddLayerNormFn.apply(a, b, norm.weight, norm.bias, norm.eps, False)[1]
-
+        training, kernel = self.training, self._kernel_dropout()
+        snap = self._dropout_begin(h.device) if kernel else None
         for i, layer in enumerate(self[5].layers):
             attn, site = layer.self_attn, ops.DROPOUT_SITE_DEFAULT + 4 * i
-            p_att, p1 = self._dropout_p(attn.dropout, "attention dropout"), self._dropout_p(layer.dropout1.p, "dropout1")
-            p2, p_ff = self._dropout_p(layer.dropout2.p, "dropout2"), self._dropout_p(layer.dropout.p, "dropout")
+            keep, keep_prob = None, 1.0
+            drops = (None, None, None, None)                   # site + k -> what its launch is handed under the kernel source
+            if kernel:
+                ps = (self._dropout_p(attn.dropout, "attention dropout"), self._dropout_p(layer.dropout1.p, "dropout1"),
+                      self._dropout_p(layer.dropout2.p, "dropout2"), self._dropout_p(layer.dropout.p, "dropout"))
+                drops = tuple((snap, site + k, p) if p > 0.0 else None for k, p in enumerate(ps))      # (p == 0: the plain form)
+            elif training and float(attn.dropout) > 0.0:
+                keep = (torch.rand((self.NHEAD, S, S), device=h.device) >= float(attn.dropout)).to(torch.uint8)
+                keep_prob = 1.0 - float(attn.dropout)
             qkv = LinearFn.apply(h, attn.in_proj_weight, attn.in_proj_bias, ACT_NONE)
-            if p_att > 0.0:
-                a = AttentionDropFn.apply(qkv, self.NHEAD, snap, site, p_att)
-            else:
-                a = _AttentionFn.apply(qkv, self.NHEAD, None, 1.0)
+            a = _AttentionFn.apply(qkv, self.NHEAD, keep, keep_prob, drops[0])
             a = LinearFn.apply(a, attn.out_proj.weight, attn.out_proj.bias, ACT_NONE)
-            h = add_ln(h, a, site + 1, p1, layer.norm1)
-            if p_ff > 0.0:
-                f = LinearDropFn.apply(h, layer.linear1.weight, layer.linear1.bias, ACT_GELU, snap, site + 3, p_ff)
-            else:
-                f = LinearFn.apply(h, layer.linear1.weight, layer.linear1.bias, ACT_GELU)
+            if not kernel:
+                a = F.dropout(a, layer.dropout1.p, training)
+            h = AddLayerNormFn.apply(h, a, layer.norm1.weight, layer.norm1.bias, layer.norm1.eps, False, drops[1])[1]
+            # the FFN's inner dropout: the kernel source decides it in linear1's epilogue, torch's on linear1's result
+            f = LinearFn.apply(h, layer.linear1.weight, layer.linear1.bias, ACT_GELU, "fp32", drops[3])
+            if not kernel:
+                f = F.dropout(f, layer.dropout.p, training)
             f = LinearFn.apply(f, layer.linear2.weight, layer.linear2.bias, ACT_NONE)
-            h = add_ln(h, f, site + 2, p2, layer.norm2)
-        return h
+            if not kernel:
+                f = F.dropout(f, layer.dropout2.p, training)
+            h = AddLayerNormFn.apply(h, f, layer.norm2.weight, layer.norm2.bias, layer.norm2.eps, False, drops[2])[1]
+        return LinearFn.apply(h, self[6].weight, self[6].bias, ACT_NONE)
 
 
 class GraphedDefaultBranch(GraphedEval):

@@ -40,7 +40,8 @@ dropout kernel).  ``activation="geglu"`` is not implemented (the ICRT configurat
 Dropout, the opt-in in-kernel source (``set_dropout_source("kernel")``): the same three sites are decided INSIDE the kernels
 that touch those elements -- the attention probabilities in lipvq_gpt_attention_drop_f32 / _bwd_drop_f32, a branch in the
 residual launch that adds it, lipvq_gpt_layernorm_drop_f32 / _bwd_drop_f32 (the attention-output branch on ln2, the MLP branch
-on the next block's ln1 or the closing output_ln).  Every decision is a pure function of (seed, step, site = 4 layer + 0 / 1 / 2,
+on the next block's ln1 or the closing output_ln).  ``forward`` is ONE block loop for both sources: per site it hands the same
+Function either the torch-drawn mask / dropped branch or ``dropout=(snap, site, p)``, and a site with p == 0 takes the plain form.  Every decision is a pure function of (seed, step, site = 4 layer + 0 / 1 / 2,
 row, col) through Philox4x32-10 (csrc/lipvq_rng.h; the contract is in include/lipvq.h): no mask tensor exists, nothing of it is
 saved, the backward regenerates it, and torch's generators are not touched.  One one-thread launch per training forward
 (lipvq_dropout_begin) hands the call its (seed, step) and advances the step on the device, so a captured graph advances on every
@@ -56,8 +57,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .derived import stamp
-from .nnfn import (AddDropLayerNormFn, AddLayerNormFn, GraphedEval, KernelDropoutSource, KernelFunction, LinearFn, first_order_only,
-                   wants_backward)
+from .nnfn import AddLayerNormFn, GraphedEval, KernelDropoutSource, KernelFunction, LinearFn, first_order_only, wants_backward
 from .ops import ACT_GELU, ACT_NONE
 
 __all__ = ["GPTBackbone", "GraphedGPTBackbone", "PromptCache", "PromptedGPTBackbone", "StalePromptCache"]
@@ -67,31 +67,16 @@ class StalePromptCache(RuntimeError):
     """forward_cached: the cache no longer belongs to the backbone's parameters or matmul precision; prefill() again."""
 
 
-class _AttentionFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, qkv, nhead, causal, keep, keep_prob):
-        out, lse = ops.gpt_attention(qkv, nhead, causal, keep, keep_prob)
-        ctx.nhead, ctx.causal, ctx.keep, ctx.keep_prob = nhead, causal, keep, keep_prob
-        ctx.save_for_backward(qkv, out, lse)
-        return out
+class _AttentionFn(KernelFunction):
+    """Batched attention over qkv [B, L, 3E] with the attention-probability dropout of either source: keep [B, H, L, L] bytes
+    with keep_prob (torch's generator), or dropout=(snap, site, p) drawn inside the kernels -- then no mask is saved, the two
+    backward launches regenerate the decisions from snap."""
 
     @staticmethod
-    @first_order_only
-    def backward(ctx, gout):
-        qkv, out, lse = ctx.saved_tensors
-        return (ops.gpt_attention_bwd(qkv, out, gout.contiguous(), lse, ctx.nhead, ctx.causal, ctx.keep, ctx.keep_prob),
-                None, None, None, None)
-
-
-class _AttentionDropFn(KernelFunction):
-    """_AttentionFn with the attention-probability dropout drawn inside the kernels (in-kernel source: snap, site, p).  No mask
-    is saved: the two backward launches regenerate the decisions from snap."""
-
-    @staticmethod
-    def forward(ctx, qkv, nhead, causal, snap, site, p):
-        out, lse = ops.gpt_attention(qkv, nhead, causal, dropout=(snap, site, p))
+    def forward(ctx, qkv, nhead, causal, keep=None, keep_prob=1.0, dropout=None):
+        out, lse = ops.gpt_attention(qkv, nhead, causal, keep, keep_prob, dropout=dropout)
         if wants_backward(ctx):
-            ctx.nhead, ctx.causal, ctx.dropout = nhead, causal, (snap, site, p)
+            ctx.nhead, ctx.causal, ctx.keep, ctx.keep_prob, ctx.dropout = nhead, causal, keep, keep_prob, dropout
             ctx.save_for_backward(qkv, out, lse)
         return out
 
@@ -99,8 +84,8 @@ class _AttentionDropFn(KernelFunction):
     @first_order_only
     def backward(ctx, gout):
         qkv, out, lse = ctx.saved_tensors
-        return (ops.gpt_attention_bwd(qkv, out, gout.contiguous(), lse, ctx.nhead, ctx.causal, dropout=ctx.dropout),
-                None, None, None, None, None)
+        return (ops.gpt_attention_bwd(qkv, out, gout.contiguous(), lse, ctx.nhead, ctx.causal, ctx.keep, ctx.keep_prob,
+                                      dropout=ctx.dropout), None, None, None, None, None)
 
 
 class _SelfAttention(nn.Module):
@@ -201,79 +186,59 @@ class GPTBackbone(KernelDropoutSource, nn.Module):
         return list(input_shape)
 
     def forward(self, inputs: torch.Tensor) -> torch.Tensor:
+        """One block loop for eval and for training under either dropout source.  Torch source: the attention mask is drawn here
+        as keep bytes and a branch is dropped by F.dropout before the residual launch.  Kernel source: one dropout_begin launch,
+        then the same launches per block as eval, each site with p > 0 handed dropout=(snap, site, p); a branch's dropout rides
+        on the residual launch that adds the branch: the attention-output branch's on ln2, the MLP branch's on the NEXT block's
+        ln1 (the closing output_ln for the last)."""
         assert inputs.shape[1:] == (self.context_length, self.embed_dim), inputs.shape
         if not inputs.is_cuda:
             raise RuntimeError("GPTBackbone runs on the HIP library only (no CPU path)")
         x = inputs.contiguous().float()
         B, L, H = x.shape[0], self.context_length, self.num_heads
-        prec = self._matmul_precision
-        if self._kernel_dropout():
-            return self._forward_kernel_dropout(x)
-        a, b = x, None
-        for blk in self.nets["transformer"]:
+        prec, causal = self._matmul_precision, bool(self.causal)
+        training, kernel = self.training, self._kernel_dropout()
+        snap = self._dropout_begin(x.device) if kernel else None
+
+        def drop(t, site, p):
+            """a branch of site `site` with p > 0 -> (the tensor to add, the dropout the adding launch applies or None)"""
+            return (t, (snap, site, p)) if kernel else (F.dropout(t, p, True), None)
+
+        a, b, b_drop = x, None, None
+        p_att = p_out = p_mlp = 0.0                            # eval: every site takes the plain form
+        for i, blk in enumerate(self.nets["transformer"]):
             att, mlp, ln1, ln2 = blk.nets["attention"], blk.nets["mlp"], blk.nets["ln1"], blk.nets["ln2"]
-            p_att = float(att.nets["attn_dropout"].p) if self.training else 0.0
-            p_out = float(att.nets["output_dropout"].p) if self.training else 0.0
-            p_mlp = float(mlp[3].p) if self.training else 0.0
-            keep, keep_prob = None, 1.0
+            if kernel:
+                p_att, p_out, p_mlp = (self._dropout_p(att.nets["attn_dropout"].p, "attn_dropout"),
+                                       self._dropout_p(att.nets["output_dropout"].p, "output_dropout"),
+                                       self._dropout_p(mlp[3].p, "mlp dropout"))
+            elif training:
+                p_att, p_out, p_mlp = float(att.nets["attn_dropout"].p), float(att.nets["output_dropout"].p), float(mlp[3].p)
+            keep, keep_prob, att_drop = None, 1.0, None
             if p_att > 0.0:
-                keep = (torch.rand((B, H, L, L), device=x.device) >= p_att).to(torch.uint8)
-                keep_prob = 1.0 - p_att
+                if kernel:
+                    att_drop = (snap, 4 * i, p_att)
+                else:
+                    keep = (torch.rand((B, H, L, L), device=x.device) >= p_att).to(torch.uint8)
+                    keep_prob = 1.0 - p_att
             if b is None:                                      # first block: the stream is the input itself, nothing to add or copy
                 s, y = a, AddLayerNormFn.apply(a, None, ln1.weight, ln1.bias, ln1.eps, False)[1]
             else:
-                s, y = AddLayerNormFn.apply(a, b, ln1.weight, ln1.bias, ln1.eps, True)
+                s, y = AddLayerNormFn.apply(a, b, ln1.weight, ln1.bias, ln1.eps, True, b_drop)
             qkv = LinearFn.apply(y, att.nets["qkv"].weight, None, ACT_NONE, prec)
-            o = _AttentionFn.apply(qkv, H, bool(self.causal), keep, keep_prob)
+            o = _AttentionFn.apply(qkv, H, causal, keep, keep_prob, att_drop)
             o = LinearFn.apply(o, att.nets["output"].weight, att.nets["output"].bias, ACT_NONE, prec)
+            o_drop = None
             if p_out > 0.0:
-                o = F.dropout(o, p_out, True)
-            s, y = AddLayerNormFn.apply(s, o, ln2.weight, ln2.bias, ln2.eps, True)
+                o, o_drop = drop(o, 4 * i + 1, p_out)
+            s, y = AddLayerNormFn.apply(s, o, ln2.weight, ln2.bias, ln2.eps, True, o_drop)
             f = LinearFn.apply(y, mlp[0].weight, mlp[0].bias, ACT_GELU, prec)
             f = LinearFn.apply(f, mlp[2].weight, mlp[2].bias, ACT_NONE, prec)
+            a, b, b_drop = s, f, None
             if p_mlp > 0.0:
-                f = F.dropout(f, p_mlp, True)
-            a, b = s, f
+                b, b_drop = drop(f, 4 * i + 2, p_mlp)
         ln = self.nets["output_ln"]
-        out = AddLayerNormFn.apply(a, b, ln.weight, ln.bias, ln.eps, False)[1]
-        return out
-
-    def _forward_kernel_dropout(self, x):
-        """The training forward under the in-kernel source: one dropout_begin launch, then the same launches per block as eval,
-        the _drop forms where a p is positive.  A branch's dropout rides on the residual launch that adds the branch: the
-        attention-output branch's on ln2, the MLP branch's on the NEXT block's ln1 (the closing output_ln for the last)."""
-        H, prec = self.num_heads, self._matmul_precision
-        snap = self._dropout_begin(x.device)
-
-        def p_of(module, what):
-            return self._dropout_p(module.p, what)
-
-        def add_ln(a, b, drop, ln, want_s):
-            if drop is not None and drop[1] > 0.0:
-                return AddDropLayerNormFn.apply(a, b, ln.weight, ln.bias, ln.eps, want_s, snap, drop[0], drop[1])
-            return AddLayerNormFn.apply(a, b, ln.weight, ln.bias, ln.eps, want_s)
-
-        a, b, b_drop = x, None, None
-        for i, blk in enumerate(self.nets["transformer"]):
-            att, mlp, ln1, ln2 = blk.nets["attention"], blk.nets["mlp"], blk.nets["ln1"], blk.nets["ln2"]
-            p_att, p_out, p_mlp = (p_of(att.nets["attn_dropout"], "attn_dropout"), p_of(att.nets["output_dropout"], "output_dropout"),
-                                   p_of(mlp[3], "mlp dropout"))
-            if b is None:
-                s, y = a, AddLayerNormFn.apply(a, None, ln1.weight, ln1.bias, ln1.eps, False)[1]
-            else:
-                s, y = add_ln(a, b, b_drop, ln1, True)
-            qkv = LinearFn.apply(y, att.nets["qkv"].weight, None, ACT_NONE, prec)
-            if p_att > 0.0:
-                o = _AttentionDropFn.apply(qkv, H, bool(self.causal), snap, 4 * i, p_att)
-            else:
-                o = _AttentionFn.apply(qkv, H, bool(self.causal), None, 1.0)
-            o = LinearFn.apply(o, att.nets["output"].weight, att.nets["output"].bias, ACT_NONE, prec)
-            s, y = add_ln(s, o, (4 * i + 1, p_out), ln2, True)
-            f = LinearFn.apply(y, mlp[0].weight, mlp[0].bias, ACT_GELU, prec)
-            f = LinearFn.apply(f, mlp[2].weight, mlp[2].bias, ACT_NONE, prec)
-            a, b, b_drop = s, f, (4 * i + 2, p_mlp)
-        ln = self.nets["output_ln"]
-        return add_ln(a, b, b_drop, ln, False)[1]
+        return AddLayerNormFn.apply(a, b, ln.weight, ln.bias, ln.eps, False, b_drop)[1]
 
     # -- the prompt cache: a rollout's constant prefix is run once, every step runs its new tokens alone ---------------------
     def _cacheable(self, what):

@@ -12,8 +12,8 @@ from . import ops
 from .capture import capture, copy_in, warm_up
 from .ops import ACT_NONE
 
-__all__ = ["LinearFn", "LinearDropFn", "AddLayerNormFn", "AddDropLayerNormFn", "AttentionDropFn", "GraphedEval", "KernelDropoutSource",
-           "KernelSampleSource", "KernelFunction", "first_order_only", "wants_backward"]
+__all__ = ["LinearFn", "AddLayerNormFn", "GraphedEval", "KernelDropoutSource", "KernelSampleSource", "KernelFunction",
+           "first_order_only", "wants_backward"]
 
 _applying = threading.local()
 
@@ -73,58 +73,28 @@ class LinearFn(KernelFunction):
     precision="bf16": the three matrix products run on the bf16 matrix pipe (ops.linear_bf16 / linear_nn_bf16 / wgrad_bf16:
     operands rounded to bf16 as they are read, fp32 accumulation, fp32 tensors); precision="bf16x3": the same pipe with every
     operand split into two bf16 numbers and three products per product (ops.linear_bf16x3 / linear_nn_bf16x3 / wgrad_bf16x3);
-    act' stays the fp32 kernel."""
+    act' stays the fp32 kernel.
+    dropout=(snap, site, p) of the in-kernel source (fp32 only): the result is act(x W^T + b) * m, decided in the Linear's epilogue
+    over the rows and columns of the 2-D result.  No mask is saved: the backward's first launch forms act'(pre) (gy m) from the
+    regenerated decisions (ops.act_bwd with dropout), whatever act is."""
 
     @staticmethod
-    def forward(ctx, x, W, b, act, precision="fp32"):
+    def forward(ctx, x, W, b, act, precision="fp32", dropout=None):
         if precision not in ("fp32", "bf16", "bf16x3"):
             raise ValueError(f"LinearFn: precision must be 'fp32', 'bf16' or 'bf16x3', got {precision!r}")
+        if dropout is not None and precision != "fp32":
+            raise ValueError(f"LinearFn: dropout (the in-kernel source) has fp32 kernels only, got precision {precision!r}")
         ctx.act, ctx.has_bias, ctx.shape, ctx.pipe = act, b is not None, x.shape, ("" if precision == "fp32" else "_" + precision)
+        ctx.dropout = dropout
         linear = getattr(ops, "linear" + ctx.pipe)
         x2 = x if x.dim() == 2 else x.reshape(-1, x.shape[-1])      # (2-D callers: no view objects on their host-bound paths)
         if not wants_backward(ctx):                            # eval / no_grad: no pre-activation is written, nothing is kept
-            y = linear(x2, W, b, act=act)
+            y = linear(x2, W, b, act=act, dropout=dropout)
         elif act != ACT_NONE:
-            y, pre = linear(x2, W, b, act=act, save_pre=True)
+            y, pre = linear(x2, W, b, act=act, save_pre=True, dropout=dropout)
             ctx.save_for_backward(x2, W, pre)
         else:
-            y = linear(x2, W, b)
-            ctx.save_for_backward(x2, W)
-        return y if x.dim() == 2 else y.view(*x.shape[:-1], W.shape[0])
-
-    @staticmethod
-    @first_order_only
-    def backward(ctx, gy):
-        gy = gy.reshape(-1, gy.shape[-1]).contiguous()
-        if ctx.act != ACT_NONE:
-            x2, W, pre = ctx.saved_tensors
-            gy = ops.act_bwd(gy, pre, ctx.act)
-        else:
-            x2, W = ctx.saved_tensors
-        gx = gW = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = (getattr(ops, "linear_nn" + ctx.pipe)(gy, W) if ctx.pipe else ops.linear(gy, W.t().contiguous())).view(ctx.shape)
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            gW, gb = getattr(ops, "wgrad" + ctx.pipe)(gy, x2, want_bias=ctx.has_bias)
-        return gx, gW, gb, None, None
-
-
-class LinearDropFn(KernelFunction):
-    """act(x W^T + b) * m with the dropout decided in the Linear's epilogue (in-kernel source: snap, site, p; field = the rows and
-    columns of the 2-D result).  fp32 only.  No mask is saved: the backward's first launch forms act'(pre) (gy m) from the
-    regenerated decisions (ops.act_bwd_drop), then the input-gradient Linear and the wgrad kernel of LinearFn follow."""
-
-    @staticmethod
-    def forward(ctx, x, W, b, act, snap, site, p):
-        ctx.act, ctx.has_bias, ctx.shape, ctx.dropout = act, b is not None, x.shape, (snap, site, p)
-        x2 = x if x.dim() == 2 else x.reshape(-1, x.shape[-1])
-        if not wants_backward(ctx):
-            y = ops.linear_act_drop(x2, W, b, act, ctx.dropout)
-        elif act != ACT_NONE:
-            y, pre = ops.linear_act_drop(x2, W, b, act, ctx.dropout, save_pre=True)
-            ctx.save_for_backward(x2, W, pre)
-        else:
-            y = ops.linear_act_drop(x2, W, b, act, ctx.dropout)
+            y = linear(x2, W, b, dropout=dropout)
             ctx.save_for_backward(x2, W)
         return y if x.dim() == 2 else y.view(*x.shape[:-1], W.shape[0])
 
@@ -136,86 +106,98 @@ class LinearDropFn(KernelFunction):
             x2, W, pre = ctx.saved_tensors
         else:
             (x2, W), pre = ctx.saved_tensors, None
-        gy = ops.act_bwd_drop(gy, pre, ctx.act, ctx.dropout)
+        if pre is not None or ctx.dropout is not None:
+            gy = ops.act_bwd(gy, pre, ctx.act, dropout=ctx.dropout)
         gx = gW = gb = None
         if ctx.needs_input_grad[0]:
-            gx = ops.linear(gy, W.t().contiguous()).view(ctx.shape)
+            gx = (getattr(ops, "linear_nn" + ctx.pipe)(gy, W) if ctx.pipe else ops.linear(gy, W.t().contiguous())).view(ctx.shape)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            gW, gb = ops.wgrad(gy, x2, want_bias=ctx.has_bias)
-        return gx, gW, gb, None, None, None, None
-
-
-class AttentionDropFn(KernelFunction):
-    """Unbatched multi-head self-attention over qkv [S, 3D] (ops.attention) with the attention-probability dropout drawn inside
-    the kernels (in-kernel source: snap, site, p).  No mask is saved: the two backward launches regenerate the decisions."""
-
-    @staticmethod
-    def forward(ctx, qkv, nhead, snap, site, p):
-        out, lse = ops.attention_drop(qkv, nhead, (snap, site, p))
-        if wants_backward(ctx):
-            ctx.nhead, ctx.dropout = nhead, (snap, site, p)
-            ctx.save_for_backward(qkv, out, lse)
-        return out
-
-    @staticmethod
-    @first_order_only
-    def backward(ctx, gout):
-        qkv, out, lse = ctx.saved_tensors
-        return ops.attention_bwd_drop(qkv, out, gout.contiguous(), lse, ctx.nhead, ctx.dropout), None, None, None, None
+            gW, gb = getattr(ops, "wgrad" + ctx.pipe)(gy, x2, want_bias=ctx.has_bias)
+        return gx, gW, gb, None, None, None
 
 
 class AddLayerNormFn(KernelFunction):
     """(s, y) = (a + b, LayerNorm(a + b) w + bias), b optional; s is None unless want_s (a post-norm residual and the closing
     LayerNorm of a pre-norm stack discard it, and without b the caller keeps using a).  Backward: the gradient of a and of b is
-    LayerNorm's plus the gradient that arrives for s (the residual stream), added inside the kernel."""
+    LayerNorm's plus the gradient that arrives for s (the residual stream), added inside the kernel.
+    dropout=(snap, site, p) of the in-kernel source: (s, y) = (a + drop(b), LayerNorm(a + drop(b)) w + bias), the branch's dropout
+    decided inside the launch.  No mask is saved: the backward launch regenerates the decisions from snap and writes the gradient
+    of a (LayerNorm's plus the stream's) and that of b (the same times the mask factor) itself."""
 
     @staticmethod
-    def forward(ctx, a, b, w, bias, eps, want_s):
+    def forward(ctx, a, b, w, bias, eps, want_s, dropout=None):
         ctx.set_materialize_grads(False)
-        ctx.has_b = b is not None
+        ctx.has_b, ctx.dropout = b is not None, dropout
         if not wants_backward(ctx):                            # eval / no_grad: nothing is kept for a backward
-            return ops.gpt_layernorm(a, b, w, bias, eps, want_s=want_s)
-        s, y, xhat, rstd = ops.gpt_layernorm(a, b, w, bias, eps, want_s=want_s, save=True)
+            return ops.gpt_layernorm(a, b, w, bias, eps, want_s=want_s, dropout=dropout)
+        s, y, xhat, rstd = ops.gpt_layernorm(a, b, w, bias, eps, want_s=want_s, save=True, dropout=dropout)
         ctx.save_for_backward(xhat, rstd, w)
         return s, y
 
     @staticmethod
     @first_order_only
     def backward(ctx, gs, gy):
-        if gy is None:
-            return gs, (gs if ctx.has_b else None), None, None, None, None
-        xhat, rstd, w = ctx.saved_tensors
-        g, gw, gb = ops.gpt_layernorm_bwd(gy.contiguous(), xhat, rstd, w, None if gs is None else gs.contiguous())
-        return g, (g if ctx.has_b else None), gw, gb, None, None
-
-
-class AddDropLayerNormFn(KernelFunction):
-    """(s, y) = (a + drop(b), LayerNorm(a + drop(b)) w + bias) with the branch's dropout decided inside the launch (in-kernel
-    source: dropout = (snap, site, p), include/lipvq.h).  No mask is saved: the backward launch regenerates the decisions from
-    snap and writes the gradient of a (LayerNorm's plus the stream's) and that of b (the same times the mask factor) itself."""
-
-    @staticmethod
-    def forward(ctx, a, b, w, bias, eps, want_s, snap, site, p):
-        ctx.set_materialize_grads(False)
-        ctx.dropout = (snap, site, p)
-        if not wants_backward(ctx):
-            return ops.gpt_layernorm_drop(a, b, w, bias, eps, ctx.dropout, want_s=want_s)
-        s, y, xhat, rstd = ops.gpt_layernorm_drop(a, b, w, bias, eps, ctx.dropout, want_s=want_s, save=True)
-        ctx.save_for_backward(xhat, rstd, w)
-        return s, y
-
-    @staticmethod
-    @first_order_only
-    def backward(ctx, gs, gy):
+        if ctx.dropout is None:                                # a and b share one gradient tensor
+            if gy is None:
+                return gs, (gs if ctx.has_b else None), None, None, None, None, None
+            xhat, rstd, w = ctx.saved_tensors
+            g, gw, gb = ops.gpt_layernorm_bwd(gy.contiguous(), xhat, rstd, w, None if gs is None else gs.contiguous())
+            return g, (g if ctx.has_b else None), gw, gb, None, None, None
         xhat, rstd, w = ctx.saved_tensors
         if gy is None and gs is None:
-            return (None,) * 9
+            return (None,) * 7
         if gy is None:                                         # only s was used: LayerNorm's part is that of a zero gradient
             gy = torch.zeros_like(xhat)
-        g, gbr, gw, gb = ops.gpt_layernorm_drop_bwd(gy.contiguous(), xhat, rstd, w, ctx.dropout, None if gs is None else gs.contiguous())
+        g, gbr, gw, gb = ops.gpt_layernorm_bwd(gy.contiguous(), xhat, rstd, w, None if gs is None else gs.contiguous(),
+                                               dropout=ctx.dropout)
         need = ctx.needs_input_grad
         return (g if need[0] else None, gbr if need[1] else None, gw if need[2] else None, gb if need[3] else None,
-                None, None, None, None, None)
+                None, None, None)
+
+
+class _SourceState:
+    """The (seed, step) state of an in-kernel random source, kept on the host module as the non-persistent buffer
+    ``_{word}_state`` beside the attribute ``_{word}_source``: what KernelDropoutSource (word "dropout") and KernelSampleSource
+    (word "sample") share.  ``reseed`` names the module's reseeding method, ``noun`` the state in the device message, and
+    ``owner(module)`` gives the class name the messages carry."""
+
+    def __init__(self, word, reseed, noun, owner):
+        self.word, self.reseed, self.noun, self.owner = word, reseed, noun, owner
+        self.state_attr, self.source_attr = f"_{word}_state", f"_{word}_source"
+
+    def set_source(self, mod, source, seed):
+        """Create-on-first-"kernel": nothing exists before it, a later call with a seed reseeds (step 0), one without leaves it."""
+        if source not in ("torch", "kernel"):
+            raise ValueError(f"{self.owner(mod)}: {self.word} source must be 'torch' or 'kernel', got {source!r}")
+        if source == "kernel":
+            if getattr(mod, self.state_attr, None) is None:
+                dev = next(mod.parameters()).device
+                mod.register_buffer(self.state_attr, torch.zeros(2, dtype=torch.int64, device=dev), persistent=False)
+                getattr(mod, self.reseed)(torch.initial_seed() if seed is None else seed)
+            elif seed is not None:
+                getattr(mod, self.reseed)(seed)
+        setattr(mod, self.source_attr, source)
+        return mod
+
+    def reseed_state(self, mod, seed, step):
+        state = getattr(mod, self.state_attr, None)
+        if state is None:
+            raise RuntimeError(f"{self.owner(mod)}.{self.reseed}: call set_{self.word}_source('kernel') first (it creates the state)")
+        words = [int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)]
+        words = [v - 2 ** 64 if v >= 2 ** 63 else v for v in words]          # (the bit pattern, as int64)
+        state.copy_(torch.tensor(words, dtype=torch.int64))
+        return mod
+
+    def begin(self, mod, device):
+        """The snap of one call: one dropout_begin launch on the module's own state."""
+        state = getattr(mod, self.state_attr)
+        if state.device != device:
+            raise RuntimeError(f"{self.owner(mod)}: the {self.noun} state is not on the input's device (move the module with .to())")
+        return ops.dropout_begin(state)
+
+
+_DROPOUT_STATE = _SourceState("dropout", "reseed_dropout", "dropout", lambda mod: mod._dropout_owner())
+_SAMPLE_STATE = _SourceState("sample", "reseed_sampling", "sampling", lambda mod: type(mod).__name__)
 
 
 class KernelDropoutSource:
@@ -246,17 +228,7 @@ class KernelDropoutSource:
         ``torch.initial_seed()``; a later call with a seed reseeds it (step 0), one without leaves it.  It is a non-persistent
         buffer: ``.to()`` moves it, ``state_dict()`` does not hold it.  Each module owns its state; the sites of different
         modules differ, so equal (seed, step) pairs still give unrelated fields.  Returns self."""
-        if source not in ("torch", "kernel"):
-            raise ValueError(f"{self._dropout_owner()}: dropout source must be 'torch' or 'kernel', got {source!r}")
-        if source == "kernel":
-            if getattr(self, "_dropout_state", None) is None:
-                dev = next(self.parameters()).device
-                self.register_buffer("_dropout_state", torch.zeros(2, dtype=torch.int64, device=dev), persistent=False)
-                self.reseed_dropout(torch.initial_seed() if seed is None else seed)
-            elif seed is not None:
-                self.reseed_dropout(seed)
-        self._dropout_source = source
-        return self
+        return _DROPOUT_STATE.set_source(self, source, seed)
 
     @property
     def dropout_state(self):
@@ -266,12 +238,7 @@ class KernelDropoutSource:
 
     def reseed_dropout(self, seed: int, step: int = 0):
         """Set the in-kernel source's (seed, step) in place: seed any integer (taken modulo 2^64), step the next forward's."""
-        if getattr(self, "_dropout_state", None) is None:
-            raise RuntimeError(f"{self._dropout_owner()}.reseed_dropout: call set_dropout_source('kernel') first (it creates the state)")
-        words = [int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)]
-        words = [v - 2 ** 64 if v >= 2 ** 63 else v for v in words]          # (the bit pattern, as int64)
-        self._dropout_state.copy_(torch.tensor(words, dtype=torch.int64))
-        return self
+        return _DROPOUT_STATE.reseed_state(self, seed, step)
 
     def _kernel_dropout(self) -> bool:
         """Is this call's dropout the in-kernel source's?  (Training mode only: eval ignores the source.)"""
@@ -279,9 +246,7 @@ class KernelDropoutSource:
 
     def _dropout_begin(self, device):
         """The snap of one training forward: one dropout_begin launch on the module's own state."""
-        if self._dropout_state.device != device:
-            raise RuntimeError(f"{self._dropout_owner()}: the dropout state is not on the input's device (move the module with .to())")
-        return ops.dropout_begin(self._dropout_state)
+        return _DROPOUT_STATE.begin(self, device)
 
     def _dropout_p(self, p, what) -> float:
         p = float(p)
@@ -292,8 +257,8 @@ class KernelDropoutSource:
 
 class KernelSampleSource:
     """Mixin of the modules that SAMPLE (GMMActionHead): where the sampling noise comes from, and the state of the in-kernel
-    source.  KernelDropoutSource's twin, with its rules and error types; unlike dropout, sampling is not a training-only act, so
-    the source applies in eval and in train mode.  Nothing is created at construction."""
+    source.  The state holder, its rules and its error types are KernelDropoutSource's (_SourceState); unlike dropout, sampling is
+    not a training-only act, so the source applies in eval and in train mode.  Nothing is created at construction."""
 
     @property
     def sample_source(self) -> str:
@@ -311,17 +276,7 @@ class KernelSampleSource:
         at construction), seeded with ``seed`` or, for None, ``torch.initial_seed()``; a later call with a seed reseeds it
         (step 0), one without leaves it.  It is a non-persistent buffer: ``.to()`` moves it, ``state_dict()`` does not hold it.
         Returns self."""
-        if source not in ("torch", "kernel"):
-            raise ValueError(f"{type(self).__name__}: sample source must be 'torch' or 'kernel', got {source!r}")
-        if source == "kernel":
-            if getattr(self, "_sample_state", None) is None:
-                dev = next(self.parameters()).device
-                self.register_buffer("_sample_state", torch.zeros(2, dtype=torch.int64, device=dev), persistent=False)
-                self.reseed_sampling(torch.initial_seed() if seed is None else seed)
-            elif seed is not None:
-                self.reseed_sampling(seed)
-        self._sample_source = source
-        return self
+        return _SAMPLE_STATE.set_source(self, source, seed)
 
     @property
     def sample_state(self):
@@ -330,18 +285,11 @@ class KernelSampleSource:
 
     def reseed_sampling(self, seed: int, step: int = 0):
         """Set the in-kernel source's (seed, step) in place: seed any integer (taken modulo 2^64), step the next sampling call's."""
-        if getattr(self, "_sample_state", None) is None:
-            raise RuntimeError(f"{type(self).__name__}.reseed_sampling: call set_sample_source('kernel') first (it creates the state)")
-        words = [int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)]
-        words = [v - 2 ** 64 if v >= 2 ** 63 else v for v in words]          # (the bit pattern, as int64)
-        self._sample_state.copy_(torch.tensor(words, dtype=torch.int64))
-        return self
+        return _SAMPLE_STATE.reseed_state(self, seed, step)
 
     def _sample_begin(self, device):
         """The snap of one sampling call: one dropout_begin launch on the module's own state."""
-        if self._sample_state.device != device:
-            raise RuntimeError(f"{type(self).__name__}: the sampling state is not on the input's device (move the module with .to())")
-        return ops.dropout_begin(self._sample_state)
+        return _SAMPLE_STATE.begin(self, device)
 
 
 def _sample_states(net):

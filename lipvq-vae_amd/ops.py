@@ -676,12 +676,68 @@ def vq_tokenize(x, packed: PackedMlp3, codebook, prep: PreparedCodebook, usage=N
 
 
 # ---------------------------------------------------------------------------------------------------
+# the in-kernel dropout source (csrc/lipvq_rng.h, csrc/lipvq_rng.hip; include/lipvq.h, "in-kernel dropout"): the wrappers below
+# that take dropout=(snap, site, p) pick the library's _drop entry point of their kernel family
+# ---------------------------------------------------------------------------------------------------
+
+# the site words of the modules outside the backbone (include/lipvq.h): the backbone's are 4 layer + {0, 1, 2}
+DROPOUT_SITE_EMBED = 0x40000000
+DROPOUT_SITE_DEFAULT = 0x80000000
+
+
+def dropout_begin(state):
+    """snap, a fresh int64[2] device tensor = the (seed, step) of ``state`` (int64[2], device) as it was; ``state``'s step is
+    advanced by one, on the device: one one-thread launch, no host synchronisation."""
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int64 or state.shape != (2,) or not state.is_cuda or not state.is_contiguous():
+        raise ValueError("dropout_begin: state must be a contiguous int64[2] device tensor (seed, step)")
+    snap = torch.empty(2, device=state.device, dtype=torch.int64)
+    with _on(state.device):
+        check(lib.lipvq_dropout_begin(_ptr(state), _ptr(snap), _stream()), "lipvq_dropout_begin")
+    return snap
+
+
+def dropout_keep(snap, site: int, rows: int, cols: int, p: float):
+    """The decisions of one site as a uint8 [rows, cols] device tensor (1 kept, 0 dropped), from a snap of dropout_begin."""
+    if not isinstance(snap, torch.Tensor) or snap.dtype != torch.int64 or snap.numel() != 2 or not snap.is_cuda or not snap.is_contiguous():
+        raise ValueError("dropout_keep: snap must be a contiguous int64[2] device tensor")
+    ok = 0 <= int(rows) < 2 ** 32 and 0 <= int(cols) <= 2 ** 32            # (anything else the library refuses before it writes)
+    out = torch.empty((int(rows), int(cols)) if ok else (0, 0), device=snap.device, dtype=torch.uint8)
+    with _on(snap.device):
+        check(lib.lipvq_dropout_keep_u8(_ptr(snap), int(site), int(rows), int(cols), float(p), _ptr(out), _stream()), "lipvq_dropout_keep_u8")
+    return out
+
+
+def dropout_keep_host(seed: int, step: int, site: int, rows: int, cols: int, p: float):
+    """The same field as a uint8 [rows, cols] CPU tensor from (seed, step), computed on the host: no GPU call."""
+    ok = 0 <= int(rows) < 2 ** 32 and 0 <= int(cols) <= 2 ** 32
+    out = torch.empty((int(rows), int(cols)) if ok else (0, 0), dtype=torch.uint8)
+    check(lib.lipvq_dropout_keep_host(int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), int(site), int(rows), int(cols), float(p),
+                                      out.data_ptr()), "lipvq_dropout_keep_host")
+    return out
+
+
+def _dropout_args(what, dropout, dev, keep=None):
+    """dropout = (snap, site, p) of the in-kernel source (include/lipvq.h, "in-kernel dropout") -> (snap, site, p) checked."""
+    if keep is not None:
+        raise ValueError(f"{what}: keep (mask bytes) and dropout (the in-kernel source) are mutually exclusive")
+    snap, site, p = dropout
+    if not isinstance(snap, torch.Tensor) or snap.dtype != torch.int64 or snap.numel() != 2 or not snap.is_contiguous() or snap.device != dev:
+        raise ValueError(f"{what}: snap must be the contiguous int64[2] tensor of dropout_begin on the input's device")
+    p = float(p)
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"{what}: dropout p={p} (0 < p < 1; p == 0 is the plain form)")
+    return snap, int(site), p
+
+
+# ---------------------------------------------------------------------------------------------------
 # the step after the tokenizer: input embedding + interleave (csrc/lipvq_embed.hip)
 # ---------------------------------------------------------------------------------------------------
 
-def linear(x, W, b=None, act=ACT_NONE, save_pre=False):
+def linear(x, W, b=None, act=ACT_NONE, save_pre=False, *, dropout=None):
     """y = act(x . W^T + b) (nn.Linear), canonical fp32 (reference obs_nets.py:2536 `embed_encoder`; with act = GELU the
-    second half of AdaptiveBinActionEmbedding.output_layer).  save_pre=True returns (y, pre-activation)."""
+    second half of AdaptiveBinActionEmbedding.output_layer).  save_pre=True returns (y, pre-activation).
+    dropout=(snap, site, p): the stored y is act(x . W^T + b) * m, m = 1 / (1 - p) where the in-kernel source keeps (row, col) of
+    the [N, E] result and 0 where it drops it, decided inside the Linear's epilogue (no mask tensor); pre stays the plain one."""
     x, W = _chk(x, "x"), _chk(W, "W")
     if x.dim() != 2 or W.dim() != 2 or W.shape[1] != x.shape[1]:
         raise ValueError(f"linear: x {tuple(x.shape)} and W {tuple(W.shape)} do not match")
@@ -689,13 +745,19 @@ def linear(x, W, b=None, act=ACT_NONE, save_pre=False):
         b = _chk(b, "b")
         if b.shape != (W.shape[0],):
             raise ValueError("linear: bias shape")
+    if dropout is not None:
+        snap, site, p = _dropout_args("linear", dropout, x.device)
     N, Kin = x.shape
     E = W.shape[0]
     y = torch.empty((N, E), device=x.device, dtype=torch.float32)
     pre = torch.empty_like(y) if save_pre else None
     with _on(x.device):
-        check(lib.lipvq_linear_act_f32(_ptr(x), _ptr(W), _ptr(b), _ptr(y), _ptr(pre), N, Kin, E, int(act), _stream()),
-              "lipvq_linear_act_f32")
+        if dropout is not None:
+            check(lib.lipvq_linear_act_drop_f32(_ptr(x), _ptr(W), _ptr(b), _ptr(y), _ptr(pre), _ptr(snap), site, p, N, Kin, E, int(act),
+                                                _stream()), "lipvq_linear_act_drop_f32")
+        else:
+            check(lib.lipvq_linear_act_f32(_ptr(x), _ptr(W), _ptr(b), _ptr(y), _ptr(pre), N, Kin, E, int(act), _stream()),
+                  "lipvq_linear_act_f32")
     return (y, pre) if save_pre else y
 
 
@@ -704,7 +766,9 @@ def _bf16_widths(what, Kin, E):
         raise ValueError(f"{what}: the bf16 mode needs both Linear widths to be multiples of 8 (got {Kin} -> {E})")
 
 
-def _linear_pipe(name, entry, x, W, b, act, save_pre):
+def _linear_pipe(name, entry, x, W, b, act, save_pre, dropout):
+    if dropout is not None:
+        raise ValueError(f"{name}: the in-kernel dropout source has fp32 entry points only (use linear)")
     x, W = _chk(x, "x"), _chk(W, "W")
     if x.dim() != 2 or W.dim() != 2 or W.shape[1] != x.shape[1]:
         raise ValueError(f"{name}: x {tuple(x.shape)} and W {tuple(W.shape)} do not match")
@@ -753,10 +817,10 @@ def _wgrad_pipe(name, entry, G, H, want_bias):
     return gW, gb
 
 
-def linear_bf16(x, W, b=None, act=ACT_NONE, save_pre=False):
+def linear_bf16(x, W, b=None, act=ACT_NONE, save_pre=False, *, dropout=None):
     """``linear`` in the bf16 matrix-pipe mode: x and W are rounded to bf16 (nearest even) as the kernel reads them, products
     are accumulated in fp32, bias and activation are the fp32 epilogue of ``linear``; every tensor stays fp32."""
-    return _linear_pipe("linear_bf16", "lipvq_linear_act_bf16", x, W, b, act, save_pre)
+    return _linear_pipe("linear_bf16", "lipvq_linear_act_bf16", x, W, b, act, save_pre, dropout)
 
 
 def linear_nn_bf16(g, W):
@@ -770,11 +834,11 @@ def wgrad_bf16(G, H, want_bias=True):
     return _wgrad_pipe("wgrad_bf16", "lipvq_wgrad_bf16", G, H, want_bias)
 
 
-def linear_bf16x3(x, W, b=None, act=ACT_NONE, save_pre=False):
+def linear_bf16x3(x, W, b=None, act=ACT_NONE, save_pre=False, *, dropout=None):
     """``linear`` in the bf16x3 mode: every element of x and W is split into hi = bf16(v) and lo = bf16(v - hi) as the kernel
     reads it, and a_lo b_hi + a_hi b_lo + a_hi b_hi is accumulated in fp32 on the bf16 matrix pipe (about 2^-16 relative per
     product instead of 2^-8; include/lipvq.h has the bound).  The epilogue and the tensors are those of ``linear_bf16``."""
-    return _linear_pipe("linear_bf16x3", "lipvq_linear_act_bf16x3", x, W, b, act, save_pre)
+    return _linear_pipe("linear_bf16x3", "lipvq_linear_act_bf16x3", x, W, b, act, save_pre, dropout)
 
 
 def linear_nn_bf16x3(g, W):
@@ -915,53 +979,25 @@ def bin_hidden(bins, P, b1, save_pre=False):
     return (h, pre) if save_pre else h
 
 
-def act_bwd(g, pre, act):
-    """g * act'(pre), elementwise."""
-    g, pre = _chk(g, "g"), _chk(pre, "pre")
-    if g.shape != pre.shape:
-        raise ValueError("act_bwd: shapes differ")
-    out = torch.empty_like(g)
-    with _on(g.device):
-        check(lib.lipvq_act_bwd_f32(_ptr(g), _ptr(pre), _ptr(out), g.numel(), int(act), _stream()), "lipvq_act_bwd_f32")
-    return out
-
-
-def linear_act_drop(x, W, b, act, dropout, save_pre=False):
-    """``linear`` whose stored y is act(x . W^T + b) * m: m = 1 / (1 - p) where dropout = (snap, site, p) keeps (row, col) of the
-    [N, E] result and 0 where it drops it, decided inside the Linear's epilogue (no mask tensor).  The pre-activation that
-    save_pre=True returns is the plain one."""
-    x, W = _chk(x, "x"), _chk(W, "W")
-    if x.dim() != 2 or W.dim() != 2 or W.shape[1] != x.shape[1]:
-        raise ValueError(f"linear_act_drop: x {tuple(x.shape)} and W {tuple(W.shape)} do not match")
-    if b is not None:
-        b = _chk(b, "b")
-        if b.shape != (W.shape[0],):
-            raise ValueError("linear_act_drop: bias shape")
-    snap, site, p = _dropout_args("linear_act_drop", dropout, x.device)
-    N, Kin = x.shape
-    E = W.shape[0]
-    y = torch.empty((N, E), device=x.device, dtype=torch.float32)
-    pre = torch.empty_like(y) if save_pre else None
-    with _on(x.device):
-        check(lib.lipvq_linear_act_drop_f32(_ptr(x), _ptr(W), _ptr(b), _ptr(y), _ptr(pre), _ptr(snap), site, p, N, Kin, E, int(act),
-                                            _stream()), "lipvq_linear_act_drop_f32")
-    return (y, pre) if save_pre else y
-
-
-def act_bwd_drop(g, pre, act, dropout):
-    """(g * m) * act'(pre) over a 2-D [rows, cols] gradient, m regenerated from dropout = (snap, site, p): the first backward
-    step of ``linear_act_drop``.  pre may be None for ACT_NONE (the result is g * m)."""
+def act_bwd(g, pre, act, *, dropout=None):
+    """g * act'(pre), elementwise.  dropout=(snap, site, p) of a ``linear(..., dropout=...)``: (g * m) * act'(pre) over the 2-D
+    [rows, cols] gradient, m regenerated -- the first backward step of that Linear; pre may then be None for ACT_NONE (g * m)."""
     g = _chk(g, "g")
-    if g.dim() != 2:
-        raise ValueError("act_bwd_drop: g must be 2-D [rows, cols] (the dropout field)")
-    if pre is not None:
+    if dropout is not None and pre is None:
+        if act != ACT_NONE:
+            raise ValueError("act_bwd: pre is required unless act is ACT_NONE")
+    else:
         pre = _chk(pre, "pre")
-        if pre.shape != g.shape:
-            raise ValueError("act_bwd_drop: shapes differ")
-    elif act != ACT_NONE:
-        raise ValueError("act_bwd_drop: pre is required unless act is ACT_NONE")
-    snap, site, p = _dropout_args("act_bwd_drop", dropout, g.device)
+        if g.shape != pre.shape:
+            raise ValueError("act_bwd: shapes differ")
     out = torch.empty_like(g)
+    if dropout is None:
+        with _on(g.device):
+            check(lib.lipvq_act_bwd_f32(_ptr(g), _ptr(pre), _ptr(out), g.numel(), int(act), _stream()), "lipvq_act_bwd_f32")
+        return out
+    if g.dim() != 2:
+        raise ValueError("act_bwd: g must be 2-D [rows, cols] (the dropout field)")
+    snap, site, p = _dropout_args("act_bwd", dropout, g.device)
     with _on(g.device):
         check(lib.lipvq_act_bwd_drop_f32(_ptr(g), _ptr(pre), _ptr(out), _ptr(snap), site, p, g.shape[0], g.shape[1], int(act), _stream()),
               "lipvq_act_bwd_drop_f32")
@@ -1105,30 +1141,47 @@ def _chk_keep(keep, H, S, dev):
     return keep
 
 
-def attention(qkv, nhead: int, keep=None, keep_prob: float = 1.0):
-    """(out [S, D], lse [H, S]) of multi-head self-attention over the unbatched sequence qkv [S, 3D] (q | k | v)."""
+def attention(qkv, nhead: int, keep=None, keep_prob: float = 1.0, *, dropout=None):
+    """(out [S, D], lse [H, S]) of multi-head self-attention over the unbatched sequence qkv [S, 3D] (q | k | v).
+    Attention-probability dropout: keep [H, S, S] bytes with keep_prob, or dropout=(snap, site, p), drawn in the kernel at field
+    row = h S + q, col = key -- the bits of keep = ``dropout_keep(snap, site, H S, S, p)`` reshaped [H, S, S], keep_prob = 1 - p."""
     qkv = _chk(qkv, "qkv")
     if qkv.dim() != 2 or qkv.shape[1] % 3 != 0:
         raise ValueError(f"attention: qkv {tuple(qkv.shape)}")
     S, D = qkv.shape[0], qkv.shape[1] // 3
+    if dropout is not None:
+        snap, site, p = _dropout_args("attention", dropout, qkv.device, keep)
     keep = _chk_keep(keep, nhead, S, qkv.device)
     out = torch.empty((S, D), device=qkv.device, dtype=torch.float32)
     lse = torch.empty((nhead, S), device=qkv.device, dtype=torch.float32)
     with _on(qkv.device):
-        check(lib.lipvq_attention_f32(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(keep), float(keep_prob), S, D, int(nhead), _stream()),
-              "lipvq_attention_f32")
+        if dropout is not None:
+            check(lib.lipvq_attention_drop_f32(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(snap), site, p, S, D, int(nhead), _stream()),
+                  "lipvq_attention_drop_f32")
+        else:
+            check(lib.lipvq_attention_f32(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(keep), float(keep_prob), S, D, int(nhead), _stream()),
+                  "lipvq_attention_f32")
     return out, lse
 
 
-def attention_bwd(qkv, out, gout, lse, nhead: int, keep=None, keep_prob: float = 1.0):
+def attention_bwd(qkv, out, gout, lse, nhead: int, keep=None, keep_prob: float = 1.0, *, dropout=None):
+    """gqkv of ``attention``; dropout=(snap, site, p) of the forward: the decisions are regenerated inside the two kernels."""
     qkv, out, gout, lse = _chk(qkv, "qkv"), _chk(out, "out"), _chk(gout, "gout"), _chk(lse, "lse")
     S, D = out.shape
+    if qkv.shape != (S, 3 * D) or gout.shape != out.shape or lse.shape != (nhead, S):
+        raise ValueError("attention_bwd: shapes do not match")
+    if dropout is not None:
+        snap, site, p = _dropout_args("attention_bwd", dropout, qkv.device, keep)
     keep = _chk_keep(keep, nhead, S, qkv.device)
     gqkv = torch.empty_like(qkv)
     delta = torch.empty_like(lse)
     with _on(qkv.device):
-        check(lib.lipvq_attention_bwd_f32(_ptr(qkv), _ptr(out), _ptr(gout), _ptr(lse), _ptr(gqkv), _ptr(delta), _ptr(keep),
-                                          float(keep_prob), S, D, int(nhead), _stream()), "lipvq_attention_bwd_f32")
+        if dropout is not None:
+            check(lib.lipvq_attention_bwd_drop_f32(_ptr(qkv), _ptr(out), _ptr(gout), _ptr(lse), _ptr(gqkv), _ptr(delta), _ptr(snap), site,
+                                                   p, S, D, int(nhead), _stream()), "lipvq_attention_bwd_drop_f32")
+        else:
+            check(lib.lipvq_attention_bwd_f32(_ptr(qkv), _ptr(out), _ptr(gout), _ptr(lse), _ptr(gqkv), _ptr(delta), _ptr(keep),
+                                              float(keep_prob), S, D, int(nhead), _stream()), "lipvq_attention_bwd_f32")
     return gqkv
 
 
@@ -1136,57 +1189,12 @@ def attention_bwd(qkv, out, gout, lse, nhead: int, keep=None, keep_prob: float =
 # the transformer backbone (csrc/lipvq_gpt.hip; reference robomimic/models/transformers.py:80-439)
 # ---------------------------------------------------------------------------------------------------
 
-def attention_drop(qkv, nhead: int, dropout):
-    """``attention`` with the attention-probability dropout drawn inside the kernel: dropout = (snap, site, p) of the in-kernel
-    source, field row = h S + q, col = key.  The bits of ``attention`` given ``dropout_keep(snap, site, H S, S, p)`` reshaped
-    [H, S, S] and keep_prob = 1 - p."""
-    qkv = _chk(qkv, "qkv")
-    if qkv.dim() != 2 or qkv.shape[1] % 3 != 0:
-        raise ValueError(f"attention_drop: qkv {tuple(qkv.shape)}")
-    S, D = qkv.shape[0], qkv.shape[1] // 3
-    snap, site, p = _dropout_args("attention_drop", dropout, qkv.device)
-    out = torch.empty((S, D), device=qkv.device, dtype=torch.float32)
-    lse = torch.empty((nhead, S), device=qkv.device, dtype=torch.float32)
-    with _on(qkv.device):
-        check(lib.lipvq_attention_drop_f32(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(snap), site, p, S, D, int(nhead), _stream()),
-              "lipvq_attention_drop_f32")
-    return out, lse
-
-
-def attention_bwd_drop(qkv, out, gout, lse, nhead: int, dropout):
-    """``attention_bwd`` with the decisions of the forward's dropout = (snap, site, p) regenerated inside the two kernels."""
-    qkv, out, gout, lse = _chk(qkv, "qkv"), _chk(out, "out"), _chk(gout, "gout"), _chk(lse, "lse")
-    S, D = out.shape
-    if qkv.shape != (S, 3 * D) or gout.shape != out.shape or lse.shape != (nhead, S):
-        raise ValueError("attention_bwd_drop: shapes do not match")
-    snap, site, p = _dropout_args("attention_bwd_drop", dropout, qkv.device)
-    gqkv = torch.empty_like(qkv)
-    delta = torch.empty_like(lse)
-    with _on(qkv.device):
-        check(lib.lipvq_attention_bwd_drop_f32(_ptr(qkv), _ptr(out), _ptr(gout), _ptr(lse), _ptr(gqkv), _ptr(delta), _ptr(snap), site,
-                                               p, S, D, int(nhead), _stream()), "lipvq_attention_bwd_drop_f32")
-    return gqkv
-
-
 def _gpt_keep(keep, B, H, L, dev):
     if keep is None:
         return None
     if keep.dtype != torch.uint8 or keep.shape != (B, H, L, L) or not keep.is_contiguous() or keep.device != dev:
         raise ValueError("gpt_attention: keep must be a contiguous uint8 [B, H, L, L] tensor on the input's device")
     return keep
-
-
-def _dropout_args(what, dropout, dev, keep=None):
-    """dropout = (snap, site, p) of the in-kernel source (include/lipvq.h, "in-kernel dropout") -> (snap, site, p) checked."""
-    if keep is not None:
-        raise ValueError(f"{what}: keep (mask bytes) and dropout (the in-kernel source) are mutually exclusive")
-    snap, site, p = dropout
-    if not isinstance(snap, torch.Tensor) or snap.dtype != torch.int64 or snap.numel() != 2 or not snap.is_contiguous() or snap.device != dev:
-        raise ValueError(f"{what}: snap must be the contiguous int64[2] tensor of dropout_begin on the input's device")
-    p = float(p)
-    if not 0.0 < p < 1.0:
-        raise ValueError(f"{what}: dropout p={p} (0 < p < 1; p == 0 is the plain form)")
-    return snap, int(site), p
 
 
 def gpt_attention(qkv, nhead: int, causal: bool = True, keep=None, keep_prob: float = 1.0, *, dropout=None):
@@ -1250,14 +1258,18 @@ def gpt_attention_bwd(qkv, out, gout, lse, nhead: int, causal: bool = True, keep
     return gqkv
 
 
-def gpt_layernorm(a, b, w, bias, eps: float, want_s: bool = True, save: bool = False):
+def gpt_layernorm(a, b, w, bias, eps: float, want_s: bool = True, save: bool = False, *, dropout=None):
     """s = a + b (b may be None) and y = LayerNorm(s) * w + bias over the last dimension, one launch.
-    Returns (s or None, y) and, with save=True, (s or None, y, xhat, rstd)."""
+    Returns (s or None, y) and, with save=True, (s or None, y, xhat, rstd).
+    dropout=(snap, site, p): the branch's dropout inside the launch, s = a + b * m, m = 1 / (1 - p) where the in-kernel source
+    keeps (row, e) and 0 where it drops it; b is then required."""
     a = _chk(a, "a")
-    if b is not None:
+    if b is not None or dropout is not None:
         b = _chk(b, "b")
         if b.shape != a.shape:
             raise ValueError("gpt_layernorm: shapes differ")
+    if dropout is not None:
+        snap, site, p = _dropout_args("gpt_layernorm", dropout, a.device)
     E = a.shape[-1]
     N = a.numel() // E if E else 0
     s = torch.empty_like(a) if want_s else None
@@ -1265,106 +1277,44 @@ def gpt_layernorm(a, b, w, bias, eps: float, want_s: bool = True, save: bool = F
     xhat = torch.empty_like(a) if save else None
     rstd = torch.empty(N, device=a.device, dtype=torch.float32) if save else None
     with _on(a.device):
-        check(lib.lipvq_gpt_layernorm_f32(_ptr(a), _ptr(b), _ptr(_chk(w, "w")), _ptr(_chk(bias, "bias")), float(eps), _ptr(s), _ptr(y),
-                                          _ptr(xhat), _ptr(rstd), N, E, _stream()), "lipvq_gpt_layernorm_f32")
+        if dropout is not None:
+            check(lib.lipvq_gpt_layernorm_drop_f32(_ptr(a), _ptr(b), _ptr(_chk(w, "w")), _ptr(_chk(bias, "bias")), float(eps), _ptr(snap),
+                                                   site, p, _ptr(s), _ptr(y), _ptr(xhat), _ptr(rstd), N, E, _stream()),
+                  "lipvq_gpt_layernorm_drop_f32")
+        else:
+            check(lib.lipvq_gpt_layernorm_f32(_ptr(a), _ptr(b), _ptr(_chk(w, "w")), _ptr(_chk(bias, "bias")), float(eps), _ptr(s), _ptr(y),
+                                              _ptr(xhat), _ptr(rstd), N, E, _stream()), "lipvq_gpt_layernorm_f32")
     return (s, y, xhat, rstd) if save else (s, y)
 
 
-def gpt_layernorm_bwd(gy, xhat, rstd, w, gres=None):
-    """(gs, gw, gb): gs = LayerNorm backward + gres (the residual stream's incoming gradient, may be None)."""
+def gpt_layernorm_bwd(gy, xhat, rstd, w, gres=None, *, dropout=None):
+    """(gs, gw, gb): gs = LayerNorm backward + gres (the residual stream's incoming gradient, may be None).
+    dropout=(snap, site, p) of the forward: (gs, gbranch, gw, gb), gbranch = gs * m the gradient of the dropped branch b, from
+    the decisions the source regenerates."""
     gy, xhat = _chk(gy, "gy"), _chk(xhat, "xhat")
     if gres is not None:
         gres = _chk(gres, "gres")
         if gres.shape != gy.shape:
             raise ValueError("gpt_layernorm_bwd: gres shape")
+    if dropout is not None:
+        snap, site, p = _dropout_args("gpt_layernorm_bwd", dropout, gy.device)
     E = gy.shape[-1]
     N = gy.numel() // E if E else 0
     gs = torch.empty_like(gy)
     gw = torch.empty(E, device=gy.device, dtype=torch.float32)
     gb = torch.empty(E, device=gy.device, dtype=torch.float32)
     ws = torch.empty(max(1, lib.lipvq_gpt_layernorm_bwd_workspace_bytes(N, E)), device=gy.device, dtype=torch.uint8)
+    if dropout is not None:
+        gbr = torch.empty_like(gy)
+        with _on(gy.device):
+            check(lib.lipvq_gpt_layernorm_bwd_drop_f32(_ptr(gy), _ptr(xhat), _ptr(_chk(rstd, "rstd")), _ptr(_chk(w, "w")), _ptr(gres),
+                                                       _ptr(snap), site, p, _ptr(gs), _ptr(gbr), _ptr(gw), _ptr(gb), _ptr(ws), N, E,
+                                                       _stream()), "lipvq_gpt_layernorm_bwd_drop_f32")
+        return gs, gbr, gw, gb
     with _on(gy.device):
         check(lib.lipvq_gpt_layernorm_bwd_f32(_ptr(gy), _ptr(xhat), _ptr(_chk(rstd, "rstd")), _ptr(_chk(w, "w")), _ptr(gres), _ptr(gs),
                                               _ptr(gw), _ptr(gb), _ptr(ws), N, E, _stream()), "lipvq_gpt_layernorm_bwd_f32")
     return gs, gw, gb
-
-
-def gpt_layernorm_drop(a, b, w, bias, eps: float, dropout, want_s: bool = True, save: bool = False):
-    """gpt_layernorm with the branch's dropout inside the launch: s = a + b * m, m = 1 / (1 - p) where dropout = (snap, site, p)
-    keeps (row, e) and 0 where it drops it; y = LayerNorm(s) * w + bias.  Returns as gpt_layernorm does."""
-    a, b = _chk(a, "a"), _chk(b, "b")
-    if b.shape != a.shape:
-        raise ValueError("gpt_layernorm_drop: shapes differ")
-    snap, site, p = _dropout_args("gpt_layernorm_drop", dropout, a.device)
-    E = a.shape[-1]
-    N = a.numel() // E if E else 0
-    s = torch.empty_like(a) if want_s else None
-    y = torch.empty_like(a)
-    xhat = torch.empty_like(a) if save else None
-    rstd = torch.empty(N, device=a.device, dtype=torch.float32) if save else None
-    with _on(a.device):
-        check(lib.lipvq_gpt_layernorm_drop_f32(_ptr(a), _ptr(b), _ptr(_chk(w, "w")), _ptr(_chk(bias, "bias")), float(eps), _ptr(snap), site,
-                                               p, _ptr(s), _ptr(y), _ptr(xhat), _ptr(rstd), N, E, _stream()),
-              "lipvq_gpt_layernorm_drop_f32")
-    return (s, y, xhat, rstd) if save else (s, y)
-
-
-def gpt_layernorm_drop_bwd(gy, xhat, rstd, w, dropout, gres=None):
-    """(gs, gbranch, gw, gb): gpt_layernorm_bwd's three and gbranch = gs * m, the gradient of the dropped branch b, from the
-    decisions the forward's (snap, site, p) regenerates."""
-    gy, xhat = _chk(gy, "gy"), _chk(xhat, "xhat")
-    if gres is not None:
-        gres = _chk(gres, "gres")
-        if gres.shape != gy.shape:
-            raise ValueError("gpt_layernorm_drop_bwd: gres shape")
-    snap, site, p = _dropout_args("gpt_layernorm_drop_bwd", dropout, gy.device)
-    E = gy.shape[-1]
-    N = gy.numel() // E if E else 0
-    gs, gbr = torch.empty_like(gy), torch.empty_like(gy)
-    gw = torch.empty(E, device=gy.device, dtype=torch.float32)
-    gb = torch.empty(E, device=gy.device, dtype=torch.float32)
-    ws = torch.empty(max(1, lib.lipvq_gpt_layernorm_bwd_workspace_bytes(N, E)), device=gy.device, dtype=torch.uint8)
-    with _on(gy.device):
-        check(lib.lipvq_gpt_layernorm_bwd_drop_f32(_ptr(gy), _ptr(xhat), _ptr(_chk(rstd, "rstd")), _ptr(_chk(w, "w")), _ptr(gres),
-                                                   _ptr(snap), site, p, _ptr(gs), _ptr(gbr), _ptr(gw), _ptr(gb), _ptr(ws), N, E,
-                                                   _stream()), "lipvq_gpt_layernorm_bwd_drop_f32")
-    return gs, gbr, gw, gb
-
-
-# the site words of the modules outside the backbone (include/lipvq.h): the backbone's are 4 layer + {0, 1, 2}
-DROPOUT_SITE_EMBED = 0x40000000
-DROPOUT_SITE_DEFAULT = 0x80000000
-
-
-def dropout_begin(state):
-    """snap, a fresh int64[2] device tensor = the (seed, step) of ``state`` (int64[2], device) as it was; ``state``'s step is
-    advanced by one, on the device: one one-thread launch, no host synchronisation."""
-    if not isinstance(state, torch.Tensor) or state.dtype != torch.int64 or state.shape != (2,) or not state.is_cuda or not state.is_contiguous():
-        raise ValueError("dropout_begin: state must be a contiguous int64[2] device tensor (seed, step)")
-    snap = torch.empty(2, device=state.device, dtype=torch.int64)
-    with _on(state.device):
-        check(lib.lipvq_dropout_begin(_ptr(state), _ptr(snap), _stream()), "lipvq_dropout_begin")
-    return snap
-
-
-def dropout_keep(snap, site: int, rows: int, cols: int, p: float):
-    """The decisions of one site as a uint8 [rows, cols] device tensor (1 kept, 0 dropped), from a snap of dropout_begin."""
-    if not isinstance(snap, torch.Tensor) or snap.dtype != torch.int64 or snap.numel() != 2 or not snap.is_cuda or not snap.is_contiguous():
-        raise ValueError("dropout_keep: snap must be a contiguous int64[2] device tensor")
-    ok = 0 <= int(rows) < 2 ** 32 and 0 <= int(cols) <= 2 ** 32            # (anything else the library refuses before it writes)
-    out = torch.empty((int(rows), int(cols)) if ok else (0, 0), device=snap.device, dtype=torch.uint8)
-    with _on(snap.device):
-        check(lib.lipvq_dropout_keep_u8(_ptr(snap), int(site), int(rows), int(cols), float(p), _ptr(out), _stream()), "lipvq_dropout_keep_u8")
-    return out
-
-
-def dropout_keep_host(seed: int, step: int, site: int, rows: int, cols: int, p: float):
-    """The same field as a uint8 [rows, cols] CPU tensor from (seed, step), computed on the host: no GPU call."""
-    ok = 0 <= int(rows) < 2 ** 32 and 0 <= int(cols) <= 2 ** 32
-    out = torch.empty((int(rows), int(cols)) if ok else (0, 0), dtype=torch.uint8)
-    check(lib.lipvq_dropout_keep_host(int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), int(site), int(rows), int(cols), float(p),
-                                      out.data_ptr()), "lipvq_dropout_keep_host")
-    return out
 
 
 # ---------------------------------------------------------------------------------------------------

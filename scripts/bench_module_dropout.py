@@ -130,13 +130,13 @@ def main():
     def fwd_bytes():
         keep = (torch.rand((H, S, S), device="cuda") >= P).to(torch.uint8)
         return ops.attention(qkv, H, keep, 1.0 - P)
-    t_k, t_t, c, lost = alternate(lambda: ops.attention_drop(qkv, H, drop), fwd_bytes, 5)
+    t_k, t_t, c, lost = alternate(lambda: ops.attention(qkv, H, dropout=drop), fwd_bytes, 5)
     line(f"attention forward S={S} D={D}: _drop kernel / keep-byte kernel + rand, compare, cast", t_k, t_t, c, lost)
     keep = (torch.rand((H, S, S), device="cuda") >= P).to(torch.uint8)
-    t_k, t_t, c, lost = alternate(lambda: ops.attention_drop(qkv, H, drop), lambda: ops.attention(qkv, H, keep, 1.0 - P), 5)
+    t_k, t_t, c, lost = alternate(lambda: ops.attention(qkv, H, dropout=drop), lambda: ops.attention(qkv, H, keep, 1.0 - P), 5)
     line(f"attention forward S={S} D={D}: _drop kernel / keep-byte kernel alone (bytes given)", t_k, t_t, c, lost)
     out, lse = ops.attention(qkv, H, keep, 1.0 - P)
-    t_k, t_t, c, lost = alternate(lambda: ops.attention_bwd_drop(qkv, out, gout, lse, H, drop),
+    t_k, t_t, c, lost = alternate(lambda: ops.attention_bwd(qkv, out, gout, lse, H, dropout=drop),
                                   lambda: ops.attention_bwd(qkv, out, gout, lse, H, keep, 1.0 - P), 5)
     line(f"attention backward S={S} D={D}: _drop kernels / keep-byte kernels (bytes given)", t_k, t_t, c, lost)
 

@@ -129,6 +129,18 @@ def test_the_backbone_keeps_its_messages():
         net.reseed_dropout(1)
 
 
+@pytest.mark.parametrize("precision", ["bf16", "bf16x3"])
+def test_linear_fn_refuses_dropout_on_the_bf16_pipes(precision):
+    """The in-kernel dropout source has fp32 Linear kernels only: LinearFn says so before it touches a tensor (CPU tensors here,
+    which every kernel wrapper would refuse with another error type)."""
+    import lipvq_vae_amd  # noqa: F401
+    from lipvq_vae_amd.nnfn import LinearFn
+    from lipvq_vae_amd.ops import ACT_NONE
+    x, W, snap = torch.zeros(3, 8), torch.zeros(16, 8, requires_grad=True), torch.zeros(2, dtype=torch.int64)
+    with pytest.raises(ValueError, match="LinearFn: dropout"):
+        LinearFn.apply(x, W, None, ACT_NONE, precision, (snap, 0x80000003, 0.1))
+
+
 def test_new_entry_points_refuse_before_they_touch_anything():
     import lipvq_vae_amd  # noqa: F401
     from lipvq_vae_amd import _capi

@@ -84,13 +84,13 @@ def test_attention_equals_the_keep_byte_kernels(ops, D, H, S):
             rows = got["out"].view(S, H, D // H).permute(1, 0, 2)[dead]
             assert not bool(rows.any()), tag
         # and through ops
-        out, lse = ops.attention_drop(qkv, H, (snap, site, p))
-        g = ops.attention_bwd_drop(qkv, out, gout, lse, H, (snap, site, p))
+        out, lse = ops.attention(qkv, H, dropout=(snap, site, p))
+        g = ops.attention_bwd(qkv, out, gout, lse, H, dropout=(snap, site, p))
         assert torch.equal(out, want_out) and torch.equal(lse, want_lse) and torch.equal(g, want_g), tag
         # another site or step is another field
         if S > 1:
-            assert not torch.equal(ops.attention_drop(qkv, H, (snap, site + 4, p))[0], out), tag
-            assert not torch.equal(ops.attention_drop(qkv, H, (_snap(SEED, 6), site, p))[0], out), tag
+            assert not torch.equal(ops.attention(qkv, H, dropout=(snap, site + 4, p))[0], out), tag
+            assert not torch.equal(ops.attention(qkv, H, dropout=(_snap(SEED, 6), site, p))[0], out), tag
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -104,7 +104,7 @@ LINEAR_SHAPES = [(33, 12, 100), (1, 7, 4), (32769, 64, 256), (131077, 8, 60)]   
 @pytest.mark.parametrize("N,Kin,E", LINEAR_SHAPES)
 def test_linear_epilogue_equals_plain_times_mask(ops, N, Kin, E, act):
     from lipvq_vae_amd._capi import check, lib
-    from lipvq_vae_amd.nnfn import LinearDropFn, LinearFn
+    from lipvq_vae_amd.nnfn import LinearFn
     act = getattr(ops, "ACT_" + act)
     p, site, snap = 0.3, ops.DROPOUT_SITE_DEFAULT + 3, _snap(SEED, 11)
     x0, W0, b0, R = _randn(1, N, Kin), _randn(2, E, Kin, scale=0.3), _randn(3, E, scale=0.3), _randn(4, N, E)
@@ -117,9 +117,9 @@ def test_linear_epilogue_equals_plain_times_mask(ops, N, Kin, E, act):
     tag = (N, Kin, E, act)
     assert torch.equal(fy.check(), y_plain * m), tag
     assert torch.equal(fpre.check(), pre_plain), tag
-    y, pre = ops.linear_act_drop(x0, W0, b0, act, (snap, site, p), save_pre=True)
+    y, pre = ops.linear(x0, W0, b0, act, save_pre=True, dropout=(snap, site, p))
     assert torch.equal(y, y_plain * m) and torch.equal(pre, pre_plain), tag
-    assert torch.equal(ops.linear_act_drop(x0, W0, None, act, (snap, site, p)), ops.linear(x0, W0, None, act=act) * m), tag
+    assert torch.equal(ops.linear(x0, W0, None, act, dropout=(snap, site, p)), ops.linear(x0, W0, None, act=act) * m), tag
     # the act-backward's first step, fenced, then the three gradients under autograd
     fg = _Fenced("gpre", N, E)
     check(lib.lipvq_act_bwd_drop_f32(R.data_ptr(), pre_plain.data_ptr(), fg.ptr(), snap.data_ptr(), site, p, N, E, act, _stream()),
@@ -133,7 +133,7 @@ def test_linear_epilogue_equals_plain_times_mask(ops, N, Kin, E, act):
         (fn(x, W, b) * R).sum().backward()
         return x.grad, W.grad, b.grad
 
-    got = grads(lambda x, W, b: LinearDropFn.apply(x, W, b, act, snap, site, p))
+    got = grads(lambda x, W, b: LinearFn.apply(x, W, b, act, "fp32", (snap, site, p)))
     want = grads(lambda x, W, b: LinearFn.apply(x, W, b, act) * m)
     for name, g, w in zip(("gx", "gW", "gb"), got, want):
         assert torch.equal(g, w), (tag, name)
@@ -147,7 +147,7 @@ def test_linear_epilogue_keeps_a_nan_at_a_dropped_output(ops):
     assert 0 < int(keep[17].sum()) < E, "the fixture's row has no dropped (or no kept) column"
     m = keep.float() * _inv_keep(p)
     for act in (ops.ACT_NONE, ops.ACT_GELU, ops.ACT_RELU):
-        y = ops.linear_act_drop(x, W, b, act, (snap, site, p))
+        y = ops.linear(x, W, b, act, dropout=(snap, site, p))
         _same(y, ops.linear(x, W, b, act=act) * m, act)
         assert bool(torch.isnan(y[17]).all()), "a NaN at a dropped output must stay a NaN (the mask is a product)"
         assert not bool(torch.isnan(y[:17]).any()) and not bool(torch.isnan(y[18:]).any())
@@ -321,10 +321,21 @@ def test_entry_points_refuse_p_zero_and_one(ops):
         torch.cuda.synchronize()
         for f in (fo, fl, fg, fd, y, o, st):
             assert f.untouched(), (p, f.what)
-        for call in (lambda: ops.attention_drop(qkv, H, (snap, site, p)), lambda: ops.linear_act_drop(x, W, None, 0, (snap, site, p)),
-                     lambda: ops.act_bwd_drop(src, src, 1, (snap, site, p))):
+        for call in (lambda: ops.attention(qkv, H, dropout=(snap, site, p)), lambda: ops.linear(x, W, None, 0, dropout=(snap, site, p)),
+                     lambda: ops.act_bwd(src, src, 1, dropout=(snap, site, p))):
             with pytest.raises(ValueError):
                 call()
+
+
+def test_attention_refuses_keep_bytes_and_dropout_together(ops):
+    """The unbatched wrappers take one mask source: keep bytes or the in-kernel dropout, never both.  Nothing is launched."""
+    S, D, H = 17, 64, 8
+    qkv, gout, snap = _randn(1, S, 3 * D), _randn(2, S, D), _snap(3)
+    keep = torch.ones(H, S, S, dtype=torch.uint8, device="cuda")
+    with pytest.raises(ValueError, match="mutually exclusive"):
+        ops.attention(qkv, H, keep, 0.5, dropout=(snap, ops.DROPOUT_SITE_DEFAULT, 0.5))
+    with pytest.raises(ValueError, match="mutually exclusive"):
+        ops.attention_bwd(qkv, gout, gout, torch.zeros(H, S, device="cuda"), H, keep, 0.5, dropout=(snap, ops.DROPOUT_SITE_DEFAULT, 0.5))
 
 
 def test_modules_refuse_p_one_and_a_state_on_another_device(ops):

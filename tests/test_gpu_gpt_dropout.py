@@ -146,9 +146,9 @@ def test_add_dropout_layernorm_equals_the_explicit_mask(ops, N, E):
             for k, v in want.items():
                 assert torch.equal(got[k], v), (tag, k)
             # and through ops
-            s1, y1, xhat1, rstd1 = ops.gpt_layernorm_drop(a, b, w, bias, EPS, (snap, site, p), want_s=want_s, save=True)
+            s1, y1, xhat1, rstd1 = ops.gpt_layernorm(a, b, w, bias, EPS, want_s=want_s, save=True, dropout=(snap, site, p))
             assert (s1 is None) == (not want_s) and torch.equal(y1, y0) and torch.equal(xhat1, xhat0) and torch.equal(rstd1, rstd0)
-            gs1, gbr1, gw1, gb1 = ops.gpt_layernorm_drop_bwd(gy, xhat1, rstd1, w, (snap, site, p), gres if want_s else None)
+            gs1, gbr1, gw1, gb1 = ops.gpt_layernorm_bwd(gy, xhat1, rstd1, w, gres if want_s else None, dropout=(snap, site, p))
             assert torch.equal(gs1, gs0) and torch.equal(gbr1, gs0 * m) and torch.equal(gw1, gw0) and torch.equal(gb1, gb0)
 
 
@@ -382,7 +382,7 @@ def test_graphed_policy_step_replays_the_eager_steps(source, p):
 def test_new_functions_are_marked_first_order_only():
     import lipvq_vae_amd  # noqa: F401
     from lipvq_vae_amd import gpt, nnfn
-    for f in (nnfn.AddDropLayerNormFn, gpt._AttentionDropFn):
+    for f in (nnfn.AddLayerNormFn, gpt._AttentionFn):
         assert issubclass(f, nnfn.KernelFunction)
         assert getattr(f.backward, "first_order_only", False) and callable(getattr(f.backward, "__wrapped__", None)), f
 
@@ -392,7 +392,7 @@ def _leaf(t, need):
 
 
 def test_add_drop_layernorm_fn_contract(ops):
-    from lipvq_vae_amd.nnfn import AddDropLayerNormFn
+    from lipvq_vae_amd.nnfn import AddLayerNormFn
     N, E, p, site = 5, 36, 0.5, 2
     a0, b0, Rs, Ry = (_randn(70 + k, N, E) for k in range(4))
     w0, bias0 = 1.0 + _randn(75, E, scale=0.1), _randn(76, E, scale=0.1)
@@ -401,7 +401,7 @@ def test_add_drop_layernorm_fn_contract(ops):
 
     def run(needs, use_s=True, use_y=True, twice=False):
         lv = [_leaf(t, n) for t, n in zip((a0, b0, w0, bias0), needs)]
-        s, y = AddDropLayerNormFn.apply(*lv, EPS, True, snap, site, p)
+        s, y = AddLayerNormFn.apply(*lv, EPS, True, (snap, site, p))
         obj = sum(t for t, u in (((s * Rs).sum(), use_s), ((y * Ry).sum(), use_y)) if u)
         obj.backward(retain_graph=twice)
         if twice:
@@ -428,10 +428,10 @@ def test_add_drop_layernorm_fn_contract(ops):
     gs_y = ops.gpt_layernorm_bwd(Ry, xhat, rstd, w0, None)[0]
     assert torch.equal(only_y[0], gs_y) and torch.equal(only_y[1], gs_y * m)
     with torch.no_grad():
-        s_ng, y_ng = AddDropLayerNormFn.apply(_leaf(a0, True), b0, w0, bias0, EPS, True, snap, site, p)
+        s_ng, y_ng = AddLayerNormFn.apply(_leaf(a0, True), b0, w0, bias0, EPS, True, (snap, site, p))
     assert torch.equal(s_ng, s) and torch.equal(y_ng, y) and not y_ng.requires_grad
     lv = [_leaf(t, True) for t in (a0, b0, w0, bias0)]
-    y2 = AddDropLayerNormFn.apply(*lv, EPS, True, snap, site, p)[1]
+    y2 = AddLayerNormFn.apply(*lv, EPS, True, (snap, site, p))[1]
     ga, = torch.autograd.grad(y2.sum(), lv[0], create_graph=True)
     assert ga.requires_grad
     with pytest.raises(RuntimeError, match="differentiable once only|once_differentiable"):
@@ -439,7 +439,7 @@ def test_add_drop_layernorm_fn_contract(ops):
 
 
 def test_attention_drop_fn_contract(ops):
-    from lipvq_vae_amd.gpt import _AttentionDropFn, _AttentionFn
+    from lipvq_vae_amd.gpt import _AttentionFn
     B, L, H, dh, p, site = 2, 33, 2, 16, 0.5, 8
     qkv0, R = _randn(80, B, L, 3 * H * dh), _randn(81, B, L, H * dh)
     snap = _snap(SEED, 4)
@@ -447,7 +447,7 @@ def test_attention_drop_fn_contract(ops):
 
     def run(twice=False):
         q = _leaf(qkv0, True)
-        out = _AttentionDropFn.apply(q, H, True, snap, site, p)
+        out = _AttentionFn.apply(q, H, True, None, 1.0, (snap, site, p))
         obj = (out * R).sum()
         obj.backward(retain_graph=twice)
         if twice:
@@ -462,12 +462,12 @@ def test_attention_drop_fn_contract(ops):
     (want * R).sum().backward()
     assert torch.equal(out, want.detach()) and torch.equal(g, q.grad)
     assert torch.equal(run(twice=True)[1], 2.0 * g)
-    frozen = _AttentionDropFn.apply(qkv0, H, True, snap, site, p)
+    frozen = _AttentionFn.apply(qkv0, H, True, None, 1.0, (snap, site, p))
     with torch.no_grad():
-        no_grad = _AttentionDropFn.apply(_leaf(qkv0, True), H, True, snap, site, p)
+        no_grad = _AttentionFn.apply(_leaf(qkv0, True), H, True, None, 1.0, (snap, site, p))
     assert not frozen.requires_grad and torch.equal(frozen, out) and torch.equal(no_grad, out)
     q = _leaf(qkv0, True)
-    o2 = _AttentionDropFn.apply(q, H, True, snap, site, p)
+    o2 = _AttentionFn.apply(q, H, True, None, 1.0, (snap, site, p))
     gq, = torch.autograd.grad(o2.sum(), q, create_graph=True)
     assert gq.requires_grad
     with pytest.raises(RuntimeError, match="differentiable once only|once_differentiable"):

@@ -373,7 +373,7 @@ def test_graphed_step_of_the_default_branch_alone():
 
 def test_new_functions_are_marked_first_order_only():
     import lipvq_vae_amd  # noqa: F401
-    from lipvq_vae_amd import embedding, nnfn
-    for f in (nnfn.LinearDropFn, nnfn.AttentionDropFn, embedding._EmbedStreamsFn):
+    from lipvq_vae_amd import default_branch, embedding, nnfn
+    for f in (nnfn.LinearFn, default_branch._AttentionFn, embedding._EmbedStreamsFn):
         assert issubclass(f, nnfn.KernelFunction)
         assert getattr(f.backward, "first_order_only", False) and callable(getattr(f.backward, "__wrapped__", None)), f
