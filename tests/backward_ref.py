@@ -31,6 +31,14 @@ def f64(t):
     return t.detach().cpu().double()
 
 
+# delta_act of the budgets below: the absolute error of the fp32 activation derivatives against the exact float64 forms (how they
+# were measured, and the device's allowance for its straight-line GELU': tests/test_gpu_backward.py, which re-exports them)
+GELU_GRAD_ABS_ERR = 1.51e-7
+SIGMOID_GRAD_ABS_ERR = 8.9e-8
+GELU_DEVICE_ALLOWANCE = 3e-7
+DELTA_ACT = {ACT_NONE: 0.0, ACT_RELU: 0.0, ACT_SIGMOID: SIGMOID_GRAD_ABS_ERR, ACT_GELU: GELU_GRAD_ABS_ERR + GELU_DEVICE_ALLOWANCE}
+
+
 def gamma(L):
     L = float(L)
     return L * U32 / (1.0 - L * U32)

@@ -34,10 +34,10 @@ def inv_keep(p):
     return np.float32(1.0) / np.float32(1.0 - p)
 
 
-def keep_field(seed, step, site, rows, cols, p):
-    """uint8 [rows, cols]: 1 where element (row, col) of the site is kept."""
+def keep_field(seed, step, site, rows, cols, p, row0=0):
+    """uint8 [rows, cols]: 1 where element (row0 + row, col) of the site is kept (row0: a window of a larger field)."""
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    row = np.arange(rows, dtype=np.uint64)[:, None]
+    row = np.arange(int(row0), int(row0) + rows, dtype=np.uint64)[:, None]
     col = np.arange(cols, dtype=np.uint64)[None, :]
     words = philox4x32_10((col >> np.uint64(2), row, int(site), int(step) & MASK32), (seed & MASK32, seed >> 32))
     pick = np.broadcast_to(col & np.uint64(3), (rows, cols))
