@@ -807,6 +807,44 @@ int lipvq_action_head_f32(const float* x, int64_t bstride, const float* W, const
 int lipvq_action_head_bwd_f32(const float* pre, const float* target, const float* g, const float* gy, float* gpre, int64_t N,
                               int A, float w2, float w1, float wc, void* stream);
 
+/* ---- the output heads' opt-in matrix-pipe modes (ActionHead / GMMActionHead.set_matmul_precision): the product stage of
+ *      lipvq_action_head_f32, lipvq_gmm_head_f32, lipvq_gmm_sample_f32 and lipvq_gmm_sample_draw_f32 on the bf16 MFMAs.
+ *      lipvq-vae_amd/csrc/lipvq_head_product.h (lq_head_product_bf16).  The _mp_f32 entry points below take the argument list of
+ *      their _f32 namesake plus `matmul` before `stream`; LIPVQ_MATMUL_FP32 IS the _f32 entry point (which forwards with it):
+ *      the same launches, the same bits.
+ *      LIPVQ_MATMUL_BF16 / LIPVQ_MATMUL_BF16X3: the pre-activations [N][P] are, bit for bit, the first P columns of
+ *      lipvq_linear_act_bf16 / lipvq_linear_act_bf16x3 (LIPVQ_ACT_NONE) on the dense rows of x and the head's weights and biases
+ *      stacked in column order and extended with zero rows to a multiple of 8 (never formed: a column picks its row of its own
+ *      Linear).  That is the contract of the two sections above: operands rounded to bf16, nearest even, as they are read (the
+ *      split mode: hi and lo, lo = 0 where hi is not finite); accumulators start at 0; per output element ONE chain of
+ *      v_mfma_f32_32x32x16_bf16 over k-steps of 16 in ascending order (split: a_lo b_hi, a_hi b_lo, a_hi b_hi per step), never
+ *      split across waves; reduction elements past E and rows past N are zeros; the bias is added once, in fp32, after the chain
+ *      (acc + bias -- the fp32 stage STARTS its chain from the bias).  A row's bits do not depend on N, on its position or on P.
+ *      Everything after the pre-activations is the fp32 code of the _f32 entry point on the same values: tanh and the loss
+ *      partial sums, the mixture's log_prob and its sum, mean / scale / logits, the inverse-CDF sample, the drawn sample.
+ *      Special values and overflow as stated above: a NaN, an Inf or an |element| >= 0x7f7f8000 in a row of x makes that row's
+ *      outputs non-finite (and what sums over the rows) and changes no other row.  The error bound of the split mode is the
+ *      one of the bf16x3 section with a = x, b = W, L = E.
+ *      Validation: the limits of the _f32 entry point; then a `matmul` outside the enum is LIPVQ_EINVAL and a bf16 mode with
+ *      E % 8 != 0 is LIPVQ_EUNSUPPORTED; sizes are checked before pointers, pointers before any launch.
+ *      The backward entry points are unchanged: they read the saved pre-activations.  In a bf16 mode the Linear gradients are
+ *      lipvq_linear_nn_<mode> (gx = gpre times the stacked weights AS STORED) and lipvq_wgrad_<mode>, with gpre's columns and the
+ *      stacked weight's rows extended with zeros to 8 ceil(P / 8) (zero lines add exact zeros) and the results cut. ---- */
+enum { LIPVQ_MATMUL_FP32 = 0, LIPVQ_MATMUL_BF16 = 1, LIPVQ_MATMUL_BF16X3 = 2 };
+int lipvq_action_head_mp_f32(const float* x, int64_t bstride, const float* W, const float* b, const float* target, float* actions,
+                             float* pre, float* losses, void* workspace, int64_t N, int T, int E, int A, float w2, float w1,
+                             float wc, int matmul, void* stream);
+int lipvq_gmm_head_mp_f32(const float* x, int64_t bstride, const float* Wm, const float* bm, const float* Ws, const float* bs,
+                          const float* Wl, const float* bl, const float* actions, float* log_prob, float* pre, float* mean,
+                          float* scale, float* logits, float* lp_sum, void* workspace, int64_t N, int T, int E, int M, int A,
+                          int scale_mode, float min_std, int matmul, void* stream);
+int lipvq_gmm_sample_mp_f32(const float* x, int64_t bstride, const float* Wm, const float* bm, const float* Ws, const float* bs,
+                            const float* Wl, const float* bl, const float* u, const float* eps, float* action, int64_t N, int T,
+                            int E, int M, int A, int scale_mode, float min_std, int matmul, void* stream);
+int lipvq_gmm_sample_draw_mp_f32(const float* x, int64_t bstride, const float* Wm, const float* bm, const float* Ws, const float* bs,
+                                 const float* Wl, const float* bl, const int64_t* snap, const int64_t* streams, float* action, int64_t N,
+                                 int T, int E, int M, int A, int scale_mode, float min_std, int matmul, void* stream);
+
 /* icl.py:885-889, :970  optim.AdamW(vq_vae_model.parameters(), lr=1e-3, weight_decay=1e-4).step() for a LIST of tensors in
  * two launches (torch's foreach form is 8-10): params / grads / exp_avg / exp_avg_sq / steps are HOST arrays of `count`
  * DEVICE pointers (count <= 32), numels their element counts; steps[i] is a float32 device scalar (torch's capturable layout),

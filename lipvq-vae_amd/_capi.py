@@ -143,6 +143,10 @@ SIGNATURES = {
     "lipvq_normal_icdf_host": (_i, [_vp, _vp, _i64]),
     "lipvq_action_head_workspace_bytes": (_sz, [_i64]),
     "lipvq_action_head_f32": (_i, [_vp, _i64] + [_vp] * 7 + [_i64, _i, _i, _i] + [C.c_float] * 3 + [_vp]),
+    "lipvq_action_head_mp_f32": (_i, [_vp, _i64] + [_vp] * 7 + [_i64, _i, _i, _i] + [C.c_float] * 3 + [_i, _vp]),
+    "lipvq_gmm_head_mp_f32": (_i, [_vp, _i64] + [_vp] * 14 + [_i64] + [_i] * 5 + [C.c_float, _i, _vp]),
+    "lipvq_gmm_sample_mp_f32": (_i, [_vp, _i64] + [_vp] * 9 + [_i64] + [_i] * 5 + [C.c_float, _i, _vp]),
+    "lipvq_gmm_sample_draw_mp_f32": (_i, [_vp, _i64] + [_vp] * 9 + [_i64] + [_i] * 5 + [C.c_float, _i, _vp]),
     "lipvq_action_head_bwd_f32": (_i, [_vp] * 5 + [_i64, _i] + [C.c_float] * 3 + [_vp]),
     "lipvq_adamw_workspace_bytes": (_sz, []),
     "lipvq_adamw_f32": (_i, [_vp] * 6 + [_i] + [C.c_double] * 5 + [_vp, _vp]),

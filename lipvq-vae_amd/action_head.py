@@ -18,6 +18,9 @@ loads with ``strict=True``.  The child is a parameter CONTAINER only: no method 
                                 four losses is read on the device
     lipvq_wgrad_f32, lipvq_linear_act_f32      the two parameter gradients and the input gradient (ops.head_linear_grads)
 
+``set_matmul_precision("bf16" | "bf16x3")`` moves the Linear onto the bf16 matrix pipe (lipvq_action_head_mp_f32; the gradients:
+lipvq_linear_nn_<mode>, lipvq_wgrad_<mode>), as the backbone's setter does for its Linears; the default is fp32.
+
 ``feats`` may be the non-contiguous view ``out[:, -T:]`` or ``out[:, -1:]`` of a ``GPTBackbone`` output: its strides go to the
 kernel and the forward makes no copy (the backward's wgrad reads a dense copy of those rows, and the input gradient comes back
 dense, in the view's shape; autograd scatters it into the backbone output's gradient).  No kernel here uses float atomics and no
@@ -48,10 +51,11 @@ class _ActionsFn(KernelFunction):
     """actions [B, T, A] over lipvq_action_head_f32 / lipvq_action_head_bwd_f32 (the gy mode)."""
 
     @staticmethod
-    def forward(ctx, feats, W, b):
+    def forward(ctx, feats, W, b, precision="fp32"):
         keep = wants_backward(ctx)
-        out = ops.action_head(feats, W, b, want_pre=keep)
+        out = ops.action_head(feats, W, b, want_pre=keep, precision=precision)
         if keep:
+            ctx.precision = precision
             ctx.save_for_backward(feats, out["pre"], W)
         return out["actions"].view(tuple(feats.shape[:-1]) + (W.shape[0],))
 
@@ -61,7 +65,8 @@ class _ActionsFn(KernelFunction):
         feats, pre, W = ctx.saved_tensors
         gpre = ops.action_head_bwd(pre, gy=gy.reshape(pre.shape))
         need = ctx.needs_input_grad
-        return ops.head_linear_grads(need[0], need[1] or need[2], feats, gpre, (W,))
+        g = ops.head_linear_grads(need[0], need[1] or need[2], feats, gpre, (W,), ctx.precision)
+        return (g + (None,))[:len(need)]                            # (precision is optional: one gradient slot per argument given)
 
 
 class _LossesFn(KernelFunction):
@@ -69,11 +74,11 @@ class _LossesFn(KernelFunction):
     gradient [4] stays on the device."""
 
     @staticmethod
-    def forward(ctx, feats, target, W, b, weights):
+    def forward(ctx, feats, target, W, b, weights, precision="fp32"):
         keep = wants_backward(ctx)
-        out = ops.action_head(feats, W, b, target, weights, want_actions=False, want_pre=keep)
+        out = ops.action_head(feats, W, b, target, weights, want_actions=False, want_pre=keep, precision=precision)
         if keep:
-            ctx.weights = weights
+            ctx.weights, ctx.precision = weights, precision
             ctx.save_for_backward(feats, target, out["pre"], W)
         return out["losses"]
 
@@ -83,8 +88,8 @@ class _LossesFn(KernelFunction):
         feats, target, pre, W = ctx.saved_tensors
         gpre = ops.action_head_bwd(pre, target, g=g, weights=ctx.weights)
         need = ctx.needs_input_grad
-        gx, gW, gb = ops.head_linear_grads(need[0], need[2] or need[3], feats, gpre, (W,))
-        return gx, None, gW, gb, None
+        gx, gW, gb = ops.head_linear_grads(need[0], need[2] or need[3], feats, gpre, (W,), ctx.precision)
+        return (gx, None, gW, gb, None, None)[:len(need)]         # (precision is optional: one gradient slot per argument given)
 
 
 class ActionHead(nn.Module):
@@ -104,6 +109,23 @@ class ActionHead(nn.Module):
         self.ac_dim = ac_dim
         self.nets = nn.ModuleDict()                                 # ObservationDecoder._create_layers: one layer, `action`
         self.nets["action"] = nn.Linear(embed_dim, ac_dim)
+        self._matmul_precision = "fp32"
+
+    @property
+    def matmul_precision(self) -> str:
+        """"fp32" (default), "bf16" or "bf16x3": how the head's Linear multiplies (set_matmul_precision)."""
+        return self._matmul_precision
+
+    def set_matmul_precision(self, precision: str) -> "ActionHead":
+        """"bf16" / "bf16x3": the head's Linear -- in ``forward`` and ``losses``, and its two gradients in their backward -- runs
+        on the bf16 matrix pipe by ``GPTBackbone.set_matmul_precision``'s rules: operands rounded to bf16 (nearest even; "bf16x3":
+        split into hi + lo, three products) as the kernel reads them, fp32 accumulation, every tensor fp32; the pre-activations
+        have the bits of ``ops.linear_bf16`` / ``ops.linear_bf16x3``, and tanh, the losses and their backward are the fp32 code.
+        "fp32" restores the default bit for bit.  The bf16 modes need embed_dim % 8 == 0.  Not part of state_dict(); a captured
+        graph keeps the mode it was captured in; returns self."""
+        ops._matmul_mode("ActionHead", precision, self.embed_dim)
+        self._matmul_precision = precision
+        return self
 
     def _check(self, feats, target=None):
         if not feats.is_cuda:
@@ -118,7 +140,7 @@ class ActionHead(nn.Module):
         """actions [B, T, A] = tanh(feats W^T + b) (policy_nets.py:1728-1731), with autograd.  No host synchronisation: capturable
         by nnfn.GraphedEval, and the ``head`` of icl.PromptedPolicy."""
         feats = self._check(feats)
-        return _ActionsFn.apply(feats, self.nets["action"].weight, self.nets["action"].bias)
+        return _ActionsFn.apply(feats, self.nets["action"].weight, self.nets["action"].bias, self._matmul_precision)
 
     def losses(self, feats, target, l2_weight=1.0, l1_weight=0.0, cos_weight=0.0):
         """ICL._compute_losses (icl.py:174-202) of the head's actions on feats [B, T, E] against target [B, T, A]: an OrderedDict
@@ -126,5 +148,5 @@ class ActionHead(nn.Module):
         tensors; a backward is possible through any of them.  No host read: capturable (icl.GraphedPolicyStep)."""
         feats = self._check(feats, target)
         out = _LossesFn.apply(feats, target.detach().float(), self.nets["action"].weight, self.nets["action"].bias,
-                              (float(l2_weight), float(l1_weight), float(cos_weight)))
+                              (float(l2_weight), float(l1_weight), float(cos_weight)), self._matmul_precision)
         return OrderedDict((k, out[i]) for i, k in enumerate(LOSS_KEYS))

@@ -11,6 +11,8 @@
 // one-workgroup launch adds them in a fixed order and writes the four losses: no float atomics, the same bits on every run.
 // The backward (action_head_bwd_kernel) is elementwise over the saved pre-activations; the upstream gradient of the four losses
 // is read on the device.
+// The _mp entry point picks the product stage: LIPVQ_MATMUL_BF16 / _BF16X3 run it on the bf16 matrix pipe with the bits of
+// lipvq_linear_act_bf16 / _bf16x3 (lq_head_product_bf16); the epilogue is the same code.
 // ABI: include/lipvq.h.
 #include <math.h>
 
@@ -23,6 +25,7 @@
 #define AH_NT 1                                       // A <= 64: two column tiles at the most, waves 0 and 1
 #define AH_KC 32
 #define AH_DEPTH 4                                    // chunks in flight: few workgroups walk E alone, so the loads' latency decides
+#define AH_DEPTHB 4                                   // the same for the bf16 stage's chunks of 32
 
 struct ActionHeadArgs {
     const float* x; const float* W; const float* b; const float* target;
@@ -69,15 +72,16 @@ __device__ __forceinline__ float ah_cos_sim(const float (&p)[3], const float (&t
     return sim;
 }
 
-// dynamic LDS: max(staging [32 + 128][33], tile [32][PS]) floats, then 3 x 32 row results
+// dynamic LDS: max(staging [32 + 128][33] (MP: the bf16 images), tile [32][PS]) floats, then 3 x 32 row results
+template <int MP>
 __global__ __launch_bounds__(256) void action_head_kernel(const ActionHeadArgs a, int side_off) {
-    extern __shared__ float ah_lds[];
+    extern __shared__ __attribute__((aligned(16))) float ah_lds[];
     float* pt = ah_lds;                                             // [32][PS], after the product
     float* s_row = ah_lds + side_off;                               // [3][32]
     const int tid = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * HEAD_ROWS;
     const int A = a.A, PS = a.PS;
-    lq_head_product<AH_NT, AH_KC, AH_DEPTH>(ah_lds, a.x, a.bstride, a.N, a.T, a.E, A, PS, ActionHeadCols{a.W, a.b, A, a.E});
+    lq_head_product_mp<MP, AH_NT, AH_KC, AH_DEPTH, AH_DEPTHB>(ah_lds, a.x, a.bstride, a.N, a.T, a.E, A, PS, ActionHeadCols{a.W, a.b, A, a.E});
     const int live = (int)((a.N - row0 < HEAD_ROWS) ? (a.N - row0) : HEAD_ROWS);          // rows of this tile that exist
     if (a.pre) {
         float* dst = a.pre + (size_t)row0 * A;
@@ -205,6 +209,33 @@ static int ah_check(const char* what, int64_t N, int T, int E, int A, int64_t bs
     return LIPVQ_OK;
 }
 
+static int ah_forward(const char* what, const float* x, int64_t bstride, const float* W, const float* b, const float* target,
+                      float* actions, float* pre, float* losses, void* workspace, int64_t N, int T, int E, int A, float w2, float w1,
+                      float wc, int matmul, void* stream) {
+    if (int rc = ah_check(what, N, T, E, A, bstride)) return rc;
+    if (int rc = lq_head_matmul_check(what, matmul, E)) return rc;
+    if (N == 0) return LIPVQ_OK;
+    if (!x || !W || !b) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
+    if (losses && !target) return fail(LIPVQ_EINVAL, "%s: the losses need a target", what);
+    if (losses && !workspace) return fail(LIPVQ_EINVAL, "%s: the losses need the workspace", what);
+    if ((((uintptr_t)x | (uintptr_t)W) & 15) != 0) return fail(LIPVQ_EINVAL, "%s: x and the weight must be 16-byte aligned", what);
+    hipStream_t st = (hipStream_t)stream;
+    const int PS = A | 1;                                           // odd row stride: the items of a wave differ in the row
+    ActionHeadArgs a{x, W, b, losses ? target : nullptr, actions, pre, losses ? (float*)workspace : nullptr, N, bstride, T, E, A, PS};
+    const int stage = matmul == LIPVQ_MATMUL_FP32 ? lq_head_stage_floats(AH_NT, AH_KC) : lq_head_stage_floats_bf16(AH_NT, matmul == LIPVQ_MATMUL_BF16X3);
+    const int tile = HEAD_ROWS * PS;
+    const int side_off = stage > tile ? stage : tile;
+    const size_t lds = (size_t)(side_off + 3 * HEAD_ROWS) * sizeof(float);          // 21.5 KB (bf16: 13, bf16x3: 25.5)
+    const int64_t tiles = (N + HEAD_ROWS - 1) / HEAD_ROWS;
+    if (matmul == LIPVQ_MATMUL_FP32) hipLaunchKernelGGL(action_head_kernel<LIPVQ_MATMUL_FP32>, dim3((unsigned)tiles), dim3(256), lds, st, a, side_off);
+    else if (matmul == LIPVQ_MATMUL_BF16) hipLaunchKernelGGL(action_head_kernel<LIPVQ_MATMUL_BF16>, dim3((unsigned)tiles), dim3(256), lds, st, a, side_off);
+    else hipLaunchKernelGGL(action_head_kernel<LIPVQ_MATMUL_BF16X3>, dim3((unsigned)tiles), dim3(256), lds, st, a, side_off);
+    if (int rc = check_launch("action_head_kernel")) return rc;
+    if (!losses) return LIPVQ_OK;
+    hipLaunchKernelGGL(action_head_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, tiles, losses, N, A, w2, w1, wc);
+    return check_launch("action_head_sum_kernel");
+}
+
 extern "C" {
 
 size_t lipvq_action_head_workspace_bytes(int64_t N) {
@@ -215,24 +246,15 @@ size_t lipvq_action_head_workspace_bytes(int64_t N) {
 int lipvq_action_head_f32(const float* x, int64_t bstride, const float* W, const float* b, const float* target, float* actions,
                           float* pre, float* losses, void* workspace, int64_t N, int T, int E, int A, float w2, float w1,
                           float wc, void* stream) {
-    if (int rc = ah_check("lipvq_action_head_f32", N, T, E, A, bstride)) return rc;
-    if (N == 0) return LIPVQ_OK;
-    if (!x || !W || !b) return fail(LIPVQ_EINVAL, "lipvq_action_head_f32: null pointer");
-    if (losses && !target) return fail(LIPVQ_EINVAL, "lipvq_action_head_f32: the losses need a target");
-    if (losses && !workspace) return fail(LIPVQ_EINVAL, "lipvq_action_head_f32: the losses need the workspace");
-    if ((((uintptr_t)x | (uintptr_t)W) & 15) != 0) return fail(LIPVQ_EINVAL, "lipvq_action_head_f32: x and the weight must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int PS = A | 1;                                           // odd row stride: the items of a wave differ in the row
-    ActionHeadArgs a{x, W, b, losses ? target : nullptr, actions, pre, losses ? (float*)workspace : nullptr, N, bstride, T, E, A, PS};
-    const int stage = lq_head_stage_floats(AH_NT, AH_KC), tile = HEAD_ROWS * PS;
-    const int side_off = stage > tile ? stage : tile;
-    const size_t lds = (size_t)(side_off + 3 * HEAD_ROWS) * sizeof(float);          // 21.5 KB
-    const int64_t tiles = (N + HEAD_ROWS - 1) / HEAD_ROWS;
-    hipLaunchKernelGGL(action_head_kernel, dim3((unsigned)tiles), dim3(256), lds, st, a, side_off);
-    if (int rc = check_launch("action_head_kernel")) return rc;
-    if (!losses) return LIPVQ_OK;
-    hipLaunchKernelGGL(action_head_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, tiles, losses, N, A, w2, w1, wc);
-    return check_launch("action_head_sum_kernel");
+    return ah_forward("lipvq_action_head_f32", x, bstride, W, b, target, actions, pre, losses, workspace, N, T, E, A, w2, w1, wc,
+                      LIPVQ_MATMUL_FP32, stream);
+}
+
+int lipvq_action_head_mp_f32(const float* x, int64_t bstride, const float* W, const float* b, const float* target, float* actions,
+                             float* pre, float* losses, void* workspace, int64_t N, int T, int E, int A, float w2, float w1,
+                             float wc, int matmul, void* stream) {
+    return ah_forward("lipvq_action_head_mp_f32", x, bstride, W, b, target, actions, pre, losses, workspace, N, T, E, A, w2, w1, wc,
+                      matmul, stream);
 }
 
 int lipvq_action_head_bwd_f32(const float* pre, const float* target, const float* g, const float* gy, float* gpre, int64_t N,

@@ -15,6 +15,8 @@
 // fixed order: no float atomics, the same bits on every run.
 // The backward (gmm_head_bwd_kernel) is one pass over the saved pre-activations, 32 rows per workgroup through the same LDS
 // tile: responsibilities r_m = softmax_m(log pi_m + l_m), then the closed forms of include/lipvq.h; again no atomics.
+// The _mp entry points pick the product stage: LIPVQ_MATMUL_BF16 / _BF16X3 run it on the bf16 matrix pipe with the bits of
+// lipvq_linear_act_bf16 / _bf16x3 (lq_head_product_bf16); every epilogue is the same code on the same tile.
 // ABI: include/lipvq.h.
 #include <math.h>
 
@@ -29,6 +31,7 @@
 #define GMM_MAXE 1024
 #define GMM_LOW_NOISE_STD 1e-4f                       // policy_nets.py:2557
 #define GMM_HALF_LOG_2PI 0.91893853320467274178f
+#define GMM_DEPTHB 2                                  // chunks of 32 features in flight in the bf16 product stage
 #define GMM_SIDE (2 * GMM_ROWS * (GMM_MAXM + 1) + GMM_ROWS)      // floats after the tile: ell, logit copies, row results
 
 struct GmmArgs {
@@ -107,18 +110,18 @@ struct GmmCols {
 // ---------------------------------------------------------------------------------------------------
 // forward / sampling.  NT = column tiles per wave (P <= 128 NT), KC = input features staged per step: the product stage of
 // lipvq_head_product.h, then the epilogues on its LDS tile.
-// dynamic LDS: max(staging [32 + 128 NT][KC + 1], tile [32][PS]) floats, then GMM_SIDE floats.
+// dynamic LDS: max(staging [32 + 128 NT][KC + 1] (MP: the bf16 images), tile [32][PS]) floats, then GMM_SIDE floats.
 // ---------------------------------------------------------------------------------------------------
-template <int NT, int KC, bool DRAW>
+template <int NT, int KC, bool DRAW, int MP>
 __global__ __launch_bounds__(256) void gmm_head_kernel(const GmmArgs a, int side_off) {
-    extern __shared__ float gmm_lds[];
+    extern __shared__ __attribute__((aligned(16))) float gmm_lds[];
     float* pt = gmm_lds;                                            // [32][PS], after the product
     float* s_ell = gmm_lds + side_off;                              // [32][17]
     float* s_lp = s_ell + 2 * GMM_ROWS * (GMM_MAXM + 1);            // [32]
     const int tid = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * GMM_ROWS;
     const int M = a.M, A = a.A, MA = a.M * a.A, P = a.P, PS = a.PS;
-    lq_head_product<NT, KC, 1>(gmm_lds, a.x, a.bstride, a.N, a.T, a.E, P, PS, GmmCols{a.Wm, a.Ws, a.Wl, a.bm, a.bs, a.bl, MA, P, a.E});
+    lq_head_product_mp<MP, NT, KC, 1, GMM_DEPTHB>(gmm_lds, a.x, a.bstride, a.N, a.T, a.E, P, PS, GmmCols{a.Wm, a.Ws, a.Wl, a.bm, a.bs, a.bl, MA, P, a.E});
     const int64_t live = (a.N - row0 < GMM_ROWS) ? (a.N - row0) : GMM_ROWS;      // rows of this tile that exist
     if (a.pre) {
         float* dst = a.pre + (size_t)row0 * P;
@@ -265,7 +268,7 @@ struct GmmBwdArgs {
 };
 
 __global__ __launch_bounds__(256) void gmm_head_bwd_kernel(const GmmBwdArgs a) {
-    extern __shared__ float gmm_lds[];
+    extern __shared__ __attribute__((aligned(16))) float gmm_lds[];
     float* pt = gmm_lds;                                            // [32][PS]
     float* s_ell = gmm_lds + GMM_ROWS * a.PS;                       // [32][17]
     float* s_lg = s_ell + GMM_ROWS * (GMM_MAXM + 1);                // [32][17]
@@ -356,23 +359,85 @@ static int gmm_check(const char* what, int64_t N, int T, int E, int M, int A, in
     return LIPVQ_OK;
 }
 
-static int gmm_launch(const char* what, GmmArgs& a, hipStream_t st, bool draw = false) {
+template <int MP>
+static int gmm_launch_mp(const char* what, GmmArgs& a, hipStream_t st, bool draw) {
     a.P = a.M * (2 * a.A + 1);
     a.PS = a.P | 1;                                                 // odd row stride: the items of a wave differ in the row
     const int tiles = (a.P + 31) / 32, nt = (tiles + 3) / 4;
     const int NT = nt <= 1 ? 1 : (nt <= 2 ? 2 : 4), KC = NT == 4 ? 16 : 32;
-    const int stage = lq_head_stage_floats(NT, KC), tile = GMM_ROWS * a.PS;
+    const int stage = MP == LIPVQ_MATMUL_FP32 ? lq_head_stage_floats(NT, KC) : lq_head_stage_floats_bf16(NT, MP == LIPVQ_MATMUL_BF16X3);
+    const int tile = GMM_ROWS * a.PS;
     const int side_off = stage > tile ? stage : tile;
-    const size_t lds = (size_t)(side_off + GMM_SIDE) * sizeof(float);
+    const size_t lds = (size_t)(side_off + GMM_SIDE) * sizeof(float);          // at the most 89.5 KB (NT = 4, bf16x3)
     typedef void (*fn_t)(const GmmArgs, int);
-    const fn_t kfn = draw ? (NT == 1 ? (fn_t)gmm_head_kernel<1, 32, true> : (NT == 2 ? (fn_t)gmm_head_kernel<2, 32, true> : (fn_t)gmm_head_kernel<4, 16, true>))
-                          : (NT == 1 ? (fn_t)gmm_head_kernel<1, 32, false> : (NT == 2 ? (fn_t)gmm_head_kernel<2, 32, false> : (fn_t)gmm_head_kernel<4, 16, false>));
-    static LqLdsReserve reserved[6];
+    const fn_t kfn = draw ? (NT == 1 ? (fn_t)gmm_head_kernel<1, 32, true, MP> : (NT == 2 ? (fn_t)gmm_head_kernel<2, 32, true, MP> : (fn_t)gmm_head_kernel<4, 16, true, MP>))
+                          : (NT == 1 ? (fn_t)gmm_head_kernel<1, 32, false, MP> : (NT == 2 ? (fn_t)gmm_head_kernel<2, 32, false, MP> : (fn_t)gmm_head_kernel<4, 16, false, MP>));
+    static LqLdsReserve reserved[6];                                // (one array per MP: a static of the template instance)
     if (lds > 64 * 1024)
         if (int rc = lipvq_reserve_lds(reserved[(NT == 1 ? 0 : (NT == 2 ? 1 : 2)) + (draw ? 3 : 0)], (const void*)kfn, lds, what)) return rc;
     const dim3 grid((unsigned)((a.N + GMM_ROWS - 1) / GMM_ROWS)), block(256);
     hipLaunchKernelGGL(kfn, grid, block, lds, st, a, side_off);
     return check_launch(what);
+}
+
+static int gmm_launch(const char* what, GmmArgs& a, hipStream_t st, int matmul, bool draw = false) {
+    if (matmul == LIPVQ_MATMUL_FP32) return gmm_launch_mp<LIPVQ_MATMUL_FP32>(what, a, st, draw);
+    if (matmul == LIPVQ_MATMUL_BF16) return gmm_launch_mp<LIPVQ_MATMUL_BF16>(what, a, st, draw);
+    return gmm_launch_mp<LIPVQ_MATMUL_BF16X3>(what, a, st, draw);
+}
+
+static int gmm_forward(const char* what, const float* x, int64_t bstride, const float* Wm, const float* bm, const float* Ws,
+                       const float* bs, const float* Wl, const float* bl, const float* actions, float* log_prob, float* pre,
+                       float* mean, float* scale, float* logits, float* lp_sum, void* workspace, int64_t N, int T, int E,
+                       int M, int A, int scale_mode, float min_std, int matmul, void* stream) {
+    if (int rc = gmm_check(what, N, T, E, M, A, scale_mode, bstride)) return rc;
+    if (int rc = lq_head_matmul_check(what, matmul, E)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 0) {
+        if (lp_sum && hipMemsetAsync(lp_sum, 0, sizeof(float), st) != hipSuccess) return fail(LIPVQ_EHIP, "%s: memset failed", what);
+        return LIPVQ_OK;
+    }
+    if (!x || !Wm || !bm || !Ws || !bs || !Wl || !bl) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
+    if ((log_prob || lp_sum) && !actions) return fail(LIPVQ_EINVAL, "%s: log_prob needs actions", what);
+    if (lp_sum && !workspace) return fail(LIPVQ_EINVAL, "%s: the sum needs the workspace", what);
+    if ((((uintptr_t)x | (uintptr_t)Wm | (uintptr_t)Ws | (uintptr_t)Wl) & 15) != 0)
+        return fail(LIPVQ_EINVAL, "%s: x and the weights must be 16-byte aligned", what);
+    GmmArgs a{x, Wm, Ws, Wl, bm, bs, bl, (log_prob || lp_sum) ? actions : nullptr, {nullptr}, {nullptr}, log_prob, pre, mean, scale, logits,
+              lp_sum ? (float*)workspace : nullptr, nullptr, N, bstride, T, E, M, A, 0, 0, scale_mode, min_std};
+    if (int rc = gmm_launch("gmm_head_kernel", a, st, matmul)) return rc;
+    if (!lp_sum) return LIPVQ_OK;
+    hipLaunchKernelGGL(gmm_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (N + GMM_ROWS - 1) / GMM_ROWS, lp_sum);
+    return check_launch("gmm_sum_kernel");
+}
+
+static int gmm_sample(const char* what, const float* x, int64_t bstride, const float* Wm, const float* bm, const float* Ws,
+                      const float* bs, const float* Wl, const float* bl, const float* u, const float* eps, float* action, int64_t N,
+                      int T, int E, int M, int A, int scale_mode, float min_std, int matmul, void* stream) {
+    if (int rc = gmm_check(what, N, T, E, M, A, scale_mode, bstride)) return rc;
+    if (int rc = lq_head_matmul_check(what, matmul, E)) return rc;
+    if (N == 0) return LIPVQ_OK;
+    if (!x || !Wm || !bm || !Ws || !bs || !Wl || !bl || !u || !eps || !action) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
+    if ((((uintptr_t)x | (uintptr_t)Wm | (uintptr_t)Ws | (uintptr_t)Wl) & 15) != 0)
+        return fail(LIPVQ_EINVAL, "%s: x and the weights must be 16-byte aligned", what);
+    GmmArgs a{x, Wm, Ws, Wl, bm, bs, bl, nullptr, {u}, {eps}, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, action,
+              N, bstride, T, E, M, A, 0, 0, scale_mode, min_std};
+    return gmm_launch("gmm_head_kernel (sample)", a, (hipStream_t)stream, matmul);
+}
+
+static int gmm_sample_draw(const char* what, const float* x, int64_t bstride, const float* Wm, const float* bm, const float* Ws,
+                           const float* bs, const float* Wl, const float* bl, const int64_t* snap, const int64_t* streams, float* action,
+                           int64_t N, int T, int E, int M, int A, int scale_mode, float min_std, int matmul, void* stream) {
+    if (int rc = gmm_check(what, N, T, E, M, A, scale_mode, bstride)) return rc;
+    if (int rc = lq_head_matmul_check(what, matmul, E)) return rc;
+    if (N == 0) return LIPVQ_OK;
+    if (!x || !Wm || !bm || !Ws || !bs || !Wl || !bl || !snap || !action) return fail(LIPVQ_EINVAL, "%s: null pointer", what);
+    if ((((uintptr_t)x | (uintptr_t)Wm | (uintptr_t)Ws | (uintptr_t)Wl) & 15) != 0)
+        return fail(LIPVQ_EINVAL, "%s: x and the weights must be 16-byte aligned", what);
+    GmmArgs a{x, Wm, Ws, Wl, bm, bs, bl, nullptr, {nullptr}, {nullptr}, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, action,
+              N, bstride, T, E, M, A, 0, 0, scale_mode, min_std};
+    a.snap = snap;
+    a.streams = streams;
+    return gmm_launch("gmm_head_kernel (sample, drawn)", a, (hipStream_t)stream, matmul, true);
 }
 
 extern "C" {
@@ -386,51 +451,44 @@ int lipvq_gmm_head_f32(const float* x, int64_t bstride, const float* Wm, const f
                        const float* Wl, const float* bl, const float* actions, float* log_prob, float* pre, float* mean,
                        float* scale, float* logits, float* lp_sum, void* workspace, int64_t N, int T, int E, int M, int A,
                        int scale_mode, float min_std, void* stream) {
-    if (int rc = gmm_check("lipvq_gmm_head_f32", N, T, E, M, A, scale_mode, bstride)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (N == 0) {
-        if (lp_sum && hipMemsetAsync(lp_sum, 0, sizeof(float), st) != hipSuccess) return fail(LIPVQ_EHIP, "lipvq_gmm_head_f32: memset failed");
-        return LIPVQ_OK;
-    }
-    if (!x || !Wm || !bm || !Ws || !bs || !Wl || !bl) return fail(LIPVQ_EINVAL, "lipvq_gmm_head_f32: null pointer");
-    if ((log_prob || lp_sum) && !actions) return fail(LIPVQ_EINVAL, "lipvq_gmm_head_f32: log_prob needs actions");
-    if (lp_sum && !workspace) return fail(LIPVQ_EINVAL, "lipvq_gmm_head_f32: the sum needs the workspace");
-    if ((((uintptr_t)x | (uintptr_t)Wm | (uintptr_t)Ws | (uintptr_t)Wl) & 15) != 0)
-        return fail(LIPVQ_EINVAL, "lipvq_gmm_head_f32: x and the weights must be 16-byte aligned");
-    GmmArgs a{x, Wm, Ws, Wl, bm, bs, bl, (log_prob || lp_sum) ? actions : nullptr, {nullptr}, {nullptr}, log_prob, pre, mean, scale, logits,
-              lp_sum ? (float*)workspace : nullptr, nullptr, N, bstride, T, E, M, A, 0, 0, scale_mode, min_std};
-    if (int rc = gmm_launch("gmm_head_kernel", a, st)) return rc;
-    if (!lp_sum) return LIPVQ_OK;
-    hipLaunchKernelGGL(gmm_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (N + GMM_ROWS - 1) / GMM_ROWS, lp_sum);
-    return check_launch("gmm_sum_kernel");
+    return gmm_forward("lipvq_gmm_head_f32", x, bstride, Wm, bm, Ws, bs, Wl, bl, actions, log_prob, pre, mean, scale, logits,
+                       lp_sum, workspace, N, T, E, M, A, scale_mode, min_std, LIPVQ_MATMUL_FP32, stream);
+}
+
+int lipvq_gmm_head_mp_f32(const float* x, int64_t bstride, const float* Wm, const float* bm, const float* Ws, const float* bs,
+                          const float* Wl, const float* bl, const float* actions, float* log_prob, float* pre, float* mean,
+                          float* scale, float* logits, float* lp_sum, void* workspace, int64_t N, int T, int E, int M, int A,
+                          int scale_mode, float min_std, int matmul, void* stream) {
+    return gmm_forward("lipvq_gmm_head_mp_f32", x, bstride, Wm, bm, Ws, bs, Wl, bl, actions, log_prob, pre, mean, scale,
+                       logits, lp_sum, workspace, N, T, E, M, A, scale_mode, min_std, matmul, stream);
 }
 
 int lipvq_gmm_sample_f32(const float* x, int64_t bstride, const float* Wm, const float* bm, const float* Ws, const float* bs,
                          const float* Wl, const float* bl, const float* u, const float* eps, float* action, int64_t N, int T,
                          int E, int M, int A, int scale_mode, float min_std, void* stream) {
-    if (int rc = gmm_check("lipvq_gmm_sample_f32", N, T, E, M, A, scale_mode, bstride)) return rc;
-    if (N == 0) return LIPVQ_OK;
-    if (!x || !Wm || !bm || !Ws || !bs || !Wl || !bl || !u || !eps || !action) return fail(LIPVQ_EINVAL, "lipvq_gmm_sample_f32: null pointer");
-    if ((((uintptr_t)x | (uintptr_t)Wm | (uintptr_t)Ws | (uintptr_t)Wl) & 15) != 0)
-        return fail(LIPVQ_EINVAL, "lipvq_gmm_sample_f32: x and the weights must be 16-byte aligned");
-    GmmArgs a{x, Wm, Ws, Wl, bm, bs, bl, nullptr, {u}, {eps}, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, action,
-              N, bstride, T, E, M, A, 0, 0, scale_mode, min_std};
-    return gmm_launch("gmm_head_kernel (sample)", a, (hipStream_t)stream);
+    return gmm_sample("lipvq_gmm_sample_f32", x, bstride, Wm, bm, Ws, bs, Wl, bl, u, eps, action, N, T, E, M, A, scale_mode,
+                      min_std, LIPVQ_MATMUL_FP32, stream);
+}
+
+int lipvq_gmm_sample_mp_f32(const float* x, int64_t bstride, const float* Wm, const float* bm, const float* Ws, const float* bs,
+                            const float* Wl, const float* bl, const float* u, const float* eps, float* action, int64_t N, int T,
+                            int E, int M, int A, int scale_mode, float min_std, int matmul, void* stream) {
+    return gmm_sample("lipvq_gmm_sample_mp_f32", x, bstride, Wm, bm, Ws, bs, Wl, bl, u, eps, action, N, T, E, M, A, scale_mode,
+                      min_std, matmul, stream);
 }
 
 int lipvq_gmm_sample_draw_f32(const float* x, int64_t bstride, const float* Wm, const float* bm, const float* Ws, const float* bs,
                               const float* Wl, const float* bl, const int64_t* snap, const int64_t* streams, float* action, int64_t N,
                               int T, int E, int M, int A, int scale_mode, float min_std, void* stream) {
-    if (int rc = gmm_check("lipvq_gmm_sample_draw_f32", N, T, E, M, A, scale_mode, bstride)) return rc;
-    if (N == 0) return LIPVQ_OK;
-    if (!x || !Wm || !bm || !Ws || !bs || !Wl || !bl || !snap || !action) return fail(LIPVQ_EINVAL, "lipvq_gmm_sample_draw_f32: null pointer");
-    if ((((uintptr_t)x | (uintptr_t)Wm | (uintptr_t)Ws | (uintptr_t)Wl) & 15) != 0)
-        return fail(LIPVQ_EINVAL, "lipvq_gmm_sample_draw_f32: x and the weights must be 16-byte aligned");
-    GmmArgs a{x, Wm, Ws, Wl, bm, bs, bl, nullptr, {nullptr}, {nullptr}, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, action,
-              N, bstride, T, E, M, A, 0, 0, scale_mode, min_std};
-    a.snap = snap;
-    a.streams = streams;
-    return gmm_launch("gmm_head_kernel (sample, drawn)", a, (hipStream_t)stream, true);
+    return gmm_sample_draw("lipvq_gmm_sample_draw_f32", x, bstride, Wm, bm, Ws, bs, Wl, bl, snap, streams, action, N, T, E, M,
+                           A, scale_mode, min_std, LIPVQ_MATMUL_FP32, stream);
+}
+
+int lipvq_gmm_sample_draw_mp_f32(const float* x, int64_t bstride, const float* Wm, const float* bm, const float* Ws, const float* bs,
+                                 const float* Wl, const float* bl, const int64_t* snap, const int64_t* streams, float* action, int64_t N,
+                                 int T, int E, int M, int A, int scale_mode, float min_std, int matmul, void* stream) {
+    return gmm_sample_draw("lipvq_gmm_sample_draw_mp_f32", x, bstride, Wm, bm, Ws, bs, Wl, bl, snap, streams, action, N, T, E,
+                           M, A, scale_mode, min_std, matmul, stream);
 }
 
 static int gmm_noise_args(const char* what, int64_t B, int T, int A) {

@@ -17,6 +17,9 @@ parameter CONTAINERS only: no method calls them.  The compute is
     lipvq_gmm_sample_draw_f32 the same launch drawing u and eps itself (``set_sample_source("kernel")``), after one
                               lipvq_dropout_begin launch on the module's (seed, step) state
 
+``set_matmul_precision("bf16" | "bf16x3")`` moves the three Linears onto the bf16 matrix pipe (the lipvq_gmm_*_mp_f32 entry points;
+the gradients: lipvq_linear_nn_<mode>, lipvq_wgrad_<mode>), as the backbone's setter does for its Linears; the default is fp32.
+
 ``feats`` may be the non-contiguous view ``out[:, -T:]`` of a ``GPTBackbone`` output: its strides go to the kernel and the
 forward makes no copy (the backward's wgrad reads a dense copy of those rows, and the input gradient comes back dense, in the
 view's shape; autograd scatters it into the backbone output's gradient).  No kernel here uses float atomics: losses and gradients
@@ -42,9 +45,9 @@ from .ops import GMM_EXP, GMM_LOW_NOISE, GMM_SOFTPLUS
 __all__ = ["GMMActionHead"]
 
 
-def _linear_grads(need_x, need_params, feats, gpre, Wm, Ws, Wl, MA):
+def _linear_grads(need_x, need_params, feats, gpre, Wm, Ws, Wl, MA, precision):
     """(gx in feats' shape, gWm, gbm, gWs, gbs, gWl, gbl) from gpre [N, P]: ops.head_linear_grads' results cut by rows."""
-    gx, gW, gb = ops.head_linear_grads(need_x, need_params, feats, gpre, (Wm, Ws, Wl))
+    gx, gW, gb = ops.head_linear_grads(need_x, need_params, feats, gpre, (Wm, Ws, Wl), precision)
     if gW is None:
         return (gx,) + (None,) * 6
     return gx, gW[:MA], gb[:MA], gW[MA:2 * MA], gb[MA:2 * MA], gW[2 * MA:], gb[2 * MA:]
@@ -54,12 +57,13 @@ class _LogProbFn(KernelFunction):
     """(log_prob [B, T], sum of log_prob or None) over lipvq_gmm_head_f32 / lipvq_gmm_head_bwd_f32."""
 
     @staticmethod
-    def forward(ctx, feats, actions, Wm, bm, Ws, bs, Wl, bl, M, A, mode, min_std, want_sum):
+    def forward(ctx, feats, actions, Wm, bm, Ws, bs, Wl, bl, M, A, mode, min_std, want_sum, precision="fp32"):
         ctx.set_materialize_grads(False)
         keep = wants_backward(ctx)
-        out = ops.gmm_head(feats, (Wm, bm, Ws, bs, Wl, bl), M, A, actions, mode, min_std, want_pre=keep, want_sum=want_sum)
+        out = ops.gmm_head(feats, (Wm, bm, Ws, bs, Wl, bl), M, A, actions, mode, min_std, want_pre=keep, want_sum=want_sum,
+                           precision=precision)
         if keep:
-            ctx.cfg = (M, A, mode, min_std)
+            ctx.cfg = (M, A, mode, min_std, precision)
             ctx.save_for_backward(feats, actions, out["pre"], Wm, Ws, Wl)
         lp = out["log_prob"].view(feats.shape[:-1])
         return lp, out.get("sum")
@@ -68,25 +72,26 @@ class _LogProbFn(KernelFunction):
     @first_order_only
     def backward(ctx, glp, gsum):
         feats, actions, pre, Wm, Ws, Wl = ctx.saved_tensors
-        M, A, mode, min_std = ctx.cfg
+        M, A, mode, min_std, precision = ctx.cfg
+        need = ctx.needs_input_grad                                 # (precision is optional: one gradient slot per argument given)
         if glp is None and gsum is None:
-            return (None,) * 13
+            return (None,) * len(need)
         gpre = ops.gmm_head_bwd(pre, actions, None if glp is None else glp.reshape(-1), gsum, M, A, mode, min_std)
-        need = ctx.needs_input_grad
-        g = _linear_grads(need[0], any(need[2:8]), feats, gpre, Wm, Ws, Wl, M * A)
-        return (g[0], None) + g[1:] + (None,) * 5
+        g = _linear_grads(need[0], any(need[2:8]), feats, gpre, Wm, Ws, Wl, M * A, precision)
+        return ((g[0], None) + g[1:] + (None,) * 6)[:len(need)]
 
 
 class _ParamsFn(KernelFunction):
     """(mean [B, T, M, A], scale [B, T, M, A], logits [B, T, M]) over lipvq_gmm_head_f32 / lipvq_gmm_params_bwd_f32."""
 
     @staticmethod
-    def forward(ctx, feats, Wm, bm, Ws, bs, Wl, bl, M, A, mode, min_std):
+    def forward(ctx, feats, Wm, bm, Ws, bs, Wl, bl, M, A, mode, min_std, precision="fp32"):
         ctx.set_materialize_grads(False)
         keep = wants_backward(ctx)
-        out = ops.gmm_head(feats, (Wm, bm, Ws, bs, Wl, bl), M, A, None, mode, min_std, want_pre=keep, want_params=True)
+        out = ops.gmm_head(feats, (Wm, bm, Ws, bs, Wl, bl), M, A, None, mode, min_std, want_pre=keep, want_params=True,
+                           precision=precision)
         if keep:
-            ctx.cfg = (M, A, mode)
+            ctx.cfg = (M, A, mode, precision)
             ctx.save_for_backward(feats, out["pre"], Wm, Ws, Wl)
         lead = tuple(feats.shape[:-1])
         return out["mean"].view(lead + (M, A)), out["scale"].view(lead + (M, A)), out["logits"].view(lead + (M,))
@@ -95,13 +100,13 @@ class _ParamsFn(KernelFunction):
     @first_order_only
     def backward(ctx, gmean, gscale, glogits):
         feats, pre, Wm, Ws, Wl = ctx.saved_tensors
-        M, A, mode = ctx.cfg
+        M, A, mode, precision = ctx.cfg
+        need = ctx.needs_input_grad                                 # (precision is optional: one gradient slot per argument given)
         if gmean is None and gscale is None and glogits is None:
-            return (None,) * 11
+            return (None,) * len(need)
         gpre = ops.gmm_params_bwd(pre, gmean, gscale, glogits, M, A, mode)
-        need = ctx.needs_input_grad
-        g = _linear_grads(need[0], any(need[1:7]), feats, gpre, Wm, Ws, Wl, M * A)
-        return (g[0],) + g[1:] + (None,) * 4
+        g = _linear_grads(need[0], any(need[1:7]), feats, gpre, Wm, Ws, Wl, M * A, precision)
+        return ((g[0],) + g[1:] + (None,) * 5)[:len(need)]
 
 
 class GMMActionHead(KernelSampleSource, nn.Module):
@@ -140,6 +145,23 @@ class GMMActionHead(KernelSampleSource, nn.Module):
         self.nets["mean"] = nn.Linear(embed_dim, num_modes * ac_dim)
         self.nets["scale"] = nn.Linear(embed_dim, num_modes * ac_dim)
         self.nets["logits"] = nn.Linear(embed_dim, num_modes)
+        self._matmul_precision = "fp32"
+
+    @property
+    def matmul_precision(self) -> str:
+        """"fp32" (default), "bf16" or "bf16x3": how the head's three Linears multiply (set_matmul_precision)."""
+        return self._matmul_precision
+
+    def set_matmul_precision(self, precision: str) -> "GMMActionHead":
+        """"bf16" / "bf16x3": the head's three Linears -- in ``forward`` (both noise sources), ``log_prob``, ``nll`` and
+        ``forward_train``, and their gradients in the backward -- run on the bf16 matrix pipe by ``GPTBackbone.
+        set_matmul_precision``'s rules: operands rounded to bf16 (nearest even; "bf16x3": split into hi + lo, three products) as the
+        kernel reads them, fp32 accumulation, every tensor fp32; the pre-activations have the bits of ``ops.linear_bf16`` /
+        ``ops.linear_bf16x3``, and everything after them is the fp32 code.  "fp32" restores the default bit for bit.  The bf16
+        modes need embed_dim % 8 == 0.  Not part of state_dict(); a captured graph keeps the mode it was captured in; returns self."""
+        ops._matmul_mode("GMMActionHead", precision, self.embed_dim)
+        self._matmul_precision = precision
+        return self
 
     def _params(self):
         n = self.nets
@@ -163,7 +185,7 @@ class GMMActionHead(KernelSampleSource, nn.Module):
     def _log_prob(self, feats, actions, low_noise_eval, want_sum):
         feats = self._check(feats, actions)
         return _LogProbFn.apply(feats, actions.detach().float(), *self._params(), self.num_modes, self.ac_dim,
-                                self._mode(low_noise_eval), float(self.min_std), want_sum)
+                                self._mode(low_noise_eval), float(self.min_std), want_sum, self._matmul_precision)
 
     def log_prob(self, feats, actions, low_noise_eval=False):
         """log-likelihood [B, T] of actions [B, T, A] under the mixture (icl.py:916-947; the training path passes low_noise_eval=False)."""
@@ -180,7 +202,7 @@ class GMMActionHead(KernelSampleSource, nn.Module):
         autograd through them; batch_shape [B, T], event_shape [A]."""
         feats = self._check(feats)
         mean, scale, logits = _ParamsFn.apply(feats, *self._params(), self.num_modes, self.ac_dim, self._mode(low_noise_eval),
-                                              float(self.min_std))
+                                              float(self.min_std), self._matmul_precision)
         component = D.Independent(D.Normal(loc=mean, scale=scale), 1)
         return D.MixtureSameFamily(mixture_distribution=D.Categorical(logits=logits), component_distribution=component)
 
@@ -205,7 +227,8 @@ class GMMActionHead(KernelSampleSource, nn.Module):
                                  "(the launch draws both)")
             with torch.no_grad():
                 act = ops.gmm_sample_draw(feats.detach(), tuple(p.detach() for p in self._params()), self.num_modes, self.ac_dim,
-                                          self._sample_begin(feats.device), streams, self._mode(None), float(self.min_std))
+                                          self._sample_begin(feats.device), streams, self._mode(None), float(self.min_std),
+                                          self._matmul_precision)
             return act.view(B, T, self.ac_dim)
         if u is None:
             u = torch.rand((B, T), device=feats.device, dtype=torch.float32)
@@ -213,5 +236,5 @@ class GMMActionHead(KernelSampleSource, nn.Module):
             eps = torch.randn((B, T, self.ac_dim), device=feats.device, dtype=torch.float32)
         with torch.no_grad():
             act = ops.gmm_sample(feats.detach(), tuple(p.detach() for p in self._params()), self.num_modes, self.ac_dim, u, eps,
-                                 self._mode(None), float(self.min_std))
+                                 self._mode(None), float(self.min_std), self._matmul_precision)
         return act.view(B, T, self.ac_dim)

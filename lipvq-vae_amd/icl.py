@@ -382,6 +382,24 @@ class PromptedPolicy:
         self.cache = None
         self._codebook, self._embedded = None, None
 
+    def set_matmul_precision(self, precision: str) -> "PromptedPolicy":
+        """Backbone and head to one matmul precision ("fp32", "bf16", "bf16x3": their own ``set_matmul_precision``), so that a
+        rollout step is not of mixed precision, and the prompt dropped: its cached keys and values were computed in the old
+        mode, so ``features`` / ``__call__`` refuse until ``set_prompt`` is called again.  Both setters validate before either
+        module changes.  Returns self."""
+        for m in (self.backbone, self.head):
+            if not hasattr(m, "set_matmul_precision"):
+                raise TypeError(f"PromptedPolicy.set_matmul_precision: {type(m).__name__} has no matmul precision to set")
+        old = self.backbone.matmul_precision
+        self.backbone.set_matmul_precision(precision)
+        try:
+            self.head.set_matmul_precision(precision)
+        except ValueError:
+            self.backbone.set_matmul_precision(old)
+            raise
+        self.cache = None
+        return self
+
     def _embedded_key(self):
         """``derived.stamp`` of everything set_prompt's embedding read: the embedding's parameters, the codebook if any."""
         return stamp([*self.embedding.parameters(), *(() if self._codebook is None else (self._codebook,))])

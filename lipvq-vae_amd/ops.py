@@ -1347,11 +1347,43 @@ def _gmm_rows(feats, what="the GMM head"):
     return feats, B * T, T, E, (feats.stride(0) if B > 1 else T * E)
 
 
-def head_linear_grads(need_x, need_params, feats, gpre, weights):
+MATMUL_PRECISIONS = {"fp32": 0, "bf16": 1, "bf16x3": 2}              # include/lipvq.h: LIPVQ_MATMUL_*
+
+
+def _matmul_mode(what, precision, E=None):
+    """The LIPVQ_MATMUL_* value of a precision name; ValueError for an unknown name, or a bf16 mode with E % 8 != 0."""
+    if precision not in MATMUL_PRECISIONS:
+        raise ValueError(f"{what}: matmul precision must be 'fp32', 'bf16' or 'bf16x3', got {precision!r}")
+    if precision != "fp32" and E is not None and E % 8:
+        raise ValueError(f"{what}: the {precision} mode needs the input width to be a multiple of 8 (got {E})")
+    return MATMUL_PRECISIONS[precision]
+
+
+def head_linear_grads(need_x, need_params, feats, gpre, weights, precision="fp32"):
     """The Linear gradients of an output head from gpre [N, P], the gradient of its pre-activations: (gx in feats' shape, gW [P, E],
     gb [P]) -- one Linear for gx = gpre . W over the stacked `weights` (a tuple of [P_i, E] matrices, P = sum P_i), one wgrad over
-    all P columns; the caller cuts gW / gb by rows.  What is not needed is None."""
+    all P columns; the caller cuts gW / gb by rows.  What is not needed is None.
+    precision "bf16" / "bf16x3": the two products run on linear_nn_<mode> (the stacked weights as stored, no transposed copy)
+    and wgrad_<mode>.  Those need widths that are multiples of 8: gpre's columns and the stacked weight's rows are extended with
+    zeros to P8 = 8 ceil(P / 8) and the results cut -- zero lines add exact zeros.  Cost: one pad of gpre (skipped when P % 8 == 0;
+    a fill and a copy of [N, P8]) and, for gx, one cat that writes the [P8, E] stack with its zero rows (it replaces the fp32
+    path's cat + transposed copy)."""
+    mode = _matmul_mode("head_linear_grads", precision, feats.shape[-1])
     gx = gW = gb = None
+    if mode:
+        P, E = gpre.shape[1], feats.shape[-1]
+        P8 = (P + 7) // 8 * 8
+        nn_fn, wg_fn = (linear_nn_bf16, wgrad_bf16) if precision == "bf16" else (linear_nn_bf16x3, wgrad_bf16x3)
+        if not (need_x or need_params):
+            return gx, gW, gb
+        g8 = gpre if P8 == P else torch.nn.functional.pad(gpre, (0, P8 - P))
+        if need_x:
+            rows = tuple(weights) + ((torch.zeros((P8 - P, E), device=gpre.device, dtype=torch.float32),) if P8 != P else ())
+            gx = nn_fn(g8, torch.cat(rows, 0) if len(rows) > 1 else rows[0]).view(feats.shape)
+        if need_params:
+            gW, gb = wg_fn(g8, feats.reshape(-1, E))
+            gW, gb = gW[:P], gb[:P]
+        return gx, gW, gb
     if need_x:
         Wt = torch.cat(tuple(weights), 0).t().contiguous()         # [E, P] -> gx = gpre . W
         gx = linear(gpre, Wt).view(feats.shape)
@@ -1368,13 +1400,15 @@ def _gmm_params(params, M, A, E):
 
 
 def gmm_head(feats, params, M: int, A: int, actions=None, scale_mode: int = GMM_SOFTPLUS, min_std: float = 0.01,
-             want_pre: bool = False, want_params: bool = False, want_sum: bool = False):
-    """The GMM head in one launch (lipvq_gmm_head_f32).  feats [B, T, E] (its strides are passed on, see _gmm_rows); params =
+             want_pre: bool = False, want_params: bool = False, want_sum: bool = False, precision: str = "fp32"):
+    """The GMM head in one launch (lipvq_gmm_head_f32; precision "bf16" / "bf16x3": lipvq_gmm_head_mp_f32, the product on the bf16
+    matrix pipe with the bits of linear_bf16 / linear_bf16x3, the epilogue unchanged).  feats [B, T, E] (its strides are passed on, see _gmm_rows); params =
     (mean.weight, mean.bias, scale.weight, scale.bias, logits.weight, logits.bias); actions [B, T, A] or None.
     Returns a dict with the outputs asked for: log_prob [N] (with actions), pre [N, P] (want_pre), mean / scale [N, M, A] and
     logits [N, M] (want_params), sum [] (want_sum: the deterministic sum of log_prob)."""
     feats, N, T, E, bstride = _gmm_rows(feats)
     Wm, bm, Ws, bs, Wl, bl = _gmm_params(params, M, A, E)
+    mode = _matmul_mode("gmm_head", precision, E)
     dev = feats.device
     P = M * (2 * A + 1)
     out = {}
@@ -1395,11 +1429,14 @@ def gmm_head(feats, params, M: int, A: int, actions=None, scale_mode: int = GMM_
     if want_sum:
         out["sum"] = torch.empty((), device=dev, dtype=torch.float32)
         ws = torch.empty(max(1, lib.lipvq_gmm_workspace_bytes(N)), device=dev, dtype=torch.uint8)
+    args = (_ptr(feats), bstride, _ptr(Wm), _ptr(bm), _ptr(Ws), _ptr(bs), _ptr(Wl), _ptr(bl), _ptr(actions), _ptr(out.get("log_prob")),
+            _ptr(out.get("pre")), _ptr(out.get("mean")), _ptr(out.get("scale")), _ptr(out.get("logits")), _ptr(out.get("sum")), _ptr(ws),
+            N, T, E, int(M), int(A), int(scale_mode), float(min_std))
     with _on(dev):
-        check(lib.lipvq_gmm_head_f32(_ptr(feats), bstride, _ptr(Wm), _ptr(bm), _ptr(Ws), _ptr(bs), _ptr(Wl), _ptr(bl), _ptr(actions),
-                                     _ptr(out.get("log_prob")), _ptr(out.get("pre")), _ptr(out.get("mean")), _ptr(out.get("scale")),
-                                     _ptr(out.get("logits")), _ptr(out.get("sum")), _ptr(ws), N, T, E, int(M), int(A), int(scale_mode),
-                                     float(min_std), _stream()), "lipvq_gmm_head_f32")
+        if mode:
+            check(lib.lipvq_gmm_head_mp_f32(*args, mode, _stream()), "lipvq_gmm_head_mp_f32")
+        else:
+            check(lib.lipvq_gmm_head_f32(*args, _stream()), "lipvq_gmm_head_f32")
     return out
 
 
@@ -1441,18 +1478,23 @@ def gmm_params_bwd(pre, gmean, gscale, glogits, M: int, A: int, scale_mode: int 
     return gpre
 
 
-def gmm_sample(feats, params, M: int, A: int, u, eps, scale_mode: int = GMM_SOFTPLUS, min_std: float = 0.01):
-    """action [N, A] = mu_m + sigma_m eps with m drawn by inverse CDF from u (lipvq_gmm_sample_f32), one launch."""
+def gmm_sample(feats, params, M: int, A: int, u, eps, scale_mode: int = GMM_SOFTPLUS, min_std: float = 0.01, precision: str = "fp32"):
+    """action [N, A] = mu_m + sigma_m eps with m drawn by inverse CDF from u (lipvq_gmm_sample_f32), one launch.  precision: as
+    for gmm_head (lipvq_gmm_sample_mp_f32)."""
     feats, N, T, E, bstride = _gmm_rows(feats)
     Wm, bm, Ws, bs, Wl, bl = _gmm_params(params, M, A, E)
+    mode = _matmul_mode("gmm_sample", precision, E)
     u, eps = _chk(u, "u"), _chk(eps, "eps")
     if u.numel() != N or eps.numel() != N * A:
         raise ValueError(f"gmm_sample: u {tuple(u.shape)} / eps {tuple(eps.shape)} do not match {N} rows of {A}")
     action = torch.empty((N, A), device=feats.device, dtype=torch.float32)
+    args = (_ptr(feats), bstride, _ptr(Wm), _ptr(bm), _ptr(Ws), _ptr(bs), _ptr(Wl), _ptr(bl), _ptr(u), _ptr(eps), _ptr(action), N, T, E,
+            int(M), int(A), int(scale_mode), float(min_std))
     with _on(feats.device):
-        check(lib.lipvq_gmm_sample_f32(_ptr(feats), bstride, _ptr(Wm), _ptr(bm), _ptr(Ws), _ptr(bs), _ptr(Wl), _ptr(bl), _ptr(u), _ptr(eps),
-                                       _ptr(action), N, T, E, int(M), int(A), int(scale_mode), float(min_std), _stream()),
-              "lipvq_gmm_sample_f32")
+        if mode:
+            check(lib.lipvq_gmm_sample_mp_f32(*args, mode, _stream()), "lipvq_gmm_sample_mp_f32")
+        else:
+            check(lib.lipvq_gmm_sample_f32(*args, _stream()), "lipvq_gmm_sample_f32")
     return action
 
 
@@ -1479,20 +1521,26 @@ def _sample_streams(what, streams, B, dev):
     return streams.contiguous()
 
 
-def gmm_sample_draw(feats, params, M: int, A: int, snap, streams=None, scale_mode: int = GMM_SOFTPLUS, min_std: float = 0.01):
+def gmm_sample_draw(feats, params, M: int, A: int, snap, streams=None, scale_mode: int = GMM_SOFTPLUS, min_std: float = 0.01,
+                    precision: str = "fp32"):
     """gmm_sample whose u and eps are drawn inside the launch (lipvq_gmm_sample_draw_f32) from snap, the (seed, step) a
     dropout_begin on the sampling state wrote, and the rows' stream ids (streams int64 [B] on the device, None = batch position):
-    the bits of gmm_sample(feats, ..., *gmm_noise(snap, B, T, A, streams)).  One launch, no noise tensor."""
+    the bits of gmm_sample(feats, ..., *gmm_noise(snap, B, T, A, streams)) at the same precision (lipvq_gmm_sample_draw_mp_f32).
+    One launch, no noise tensor."""
     B = feats.shape[0] if isinstance(feats, torch.Tensor) and feats.dim() == 3 else 1
     feats, N, T, E, bstride = _gmm_rows(feats)
     Wm, bm, Ws, bs, Wl, bl = _gmm_params(params, M, A, E)
+    mode = _matmul_mode("gmm_sample_draw", precision, E)
     snap = _sample_snap("gmm_sample_draw", snap, feats.device)
     streams = _sample_streams("gmm_sample_draw", streams, B, feats.device)
     action = torch.empty((N, A), device=feats.device, dtype=torch.float32)
+    args = (_ptr(feats), bstride, _ptr(Wm), _ptr(bm), _ptr(Ws), _ptr(bs), _ptr(Wl), _ptr(bl), _ptr(snap), _ptr(streams), _ptr(action),
+            N, T, E, int(M), int(A), int(scale_mode), float(min_std))
     with _on(feats.device):
-        check(lib.lipvq_gmm_sample_draw_f32(_ptr(feats), bstride, _ptr(Wm), _ptr(bm), _ptr(Ws), _ptr(bs), _ptr(Wl), _ptr(bl), _ptr(snap),
-                                            _ptr(streams), _ptr(action), N, T, E, int(M), int(A), int(scale_mode), float(min_std),
-                                            _stream()), "lipvq_gmm_sample_draw_f32")
+        if mode:
+            check(lib.lipvq_gmm_sample_draw_mp_f32(*args, mode, _stream()), "lipvq_gmm_sample_draw_mp_f32")
+        else:
+            check(lib.lipvq_gmm_sample_draw_f32(*args, _stream()), "lipvq_gmm_sample_draw_f32")
     return action
 
 
@@ -1539,8 +1587,10 @@ def normal_icdf_host(words):
 # the deterministic policy's output head (csrc/lipvq_action_head.hip)
 # ---------------------------------------------------------------------------------------------------
 
-def action_head(feats, W, b, target=None, weights=(1.0, 0.0, 0.0), want_actions: bool = True, want_pre: bool = False):
-    """The Linear + tanh head and its losses (lipvq_action_head_f32).  feats [B, T, E] (its strides are passed on, see _gmm_rows);
+def action_head(feats, W, b, target=None, weights=(1.0, 0.0, 0.0), want_actions: bool = True, want_pre: bool = False,
+                precision: str = "fp32"):
+    """The Linear + tanh head and its losses (lipvq_action_head_f32; precision "bf16" / "bf16x3": lipvq_action_head_mp_f32, the
+    product on the bf16 matrix pipe with the bits of linear_bf16 / linear_bf16x3, the epilogue unchanged).  feats [B, T, E] (its strides are passed on, see _gmm_rows);
     W [A, E], b [A]; target [B, T, A] or None; weights = (l2_weight, l1_weight, cos_weight).
     Returns a dict with the outputs asked for: actions [N, A] (want_actions), pre [N, A] (want_pre), losses [4] = (l2, l1, cos,
     action) (with a target: one more one-workgroup launch, a deterministic sum)."""
@@ -1549,6 +1599,7 @@ def action_head(feats, W, b, target=None, weights=(1.0, 0.0, 0.0), want_actions:
     if W.dim() != 2 or W.shape[1] != E or b.shape != (W.shape[0],):
         raise ValueError(f"action_head: W {tuple(W.shape)} / b {tuple(b.shape)} do not match E={E}")
     A = W.shape[0]
+    mode = _matmul_mode("action_head", precision, E)
     dev = feats.device
     out = {}
     if want_actions:
@@ -1563,9 +1614,13 @@ def action_head(feats, W, b, target=None, weights=(1.0, 0.0, 0.0), want_actions:
         out["losses"] = torch.empty(4, device=dev, dtype=torch.float32)
         ws = torch.empty(max(1, lib.lipvq_action_head_workspace_bytes(N)), device=dev, dtype=torch.uint8)
     w2, w1, wc = (float(w) for w in weights)
+    args = (_ptr(feats), bstride, _ptr(W), _ptr(b), _ptr(target), _ptr(out.get("actions")), _ptr(out.get("pre")), _ptr(out.get("losses")),
+            _ptr(ws), N, T, E, int(A), w2, w1, wc)
     with _on(dev):
-        check(lib.lipvq_action_head_f32(_ptr(feats), bstride, _ptr(W), _ptr(b), _ptr(target), _ptr(out.get("actions")), _ptr(out.get("pre")),
-                                        _ptr(out.get("losses")), _ptr(ws), N, T, E, int(A), w2, w1, wc, _stream()), "lipvq_action_head_f32")
+        if mode:
+            check(lib.lipvq_action_head_mp_f32(*args, mode, _stream()), "lipvq_action_head_mp_f32")
+        else:
+            check(lib.lipvq_action_head_f32(*args, _stream()), "lipvq_action_head_f32")
     return out
 
 
