@@ -448,8 +448,10 @@ LQ_EXPORT void lq_ref_ema_update(float* cs, float* es, const int64_t* counts, co
     }
 }
 
-/* Probes for tests/test_oracle_math.py */
+/* Probes for tests/test_oracle_math.py and tests/test_math_cases_host.py; the device's counterpart (csrc/probe/lipvq_math_probe.hip,
+ * lq_probe_map) keeps these numbers */
 LQ_EXPORT void lq_ref_math_probe(const float* x, float* out, int64_t n, int fn) {
+#pragma omp parallel for schedule(static)
     for (int64_t i = 0; i < n; ++i) {
         float v = x[i], r;
         switch (fn) {
@@ -459,6 +461,10 @@ LQ_EXPORT void lq_ref_math_probe(const float* x, float* out, int64_t n, int fn) 
             case 3: r = lq_sigmoid(v); break;
             case 4: r = lq_softplus(v); break;
             case 5: r = lq_gelu_grad(v); break;
+            case 6: r = lq_logf_ge1(v); break;      /* finite v >= 1 */
+            case 7: r = lq_sqrt(v); break;
+            case 8: r = lq_gelu_poly(v); break;     /* v * v < 18 */
+            case 9: r = lq_gelu_tail(v); break;
             default: r = v;
         }
         out[i] = r;

@@ -168,6 +168,8 @@ class CanonicalOracle:
         return out
 
     def math_probe(self, x, fn):
+        """fn: 0 lq_expf, 1 lq_erff, 2 lq_gelu, 3 lq_sigmoid, 4 lq_softplus, 5 lq_gelu_grad, 6 lq_logf_ge1, 7 lq_sqrt,
+        8 lq_gelu_poly, 9 lq_gelu_tail (lipvq_math.h), element by element."""
         x = _f32(x).reshape(-1)
         out = np.empty_like(x)
         self.lib.lq_ref_math_probe(_p(x), _p(out), C.c_int64(x.size), C.c_int(fn))
